@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- BPR training steps/sec of the MI355X-native LightGCN hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--dump-outputs DIR] [--full]
 
 A "step" is one BPRLoss.stageOne (utils.py:53-64 of the reference): K-layer
 propagation + BPR loss + backward + Adam on one batch of B triplets, with the
 epoch's triplets already resident in HBM.  Workload at N=1 = BASELINE.json
 configs[1]: Gowalla (real graph, reconstructed; 29 858 x 40 981, 810 128 train
 interactions), 3 layers, dim 64, BPR batch 2048.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps, writes the timed path's outputs
+(--dump-outputs) and prints the line.  Everything else the script measures -- the
+other activation storage type, the steady-state region, the roofline objects, the
+evaluation kernel, end-to-end epochs with the 10-epoch quality check and the CPU
+baselines -- runs only with --full.
 
 N > 1: one process per GPU over RCCL.  Started under torch.distributed.run the
 script reads RANK/LOCAL_RANK/WORLD_SIZE; started plainly (`python bench.py
@@ -36,6 +42,8 @@ HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6300 
 FP32_MFMA_PEAK_TF = 157.3      # v_mfma_f32_32x32x2_f32 (same guide)
 BF16_MFMA_PEAK_TF = 157.3 * 16  # dense bf16 MFMA = 16 x the fp32 rate (~2.5 PFLOP/s)
 GOLDEN_LONG = os.path.join(REPO, "tests", "golden", "gowalla", "golden_long.json")
+DUMP_TABLE_BYTES = 28 << 20    # --dump-outputs: per embedding table; larger tables are written as a seeded sample of rows
+DUMP_SEED = 2020
 
 
 def materialize_gowalla(npz, dst):
@@ -79,6 +87,26 @@ def synthetic_dataset(pkg, name, config, device):
     rng = np.random.Generator(np.random.PCG64(7))
     test = {int(u): [int(rng.integers(0, m_items))] for u in range(min(n_users, 1000))}
     return pkg.dataloader.CsrLoader(indptr, indices, m_items, test_dict=test, config=config)
+
+
+def dump_outputs(out_dir, losses, model):
+    """--dump-outputs: what the timed path hands its caller after its last step -- the per-step (loss, bpr, reg) of the
+    timed region and the two embedding tables it updated -- as float32 .npy files.  A table above DUMP_TABLE_BYTES is
+    written as a fixed, seeded sample of its rows (sorted), with the row indices beside it as <name>_rows.npy."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"losses": losses.detach().float().cpu().numpy()}
+    table = model._table.detach()
+    for name, t in (("embedding_user", table[:model.n_users]), ("embedding_item", table[model.n_users:])):
+        cap = max(1, DUMP_TABLE_BYTES // (t.shape[1] * 4))
+        if t.shape[0] > cap:
+            rows = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(t.shape[0], cap, replace=False))
+            arrays[name + "_rows"] = rows.astype(np.float64)
+            t = t[torch.from_numpy(rows).to(t.device)]
+        arrays[name] = t.float().cpu().numpy()
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return sorted(arrays)
 
 
 def free_port():
@@ -135,6 +163,13 @@ def main():
     ap.add_argument("--row_order", default=None, choices=["natural", "rcm", "cocluster", "xcd"])
     ap.add_argument("--hub_nnz", type=int, default=0, help="hub plan threshold of the batch-row kernel (0: library default, < 0: off)")
     ap.add_argument("--hub_chunk", type=int, default=0, help="non-zeros per chunk of the hub plan's rows (0: library default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline: the other activation dtype, the steady-state region, "
+                         "roofline objects, the evaluation kernel, end-to-end epochs + quality, CPU baselines (the --no_* "
+                         "options below skip single legs of it)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what they computed (per-step losses, the updated embedding tables) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--no_secondary", action="store_true", help="skip the extra run with the other activation dtype")
     ap.add_argument("--spmm_only", action="store_true", help="only the dominant-kernel loop (profiling helper)")
@@ -192,8 +227,10 @@ def main():
                               "act_dtype": a.act_dtype,
                               "global_batch": B * world if a.scaling == "weak" else B,
                               "rccl_ranks_observed": int(ones.item()),
-                              "steady_state_steps": 0 if (a.workload == "synthetic-10m" or a.no_steady) else 400,
-                              "extra_objects": (["roofline", "cpu_baseline", "eval_topk", "end_to_end_epoch", "quality"]
+                              "full": a.full,
+                              "steady_state_steps": 0 if (a.workload == "synthetic-10m" or a.no_steady or not a.full) else 400,
+                              "extra_objects": ([] if not a.full else
+                                                ["roofline", "cpu_baseline", "eval_topk", "end_to_end_epoch", "quality"]
                                                 if world == 1 and a.workload == "gowalla" else ["roofline"])}))
         dist.destroy_process_group()
         return
@@ -319,6 +356,7 @@ def main():
 
     # triplets for warmup + timed steps, resident in HBM before the timed region
     Bg = B * world if a.scaling == "weak" else B     # weak: per-GPU batch fixed; strong: the global batch is the reference's B
+    # (the steady-state region's triplets are drawn whether or not --full runs it: the timed steps get the same inputs either way)
     steady_steps = 0 if (a.workload == "synthetic-10m" or a.no_steady) else 400
     need = (a.warmup + a.steps + steady_steps) * Bg
     if ds.trainDataSize <= 4 * need:
@@ -350,14 +388,17 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # The measurements that are NOT the headline come first -- the dominant kernel's live timing (every rank) and the
-    # same workload with the other activation storage type -- so that the headline's K steps run on a GPU that is
-    # already at its working clocks (a 20-step region right after set-up measured 4-5 % under steady state).
+    # The measurements that are NOT the headline come first -- the dominant kernel's live timing (every rank) and a leg of
+    # the training path on a second model of the same graph -- so that the headline's K steps run on a GPU that is already
+    # at its working clocks (a 20-step region right after set-up measured 4-5 % under steady state).  With --full that leg is
+    # the same workload with the other activation storage type, timed and reported; in a plain run it keeps the headline's
+    # storage type and is warm-up only (without it the headline read 2.8 % lower over 20 steps, 0.7 % over 400; a longer
+    # burst of the dominant kernel alone does not make that up).  Neither touches the model the headline trains.
     reps = a.spmm_reps if a.workload != "synthetic-10m" else 5
     t_spmm = spmm_kernel_time(reps)      # ~50 ms of back-to-back launches: also what brings the GPU to its working clocks for the legs below
     secondary = None
-    if rank == 0 and not use_dp and not a.no_secondary and a.workload != "synthetic-10m":
-        other = "bf16" if a.act_dtype != "bf16" else "fp32"
+    if rank == 0 and not use_dp and not (a.full and a.no_secondary) and a.workload != "synthetic-10m":
+        other = a.act_dtype if not a.full else "bf16" if a.act_dtype != "bf16" else "fp32"
         cfg2 = dict(w.config); cfg2['act_dtype'] = other
         with contextlib.redirect_stdout(io.StringIO()):
             pkg.utils.set_seed(2020)
@@ -366,14 +407,17 @@ def main():
         model2.fused_epoch(users[:a.warmup * B], pos[:a.warmup * B], neg[:a.warmup * B], B)
         spmm_kernel_time(min(200, reps), ACT[other][0])
         model2.fused_epoch(users[:a.warmup * B], pos[:a.warmup * B], neg[:a.warmup * B], B)
+        k2 = a.steps if a.full else min(a.steps, 2000)       # (plain run: at most ~0.25 s of warm-up, whatever K is)
         torch.cuda.synchronize(); t0 = time.perf_counter()
-        model2.fused_epoch(users[a.warmup * B:(a.warmup + a.steps) * B], pos[a.warmup * B:(a.warmup + a.steps) * B],
-                           neg[a.warmup * B:(a.warmup + a.steps) * B], B)
+        model2.fused_epoch(users[a.warmup * B:(a.warmup + k2) * B], pos[a.warmup * B:(a.warmup + k2) * B],
+                           neg[a.warmup * B:(a.warmup + k2) * B], B)
         done2 = torch.cuda.Event(); done2.record()
         while not done2.query():
             pass
         torch.cuda.synchronize(); dt2 = time.perf_counter() - t0
-        secondary = (other, a.steps / dt2, spmm_kernel_time(max(200, reps // 4), ACT[other][0]))
+        t_spmm2 = spmm_kernel_time(max(200, reps // 4), ACT[other][0])
+        if a.full:
+            secondary = (other, a.steps / dt2, t_spmm2)
         del model2
     spmm_kernel_time(min(200, reps))     # (a short burst directly ahead of the warm-up steps)
 
@@ -393,8 +437,13 @@ def main():
         dt = float(t.item())
     progress(f"timed region done: {dt:.3f} s")
     model.check_device_errors()
+    if a.dump_outputs and rank == 0:
+        names = dump_outputs(a.dump_outputs, losses, model)
+        progress(f"outputs of the timed steps written to {a.dump_outputs}: {', '.join(names)}")
     # ---- the same loop for 400 more steps: the K-step region above is ~3 ms at the driver's K = 20 and reads ~2 % under this
     steady = None
+    if not a.full:
+        steady_steps = 0
     if steady_steps:
         barrier()
         t0s = time.perf_counter()
@@ -449,7 +498,7 @@ def main():
             "step_roofline_frac": step_bytes(N, nnz, d, s, K, B) * steps_per_sec / (HBM_PEAK_GBS * 1e9),
         }
 
-    if rank == 0:
+    if rank == 0 and a.full:
         if secondary is not None:       # the same workload with the other activation storage type (reported, not the headline)
             out["config"][f"{secondary[0]}_activation_storage_steps_per_sec"] = secondary[1]
             out[f"value_{secondary[0]}"] = secondary[1]        # same K-step region, same triplets, the other storage type
@@ -466,7 +515,7 @@ def main():
 
     # ---- the evaluation kernel on the same model (reported, not the headline): Procedure.Test's scoring +
     #      masking + top-20 in one launch, priced against the fp32 matrix-core peak (the reference ranks in fp32)
-    if rank == 0 and world == 1 and not a.no_eval and a.workload == "gowalla" and getattr(ds, "testDict", None):   # (the synthetic shapes hold 1 000 test users)
+    if a.full and rank == 0 and world == 1 and not a.no_eval and a.workload == "gowalla" and getattr(ds, "testDict", None):   # (the synthetic shapes hold 1 000 test users)
         try:
             with contextlib.redirect_stdout(io.StringIO()):
                 model.eval()
@@ -518,7 +567,7 @@ def main():
     #      produce after 10 epochs evaluated against the Recall@20 the imported reference reached on CPU with that seed
     #      (tests/golden/gowalla/golden_long.json: 0.1203589; north_star bar 1e-4).  SURVEY 8d: "sampler time folded into an
     #      end-to-end epoch steps/sec".
-    if rank == 0 and world == 1 and not a.no_epochs and a.workload == "gowalla" and os.path.exists(GOLDEN_LONG):
+    if a.full and rank == 0 and world == 1 and not a.no_epochs and a.workload == "gowalla" and os.path.exists(GOLDEN_LONG):
         try:
             gold = json.load(open(GOLDEN_LONG))["trajectory"][9]["test"]
             steps_per_epoch = (ds.n_users * (ds.trainDataSize // ds.n_users) + B - 1) // B
@@ -575,7 +624,7 @@ def main():
 
     # ---- CPU baseline on the host cores: the oracle (C/OpenMP port of the reference path) and an
     #      op-for-op torch-CPU eager restatement of the reference's stageOne, same workload
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.workload != "synthetic-10m":
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and a.workload != "synthetic-10m":
         from oracle import oracle as orc
         from oracle import torch_eager
         adj = ds.getSparseGraphCSR()

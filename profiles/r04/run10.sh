@@ -19,11 +19,11 @@ for wl in gowalla yelp2018-shaped amazon-book-shaped; do        # (synthetic-10m
   python3 $ROOT/profiles/pmc_traffic.py $OUT/pmc_$wl --write $wl --out $OUT/hbm_traffic.json | tee $OUT/pmc_${wl}_spmm.txt
   echo "pmc $wl done" | tee -a $OUT/status.log
 done
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_gowalla/trace -- python3 $ROOT/bench.py --steps 100 --warmup 10 --no_cpu_baseline > $OUT/trace_gowalla.log 2>&1 || echo "trace failed" | tee -a $OUT/status.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_gowalla/trace -- python3 $ROOT/bench.py --full --steps 100 --warmup 10 --no_cpu_baseline > $OUT/trace_gowalla.log 2>&1 || echo "trace failed" | tee -a $OUT/status.log
 python3 $ROOT/profiles/summarize.py $OUT/trace_gowalla > $OUT/trace_gowalla_fp32_summary.txt 2>&1; head -18 $OUT/trace_gowalla_fp32_summary.txt | cut -c1-150
 for spec in "yelp2018-shaped fp32" "amazon-book-shaped fp32" "amazon-book-shaped fp8"; do
   set -- $spec
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$1_$2/trace -- python3 $ROOT/bench.py --workload $1 --act_dtype $2 --steps 40 --warmup 5 --no_cpu_baseline --no_secondary --no_steady > $OUT/trace_$1_$2.log 2>&1 || echo "trace $1 $2 failed" | tee -a $OUT/status.log
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$1_$2/trace -- python3 $ROOT/bench.py --full --workload $1 --act_dtype $2 --steps 40 --warmup 5 --no_cpu_baseline --no_secondary --no_steady > $OUT/trace_$1_$2.log 2>&1 || echo "trace $1 $2 failed" | tee -a $OUT/status.log
   python3 $ROOT/profiles/summarize.py $OUT/trace_$1_$2 > $OUT/trace_$1_$2_summary.txt 2>&1; head -12 $OUT/trace_$1_$2_summary.txt | cut -c1-150
 done
 echo "traces done" | tee -a $OUT/status.log

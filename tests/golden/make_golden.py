@@ -7,7 +7,7 @@ path, and nothing of the reference's source text is written to the repo: the
 outputs are data only (inputs + expected outputs as .npz / .json / .txt
 interaction lists).
 
-Usage:  python tests/golden/make_golden.py [tiny] [lastfm] [gowalla] [gowalla_long] [tiny_gate] [tiny_i2i] [tiny_gate_i2i] [tiny_gate_i2i_k1|_k2|_k4]
+Usage:  python tests/golden/make_golden.py [tiny] [lastfm] [gowalla] [gowalla_long] [tiny_gate] [tiny_i2i] [tiny_gate_i2i] [tiny_gate_i2i_k1|_k2|_k4] [ref_plugin]
 
 What the reference pieces are (all paths relative to
 /root/reference/LightGCN_work/code):
@@ -498,6 +498,53 @@ def gen_variant(tag, gate, i2i, out_dir, K=3):
     shutil.rmtree(work, ignore_errors=True)
 
 
+# --------------------------------------------------------------------------
+# the reference's compiled sampler on the inputs of tests/test_oracle.py::test_sampler_vs_compiled_reference and
+# tests/test_host.py::test_sampler_vs_compiled_reference_and_oracle (same generators, same call order), recorded as
+# dtype / shape / sha256 of every array it returned and the value of every randint: those tests check against this
+# record, and against the live plugin too where oracle/_ref is built.
+# --------------------------------------------------------------------------
+def plugin_record(a):
+    a = np.asarray(a)
+    return {"dtype": str(a.dtype), "shape": list(a.shape), "sha256": sha(a.astype(np.int64))}
+
+
+def random_rows(rng, n_users, m_items, max_len):
+    rows = [np.sort(rng.choice(m_items, size=int(rng.integers(1, max_len)), replace=False)).astype(np.int32)
+            for _ in range(n_users)]
+    return rows, sum(len(r) for r in rows)
+
+
+def gen_ref_plugin(out_json):
+    sys.path.insert(0, os.path.join(REPO, "oracle", "_ref"))
+    import sampling as ref
+    out = {"test_oracle": {}, "test_host": {}}
+    rec = out["test_oracle"]
+    rng = np.random.Generator(np.random.PCG64(5))
+    n_users, m_items = 300, 500
+    rows, train_num = random_rows(rng, n_users, m_items, 60)
+    for seed in (2020, 7):
+        ref.seed(seed)
+        for k in range(2):
+            rec[f"{seed}/sample_negative/{k}"] = plugin_record(ref.sample_negative(n_users, m_items, train_num, rows, 1))
+        us = rng.integers(0, n_users, 77).astype(np.int32)
+        rec[f"{seed}/sample_negative_ByUser"] = plugin_record(ref.sample_negative_ByUser(us.tolist(), m_items, rows, 3))
+        rec[f"{seed}/randint"] = int(ref.randint(1000))
+    rec = out["test_host"]
+    rng = np.random.Generator(np.random.PCG64(11))
+    n_users, m_items = 257, 403
+    rows, train_num = random_rows(rng, n_users, m_items, 90)
+    for seed in (2020, 3):
+        ref.seed(seed)
+        for neg in (1, 2):
+            rec[f"{seed}/sample_negative/{neg}"] = plugin_record(ref.sample_negative(n_users, m_items, train_num, rows, neg))
+        us = rng.integers(0, n_users, 50).astype(np.int32)
+        rec[f"{seed}/sample_negative_ByUser"] = plugin_record(ref.sample_negative_ByUser(us.tolist(), m_items, rows, 2))
+    with open(out_json, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+    print("ref_plugin", len(out["test_oracle"]) + len(out["test_host"]), "records ->", out_json)
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["tiny", "lastfm", "gowalla"]
     # each target runs in a fresh interpreter: `world` parses argv at import and the
@@ -524,5 +571,7 @@ if __name__ == "__main__":
         gen_variant(w[5:], True, True, os.path.join(HERE, "tiny"), K=int(w[-1]))
     elif w == "gowalla_long":
         gen_gowalla(os.path.join(HERE, "gowalla"), 10, "long")
+    elif w == "ref_plugin":
+        gen_ref_plugin(os.path.join(HERE, "ref_plugin.json"))
     else:
         raise SystemExit("unknown target " + w)

@@ -19,7 +19,7 @@ def _run(args, extra_env=None):
 
 
 def test_bench_self_launches_two_ranks():
-    p = _run(["--gpus", "2", "--steps", "7", "--warmup", "2", "--workload", "amazon-book-shaped"])
+    p = _run(["--gpus", "2", "--steps", "7", "--warmup", "2", "--workload", "amazon-book-shaped", "--full"])
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -30,6 +30,12 @@ def test_bench_self_launches_two_ranks():
     assert j["scaling"] == "strong" and j["global_batch"] == 2048
     # the ranks the collectives really span (an all-reduce of 1 per rank), not WORLD_SIZE; the 400-step steady-state region
     assert j["rccl_ranks_observed"] == 2 and j["steady_state_steps"] == 400
+    # without --full the same launch runs the K timed steps only: no steady-state region, no extra objects
+    p = _run(["--gpus", "2", "--steps", "7", "--warmup", "2", "--workload", "amazon-book-shaped"])
+    assert p.returncode == 0, p.stderr[-2000:]
+    j = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+    assert j["n_gpus"] == 2 and j["steps"] == 7 and j["rccl_ranks_observed"] == 2
+    assert not j["full"] and j["steady_state_steps"] == 0 and j["extra_objects"] == []
 
 
 def test_bench_weak_scaling_flag():
@@ -44,6 +50,11 @@ def test_bench_single_rank_and_mismatch():
     assert p.returncode == 0, p.stderr[-2000:]
     j = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     assert j["n_gpus"] == 1 and j["workload"] == "gowalla" and j["steps"] == 400 and j["warmup"] == 20
+    assert not j["full"] and j["steady_state_steps"] == 0 and j["extra_objects"] == []
+    p = _run(["--full"])
+    assert p.returncode == 0, p.stderr[-2000:]
+    j = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+    assert j["full"] and j["steps"] == 400 and j["warmup"] == 20 and j["steady_state_steps"] == 400
     # BASELINE configs[1] ("Gowalla 3-layer dim=64 bf16") names the storage type: the default there, fp32 on the other workloads
     assert j["act_dtype"] == "bf16"
     j32 = json.loads([l for l in _run(["--act_dtype", "fp32"]).stdout.splitlines() if l.startswith("{")][0])

@@ -140,11 +140,18 @@ def test_sampler_rejects_user_without_positives(pkg, lastfm, tmp_path):
 
 
 def test_sampler_vs_compiled_reference_and_oracle(pkg, oracle):
+    """The native sampler against the oracle, against what the reference's compiled plugin returned for these inputs
+    (tests/golden/ref_plugin.json, make_golden.py ref_plugin) and against the live plugin where oracle/_ref is built."""
+    rec = json.load(open(os.path.join(GOLDEN, "ref_plugin.json")))["test_host"]
     ref_dir = os.path.join(REPO, "oracle", "_ref")
     have_ref = os.path.isdir(ref_dir) and any(f.startswith("sampling") and f.endswith(".so") for f in os.listdir(ref_dir))
     if have_ref:
         sys.path.insert(0, ref_dir)
         ref = importlib.import_module("sampling")
+
+    def record(x):
+        x = np.asarray(x)
+        return {"dtype": str(x.dtype), "shape": list(x.shape), "sha256": sha(x.astype(np.int64))}
     rng = np.random.Generator(np.random.PCG64(11))
     n_users, m_items = 257, 403
     rows = [np.sort(rng.choice(m_items, size=int(rng.integers(1, 90)), replace=False)).astype(np.int32)
@@ -160,12 +167,15 @@ def test_sampler_vs_compiled_reference_and_oracle(pkg, oracle):
             a = pkg.sampling.sample_negative(n_users, m_items, train_num, rows, neg)
             b = oracle.sample_negative(n_users, m_items, train_num, indptr, indices, neg)
             assert np.array_equal(a, b)
+            assert record(a) == rec[f"{seed}/sample_negative/{neg}"]          # dtype, shape and rows of the reference's output
             if have_ref:
                 c = ref.sample_negative(n_users, m_items, train_num, rows, neg)
                 assert c.dtype == a.dtype and c.shape == a.shape and np.array_equal(a, c)
         us = rng.integers(0, n_users, 50).astype(np.int32)
         a = pkg.sampling.sample_negative_ByUser(us, m_items, rows, 2)
         assert np.array_equal(a, oracle.sample_negative_by_user(us, m_items, indptr, indices, 2))
+        r = rec[f"{seed}/sample_negative_ByUser"]
+        assert record(a)["shape"] == r["shape"] and record(a)["sha256"] == r["sha256"]
         if have_ref:
             assert np.array_equal(a, ref.sample_negative_ByUser(us.tolist(), m_items, rows, 2))
 
