@@ -201,23 +201,15 @@ class _EvalIndex:
 
 
 def _test_fused(Recmodel, ev, max_K):
-    """Procedure.py:162-192 in two launches: lgcn_eval_topk (scores on the matrix cores + train mask +
-    top-K, no score matrix in memory) and lgcn_eval_metrics (hits, precision / recall / NDCG, sums)."""
-    lib = _lib.load()
+    """Procedure.py:162-192 in two launches: lgcn_eval_topk_ex (scores on the matrix cores + train mask +
+    top-K, no score matrix in memory) and lgcn_eval_metrics_ex (hits, precision / recall / NDCG, sums)."""
     E = Recmodel.rating_table()
     n = len(ev.users)
-    dev = E.device
-    topk = torch.empty(n, max_K, dtype=torch.int32, device=dev)
-    _lib.check(lib.lgcn_eval_topk_masked(_lib.tp(E), Recmodel.n_users, Recmodel.m_items, int(E.shape[1]),      # (a column shard scores with the gathered table)
-                                         _lib.tp(ev.users32), n, _lib.tp(ev.train_ptr), _lib.tp(ev.train_idx32),
-                                         max_K, _lib.tp(topk), None, _lib.tp(ev.masks) if ev.masks is not None else None,
-                                         _lib.current_stream()), "lgcn_eval_topk")
-    ks = torch.tensor(list(world.topks), dtype=torch.int32)
-    per_user = torch.empty(n, 3 * len(ks), dtype=torch.float64, device=dev)
-    sums = torch.empty(3 * len(ks), dtype=torch.float64, device=dev)
-    _lib.check(lib.lgcn_eval_metrics(_lib.tp(topk), n, max_K, _lib.tp(ev.test_ptr), _lib.tp(ev.test_sorted32),
-                                     _lib.tp(ks), len(ks), _lib.tp(per_user), _lib.tp(sums), _lib.current_stream()),
-               "lgcn_eval_metrics")
+    topk = torch.empty(n, max_K, dtype=torch.int32, device=E.device)
+    _lib.eval_topk(E, Recmodel.n_users, ev.users32, ev.train_ptr, ev.train_idx32, max_K, topk,      # (a column shard scores with the gathered table)
+                   masks=ev.masks)
+    ks = list(world.topks)
+    _, sums = _lib.eval_metrics(topk, ev.test_ptr, ev.test_sorted32, ks)
     m = (sums.cpu().numpy() / max(n, 1)).reshape(3, len(ks))
     return {'precision': m[0], 'recall': m[1], 'ndcg': m[2]}, topk
 
@@ -239,7 +231,7 @@ def Test(dataset, Recmodel, epoch, w=None, multicore=0):
             dataset._lgcn_eval_index = ev
         except Exception:
             pass
-    fused = max_K <= 64 and int(world.config.get('eval_fused', 1)) and hasattr(Recmodel, 'propagated_table')
+    fused = max_K <= _lib.eval_kmax() and int(world.config.get('eval_fused', 1)) and hasattr(Recmodel, 'propagated_table')
     if fused:
         with torch.no_grad():
             results, _ = _test_fused(Recmodel, ev, max_K)

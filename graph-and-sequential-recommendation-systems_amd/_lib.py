@@ -9,7 +9,7 @@ import os
 from . import build as _build
 
 F32, BF16, FP8 = 0, 1, 2
-ABI_VERSION = 11
+ABI_VERSION = 12
 MAX_LAYERS = 8
 
 _c_i32p = C.POINTER(C.c_int32)
@@ -95,6 +95,10 @@ SIGNATURES = {
     "lgcn_eval_build_masks": (C.c_int, [_vp, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp]),
     "lgcn_eval_topk_fp32": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp]),
     "lgcn_eval_metrics": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp]),
+    "lgcn_eval_kmax": (C.c_int32, []),
+    "lgcn_eval_topk_ex": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, _vp,
+                                    C.c_int64, C.c_int32, _vp]),
+    "lgcn_eval_metrics_ex": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp]),
     "lgcn_dp_available": (C.c_int, []),
     "lgcn_dp_unique_id": (C.c_int, [_vp]),
     "lgcn_dp_init": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(_vp)]),
@@ -184,6 +188,90 @@ def require_gpu():
 def current_stream():
     import torch
     return _vp(torch.cuda.current_stream().cuda_stream)
+
+
+EVAL_FP32 = 1          # LGCN_EVAL_FP32
+
+
+def eval_kmax():
+    """Largest K of the fused evaluation (lgcn_eval_kmax)."""
+    return int(load().lgcn_eval_kmax())
+
+
+def _want(t, name, dtype, shape, dev=None):
+    """ValueError unless t is a contiguous tensor of this dtype and shape (on dev when given)."""
+    import torch
+    if not torch.is_tensor(t):
+        raise ValueError(f"{name} must be a tensor")
+    if t.dtype != dtype:
+        raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if dev is not None and t.device != dev:
+        raise ValueError(f"{name} must be on {dev}, got {t.device}")
+
+
+def eval_topk(E, n_users, users32, train_ptr, train_idx32, K, out_items, out_scores=None, masks=None, fp32=False):
+    """lgcn_eval_topk_ex, checked: E the propagated table [n_users + m_items, d] fp32 on the device, users32 int32 [n_eval],
+    train_ptr int64 [n_users + 1], train_idx32 int32, out_items int32 [n_eval, K] (out_scores fp32 [n_eval, K] or None),
+    masks from lgcn_eval_build_masks or None.  Everything is validated before anything is launched (ValueError)."""
+    import torch
+    _want(E, "E", torch.float32, None)
+    if E.dim() != 2 or E.device.type != "cuda":
+        raise ValueError("E must be a 2-D device tensor")
+    dev = E.device
+    n_users, d = int(n_users), int(E.shape[1])
+    m_items = int(E.shape[0]) - n_users
+    if d not in (32, 64, 128, 256) or n_users <= 0 or m_items <= 0:
+        raise ValueError(f"E [{tuple(E.shape)}] with n_users={n_users}: d must be 32, 64, 128 or 256 and both sides non-empty")
+    K = int(K)
+    if not 1 <= K <= eval_kmax() or K > m_items:
+        raise ValueError(f"K={K} must be in 1..{eval_kmax()} and <= m_items={m_items}")
+    _want(users32, "users32", torch.int32, None, dev)
+    n = int(users32.numel())
+    _want(train_ptr, "train_ptr", torch.int64, None, dev)
+    if train_ptr.dim() != 1 or train_ptr.numel() < n_users + 1:
+        raise ValueError(f"train_ptr must hold n_users + 1 = {n_users + 1} offsets")
+    _want(train_idx32, "train_idx32", torch.int32, None, dev)
+    _want(out_items, "out_items", torch.int32, (n, K), dev)
+    if out_scores is not None:
+        _want(out_scores, "out_scores", torch.float32, (n, K), dev)
+    if masks is not None:
+        _want(masks, "masks", torch.int32, (int(load().lgcn_eval_mask_words(m_items, n)),), dev)
+    check(load().lgcn_eval_topk_ex(tp(E), n_users, m_items, d, tp(users32), n, tp(train_ptr), tp(train_idx32), tp(masks),
+                                   K, tp(out_items), tp(out_scores), n * K, EVAL_FP32 if fp32 else 0, current_stream()),
+          "lgcn_eval_topk_ex")
+    return out_items
+
+
+def eval_metrics(topk, test_ptr, test_sorted32, ks, per_user=None, sums=None):
+    """lgcn_eval_metrics_ex, checked: topk int32 [n_eval, K] on the device, test_ptr int64 [n_eval + 1], test_sorted32 int32 (ids
+    ascending per slot), ks 1..8 cut-offs in 1..K.  Returns (per_user float64 [n_eval, 3 len(ks)], sums float64 [3 len(ks)])."""
+    import torch
+    if not torch.is_tensor(topk) or topk.dim() != 2:
+        raise ValueError("topk must be a 2-D tensor")
+    dev = topk.device
+    _want(topk, "topk", torch.int32, None)
+    if dev.type != "cuda":
+        raise ValueError("topk must be a device tensor")
+    n, K = int(topk.shape[0]), int(topk.shape[1])
+    ks = [int(k) for k in ks]
+    if not 1 <= len(ks) <= 8 or any(not 1 <= k <= K for k in ks) or not 1 <= K <= eval_kmax():
+        raise ValueError(f"1..8 cut-offs in 1..K (K={K} <= {eval_kmax()}), got {ks}")
+    _want(test_ptr, "test_ptr", torch.int64, (n + 1,), dev)
+    _want(test_sorted32, "test_sorted32", torch.int32, None, dev)
+    if per_user is None:
+        per_user = torch.empty(n, 3 * len(ks), dtype=torch.float64, device=dev)
+    if sums is None:
+        sums = torch.empty(3 * len(ks), dtype=torch.float64, device=dev)
+    _want(per_user, "per_user", torch.float64, (n, 3 * len(ks)), dev)
+    _want(sums, "sums", torch.float64, (3 * len(ks),), dev)
+    ks_h = torch.tensor(ks, dtype=torch.int32)
+    check(load().lgcn_eval_metrics_ex(tp(topk), n, K, tp(test_ptr), tp(test_sorted32), tp(ks_h), len(ks), tp(per_user), tp(sums),
+                                      current_stream()), "lgcn_eval_metrics_ex")
+    return per_user, sums
 
 
 class Graph:

@@ -52,6 +52,25 @@ template <> struct ListId<uint16_t> { static constexpr uint16_t EMPTY = 0xffffu;
 #define EVAL_SPLIT3 1          /* compact form: fp32 scores from six bf16 product planes (0: fp32 matrix instructions) */
 #endif
 #define EVAL_ID16_MAX_TILES 2047        /* 2047 * 32 + 31 < 0xffff */
+#define EVAL_KMAX_EX 256                /* lgcn_eval_topk_ex: 64 < K <= 256 take the large-K sweep */
+#define EVAL_LDS_BYTES (160 * 1024)     /* LDS of one CU */
+#ifndef EVAL_BIG_PARTS
+#define EVAL_BIG_PARTS 0                /* large-K sweep: parts per user block (0: from the grid size, see eval_topk_big) */
+#endif
+
+// LDS shape of one k_eval_topk instantiation: NW waves = 32 NW users, one list of KS slots per user, NBUF item tiles.
+// The large-K lists (KS > 64) pad each score row by 16 bytes, so the 16-byte reads of 16 lanes at one column start 4 banks
+// apart; the K <= 64 lists keep their shape.
+template <int D, int KS, typename IDT, int NW, bool SPLIT3> struct EvalShape {
+    static constexpr int RS = D + 4, RSB = D + 8, PLANE_B = 32 * RSB * 2;
+    static constexpr int TILE_F = SPLIT3 ? 3 * PLANE_B / 4 : 32 * RS;       // floats per item tile
+    static constexpr int KSP = (KS + 7) / 8 * 8;
+    static constexpr int KSPP = KS > EVAL_KMAX ? KSP + 4 : KSP;             // score row stride (floats)
+    static constexpr int USERS = 32 * NW;
+    static constexpr int lds(int nbuf) {
+        return nbuf * TILE_F * 4 + USERS * KSPP * 4 + USERS * (KS + (sizeof(IDT) == 4 ? 1 : 0)) * (int)sizeof(IDT);
+    }
+};
 
 struct EvalArgs {
     const float *E; int32_t n_users, m_items;
@@ -108,31 +127,33 @@ static __device__ __forceinline__ f32x16 mfma_bf16(const u32x4 &a, const u32x4 &
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
-template <int D, int KS, typename IDT, int WGS, int NBUF = 2, bool SPLIT3 = false, bool MASKS = false>
+template <int D, int KS, typename IDT, int WGS, int NBUF = 2, bool SPLIT3 = false, bool MASKS = false, int NW = 4>
                                                                 // KS: list slots per lane (a multiple of 4, >= K); WGS: workgroups per CU;
-                                                                // NBUF: item tile buffers in LDS (1: one more barrier per tile)
-__global__ void __launch_bounds__(256, WGS) k_eval_topk(EvalArgs a) {
+                                                                // NBUF: item tile buffers in LDS (1: one more barrier per tile); NW: waves
+__global__ void __launch_bounds__(64 * NW, WGS) k_eval_topk(EvalArgs a) {
+    constexpr int NT = 64 * NW, NU = 32 * NW;          // threads, users of the workgroup
+    static_assert(EvalShape<D, KS, IDT, NW, SPLIT3>::lds(NBUF) <= EVAL_LDS_BYTES, "lists + item tiles exceed the LDS of a CU");
     constexpr int HALF = D / 2, RS = D + 4;            // row stride of the LDS item tile (floats)
     // SPLIT3: three bf16 planes per tile, rows of D + 8 bf16 (144 bytes at d = 64: the 16-byte reads of 16 lanes at one
     // column start 36 banks apart and cover the 64 banks once)
     constexpr int RSB = D + 8, NCH = D / 16, PLANE_B = 32 * RSB * 2;
     constexpr int TILE_F = SPLIT3 ? 3 * PLANE_B / 4 : 32 * RS;
-    constexpr int LPT = 32 * D * 4 / 16 / 256;          // 16-byte pieces per thread per item tile
+    constexpr int LPT = 32 * D * 4 / 16 / NT;           // 16-byte pieces per thread per item tile
     static_assert(LPT >= 1, "tile smaller than the workgroup");
     __shared__ __attribute__((aligned(16))) float tile_lds[NBUF][TILE_F];
     // per-lane candidate lists: KS slots (slots >= K hold +inf: never the minimum, never output),
     // 16-byte aligned rows so the minimum scan is KS/4 independent ds_read_b128
     // (row stride KS floats = 80 / 128 bytes: 16 lanes' 16-byte reads start 20 / 32 banks apart and cover the 64 banks once)
     constexpr int KSP = (KS + 7) / 8 * 8, KH = KSP / 2;       // slots padded so that each of a user's two lanes scans KH of them
-    __shared__ __attribute__((aligned(16))) float list_s[128][KSP];
-    __shared__ IDT list_i[128][KS + ListId<IDT>::PAD];
+    __shared__ __attribute__((aligned(16))) float list_s[NU][EvalShape<D, KS, IDT, NW, SPLIT3>::KSPP];
+    __shared__ IDT list_i[NU][KS + ListId<IDT>::PAD];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int j = lane & 31, h = lane >> 5;
     const int K = a.K;
     const float *items = a.E + (int64_t)a.n_users * D;
 
     // ---- this lane's user: half a row in registers (B operand)
-    const int64_t slot = (int64_t)blockIdx.x * 128 + wid * 32 + j;
+    const int64_t slot = (int64_t)blockIdx.x * NU + wid * 32 + j;
     const bool have = slot < a.n_eval;
     const int32_t uid = have ? a.users[slot] : 0;
     float b[SPLIT3 ? 1 : HALF];
@@ -182,7 +203,7 @@ __global__ void __launch_bounds__(256, WGS) k_eval_topk(EvalArgs a) {
     auto load_tile = [&](int t) {
 #pragma unroll
         for (int q = 0; q < LPT; q++) {
-            const int p = tid + q * 256, r = p / (D / 4), c = p % (D / 4);
+            const int p = tid + q * NT, r = p / (D / 4), c = p % (D / 4);
             const int64_t item = (int64_t)t * 32 + r;
             pre[q] = item < a.m_items ? *reinterpret_cast<const f32x4 *>(items + item * D + c * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
         }
@@ -190,7 +211,7 @@ __global__ void __launch_bounds__(256, WGS) k_eval_topk(EvalArgs a) {
     auto store_tile = [&](int buf) {
 #pragma unroll
         for (int q = 0; q < LPT; q++) {
-            const int p = tid + q * 256, r = p / (D / 4), c = p % (D / 4);
+            const int p = tid + q * NT, r = p / (D / 4), c = p % (D / 4);
             if constexpr (SPLIT3) {                             // split once per workgroup, not once per wave
                 const Planes2 p0 = split3(pre[q].x, pre[q].y), p1 = split3(pre[q].z, pre[q].w);
                 char *dst = reinterpret_cast<char *>(tile_lds[buf]) + (r * RSB + 4 * c) * 2;
@@ -324,8 +345,23 @@ __global__ void __launch_bounds__(256, WGS) k_eval_topk(EvalArgs a) {
 #pragma unroll
                 for (int k4 = 0; k4 < KH / 4; k4++) q[k4] = *reinterpret_cast<const f32x4 *>(&list_s[ul][h * KH + 4 * k4]);
                 float m = q[0].x; int pm = 0;
+                if constexpr (KS > EVAL_KMAX) {
+                    // large K: four independent chains (one per vector component: slots 4 k4 + c), then the first slot of the
+                    // smallest -- the serial scan's answer with a quarter of its dependent chain
+                    float mc[4]; int pc[4];
 #pragma unroll
-                for (int k = 1; k < KH; k++) { const float v = q[k / 4][k % 4]; if (v < m) { m = v; pm = k; } }
+                    for (int c = 0; c < 4; c++) { mc[c] = q[0][c]; pc[c] = c; }
+#pragma unroll
+                    for (int k4 = 1; k4 < KH / 4; k4++)
+#pragma unroll
+                        for (int c = 0; c < 4; c++) { const float v = q[k4][c]; if (v < mc[c]) { mc[c] = v; pc[c] = 4 * k4 + c; } }
+                    m = mc[0]; pm = pc[0];
+#pragma unroll
+                    for (int c = 1; c < 4; c++) if (mc[c] < m || (mc[c] == m && pc[c] < pm)) { m = mc[c]; pm = pc[c]; }
+                } else {
+#pragma unroll
+                    for (int k = 1; k < KH; k++) { const float v = q[k / 4][k % 4]; if (v < m) { m = v; pm = k; } }
+                }
                 pm += h * KH;
                 const u32x2 mv = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
                 const u32x2 pv = __builtin_amdgcn_permlane32_swap((uint32_t)pm, (uint32_t)pm, false, false);
@@ -340,7 +376,43 @@ __global__ void __launch_bounds__(256, WGS) k_eval_topk(EvalArgs a) {
     }
     // ---- sort the user's list descending (ties: lower item id first)
     __syncthreads();
-    if (h == 0 && have) {
+    if constexpr (KS > EVAL_KMAX) {
+        // large K: every entry's place is the number of entries ahead of it (score, then lower id), each of the user's two
+        // lanes placing half of them -- K^2 / 2 compares per lane instead of the selection sort's K^2.  Entries of one part are
+        // distinct items, so the places are a permutation; the empty slots (a part with fewer than K items) keep their
+        // EVAL_NEG_INF, below every inserted score, and their places are filled with -1 after the entries.
+        if (have) {
+            int n_full = 0;
+            for (int k = 0; k < K; k++) n_full += list_i[ul][k] != ListId<IDT>::EMPTY;
+            for (int k = h; k < K; k += 2) {
+                const IDT raw = list_i[ul][k];
+                if (raw == ListId<IDT>::EMPTY) continue;
+                const float v = list_s[ul][k];
+                const int id = id0 + (int)raw;
+                int r = 0;
+                for (int k2 = 0; k2 < K; k2++) {
+                    const float v2 = list_s[ul][k2];
+                    r += (v2 > v || (v2 == v && id0 + (int)list_i[ul][k2] < id)) ? 1 : 0;
+                }
+                if (a.part_items) {
+                    const int64_t o = (slot * gridDim.y + blockIdx.y) * K + r;
+                    a.part_items[o] = id; a.part_scores[o] = v;
+                } else {
+                    a.out_items[slot * K + r] = id;
+                    if (a.out_scores) a.out_scores[slot * K + r] = v;
+                }
+            }
+            for (int r = n_full + h; r < K; r += 2) {
+                if (a.part_items) {
+                    const int64_t o = (slot * gridDim.y + blockIdx.y) * K + r;
+                    a.part_items[o] = -1; a.part_scores[o] = EVAL_NEG_INF * 2.0f;
+                } else {
+                    a.out_items[slot * K + r] = -1;
+                    if (a.out_scores) a.out_scores[slot * K + r] = EVAL_NEG_INF * 2.0f;
+                }
+            }
+        }
+    } else if (h == 0 && have) {
         for (int r = 0; r < K; r++) {
             float best = EVAL_NEG_INF * 2.0f; int bi = 0x7fffffff, bk = -1;
             for (int k = 0; k < K; k++) {
@@ -413,6 +485,32 @@ __global__ void __launch_bounds__(256) k_eval_metrics(MetricArgs a) {
         o[q] = right / (double)k;                         // utils.py:173-187
         o[a.n_ks + q] = len > 0 ? right / (double)len : 0.0;
         o[2 * a.n_ks + q] = dcg / idcg;                   // utils.py:190-203
+    }
+}
+
+// The same without the 64-bit hit mask (any K): running sums of hits, DCG and ideal DCG over the ranks, read out when the rank
+// reaches a cut-off.  The additions are those of k_eval_metrics in the same order, so for K <= 64 the results are bitwise its own.
+__global__ void __launch_bounds__(256) k_eval_metrics_ex(MetricArgs a, int32_t kmax) {
+    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s >= a.n_eval) return;
+    const int64_t b = a.test_ptr[s], e = a.test_ptr[s + 1];
+    const int len = (int)(e - b);
+    double right = 0.0, dcg = 0.0, idcg = 0.0;
+    double *o = a.per_user + s * 3 * a.n_ks;
+    for (int r = 0; r < kmax; r++) {
+        const int32_t id = a.topk[s * a.K + r];
+        int64_t lo = b, hi = e;
+        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a.test_idx[mid] < id) lo = mid + 1; else hi = mid; }
+        const double disc = 1.0 / log2((double)(r + 2));
+        if (lo < e && a.test_idx[lo] == id) { right += 1.0; dcg += disc; }
+        if (r < len) idcg += disc;
+        for (int q = 0; q < a.n_ks; q++) {
+            if (a.ks[q] != r + 1) continue;
+            const int k = a.ks[q];
+            o[q] = right / (double)k;                     // utils.py:173-187
+            o[a.n_ks + q] = len > 0 ? right / (double)len : 0.0;
+            o[2 * a.n_ks + q] = dcg / (idcg == 0.0 ? 1.0 : idcg);      // utils.py:190-203
+        }
     }
 }
 
@@ -578,5 +676,144 @@ extern "C" int lgcn_eval_metrics(const int32_t *topk_items, int32_t n_eval, int3
     if (n_eval > 0) hipLaunchKernelGGL(k_eval_metrics, dim3((unsigned)((n_eval + 255) / 256)), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_eval_sum, dim3(1), dim3(256), 0, st, per_user, n_eval, 3 * n_ks, sums);
     if (hipGetLastError() != hipSuccess) { lgcn_set_error("lgcn_eval_metrics: launch failed"); return 10; }
+    return 0;
+}
+
+// ---- large K (64 < K <= 256): the same sweep with longer lists and fewer users per workgroup
+//
+// One workgroup per CU (the lists alone are ~96-130 KB): KS = 128 with 4 waves (128 users), KS = 256 with 2 waves (64 users),
+// halved again where int32 ids and a wide fp32 tile would not fit; two tile buffers where they fit, else one.  The split bf16
+// product with 16-bit ids at d <= 128; int32 ids and d = 256 take the fp32 matrix instructions.
+template <int D, int KS, typename IDT, bool SPLIT3> struct BigForm {
+    template <int NW> using S = EvalShape<D, KS, IDT, NW, SPLIT3>;
+    static constexpr int NW = S<KS <= 128 ? 4 : 2>::lds(1) <= EVAL_LDS_BYTES ? (KS <= 128 ? 4 : 2)
+                            : S<KS <= 128 ? 2 : 1>::lds(1) <= EVAL_LDS_BYTES ? (KS <= 128 ? 2 : 1) : 0;
+    static_assert(NW > 0, "no large-K form fits the LDS");
+    static constexpr int NBUF = S<NW>::lds(2) <= EVAL_LDS_BYTES ? 2 : 1;
+};
+
+template <int D, int KS, typename IDT, bool SPLIT3>
+static void launch_big(const EvalArgs &a, int parts, bool mk, hipStream_t st) {
+    using F = BigForm<D, KS, IDT, SPLIT3>;
+    const dim3 grid((unsigned)((a.n_eval + 32 * F::NW - 1) / (32 * F::NW)), (unsigned)parts);
+    if (mk) hipLaunchKernelGGL((k_eval_topk<D, KS, IDT, 1, F::NBUF, SPLIT3, true, F::NW>), grid, dim3(64 * F::NW), 0, st, a);
+    else hipLaunchKernelGGL((k_eval_topk<D, KS, IDT, 1, F::NBUF, SPLIT3, false, F::NW>), grid, dim3(64 * F::NW), 0, st, a);
+}
+
+template <int D, int KS>
+static void launch_big_d(const EvalArgs &a, int parts, bool id16, bool split3, bool mk, hipStream_t st) {
+    if constexpr (D <= 128) {       // (d = 256: the six planes of both operands need more than 512 registers)
+        if (id16 && split3) { launch_big<D, KS, uint16_t, true>(a, parts, mk, st); return; }
+    }
+    if (id16) launch_big<D, KS, uint16_t, false>(a, parts, mk, st);
+    else launch_big<D, KS, int32_t, false>(a, parts, mk, st);          // int32 ids: the fp32 matrix instructions, as the generic form
+}
+
+template <int KS>
+static void launch_big_k(int32_t d, const EvalArgs &a, int parts, bool id16, bool split3, bool mk, hipStream_t st) {
+    switch (d) {
+    case 32: launch_big_d<32, KS>(a, parts, id16, split3, mk, st); break;
+    case 64: launch_big_d<64, KS>(a, parts, id16, split3, mk, st); break;
+    case 128: launch_big_d<128, KS>(a, parts, id16, split3, mk, st); break;
+    default: launch_big_d<256, KS>(a, parts, id16, split3, mk, st); break;
+    }
+}
+
+static int eval_topk_big(const float *E, int32_t n_users, int32_t m_items, int32_t d, const int32_t *users, int32_t n_eval,
+                         const int64_t *train_indptr, const int32_t *train_indices, int32_t K, int32_t *topk_items,
+                         float *topk_scores, const uint32_t *masks, void *stream, bool split3) {
+    if (d != 32 && d != 64 && d != 128 && d != 256) { lgcn_set_error("embedding dim must be 32, 64, 128 or 256"); return 3; }
+    if (n_eval == 0) return 0;
+    EvalArgs a{E, n_users, m_items, users, n_eval, train_indptr, train_indices, K, topk_items, topk_scores, nullptr, nullptr, nullptr,
+               masks, eval_mask_stride(n_eval)};
+    hipStream_t st = (hipStream_t)stream;
+    // One workgroup per CU whatever the split, so the parts trade spreading the user blocks over the 256 CUs (whole rounds of
+    // workgroups: ceil(blocks * parts / 256)) against list work that each part repeats (~K (1 + ln(items per part / K)) insertions
+    // per user and part).  The part count minimises rounds x (tiles per part + 0.53 K (1 + ln(items per part / K))), the weight
+    // fitted to the measured 1 / 2 / 4-part sweeps (Gowalla: 1 part; 300 000 items x 20 000 users: 3 parts at K = 100, 2 at
+    // K = 256).  At most 4 parts (k_eval_merge); a part covers >= 1024 items (catalogues of >= 4096), so it always holds K of them.
+    // 16-bit ids (and the split bf16 product) when a part spans at most 2047 tiles; else int32 ids.
+    const int ntiles = (m_items + 31) / 32;
+    const int64_t nu0 = K <= 128 ? 128 : 64;
+    const int64_t blocks0 = (n_eval + nu0 - 1) / nu0;
+    int parts = 1;
+    if (m_items >= 4096) {
+        if (EVAL_BIG_PARTS > 0) parts = EVAL_BIG_PARTS;
+        else {
+            double best = 0.0;
+            for (int p = 1; p <= 4; p++) {
+                const double rounds = (double)((blocks0 * p + 255) / 256);
+                const double cost = rounds * ((double)ntiles / p + 0.53 * K * (1.0 + log((double)m_items / p / K)));
+                if (p == 1 || cost < best) { best = cost; parts = p; }
+            }
+        }
+    }
+    const bool id16 = (ntiles + parts - 1) / parts + 1 <= EVAL_ID16_MAX_TILES;
+    void *tmp = nullptr;
+    bool tmp_sync = false;
+    if (parts > 1) {
+        const size_t n = (size_t)n_eval * parts * K;
+        const size_t lists = (n * (sizeof(int32_t) + sizeof(float)) + 255) & ~(size_t)255;
+        const size_t pub = EVAL_PUB_TILES > 0 ? (size_t)parts * n_eval * sizeof(float) : 0;
+        if (hipMallocAsync(&tmp, lists + pub, st) != hipSuccess) {
+            (void)hipGetLastError();
+            tmp = nullptr;
+            if (hipMalloc(&tmp, lists + pub) != hipSuccess) { lgcn_set_error("lgcn_eval_topk_ex: cannot allocate the partial lists"); return 4; }
+            tmp_sync = true;
+        }
+        a.part_items = (int32_t *)tmp; a.part_scores = (float *)((int32_t *)tmp + n);
+        if (pub) {
+            a.thr_pub = (float *)((char *)tmp + lists);
+            if (hipMemsetAsync(a.thr_pub, 0xff, pub, st) != hipSuccess) { lgcn_set_error("lgcn_eval_topk_ex: memset failed"); return 10; }
+        }
+    }
+    if (K <= 128) launch_big_k<128>(d, a, parts, id16, split3, masks != nullptr, st);
+    else launch_big_k<256>(d, a, parts, id16, split3, masks != nullptr, st);
+    if (parts > 1) {
+        hipLaunchKernelGGL(k_eval_merge, dim3((unsigned)((n_eval + 255) / 256)), dim3(256), 0, st, a, parts);
+        if (tmp_sync) { (void)hipStreamSynchronize(st); (void)hipFree(tmp); }
+        else (void)hipFreeAsync(tmp, st);
+    }
+    if (hipGetLastError() != hipSuccess) { lgcn_set_error("lgcn_eval_topk_ex: launch failed"); return 10; }
+    return 0;
+}
+
+extern "C" int32_t lgcn_eval_kmax(void) { return EVAL_KMAX_EX; }
+
+extern "C" int lgcn_eval_topk_ex(const float *E, int32_t n_users, int32_t m_items, int32_t d, const int32_t *users, int32_t n_eval,
+                                 const int64_t *train_indptr, const int32_t *train_indices, const uint32_t *masks,
+                                 int32_t K, int32_t *topk_items, float *topk_scores, int64_t out_capacity,
+                                 int32_t flags, void *stream) {
+    if (!E || !users || !train_indptr || !train_indices || !topk_items || n_users <= 0 || m_items <= 0 || n_eval < 0 || (flags & ~LGCN_EVAL_FP32)) {
+        lgcn_set_error("lgcn_eval_topk_ex: invalid argument"); return 3;
+    }
+    if (K < 1 || K > EVAL_KMAX_EX || K > m_items) { lgcn_set_error("lgcn_eval_topk_ex: K must be in 1..lgcn_eval_kmax() and <= m_items"); return 3; }
+    if (out_capacity < 0 || (int64_t)n_eval * K > out_capacity) { lgcn_set_error("lgcn_eval_topk_ex: output buffers hold fewer than n_eval * K elements"); return 3; }
+    const bool split3 = EVAL_SPLIT3 != 0 && !(flags & LGCN_EVAL_FP32);
+    if (K <= EVAL_KMAX)        // the K <= 64 sweep itself: bitwise lgcn_eval_topk_masked / lgcn_eval_topk_fp32
+        return eval_topk(E, n_users, m_items, d, users, n_eval, train_indptr, train_indices, K, topk_items, topk_scores, masks, stream, split3);
+    return eval_topk_big(E, n_users, m_items, d, users, n_eval, train_indptr, train_indices, K, topk_items, topk_scores, masks, stream, split3);
+}
+
+extern "C" int lgcn_eval_metrics_ex(const int32_t *topk_items, int32_t n_eval, int32_t K,
+                                    const int64_t *test_indptr, const int32_t *test_items_sorted,
+                                    const int32_t *ks, int32_t n_ks, double *per_user, double *sums, void *stream) {
+    if (!topk_items || !test_indptr || !test_items_sorted || !ks || !per_user || !sums || n_eval < 0) {
+        lgcn_set_error("lgcn_eval_metrics_ex: invalid argument"); return 3;
+    }
+    if (n_ks < 1 || n_ks > 8 || K < 1 || K > EVAL_KMAX_EX) { lgcn_set_error("lgcn_eval_metrics_ex: 1..8 cut-offs, K <= lgcn_eval_kmax()"); return 3; }
+    MetricArgs a{};
+    a.topk = topk_items; a.n_eval = n_eval; a.K = K; a.test_ptr = test_indptr; a.test_idx = test_items_sorted;
+    a.n_ks = n_ks; a.per_user = per_user;
+    int32_t kmax = 0;
+    for (int q = 0; q < n_ks; q++) {
+        if (ks[q] < 1 || ks[q] > K) { lgcn_set_error("lgcn_eval_metrics_ex: a cut-off exceeds K"); return 3; }
+        a.ks[q] = ks[q];
+        kmax = ks[q] > kmax ? ks[q] : kmax;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (n_eval > 0) hipLaunchKernelGGL(k_eval_metrics_ex, dim3((unsigned)((n_eval + 255) / 256)), dim3(256), 0, st, a, kmax);
+    hipLaunchKernelGGL(k_eval_sum, dim3(1), dim3(256), 0, st, per_user, n_eval, 3 * n_ks, sums);
+    if (hipGetLastError() != hipSuccess) { lgcn_set_error("lgcn_eval_metrics_ex: launch failed"); return 10; }
     return 0;
 }

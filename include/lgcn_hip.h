@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define LGCN_ABI_VERSION 11
+#define LGCN_ABI_VERSION 12
 #define LGCN_MAX_LAYERS 8
 
 /* storage type of propagated activations (accumulation is always fp32) */
@@ -352,6 +352,27 @@ int lgcn_eval_topk_fp32(const float *E, int32_t n_users, int32_t m_items, int32_
 int lgcn_eval_metrics(const int32_t *topk_items, int32_t n_eval, int32_t K,
                       const int64_t *test_indptr, const int32_t *test_items_sorted,
                       const int32_t *ks, int32_t n_ks, double *per_user, double *sums, void *stream);
+/* Evaluation past K = 64 (the entry points above keep their 1..64 contract).  lgcn_eval_kmax: the largest K the _ex forms
+ * take (256; a larger max(topks) stays with the caller's own ranking).  lgcn_eval_topk_ex ranks as lgcn_eval_topk_masked
+ * (same semantics, same tie caveat; a user with fewer than K items that are not train positives gets train positives at -(1<<10)
+ * in the tail): 1 <= K <= lgcn_eval_kmax(), K <= m_items; topk_items and topk_scores (or NULL) are [n_eval, K] contiguous and
+ * out_capacity is the number of elements each of them holds -- rc 3, and nothing launched, if n_eval * K > out_capacity.
+ * masks: as lgcn_eval_topk_masked, or NULL (the cursor over the train CSR).  flags: LGCN_EVAL_FP32 = every score from the fp32
+ * matrix instructions (the cross-check, as lgcn_eval_topk_fp32), else the split bf16 product where the sweep supports it.
+ * K <= 64 runs the very sweep of lgcn_eval_topk_masked / lgcn_eval_topk_fp32 (bitwise the same output); 64 < K <= 256 a
+ * sweep with 128- or 256-slot lists and 128 or 64 users per workgroup.
+ * lgcn_eval_metrics_ex: lgcn_eval_metrics for K <= lgcn_eval_kmax() (cut-offs in any order), same outputs; for K <= 64
+ * bitwise those of lgcn_eval_metrics.                                                                                 */
+#define LGCN_EVAL_FP32 1
+int32_t lgcn_eval_kmax(void);
+int lgcn_eval_topk_ex(const float *E, int32_t n_users, int32_t m_items, int32_t d,
+                      const int32_t *users, int32_t n_eval,
+                      const int64_t *train_indptr, const int32_t *train_indices, const uint32_t *masks,
+                      int32_t K, int32_t *topk_items, float *topk_scores, int64_t out_capacity,
+                      int32_t flags, void *stream);
+int lgcn_eval_metrics_ex(const int32_t *topk_items, int32_t n_eval, int32_t K,
+                         const int64_t *test_indptr, const int32_t *test_items_sorted,
+                         const int32_t *ks, int32_t n_ks, double *per_user, double *sums, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* Data parallel over RCCL (no counterpart in the reference: SURVEY 2, north_star) */
