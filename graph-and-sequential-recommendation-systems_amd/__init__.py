@@ -13,6 +13,7 @@ include/lgcn_hip.h (hand-written gfx950 kernels in csrc/).
     sampling                   the pybind11 `sampling` plugin's four functions
     parallel                   batch-sharded data parallel step over RCCL
     reorder                    locality ordering of graph rows for the SpMM kernels
+    preprocess_instacart_i2i   build_item_item: the item-item graph, built on the GPU
 
 The directory name contains '-', so import it with
     importlib.import_module("graph-and-sequential-recommendation-systems_amd")
@@ -22,7 +23,7 @@ exactly like the reference's world.py.
 import importlib as _importlib
 
 __all__ = ["build", "_lib", "world", "parse", "register", "dataloader", "model", "utils",
-           "Procedure", "sampling", "parallel", "reorder", "synthetic"]
+           "Procedure", "sampling", "parallel", "reorder", "synthetic", "preprocess_instacart_i2i"]
 
 
 def __getattr__(name):

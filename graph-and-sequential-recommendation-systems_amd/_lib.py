@@ -9,7 +9,7 @@ import os
 from . import build as _build
 
 F32, BF16, FP8 = 0, 1, 2
-ABI_VERSION = 12
+ABI_VERSION = 13
 MAX_LAYERS = 8
 
 _c_i32p = C.POINTER(C.c_int32)
@@ -99,6 +99,8 @@ SIGNATURES = {
     "lgcn_eval_topk_ex": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, _vp,
                                     C.c_int64, C.c_int32, _vp]),
     "lgcn_eval_metrics_ex": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp]),
+    "lgcn_i2i_topk": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
+    "lgcn_i2i_finish": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp, C.POINTER(C.c_int64), _vp]),
     "lgcn_dp_available": (C.c_int, []),
     "lgcn_dp_unique_id": (C.c_int, [_vp]),
     "lgcn_dp_init": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(_vp)]),
@@ -272,6 +274,85 @@ def eval_metrics(topk, test_ptr, test_sorted32, ks, per_user=None, sums=None):
     check(load().lgcn_eval_metrics_ex(tp(topk), n, K, tp(test_ptr), tp(test_sorted32), tp(ks_h), len(ks), tp(per_user), tp(sums),
                                       current_stream()), "lgcn_eval_metrics_ex")
     return per_user, sums
+
+
+I2I_WEIGHTS = {"cooc": 0, "jaccard": 1, "pmi": 2}       # LGCN_I2I_COOC / _JACCARD / _PMI
+I2I_TOPK_MAX = 256
+
+
+def _i2i_sizes(m_items, topk):
+    m_items, topk = int(m_items), int(topk)
+    if m_items <= 0:
+        raise ValueError(f"m_items={m_items} must be positive")
+    if not 1 <= topk <= I2I_TOPK_MAX:
+        raise ValueError(f"topk={topk} must be in 1..{I2I_TOPK_MAX}")
+    if 2 * m_items * topk >= 2 ** 31 - 16:
+        raise ValueError(f"2 * m_items * topk = {2 * m_items * topk} must stay below 2^31")
+    return m_items, topk
+
+
+def i2i_topk(indptr, indices, m_items, topk=50, weight="cooc", min_basket=1, cols=None, w=None, length=None):
+    """lgcn_i2i_topk, checked: baskets as a device CSR (indptr int64 [n_baskets + 1], indices int32 [nnz], items distinct within
+    a basket) -> (cols int32 [m_items, topk] in rank order padded with -1, w fp32 [m_items, topk], len int32 [m_items]).
+    Everything the host can see is validated before anything is launched (ValueError); an id outside [0, m_items) is found on
+    the device (LgcnError, outputs untouched)."""
+    import torch
+    m_items, topk = _i2i_sizes(m_items, topk)
+    if weight not in I2I_WEIGHTS:
+        raise ValueError(f"weight must be one of {sorted(I2I_WEIGHTS)}, got {weight!r}")
+    min_basket = int(min_basket)
+    if min_basket < 0:
+        raise ValueError(f"min_basket={min_basket} must be >= 0")
+    _want(indptr, "indptr", torch.int64, None)
+    if indptr.dim() != 1 or indptr.numel() < 2 or indptr.device.type != "cuda":
+        raise ValueError("indptr must be a 1-D device tensor of n_baskets + 1 >= 2 offsets")
+    dev = indptr.device
+    _want(indices, "indices", torch.int32, None, dev)
+    if indices.dim() != 1 or indices.numel() == 0:
+        raise ValueError("indices must be a non-empty 1-D tensor")
+    n_baskets, nnz = int(indptr.numel()) - 1, int(indices.numel())
+    if cols is None:
+        cols = torch.empty(m_items, topk, dtype=torch.int32, device=dev)
+    if w is None:
+        w = torch.empty(m_items, topk, dtype=torch.float32, device=dev)
+    if length is None:
+        length = torch.empty(m_items, dtype=torch.int32, device=dev)
+    _want(cols, "cols", torch.int32, (m_items, topk), dev)
+    _want(w, "w", torch.float32, (m_items, topk), dev)
+    _want(length, "length", torch.int32, (m_items,), dev)
+    check(load().lgcn_i2i_topk(tp(indptr), tp(indices), n_baskets, nnz, m_items, topk, I2I_WEIGHTS[weight], min_basket,
+                               tp(cols), tp(w), tp(length), current_stream()), "lgcn_i2i_topk")
+    return cols, w, length
+
+
+def i2i_finish(cols, w, length, capacity=None, indptr=None, indices=None, vals=None):
+    """lgcn_i2i_finish, checked: the three arrays of i2i_topk -> (indptr int32 [m_items + 1], indices int32 [capacity],
+    vals fp32 [capacity], nnz): symmetrised by maximum, D^-1/2 A D^-1/2, columns ascending.  capacity (default
+    2 * m_items * topk, always enough) must be at least 2 * sum(len): checked on the device (LgcnError, outputs untouched)."""
+    import torch
+    if not torch.is_tensor(cols) or cols.dim() != 2 or cols.device.type != "cuda":
+        raise ValueError("cols must be a 2-D device tensor [m_items, topk]")
+    dev = cols.device
+    m_items, topk = _i2i_sizes(cols.shape[0], cols.shape[1])
+    _want(cols, "cols", torch.int32, None)
+    _want(w, "w", torch.float32, (m_items, topk), dev)
+    _want(length, "length", torch.int32, (m_items,), dev)
+    capacity = 2 * m_items * topk if capacity is None else int(capacity)
+    if capacity <= 0:
+        raise ValueError(f"capacity={capacity} must be positive")
+    if indptr is None:
+        indptr = torch.empty(m_items + 1, dtype=torch.int32, device=dev)
+    if indices is None:
+        indices = torch.empty(capacity, dtype=torch.int32, device=dev)
+    if vals is None:
+        vals = torch.empty(capacity, dtype=torch.float32, device=dev)
+    _want(indptr, "indptr", torch.int32, (m_items + 1,), dev)
+    _want(indices, "indices", torch.int32, (capacity,), dev)
+    _want(vals, "vals", torch.float32, (capacity,), dev)
+    nnz = C.c_int64(-1)
+    check(load().lgcn_i2i_finish(tp(cols), tp(w), tp(length), m_items, topk, capacity, tp(indptr), tp(indices), tp(vals),
+                                 C.byref(nnz), current_stream()), "lgcn_i2i_finish")
+    return indptr, indices, vals, int(nnz.value)
 
 
 class Graph:

@@ -130,6 +130,17 @@ class LightGCN(nn.Module):
                 world.cprint(f"[I2I] loaded {config['i2i_path']}, nnz={m.nnz}")
             except Exception as e:      # noqa: BLE001 -- the reference warns and goes on without it
                 world.cprint(f"[I2I] WARNING: cannot load {config['i2i_path']}: {e}")
+        elif self.use_item_item and config.get('i2i_build', 'none') not in (None, 'none'):
+            # NEW: no file given -- the graph the reference's preprocess_instacart_i2i.py would have written, built on the GPU
+            # from the train baskets (one per user with train items, in user order).  A failure here is an error, not a warning.
+            from . import preprocess_instacart_i2i as i2i
+            r = dataset.UserItemNet.tocsr()
+            sizes = np.diff(r.indptr)
+            keep = sizes > 0
+            indptr = np.concatenate([[0], np.cumsum(sizes[keep])]).astype(np.int64)
+            self._i2i = i2i.build_from_csr(indptr, r.indices, self.m_items, topk=int(config.get('i2i_topk', 50)),
+                                           weight=config['i2i_build'], min_basket=int(config.get('i2i_min_basket', 1)))
+            world.cprint(f"[I2I] built {config['i2i_build']} topk={int(config.get('i2i_topk', 50))} on the GPU, nnz={self._i2i.nnz}")
 
         self._adj = dataset.getSparseGraphCSR() if hasattr(dataset, 'getSparseGraphCSR') else None
         if self._adj is None:                       # generic BasicDataset: COO -> CSR

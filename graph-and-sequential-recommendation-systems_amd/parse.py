@@ -93,6 +93,13 @@ def build_parser():
                    help="NEW: rows the L2 term of bpr_loss is taken on. 'propagated' (default) = this reference (model.py:173: the "
                         "propagated rows of the batch); 'ego' = upstream LightGCN (userEmb0 / posEmb0 / negEmb0, the embedding "
                         "tables' own rows) -- the loss behind the recorded 1000-epoch run and the README table the reference keeps")
+    p.add_argument('--i2i_build', type=str, default='none', choices=['none', 'cooc', 'jaccard', 'pmi'],
+                   help='NEW: with --use_item_item and no --i2i_path, build the item-item graph from the train baskets on the GPU '
+                        '(preprocess_instacart_i2i.build_item_item with this weighting); none (default) = as the reference: no '
+                        'file, no item-item branch. One basket per user with train items, in user order: the graph of the module\'s '
+                        'CLI (one basket per line of train.txt) whenever every user is one line')
+    p.add_argument('--i2i_topk', type=int, default=50, help='NEW: neighbours kept per item by --i2i_build (1..256)')
+    p.add_argument('--i2i_min_basket', type=int, default=1, help='NEW: --i2i_build skips baskets with fewer items')
     p.add_argument('--data_path', type=str, default=None,
                    help='NEW: directory that holds <dataset>/train.txt (default: <root>/data)')
     return p

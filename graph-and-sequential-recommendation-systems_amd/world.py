@@ -107,6 +107,9 @@ def configure(argv=None):
     config['dense_last'] = args.dense_last
     config['hub_nnz'] = args.hub_nnz
     config['fused_variants'] = args.fused_variants
+    config['i2i_build'] = args.i2i_build
+    config['i2i_topk'] = args.i2i_topk
+    config['i2i_min_basket'] = args.i2i_min_basket
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     return config
 

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define LGCN_ABI_VERSION 12
+#define LGCN_ABI_VERSION 13
 #define LGCN_MAX_LAYERS 8
 
 /* storage type of propagated activations (accumulation is always fp32) */
@@ -373,6 +373,39 @@ int lgcn_eval_topk_ex(const float *E, int32_t n_users, int32_t m_items, int32_t 
 int lgcn_eval_metrics_ex(const int32_t *topk_items, int32_t n_eval, int32_t K,
                          const int64_t *test_indptr, const int32_t *test_items_sorted,
                          const int32_t *ks, int32_t n_ks, double *per_user, double *sums, void *stream);
+
+/* ------------------------------------------------------------------------ */
+/* Item-item co-occurrence graph (preprocess_instacart_i2i.py:61-170)         */
+/* ------------------------------------------------------------------------ */
+/* build_item_item on the device, in two stages.  UNLIKE the entry points above these two own their
+ * temporaries (stream-ordered allocations) and synchronise `stream` ONCE, at the end, to read the device's verdict; every
+ * kernel that writes an output reads that verdict first, so a refused call leaves all outputs as they were.  All pointers
+ * are device pointers except nnz_out.
+ * The first stage (topk): baskets as a CSR (indptr[n_baskets + 1] with indptr[n_baskets] == nnz, indices[nnz]; the items of
+ * a basket DISTINCT, in any order); baskets are numbered in input order, one with fewer than min_basket items is skipped.
+ * c[i][j] = kept baskets holding both, deg[i] = kept baskets holding i, total = kept baskets (1.0 if none); weight in fp64:
+ * LGCN_I2I_COOC c | LGCN_I2I_JACCARD c / (deg_i + deg_j - c) (0 if that is <= 0) | LGCN_I2I_PMI max(log(c total / (deg_i
+ * deg_j) + 1e-12), 0).  Per item the topk best by (weight descending, first kept basket holding both ascending, j ascending)
+ * -- the order heapq.nlargest leaves the reference's dict in -- in RANK order: cols [m_items, topk] padded with -1,
+ * w [m_items, topk] = (float)weight padded with 0, len [m_items].  Bitwise reproducible.
+ *   rc 3  topk outside 1..256, unknown weight, min_basket < 0, n_baskets / nnz / m_items <= 0 (or above 0x7f000000),
+ *         2 m_items topk >= 2^31, a null pointer: nothing launched
+ *   rc 4  the temporaries cannot be allocated from the stream-ordered pool: nothing launched
+ *   rc 5  an item id outside [0, m_items)      } found on the device before anything is counted;
+ *   rc 6  indptr not ascending from 0 to nnz   } cols / w / len untouched
+ *   rc 10 a runtime call failed
+ * The second stage (finish): entry (i, j) exists if j is in i's list or i in j's (weight = the maximum; weights <= 0 are
+ * not stored), deg = fp32 row sum (0 -> 1), value = (v * deg_i^-1/2) * deg_j^-1/2 in fp32 -> CSR with ascending columns:
+ * indptr [m_items + 1], indices / vals [capacity], *nnz_out (HOST) = entries written.  cols of a row must be distinct.
+ *   rc 3  topk outside 1..256, m_items <= 0, capacity <= 0, 2 m_items topk >= 2^31, a null pointer: nothing launched
+ *   rc 4  the temporaries cannot be allocated from the stream-ordered pool: nothing launched
+ *   rc 7  capacity < 2 * sum(len) (summed on the device): indptr / indices / vals / *nnz_out untouched
+ *   rc 10 a runtime call failed                                                                                        */
+enum { LGCN_I2I_COOC = 0, LGCN_I2I_JACCARD = 1, LGCN_I2I_PMI = 2 };
+int lgcn_i2i_topk(const int64_t *indptr, const int32_t *indices, int64_t n_baskets, int64_t nnz, int32_t m_items,
+                  int32_t topk, int32_t weight, int32_t min_basket, int32_t *cols, float *w, int32_t *len, void *stream);
+int lgcn_i2i_finish(const int32_t *cols, const float *w, const int32_t *len, int32_t m_items, int32_t topk, int64_t capacity,
+                    int32_t *indptr, int32_t *indices, float *vals, int64_t *nnz_out, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* Data parallel over RCCL (no counterpart in the reference: SURVEY 2, north_star) */
