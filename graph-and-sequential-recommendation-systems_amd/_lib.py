@@ -115,6 +115,9 @@ SIGNATURES = {
     "lgcn_train_epoch_dp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "lgcn_rs_phase": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     "lgcn_rs_buffer": (C.c_int, [_vp, C.c_int32, C.c_int32, C.POINTER(_vp), C.POINTER(C.c_int32)]),
+    "lgcn_ctx_set_dropout": (C.c_int, [_vp, C.c_float, C.c_uint64]),
+    "lgcn_dropout_mask": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_float, C.c_uint64, C.c_int64, _vp, _vp]),
+    "lgcn_spmm_csr_drop": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int64, C.c_int, _vp]),
 }
 
 _LIB = None
@@ -435,6 +438,32 @@ class Graph:
         else:
             y = torch.empty(x.shape, dtype=torch.bfloat16 if yd == BF16 else torch.float32, device=x.device)
         check(load().lgcn_spmm_csr(self.handle, tp(x), xd, tp(y), yd, int(x.shape[1]), current_stream()), "lgcn_spmm_csr")
+        return y
+
+    def dropout_mask(self, keep_prob, seed, step):
+        """lgcn_dropout_mask on this graph's CSR: uint8 [nnz], 1 where the entry at that CSR position is kept in step `step`."""
+        import torch
+        out = torch.empty(max(self.nnz, 1), dtype=torch.uint8, device=self.indptr.device)
+        check(load().lgcn_dropout_mask(tp(self.indptr), tp(self.indices), self.n_rows, self.nnz, float(keep_prob),
+                                       int(seed) & (2 ** 64 - 1), int(step), tp(out), current_stream()), "lgcn_dropout_mask")
+        return out[:self.nnz]
+
+    def spmm_drop(self, x, keep_prob, seed, step, transposed=False, y_dtype=None):
+        """lgcn_spmm_csr_drop: A_drop @ x (or A_drop^T @ x) with the edge-dropout mask of (seed, step); x fp32 or bf16."""
+        import torch
+        if x.dim() != 2 or x.shape[0] != self.n_rows or x.shape[1] not in (32, 64, 128, 256) or x.shape[1] > self.d_max:
+            raise LgcnError(f"Graph.spmm_drop: x must be [{self.n_rows}, d] with d in (32,64,128,256) and d <= d_max={self.d_max}; "
+                            f"got {tuple(x.shape)}")
+        if x.device != self.indptr.device:
+            raise LgcnError("Graph.spmm_drop: x is not on the graph's device")
+        x = x.contiguous()
+        xd = BF16 if x.dtype == torch.bfloat16 else F32
+        if xd == F32:
+            x = x.float()
+        yd = xd if y_dtype is None else y_dtype
+        y = torch.empty(x.shape, dtype=torch.bfloat16 if yd == BF16 else torch.float32, device=x.device)
+        check(load().lgcn_spmm_csr_drop(self.handle, tp(x), xd, tp(y), yd, int(x.shape[1]), float(keep_prob), int(seed) & (2 ** 64 - 1),
+                                        int(step), 1 if transposed else 0, current_stream()), "lgcn_spmm_csr_drop")
         return y
 
     def close(self):

@@ -196,11 +196,38 @@ template <int C> __device__ __forceinline__ typename VecF<C>::T loadv_fixed(cons
     return r;
 }
 
+// ---------------------------------------------------------------------------------
+// Edge dropout of one training step (upstream LightGCN's __dropout_x): every stored non-zero (i, j) of A_hat is
+// kept when  H(seed, step, i, j) < thr = floor(keep_prob * 2^32)  and the survivors are scaled by 1 / keep_prob.  H is a
+// counter-based hash of the adjacency's own row and column ids and of nothing else -- not of where the entry lies in the CSR
+// arrays, the plan's packed stream or the launch -- so every kernel that meets the entry decides alike:
+//     (k0, k1) = low / high word of  splitmix64(splitmix64(seed) + step)        (host, once per step)
+//     H        = fmix32( fmix32(i ^ k0) ^ (j * 0x9E3779B1) ^ k1 )               (fmix32: MurmurHash3's 32-bit finaliser)
+// 32-bit multiplies, shifts and xors on the VALU (about two dozen instructions per staged entry, five of them multiplies), no table, no LDS.  The mask is applied
+// where an entry is STAGED (tile_stage's callers, the pack path of k_spmm): its weight becomes val * (1 / keep_prob) or zero;
+// gather loops, epilogues and the chunk hand-off never see it.  tr: the launch computes A_drop^T h (backward), where the
+// entry stored at (row, col) stands for A_drop[col, row] and carries keep(col, row).
+// ---------------------------------------------------------------------------------
+struct DropArgs { uint32_t k0, k1, thr; float inv; int32_t tr; int32_t on; };
+__host__ __device__ __forceinline__ uint32_t drop_fmix32(uint32_t h) {
+    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+    return h;
+}
+__host__ __device__ __forceinline__ uint32_t drop_hash(uint32_t k0, uint32_t k1, uint32_t i, uint32_t j) {
+    return drop_fmix32(drop_fmix32(i ^ k0) ^ (j * 0x9E3779B1u) ^ k1);
+}
+// is the entry the launch reads at (row, col) of the stored matrix alive this step?
+__device__ __forceinline__ bool drop_live(const DropArgs &d, int row, int col) {
+    const uint32_t i = (uint32_t)(d.tr ? col : row), j = (uint32_t)(d.tr ? row : col);
+    return drop_hash(d.k0, d.k1, i, j) < d.thr;
+}
+
 struct GatherSrc {           // what a row gather reads
     const float *S;          // fp8 table: its row scales (an entry's weight is multiplied by S[col] when it is staged), else NULL
     const void *X;           // [N,D] of TI; SPARSE: the fp32 copy of the flagged gradient rows (k_g32)
     const uint32_t *bm;      // SPARSE: non-zero-row bitmap (global, or the workgroup's LDS copy)
     float div;               // unused by the gathers (K+1; the epilogues take it from SpmmArgs)
+    DropArgs dr;             // DROP instantiations only: the step's edge-dropout mask
 };
 
 // Raw (unconverted) piece of a gathered row: 16 bytes per lane for fp32 AND bf16 tables (4 / 8
@@ -277,13 +304,15 @@ template <int D, typename TI, bool SPARSE> struct Geo {
 #define TILE_PAD 64           /* >= 4 * NPW of every geometry (d = 32 with a bf16 table: NPW = 16) */
 #define TILE_ST (64 + TILE_PAD)
 __device__ __forceinline__ void tile_pad_init(int2 *stage, int lane) { stage[64 + lane] = make_int2(0, 0); }
+// live: edge dropout kept the entry (its weight is already scaled; a dropped entry's is zero).  SPARSE treats a dropped
+// entry as unflagged, so the compaction skips its gather; the dense form stages it with its zero weight.
 template <bool SPARSE>
-__device__ __forceinline__ int tile_stage(int col, float val, int n, const GatherSrc &src, int lane, int2 *stage) {
+__device__ __forceinline__ int tile_stage(int col, float val, int n, const GatherSrc &src, int lane, int2 *stage, bool live = true) {
     if (!SPARSE) {
         stage[lane] = lane < n ? make_int2(col, __float_as_int(val)) : make_int2(0, 0);
         return n;
     }
-    const bool act = (lane < n) && bit_set(src.bm, col);
+    const bool act = (lane < n) && live && bit_set(src.bm, col);
     const unsigned long long mask = __ballot(act);
     const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
     const int cnt = __popcll(mask);
@@ -370,9 +399,17 @@ struct PackedSrc {
     __device__ __forceinline__ int2 at(int64_t i) const { return pk[i]; }
 };
 
-template <int D, typename TI, bool SPARSE, bool BIG, typename ES>
+// the staged weight of an entry of row `row` under edge dropout: val / keep_prob (as val * inv) or zero; returns whether it lives
+__device__ __forceinline__ bool drop_apply(const DropArgs &d, int row, int2 &cv) {
+    const bool live = drop_live(d, row, cv.x);
+    cv.y = live ? __float_as_int(__int_as_float(cv.y) * d.inv) : 0;
+    return live;
+}
+
+// DROP: edge dropout is on (src.dr); `row` is the id of the row the segment belongs to (unused otherwise)
+template <int D, typename TI, bool SPARSE, bool BIG, bool DROP = false, typename ES>
 __device__ __forceinline__ typename Geo<D, TI, SPARSE>::Acc
-row_gather(const ES &es, int64_t start, int64_t end, const GatherSrc &src, int lane, int2 *stage) {
+row_gather(const ES &es, int64_t start, int64_t end, const GatherSrc &src, int lane, int2 *stage, int row = 0) {
     typedef Geo<D, TI, SPARSE> G;
     typename G::Acc acc = zerov<G::CPL>();
     tile_pad_init(stage, lane);
@@ -382,7 +419,9 @@ row_gather(const ES &es, int64_t start, int64_t end, const GatherSrc &src, int l
     for (int64_t base = start; base < end; base += 64) {
         const int n = (int)min((int64_t)64, end - base);
         if (!SPARSE && src.S) cv.y = __float_as_int(__int_as_float(cv.y) * src.S[cv.x]);     // fp8 table: weight x row scale of the column
-        const int cnt = tile_stage<SPARSE>(cv.x, __int_as_float(cv.y), n, src, lane, stage);
+        bool live = true;
+        if constexpr (DROP) live = drop_apply(src.dr, row, cv);
+        const int cnt = tile_stage<SPARSE>(cv.x, __int_as_float(cv.y), n, src, lane, stage, live);
         __builtin_amdgcn_wave_barrier();
         cv = make_int2(0, 0);
         if (base + 64 + lane < end) cv = es.at(base + 64 + lane);
@@ -465,6 +504,7 @@ struct SpmmArgs {
     int remap;
     const float *selfX;           // M_ADDSELF: Y[row] = selfX[row] + (A X)[row]  (item-item smoothing, model.py:228-229)
     int32_t *cnt; float lam;      // reg_ego: slots of the batch naming each row (zeroed as consumed), decay / B: grad += lam * cnt[row] * P[row]
+    DropArgs dr;                  // edge dropout of the step (dr.on: the DROP instantiation is launched); last, so that every other field keeps its offset
 };
 
 enum { M_SPARSE = 1, M_ADDG = 2, M_ADAM = 4, M_ADDSELF = 8 };
@@ -670,8 +710,9 @@ template <int LPR, int GPR> __device__ __forceinline__ float sum_row_groups(floa
     return v;
 }
 
-template <int D, typename TI, typename TO, int MODE, bool BIG>
+template <int D, typename TI, typename TO, int MODE, bool BIG, bool DROP = false>
 // (fp8 tables: 16 accumulators per lane and, with Adam, 3 x 16 operands: a 128-register budget, 4 waves per SIMD)
+// DROP: edge dropout (a.dr) -- a compile-time axis, so that the instantiations without it are what they were
 __global__ void __launch_bounds__(64 * SPMM_WPB, sizeof(TI) == 1 ? 4 : ((MODE & M_ADAM) && sizeof(TI) == 4) ? SPMM_MIN_WAVES_ADAM : SPMM_MIN_WAVES) k_spmm(SpmmArgs a) {
     constexpr bool SP = (MODE & M_SPARSE) != 0;
     typedef Geo<D, TI, SP> G;
@@ -694,6 +735,7 @@ __global__ void __launch_bounds__(64 * SPMM_WPB, sizeof(TI) == 1 ? 4 : ((MODE & 
     GatherSrc src;
     src.X = SP ? (const void *)a.G32 : a.X; src.bm = a.bitmap; src.div = a.div;
     src.S = (!SP && sizeof(TI) == 1) ? fp8_scales(a.X, a.n_rows, D) : nullptr;
+    if constexpr (DROP) src.dr = a.dr;
     // (a per-workgroup LDS copy of the row bitmap -- 9 KiB on Gowalla -- was measured: no gain, the copy's
     //  own round trip per workgroup costs what the per-neighbour tests save once a pack's tests are batched)
     // (block 0 is dispatched first: the reduction overlaps the whole launch; on the last block it
@@ -732,7 +774,7 @@ __global__ void __launch_bounds__(64 * SPMM_WPB, sizeof(TI) == 1 ? 4 : ((MODE & 
         const int nch = a.lp.long_nch[o];
         const bool rflag = (MODE & M_ADDG) ? bit_set(a.bitmap, (int)row) : false;
 #endif
-        Acc acc = row_gather<D, TI, SP, BIG>(PackedSrc{a.pk}, ch.y, ch.z, src, lane, stage_lds[wid]);
+        Acc acc = row_gather<D, TI, SP, BIG, DROP>(PackedSrc{a.pk}, ch.y, ch.z, src, lane, stage_lds[wid], (int)row);
         if (nch == 1) {                                   // LONG_T < nnz <= LONG_CH: one wave, no hand-off
             if (lane < LPR) spmm_epilogue<D, TO, MODE, C, IL>(a, row, lane, acc, rflag);
             return;
@@ -837,6 +879,30 @@ __global__ void __launch_bounds__(64 * SPMM_WPB, sizeof(TI) == 1 ? 4 : ((MODE & 
             for (int it = 0; it < RPK; it++)
                 if (it * 64 < tot) cvr[it].y = __float_as_int(__int_as_float(cvr[it].y) * src.S[cvr[it].x]);
         }
+        // edge dropout: a lane learns the row of the entry it stages from the pack's prefix `off` (scalar registers), scales the
+        // weight of a kept entry and zeroes a dropped one; the sparse form below also leaves a dropped entry out of its compaction
+        bool live[RPK];
+#pragma unroll
+        for (int it = 0; it < RPK; it++) live[it] = true;
+        if constexpr (DROP) {
+#pragma unroll
+            for (int it = 0; it < RPK; it++) {
+                if (it * 64 < tot) {
+                    const int e = it * 64 + lane;
+#if SPMM_SCALAR_ROWINFO
+                    int rid = row_s[0];
+#pragma unroll
+                    for (int k = 1; k < RPK; k++) rid = (e >= off[k]) ? row_s[k] : rid;
+#else
+                    int r = 0;
+#pragma unroll
+                    for (int k = 1; k < RPK; k++) r += (e >= off[k]) ? 1 : 0;
+                    const int rid = __shfl(my_row, r);
+#endif
+                    live[it] = drop_apply(src.dr, rid, cvr[it]);
+                }
+            }
+        }
         if (!SP) {
 #pragma unroll
             for (int it = 0; it < RPK; it++) {
@@ -873,7 +939,7 @@ __global__ void __launch_bounds__(64 * SPMM_WPB, sizeof(TI) == 1 ? 4 : ((MODE & 
             for (int it = 0; it < RPK; it++) {
                 if (it * 64 < tot) {
                     const int e = it * 64 + lane;
-                    const bool flag = e < tot && ((w[it] >> (cvr[it].x & 31)) & 1u);
+                    const bool flag = e < tot && live[it] && ((w[it] >> (cvr[it].x & 31)) & 1u);
                     const unsigned long long m = __ballot(flag);
                     int r = 0, o_r = 0, before = cntr[0];
 #pragma unroll
@@ -1053,6 +1119,7 @@ struct BprArgs {
     // the slot rows -- it writes them to erows [3][B_local][D] and the PARTIAL dot products / squared norms over its columns to
     // colsum [3][B_local] (pos score, neg score, reg term); the ranks all-reduce colsum; k_cols_finish does the rest.
     int32_t cols_phase; float *erows; float *colsum;
+    DropArgs dr;          // edge dropout of the step (dr.on: k_triplet's DROP instantiation gathers the last layer); last: the other offsets stay
 };
 
 __device__ __forceinline__ float logsigmoid_f(float x) { return fminf(x, 0.f) - log1pf(expf(-fabsf(x))); }
@@ -1176,9 +1243,9 @@ template <typename TI> struct TripletGeo { static constexpr int NW = sizeof(TI) 
 #endif
 // units u_first, u_first + NW, ... of the row [start, start + n): one wave's share of a slot row.  The next
 // tile's (col,val) pairs are in flight while this tile gathers, across the unit boundaries too.
-template <int D, typename TG, bool BIG, int NW, typename ES>
+template <int D, typename TG, bool BIG, int NW, bool DROP = false, typename ES>
 __device__ __forceinline__ typename Geo<D, TG, false>::Acc
-units_gather(const ES &es, int64_t start, int n, int u_first, const GatherSrc &src, int lane, int2 *stage) {
+units_gather(const ES &es, int64_t start, int n, int u_first, const GatherSrc &src, int lane, int2 *stage, int row = 0) {
     typedef Geo<D, TG, false> G;
     constexpr int UT = ROWS_UNIT_TILES;
     typename G::Acc acc = zerov<G::CPL>();
@@ -1189,6 +1256,7 @@ units_gather(const ES &es, int64_t start, int n, int u_first, const GatherSrc &s
     if (t * 64 + lane < n) cv = es.at(start + t * 64 + lane);
     for (;;) {
         if (src.S) cv.y = __float_as_int(__int_as_float(cv.y) * src.S[cv.x]);      // fp8 table: weight x row scale of the column
+        if constexpr (DROP) drop_apply(src.dr, row, cv);                            // edge dropout: scaled or zero weight
         const int cnt = tile_stage<false>(cv.x, __int_as_float(cv.y), min(64, n - t * 64), src, lane, stage);
         __builtin_amdgcn_wave_barrier();
         int tn = t + 1;
@@ -1205,7 +1273,7 @@ units_gather(const ES &es, int64_t start, int n, int u_first, const GatherSrc &s
 }
 
 // TG: type of the table the last layer gathers from (X_{K-1}; E0 itself when K == 1)
-template <int D, typename TG, typename TI, bool BIG>
+template <int D, typename TG, typename TI, bool BIG, bool DROP = false>
 __device__ __forceinline__ void triplet_body(const BprArgs &a, const void *Xg, int2 *stage, float (*part)[TripletGeo<TI>::NW][D], float (*base)[D], float (*ego)[D]) {
     constexpr int NW = TripletGeo<TI>::NW;
     typedef Geo<D, TG, false> G;
@@ -1238,6 +1306,7 @@ __device__ __forceinline__ void triplet_body(const BprArgs &a, const void *Xg, i
     }
     GatherSrc src; src.bm = nullptr; src.div = 1.f; src.X = Xg;
     src.S = sizeof(TG) == 1 ? fp8_scales(Xg, a.N, D) : nullptr;
+    if constexpr (DROP) src.dr = a.dr;
     tile_pad_init(stage, threadIdx.x & 63);
     bool any = NW == 3 || (w == 0 || w == 3);
 #pragma unroll 1
@@ -1245,7 +1314,8 @@ __device__ __forceinline__ void triplet_body(const BprArgs &a, const void *Xg, i
         const int stc = c == 0 ? st0 : (c == 1 ? st1 : st2), nc = c == 0 ? n0 : (c == 1 ? n1 : n2);
         const int u0 = NW == 4 ? ((w - c + 4) & 3) : ((w - c + 3) % 3), units = (a.hub_nnz && nc > a.hub_nnz) ? 0 : (nc + UN - 1) / UN;      // a hub row: computed by the hub plan
         if (u0 < units) {
-            const typename G::Acc x = units_gather<D, TG, BIG, NW>(CsrSrc{a.indices, a.vals}, stc, nc, u0, src, lane, stage);
+            const typename G::Acc x = units_gather<D, TG, BIG, NW, DROP>(CsrSrc{a.indices, a.vals}, stc, nc, u0, src, lane, stage,
+                                                                         (int)(c == 0 ? row0 : (c == 1 ? row1 : row2)));
             if (lane < LPR) {
                 if constexpr (sizeof(TG) == 1) {       // an fp8 gather: the lane's values are the chunks j*LPR + lane (see fp8_t)
 #pragma unroll
@@ -1287,7 +1357,7 @@ __device__ __forceinline__ void triplet_body(const BprArgs &a, const void *Xg, i
     } else triplet_loss_regs<D>(a, b, lane, e[0], e[1], e[2]);
 }
 
-template <int D, typename TI, bool BIG>
+template <int D, typename TI, bool BIG, bool DROP = false>
 __global__ void __launch_bounds__(64 * TripletGeo<TI>::NW, sizeof(TI) == 4 ? TRIPLET_MIN_WAVES_F32 : TRIPLET_MIN_WAVES) k_triplet(BprArgs a) {
     constexpr int NW = TripletGeo<TI>::NW;
     __shared__ int2 stage_lds[NW][TILE_ST];
@@ -1298,8 +1368,8 @@ __global__ void __launch_bounds__(64 * TripletGeo<TI>::NW, sizeof(TI) == 4 ? TRI
     for (int64_t i = (int64_t)blockIdx.x * (64 * NW) + threadIdx.x; i < a.bitmap_words; i += (int64_t)gridDim.x * (64 * NW))
         a.stale_bitmap[i] = 0u;
     int2 *stage = stage_lds[threadIdx.x >> 6];
-    if (a.K == 1) triplet_body<D, float, TI, BIG>(a, a.X0, stage, part_lds, base_lds, ego_lds);
-    else triplet_body<D, TI, TI, BIG>(a, a.Xl[a.K - 1], stage, part_lds, base_lds, ego_lds);
+    if (a.K == 1) triplet_body<D, float, TI, BIG, DROP>(a, a.X0, stage, part_lds, base_lds, ego_lds);
+    else triplet_body<D, TI, TI, BIG, DROP>(a, a.Xl[a.K - 1], stage, part_lds, base_lds, ego_lds);
 }
 
 // The same when the last layer was propagated densely (cfg.dense_last): e = mean_k X_k[row] is K+1 row reads per slot,
@@ -1755,7 +1825,7 @@ __global__ void __launch_bounds__(256) k_apply_perm(const int32_t *S, int cols, 
 // gathered tables of 4 GiB or more need 64-bit offsets (priced at the fp32 row size whatever the table type)
 static inline bool big_table(int64_t n_rows, int d) { return n_rows * (int64_t)d * 4 >= (1ll << 32); }
 
-template <int D, typename TI, typename TO, int MODE>
+template <int D, typename TI, typename TO, int MODE, bool DROP = false>
 static void launch_spmm_t(const SpmmArgs &a, hipStream_t st) {
     constexpr int RPB = PackGeo<RowGeo<D, TI, (MODE & M_SPARSE) != 0>::RPK>::RPB;
     static_assert(SLICE_PAD % RPB == 0, "slice padding must hold whole workgroups of every variant");
@@ -1766,8 +1836,8 @@ static void launch_spmm_t(const SpmmArgs &a, hipStream_t st) {
     }
     if (a.remap) grid = widest * XCDS;
     if (grid == 0) return;
-    if (big_table(a.n_rows, D)) hipLaunchKernelGGL((k_spmm<D, TI, TO, MODE, true>), dim3(grid), dim3(64 * SPMM_WPB), 0, st, a);
-    else hipLaunchKernelGGL((k_spmm<D, TI, TO, MODE, false>), dim3(grid), dim3(64 * SPMM_WPB), 0, st, a);
+    if (big_table(a.n_rows, D)) hipLaunchKernelGGL((k_spmm<D, TI, TO, MODE, true, DROP>), dim3(grid), dim3(64 * SPMM_WPB), 0, st, a);
+    else hipLaunchKernelGGL((k_spmm<D, TI, TO, MODE, false, DROP>), dim3(grid), dim3(64 * SPMM_WPB), 0, st, a);
 }
 
 template <int D, int MODE>
@@ -1775,6 +1845,7 @@ static int launch_spmm_d(const SpmmArgs &a, int x_dtype, int y_dtype, hipStream_
     if (MODE & M_SPARSE) x_dtype = LGCN_F32;           // source is the fixed-point table; TI unused
     if (MODE & M_ADAM) y_dtype = LGCN_F32;
     if (x_dtype == LGCN_FP8 || y_dtype == LGCN_FP8) {
+        if (a.dr.on) { lgcn_set_error("edge dropout is not implemented for fp8 tables"); return 3; }
         // fp8 tables: 16 elements per lane, so d >= 64; fp8 <-> bf16 conversions are not instantiated
         if constexpr (D >= 64) {
             if (x_dtype == LGCN_FP8 && y_dtype == LGCN_FP8) { launch_spmm_t<D, fp8_t, fp8_t, MODE>(a, st); return 0; }
@@ -1783,6 +1854,20 @@ static int launch_spmm_d(const SpmmArgs &a, int x_dtype, int y_dtype, hipStream_
         }
         lgcn_set_error("fp8 tables: embedding dim 64, 128 or 256, and fp8 <-> fp32 only (no fp8 <-> bf16 launch)");
         return 3;
+    }
+    // every MODE that comes through here (0, ADDG, ADDG|ADAM, SPARSE|ADDG, SPARSE|ADDG|ADAM) is one the dropout step launches;
+    // M_ADDSELF has its own helper below and no DROP instantiation
+    static_assert(!(MODE & M_ADDSELF), "item-item smoothing never takes the dropout branch");
+    if (a.dr.on) {
+        // edge dropout: its own instantiations, and only the type pairs a launch can ask for (a sparse input is fp32, Adam writes fp32)
+        if (x_dtype == LGCN_F32 && y_dtype == LGCN_F32) launch_spmm_t<D, float, float, MODE, true>(a, st);
+        else if constexpr ((MODE & M_SPARSE) != 0) {
+            if constexpr (!(MODE & M_ADAM)) launch_spmm_t<D, float, bf16_t, MODE, true>(a, st);
+        } else if constexpr ((MODE & M_ADAM) != 0) launch_spmm_t<D, bf16_t, float, MODE, true>(a, st);
+        else if (x_dtype == LGCN_F32) launch_spmm_t<D, float, bf16_t, MODE, true>(a, st);
+        else if (y_dtype == LGCN_F32) launch_spmm_t<D, bf16_t, float, MODE, true>(a, st);
+        else launch_spmm_t<D, bf16_t, bf16_t, MODE, true>(a, st);
+        return 0;
     }
     if (x_dtype == LGCN_F32 && y_dtype == LGCN_F32) launch_spmm_t<D, float, float, MODE>(a, st);
     else if (x_dtype == LGCN_F32 && y_dtype == LGCN_BF16) launch_spmm_t<D, float, bf16_t, MODE>(a, st);
@@ -2082,6 +2167,70 @@ extern "C" int lgcn_spmm_csr(const lgcn_graph *g, const void *X, int x_dtype, vo
     return 0;
 }
 
+// ---------------------------------------------------------------------------------
+// edge dropout: the step's keys, the exported mask, the masked SpMM
+// ---------------------------------------------------------------------------------
+static inline uint64_t splitmix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+static inline bool drop_prob_ok(float keep_prob) { return keep_prob > 0.f && keep_prob <= 1.f; }      // (NaN fails both)
+// floor(keep_prob * 2^32): exact in double; 2^32 itself (keep_prob = 1) means "keep everything"
+static inline uint64_t drop_threshold(float keep_prob) { return (uint64_t)floor((double)keep_prob * 4294967296.0); }
+// the mask of one step; keep_prob in (0, 1): at 1 there is nothing to drop and on stays 0 (the launch is the plain one)
+static DropArgs make_drop(float keep_prob, uint64_t seed, int64_t step, int transposed) {
+    DropArgs d{};
+    if (!(keep_prob < 1.f)) return d;
+    const uint64_t k = splitmix64(splitmix64(seed) + (uint64_t)step);
+    d.k0 = (uint32_t)k; d.k1 = (uint32_t)(k >> 32);
+    d.thr = (uint32_t)drop_threshold(keep_prob); d.inv = 1.0f / keep_prob; d.tr = transposed ? 1 : 0; d.on = 1;
+    return d;
+}
+
+// keep_out[p] = keep(row of p, indices[p]): one wave per row, its lanes over the row's entries
+__global__ void __launch_bounds__(256) k_dropout_mask(const int32_t *indptr, const int32_t *indices, int64_t n_rows, int64_t nnz,
+                                                      uint32_t k0, uint32_t k1, uint64_t thr, uint8_t *keep_out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
+    for (int64_t row = wave; row < n_rows; row += nwaves) {
+        const int64_t s = max((int64_t)indptr[row], (int64_t)0), e = min((int64_t)indptr[row + 1], nnz);      // never past the arrays
+        for (int64_t p = s + lane; p < e; p += 64)
+            keep_out[p] = (uint64_t)drop_hash(k0, k1, (uint32_t)row, (uint32_t)indices[p]) < thr ? 1 : 0;
+    }
+}
+
+extern "C" int lgcn_dropout_mask(const int32_t *indptr, const int32_t *indices, int64_t n_rows, int64_t nnz,
+                                 float keep_prob, uint64_t seed, int64_t step, uint8_t *keep_out, void *stream) {
+    if (!indptr || n_rows <= 0 || nnz < 0 || (nnz > 0 && (!indices || !keep_out))) { lgcn_set_error("lgcn_dropout_mask: invalid argument"); return 3; }
+    if (!drop_prob_ok(keep_prob)) { lgcn_set_error("lgcn_dropout_mask: dropout keep_prob must be in (0, 1]"); return 3; }
+    if (nnz == 0) return 0;
+    const uint64_t k = splitmix64(splitmix64(seed) + (uint64_t)step);
+    const int64_t blocks = (n_rows + 3) / 4;
+    hipLaunchKernelGGL(k_dropout_mask, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, (hipStream_t)stream,
+                       indptr, indices, n_rows, nnz, (uint32_t)k, (uint32_t)(k >> 32), drop_threshold(keep_prob), keep_out);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int lgcn_spmm_csr_drop(const lgcn_graph *g, const void *X, int x_dtype, void *Y, int y_dtype, int d,
+                                  float keep_prob, uint64_t seed, int64_t step, int transposed, void *stream) {
+    if (!g || !X || !Y) { lgcn_set_error("lgcn_spmm_csr_drop: null/invalid argument"); return 3; }
+    if (check_dtype(x_dtype) || check_dtype(y_dtype)) return 3;
+    if (x_dtype == LGCN_FP8 || y_dtype == LGCN_FP8) { lgcn_set_error("lgcn_spmm_csr_drop: edge dropout is not implemented for fp8 tables"); return 3; }
+    if (!drop_prob_ok(keep_prob)) { lgcn_set_error("lgcn_spmm_csr_drop: dropout keep_prob must be in (0, 1]"); return 3; }
+    if (d > g->d_max) { lgcn_set_error("lgcn_spmm_csr_drop: d exceeds the graph's d_max"); return 3; }
+    SpmmArgs a = graph_spmm(g);
+    a.X = X; a.Y = Y; a.remap = 1; a.dr = make_drop(keep_prob, seed, step, transposed);
+    int rc = graph_acquire(g, (hipStream_t)stream);
+    if (rc) return rc;
+    rc = launch_spmm<0>(a, d, x_dtype, y_dtype, (hipStream_t)stream);
+    if (rc) return rc;
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 // bytes of one [N,d] table of a storage type (fp8: rows + fp32 row scales, padded so that the next table stays 256-byte aligned)
 static inline size_t table_bytes(int64_t N, int d, int dtype) {
     if (dtype == LGCN_FP8) return (((size_t)N * d + (size_t)N * 4) + 255) & ~(size_t)255;
@@ -2178,6 +2327,9 @@ struct lgcn_ctx {
     int32_t gate_P, gate_wgs;
     int32_t *cnt;                 // reg_ego: [N] slots of the running step naming each row (library-owned, zero between steps)
     float *colsum;                // [3 * max_batch] partial scores / reg terms of a column-sharded step (library-owned)
+    // edge dropout (lgcn_ctx_set_dropout): drop_keep < 1 = on.  dr is the mask of the running step, made by lgcn_train_step from
+    // the step counter as it stands BEFORE the step; forward, batch rows and backward all read it (dr.on = 0: off)
+    float drop_keep; uint64_t drop_seed; DropArgs dr;
 };
 // a multi-step call: nobody but this library touches E0 between its steps
 struct LoopScope {
@@ -2213,6 +2365,7 @@ extern "C" int lgcn_ctx_create(const lgcn_train_config *cfg, lgcn_ctx **out) {
     lgcn_ctx *x = new (std::nothrow) lgcn_ctx;
     if (!x) { lgcn_set_error("out of memory"); return 4; }
     x->c = c; x->step = 0; x->N = c.graph->n_rows; x->cnt = nullptr; x->colsum = nullptr;
+    x->drop_keep = 1.f; x->drop_seed = 0; x->dr = DropArgs{};
     x->bm_words = (x->N + 31) / 32; x->flip = 0;
     const size_t stride = table_bytes(x->N, c.d, c.act_dtype);
     for (int k = 0; k <= LGCN_MAX_LAYERS; k++) x->act[k] = nullptr;
@@ -2299,6 +2452,22 @@ extern "C" int64_t lgcn_ctx_get_step(const lgcn_ctx *ctx) { return ctx ? ctx->st
 extern "C" int64_t lgcn_ctx_hub_rows(const lgcn_ctx *ctx) { return (ctx && ctx->hub_graph) ? ctx->hub_rows : 0; }
 extern "C" void lgcn_ctx_set_step(lgcn_ctx *ctx, int64_t s) { if (ctx) ctx->step = s; }
 extern "C" void lgcn_ctx_set_lr(lgcn_ctx *ctx, double lr) { if (ctx) ctx->c.lr = lr; }
+extern "C" int lgcn_ctx_set_dropout(lgcn_ctx *ctx, float keep_prob, uint64_t seed) {
+    if (!ctx) { lgcn_set_error("lgcn_ctx_set_dropout: null context"); return 3; }
+    if (!drop_prob_ok(keep_prob)) { lgcn_set_error("lgcn_ctx_set_dropout: dropout keep_prob must be in (0, 1]"); return 3; }
+    if (ctx->c.act_dtype == LGCN_FP8) { lgcn_set_error("lgcn_ctx_set_dropout: edge dropout is not implemented for LGCN_FP8 activation storage"); return 3; }
+    if (ctx->variant) { lgcn_set_error("lgcn_ctx_set_dropout: edge dropout is not implemented with the optional branches (item-item smoothing / popularity gate)"); return 3; }
+    ctx->drop_keep = keep_prob; ctx->drop_seed = seed; ctx->dr = DropArgs{};
+    return 0;
+}
+// the entry points that split a step over ranks have no dropout form: say so instead of training undropped
+static int refuse_dropout(const lgcn_ctx *x, const char *who) {
+    if (!x || !(x->drop_keep < 1.f)) return 0;
+    char buf[192];
+    snprintf(buf, sizeof buf, "%s: edge dropout (lgcn_ctx_set_dropout) is implemented for the single-GPU step only", who);
+    lgcn_set_error(buf);
+    return 3;
+}
 
 static SpmmArgs base_spmm(const lgcn_ctx *x) {
     SpmmArgs a = graph_spmm(x->c.graph);
@@ -2326,7 +2495,7 @@ static int run_forward(lgcn_ctx *x, hipStream_t st) {
     }
     for (int k = 1; k <= x->fwd_layers; k++) {
         SpmmArgs a = base_spmm(x);
-        a.X = prev; a.Y = x->act[k];
+        a.X = prev; a.Y = x->act[k]; a.dr = x->dr;
         int rc = launch_spmm<0>(a, c.d, prev_dt, c.act_dtype, st);
         if (rc) return rc;
         prev = x->act[k]; prev_dt = c.act_dtype;
@@ -2340,6 +2509,7 @@ static int run_bpr(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const 
     const lgcn_train_config &c = x->c;
     BprArgs a{};
     a.reg_ego = c.reg_ego; a.cnt = (atomics && count_slots) ? x->cnt : nullptr;
+    a.dr = x->dr;
     a.cols_phase = cols_phase; a.erows = c.contrib; a.colsum = x->colsum;
     a.indptr = c.graph->indptr; a.indices = c.graph->indices; a.vals = c.graph->vals; a.X0 = c.E0; a.K = c.K;
     for (int k = 1; k <= x->fwd_layers; k++) a.Xl[k] = x->act[k];
@@ -2364,7 +2534,7 @@ static int run_bpr(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const 
         // last layer of the hub rows, X_K[hub] = (A_hat X_{K-1})[hub] in fp32, into the library's [N,d] table (free until k_g32)
         { int rc0 = graph_acquire(x->hub_graph, st); if (rc0) return rc0; }
         SpmmArgs h = graph_spmm(x->hub_graph);
-        h.X = c.K == 1 ? (const void *)c.E0 : x->act[c.K - 1]; h.Y = x->g32; h.remap = c.xcd_remap;
+        h.X = c.K == 1 ? (const void *)c.E0 : x->act[c.K - 1]; h.Y = x->g32; h.remap = c.xcd_remap; h.dr = x->dr;
         int rc = launch_spmm<0>(h, c.d, c.K == 1 ? LGCN_F32 : c.act_dtype, LGCN_F32, st);
         if (rc) return rc;
         a.Xhub = x->g32; a.hub_nnz = x->hub_nnz;
@@ -2389,6 +2559,12 @@ static int run_bpr(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const 
             const unsigned gd = (unsigned)((B_local + tpb - 1) / tpb);
             if (c.act_dtype == LGCN_F32) hipLaunchKernelGGL((k_triplet_dense<D, float>), dim3(gd), dim3(256), 0, st, a);
             else hipLaunchKernelGGL((k_triplet_dense<D, bf16_t>), dim3(gd), dim3(256), 0, st, a);
+        } else if (a.dr.on) {      // edge dropout: the last layer's gathers take the step's mask
+            if (big_table(x->N, D)) {
+                if (c.act_dtype == LGCN_F32) hipLaunchKernelGGL((k_triplet<D, float, true, true>), dim3(B_local), dim3(64 * TripletGeo<float>::NW), 0, st, a);
+                else hipLaunchKernelGGL((k_triplet<D, bf16_t, true, true>), dim3(B_local), dim3(64 * TripletGeo<bf16_t>::NW), 0, st, a);
+            } else if (c.act_dtype == LGCN_F32) hipLaunchKernelGGL((k_triplet<D, float, false, true>), dim3(B_local), dim3(64 * TripletGeo<float>::NW), 0, st, a);
+            else hipLaunchKernelGGL((k_triplet<D, bf16_t, false, true>), dim3(B_local), dim3(64 * TripletGeo<bf16_t>::NW), 0, st, a);
         } else if (big_table(x->N, D)) {
             if (c.act_dtype == LGCN_F32) hipLaunchKernelGGL((k_triplet<D, float, true>), dim3(B_local), dim3(64 * TripletGeo<float>::NW), 0, st, a);
             else hipLaunchKernelGGL((k_triplet<D, bf16_t, true>), dim3(B_local), dim3(64 * TripletGeo<bf16_t>::NW), 0, st, a);
@@ -2542,6 +2718,7 @@ static int backward_layer(lgcn_ctx *x, int k, const int32_t *users, const int32_
         }
     }
     SpmmArgs a = base_spmm(x);
+    a.dr = x->dr; a.dr.tr = 1;           // the chain multiplies by A_drop^T: the entry stored at (i, j) carries keep(j, i)
     a.X = first ? nullptr : bwd_buffer(x, k + 1);
     if (!last) a.Y = bwd_buffer(x, k);
     else {
@@ -2623,6 +2800,7 @@ extern "C" int lgcn_train_step(lgcn_ctx *x, const int32_t *users, const int32_t 
     if (rc) return rc;
     if (!loss_out) { lgcn_set_error("train step: loss_out is null"); return 3; }
     hipStream_t st = (hipStream_t)stream;
+    x->dr = make_drop(x->drop_keep, x->drop_seed, x->step, 0);        // ONE mask per step, from the counter before the step
     if ((rc = run_forward(x, st))) return rc;
     if (x->variant) rc = run_variant_loss(x, users, pos, neg, B, 0, B, B, true, false, st);
     else rc = run_bpr(x, users, pos, neg, B, 0, B, B, true, false, st);
@@ -2650,6 +2828,7 @@ extern "C" int lgcn_train_step_dp_part1(lgcn_ctx *x, const int32_t *users, const
                                         int32_t B_global, int32_t world, int32_t rank, void *stream) {
     int rc = check_batch(x, users, pos, neg, B_global);
     if (rc) return rc;
+    if ((rc = refuse_dropout(x, "lgcn_train_step_dp_part1"))) return rc;
     if (!x->c.contrib) { lgcn_set_error("dp step: cfg.contrib exchange buffer missing"); return 3; }
     if (world < 1 || rank < 0 || rank >= world) { lgcn_set_error("dp step: bad world/rank"); return 3; }
     const int32_t shard = (B_global + world - 1) / world;
@@ -2672,6 +2851,7 @@ extern "C" int lgcn_train_step_dp_dense_part1(lgcn_ctx *x, const int32_t *users,
                                               int32_t B_global, int32_t world, int32_t rank, void *stream) {
     int rc = check_batch(x, users, pos, neg, B_global);
     if (rc) return rc;
+    if ((rc = refuse_dropout(x, "lgcn_train_step_dp_dense_part1"))) return rc;
     if (world < 1 || rank < 0 || rank >= world) { lgcn_set_error("dp step: bad world/rank"); return 3; }
     const int32_t shard = (B_global + world - 1) / world;
     const int32_t b_off = rank * shard;
@@ -2715,6 +2895,7 @@ extern "C" int lgcn_train_step_dp_part2(lgcn_ctx *x, const int32_t *users, const
                                         void *stream) {
     int rc = check_batch(x, users, pos, neg, B_global);
     if (rc) return rc;
+    if ((rc = refuse_dropout(x, "lgcn_train_step_dp_part2"))) return rc;
     if (!loss_out || world < 1) { lgcn_set_error("dp step part 2: invalid argument"); return 3; }
     const int32_t shard = (B_global + world - 1) / world;
     // gathered == NULL is the dense form: G64, the terms and (popularity gate) gate_total hold the reduced sums of the global batch
@@ -2736,6 +2917,7 @@ extern "C" int lgcn_train_step_cols_part1(lgcn_ctx *x, const int32_t *users, con
                                           int32_t B, float **partials, void *stream) {
     int rc = check_batch(x, users, pos, neg, B);
     if (rc) return rc;
+    if ((rc = refuse_dropout(x, "lgcn_train_step_cols_part1"))) return rc;
     if (x->variant) { lgcn_set_error("column-sharded step: the popularity gate / item-item smoothing mix columns (MLPs over the row): not supported"); return 3; }
     if (!x->c.contrib) { lgcn_set_error("column-sharded step: cfg.contrib (3*max_batch*d floats: the batch's slot rows) missing"); return 3; }
     hipStream_t st = (hipStream_t)stream;
@@ -2749,6 +2931,7 @@ extern "C" int lgcn_train_step_cols_part2(lgcn_ctx *x, const int32_t *users, con
                                           int32_t B, float *loss_out, void *stream) {
     int rc = check_batch(x, users, pos, neg, B);
     if (rc) return rc;
+    if ((rc = refuse_dropout(x, "lgcn_train_step_cols_part2"))) return rc;
     if (!loss_out) { lgcn_set_error("column-sharded step part 2: loss_out is null"); return 3; }
     hipStream_t st = (hipStream_t)stream;
     if ((rc = run_bpr(x, users, pos, neg, B, 0, B, B, true, false, st, true, 2))) return rc;
@@ -2766,6 +2949,7 @@ extern "C" int lgcn_rs_phase(lgcn_ctx *x, int32_t phase, int32_t k, const int32_
                              int32_t B_global, int32_t world, int32_t rank, const float *gathered, float *loss_out, void *stream) {
     int rc = check_batch(x, users, pos, neg, B_global);
     if (rc) return rc;
+    if ((rc = refuse_dropout(x, "lgcn_rs_phase"))) return rc;
     if (x->variant) { lgcn_set_error("lgcn_rs_phase: the popularity gate / item-item smoothing run on one GPU only"); return 3; }
     const lgcn_train_config &c = x->c;
     hipStream_t st = (hipStream_t)stream;
@@ -2923,6 +3107,7 @@ static int train_epoch_dp_impl(lgcn_ctx *x, lgcn_dp *dp, const int32_t *users, c
 extern "C" int lgcn_train_epoch_dp(lgcn_ctx *x, lgcn_dp *dp, const int32_t *users, const int32_t *pos, const int32_t *neg,
                                    int64_t T, int32_t B_global, int32_t reduce, const int64_t *row_ranges, float *gathered,
                                    float *loss_out, void *stream) {
+    if (refuse_dropout(x, "lgcn_train_epoch_dp")) return 3;         // (every rank's context says the same: nobody waits in a collective)
     const int rc = train_epoch_dp_impl(x, dp, users, pos, neg, T, B_global, reduce, row_ranges, gathered, loss_out, stream);
     // a rank that leaves the loop early never reaches its next collective: release the loopback ranks waiting for it
     // (RCCL has its own abort / timeout machinery)

@@ -81,7 +81,14 @@ class LightGCN(nn.Module):
         self.m_items = dataset.m_items
         self.latent_dim = config['latent_dim_rec']
         self.n_layers = config['lightGCN_n_layers']
-        self.keep_prob = config.get('keep_prob', 0.6)
+        # edge dropout (upstream LightGCN's __dropout_x; --dropout 1 --keepprob p): the fused training step draws one mask per
+        # optimiser step (lgcn_ctx_set_dropout); evaluation never drops
+        self.dropout = bool(config.get('dropout', 0))
+        self.keep_prob = float(config.get('keep_prob', 0.6))
+        if self.dropout and not (0.0 < self.keep_prob <= 1.0):
+            raise ValueError(f"--keepprob must be in (0, 1] with --dropout 1, got {self.keep_prob}")
+        if self.dropout and str(config.get('act_dtype', 'fp32')) == 'fp8':
+            raise _lib.LgcnError("--dropout 1 is not implemented together with --act_dtype fp8 (fp32 and bf16 storage only)")
         if self.latent_dim not in (32, 64, 128, 256):
             raise ValueError("latent_dim_rec must be 32, 64, 128 or 256 for the HIP kernels")
         if not (1 <= self.n_layers <= _lib.MAX_LAYERS):
@@ -155,6 +162,9 @@ class LightGCN(nn.Module):
             raise ValueError("adjacency shape does not match n_users + m_items")
         if len(self._adj.indices) and (self._adj.indices.min() < 0 or self._adj.indices.max() >= N):
             raise ValueError("adjacency column index out of range")
+        if self.dropout and self.has_variants:
+            raise _lib.LgcnError("--dropout 1 is not implemented together with --use_pop_gate / --use_item_item "
+                                 "(the popularity gate and the item-item smoothing train without edge dropout only)")
         self._gate_flat = None      # the eight MLP tensors of the gate in ONE buffer (what the fused step reads / updates)
         self._Graph = None
         self._dev = None            # device-side state (graph, workspace, context)
@@ -368,6 +378,12 @@ class LightGCN(nn.Module):
         h = C.c_void_p()
         _lib.check(lib.lgcn_ctx_create(C.byref(cfg), C.byref(h)), "lgcn_ctx_create")
         lib.lgcn_ctx_set_step(h, old_step)
+        if self.dropout:
+            rc = lib.lgcn_ctx_set_dropout(h, self.keep_prob, int(self.config.get('seed', 2020)) & (2 ** 64 - 1))
+            if rc:
+                msg = lib.lgcn_last_error()
+                lib.lgcn_ctx_destroy(h)
+                raise _lib.LgcnError(f"lgcn_ctx_set_dropout failed (rc={rc}): {msg.decode() if msg else ''}")
         st['ctx'], st['max_batch'], st['dp_world'], st['table_ptr'] = h, max_batch, dp_world, self._table.data_ptr()
         st['ctx_rows'] = rows
 
@@ -485,6 +501,9 @@ class LightGCN(nn.Module):
             return out[:self.n_users, :], out[self.n_users:, :]
         if torch.is_grad_enabled() and (self.embedding_user.weight.requires_grad
                                         or self.embedding_item.weight.requires_grad):
+            if self.dropout and self.training:
+                raise RuntimeError("--dropout 1 is implemented in the fused training step only (BPRLoss.stageOne / fused_step / "
+                                   "fused_epoch): the autograd path of computer() / bpr_loss would train without edge dropout")
             out = _Propagate.apply(self.embedding_user.weight, self.embedding_item.weight, self)
         else:
             out = self._propagate_dense()

@@ -132,6 +132,9 @@ class DataParallelBPR:
 
     def __init__(self, recmodel, config, group=None, reduce='rows', shard='batch'):
         from .utils import _AdamView
+        if getattr(recmodel, 'dropout', False):
+            raise RuntimeError("--dropout 1 is implemented for single-GPU training only: DataParallelBPR (every reduce / shard mode) "
+                               "has no edge-dropout form")
         if not dist.is_initialized():
             raise RuntimeError("torch.distributed is not initialised")
         # (row-sharded and column-sharded propagation refuse the optional branches: the first was never wired to carry the smoothing's

@@ -141,6 +141,22 @@ void lgcn_graph_destroy(lgcn_graph *g);
 int lgcn_spmm_csr(const lgcn_graph *g, const void *X, int x_dtype, void *Y, int y_dtype, int d,
                   void *stream);
 
+/* Edge dropout (upstream LightGCN's __dropout_x, which the fork left as a TODO in computer()).  For one optimiser step
+ * `step` and a 64-bit seed every stored non-zero (i, j) of A_hat is kept when
+ *     H(seed, step, i, j) < floor(keep_prob * 2^32)
+ * and the survivors are scaled by 1 / keep_prob (fp32).  H is a 32-bit counter-based hash of the seed, the step and the row
+ * and column ids of the [N, N] adjacency only (DESIGN 4 spells it out): not of CSR positions, plans or kernels.  keep(i, j)
+ * and keep(j, i) are independent draws; for fixed (seed, step) the kept set grows with keep_prob.  keep_prob in (0, 1].
+ *
+ * lgcn_dropout_mask: keep_out[p] (device uint8[nnz]) = keep(row of p, indices[p]) for CSR position p.  Device pointers.   */
+int lgcn_dropout_mask(const int32_t *indptr, const int32_t *indices, int64_t n_rows, int64_t nnz,
+                      float keep_prob, uint64_t seed, int64_t step, uint8_t *keep_out, void *stream);
+/* Y = A_drop X (transposed = 0) or, at row i, the sum over the stored (i, j) of keep(j, i) * v / keep_prob * X[j]
+ * (transposed = 1: A_drop^T X with A_hat's own values, as every backward here uses them): lgcn_spmm_csr with the step's
+ * mask; fp32 / bf16 tables, the same dims.  keep_prob = 1 is lgcn_spmm_csr itself.                                       */
+int lgcn_spmm_csr_drop(const lgcn_graph *g, const void *X, int x_dtype, void *Y, int y_dtype, int d,
+                       float keep_prob, uint64_t seed, int64_t step, int transposed, void *stream);
+
 /* out[N,d] fp32 = mean(X_0, A X_0, ..., A^K X_0) -- replaces LightGCN.computer()
  * model.py:201-231 (cat + K sparse.mm + stack + mean).  work: (K-1)*N*d elements
  * of act_dtype (may be NULL for K == 1).                                       */
@@ -240,6 +256,14 @@ int64_t lgcn_ctx_get_step(const lgcn_ctx *ctx);
 int64_t lgcn_ctx_hub_rows(const lgcn_ctx *ctx);
 void lgcn_ctx_set_step(lgcn_ctx *ctx, int64_t step);
 void lgcn_ctx_set_lr(lgcn_ctx *ctx, double lr);
+/* Edge dropout in the training step (--dropout 1 --keepprob p): lgcn_train_step / _i64 / lgcn_train_epoch then draw ONE mask
+ * per step from (seed, lgcn_ctx_get_step() before the step) and use A_drop in all K forward layers, on the batch rows and
+ * (transposed) in the whole backward; the layer mean still includes X_0.  A step is bitwise reproducible for a given
+ * (seed, step), and a resumed run replays the same masks.  Evaluation entry points never drop.  keep_prob in (0, 1];
+ * 1.0 = off (the step then launches exactly the kernels it launches without this call).  rc 3: out of range, or the context
+ * uses LGCN_FP8 storage or an optional branch (i2i / popularity gate).  While dropout is on, every entry point that splits
+ * a step over ranks (lgcn_train_step_dp_* / _cols_*, lgcn_rs_phase, lgcn_train_epoch_dp) returns 3 and says so.          */
+int lgcn_ctx_set_dropout(lgcn_ctx *ctx, float keep_prob, uint64_t seed);
 /* Data parallel, rows mode: 1 = part 1 of a step also adds this rank's OWN gradient rows into its G64 (besides writing
  * them to the exchange block) and part 2 scatters only the other ranks' blocks -- what lgcn_train_epoch_dp does itself;
  * 0 (default) = part 2 scatters every block (one context may then play several ranks, as the emulation tests do). */
