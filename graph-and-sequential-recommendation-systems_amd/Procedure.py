@@ -190,6 +190,23 @@ class _EvalIndex:
                 _lib.check(lib.lgcn_eval_build_masks(_lib.tp(self.users32), len(self.users), _lib.tp(self.train_ptr), _lib.tp(self.train_idx32),
                                                      int(dataset.m_items), _lib.tp(self.masks), _lib.current_stream()), "lgcn_eval_build_masks")
 
+    def rank_lists(self):
+        """(users32, test_ptr, test_sorted32) with the slots ordered by test-list length (longest first, stable), built once: what the rank
+        kernels are given.  The compare loop of a wave runs to its longest list, and a workgroup sweeps the items once more
+        for every further 64 test items of its longest list, so slots of similar length share a wave.  The metrics are sums
+        over the slots: their order moves nothing but the last bits of the float64 sums."""
+        if getattr(self, '_rank_lists', None) is None:
+            dev = self.test_ptr.device
+            perm = np.argsort(-self.test_len, kind='stable')            # longest first: the heavy workgroups start first
+            ptr = self.test_ptr.cpu().numpy()
+            items = self.test_sorted32.cpu().numpy()
+            ptr2 = np.zeros(len(perm) + 1, np.int64)
+            np.cumsum(self.test_len[perm], out=ptr2[1:])
+            items2 = np.concatenate([items[ptr[s]:ptr[s + 1]] for s in perm.tolist()]) if len(perm) else items
+            self._rank_lists = (self.users32[torch.from_numpy(perm).to(dev)].contiguous(), torch.from_numpy(ptr2).to(dev),
+                                torch.from_numpy(np.ascontiguousarray(items2, np.int32)).to(dev))
+        return self._rank_lists
+
     @staticmethod
     def _expand(ptr, rows):
         """(local row id, position) pairs of the CSR rows `rows`."""
@@ -214,6 +231,26 @@ def _test_fused(Recmodel, ev, max_K):
     return {'precision': m[0], 'recall': m[1], 'ndcg': m[2]}, topk
 
 
+RANKS_BY_LENGTH = True      # --rank_metrics: evaluation slots visited in order of test-list length (measured: profiles/eval_ranks)
+
+
+def _test_ranks(Recmodel, ev):
+    """Test through the rank kernels (--rank_metrics 1): lgcn_eval_ranks (one item sweep on the matrix cores: for every test
+    item the number of candidates above / level with it) and lgcn_eval_rank_metrics (position in the full ranking -> precision /
+    recall / NDCG at any cut-off up to m_items, utils.AUC, MRR).  The same table as _test_fused, so the gate, item-item
+    smoothing and gathered column shards score as they do there."""
+    E = Recmodel.rating_table()
+    n = len(ev.users)
+    m_items = int(E.shape[0]) - Recmodel.n_users
+    ks = list(world.topks)
+    users32, test_ptr, test_sorted32 = ev.rank_lists() if RANKS_BY_LENGTH else (ev.users32, ev.test_ptr, ev.test_sorted32)
+    scores, gt, eq = _lib.eval_ranks(E, Recmodel.n_users, users32, ev.train_ptr, ev.train_idx32, test_ptr, test_sorted32)
+    _, sums = _lib.eval_rank_metrics(m_items, users32, ev.train_ptr, ev.train_idx32, test_ptr, test_sorted32, scores, gt, eq, ks)
+    m = sums.cpu().numpy() / max(n, 1)
+    nk = len(ks)
+    return {'precision': m[:nk], 'recall': m[nk:2 * nk], 'ndcg': m[2 * nk:3 * nk], 'auc': float(m[3 * nk]), 'mrr': float(m[3 * nk + 1])}
+
+
 def Test(dataset, Recmodel, epoch, w=None, multicore=0):
     """Procedure.py:127-206 (multicore is accepted and ignored: the reference creates a Pool
     and never uses it).  Per-user results do not depend on the user batch size, so
@@ -231,6 +268,14 @@ def Test(dataset, Recmodel, epoch, w=None, multicore=0):
             dataset._lgcn_eval_index = ev
         except Exception:
             pass
+    if int(world.config.get('rank_metrics', 0)):
+        if not hasattr(Recmodel, 'rating_table') or torch.device(dev).type != 'cuda':
+            raise RuntimeError("--rank_metrics 1 needs the HIP model on the GPU (there is no torch fall-back for the rank kernels)")
+        if max_K > dataset.m_items or min(world.topks) < 1:
+            raise ValueError(f"--topks {world.topks}: with --rank_metrics every cut-off must be in 1..m_items = {dataset.m_items}")
+        with torch.no_grad():
+            results = _test_ranks(Recmodel, ev)
+        return _finish_test(results, epoch, w)
     fused = max_K <= _lib.eval_kmax() and int(world.config.get('eval_fused', 1)) and hasattr(Recmodel, 'propagated_table')
     if fused:
         with torch.no_grad():
@@ -273,5 +318,8 @@ def _finish_test(results, epoch, w):
         for m, tag in (('recall', 'Recall'), ('precision', 'Precision'), ('ndcg', 'NDCG')):
             w.add_scalars(f'Test/{tag}@{world.topks}',
                           {str(world.topks[i]): results[m][i] for i in range(len(world.topks))}, epoch)
+        for m, tag in (('auc', 'AUC'), ('mrr', 'MRR')):       # (--rank_metrics 1 only)
+            if m in results:
+                w.add_scalar(f'Test/{tag}', results[m], epoch)
     print(results)
     return results

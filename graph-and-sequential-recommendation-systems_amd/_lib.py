@@ -99,6 +99,10 @@ SIGNATURES = {
     "lgcn_eval_topk_ex": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, _vp,
                                     C.c_int64, C.c_int32, _vp]),
     "lgcn_eval_metrics_ex": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp]),
+    "lgcn_eval_ranks": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp,
+                                  C.c_int32, _vp]),
+    "lgcn_eval_rank_metrics": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int32,
+                                         _vp, _vp, _vp]),
     "lgcn_i2i_topk": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "lgcn_i2i_finish": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp, C.POINTER(C.c_int64), _vp]),
     "lgcn_dp_available": (C.c_int, []),
@@ -276,6 +280,85 @@ def eval_metrics(topk, test_ptr, test_sorted32, ks, per_user=None, sums=None):
     ks_h = torch.tensor(ks, dtype=torch.int32)
     check(load().lgcn_eval_metrics_ex(tp(topk), n, K, tp(test_ptr), tp(test_sorted32), tp(ks_h), len(ks), tp(per_user), tp(sums),
                                       current_stream()), "lgcn_eval_metrics_ex")
+    return per_user, sums
+
+
+def _rank_lists(users32, train_ptr, train_idx32, test_ptr, test_sorted32, n_users=None):
+    """Shared checks of the rank entry points: returns (dev, n_eval, n_test)."""
+    import torch
+    _want(users32, "users32", torch.int32, None)
+    if users32.dim() != 1 or users32.device.type != "cuda":
+        raise ValueError("users32 must be a 1-D device tensor")
+    dev = users32.device
+    n = int(users32.numel())
+    _want(train_ptr, "train_ptr", torch.int64, None, dev)
+    if train_ptr.dim() != 1 or train_ptr.numel() < 2 or (n_users is not None and train_ptr.numel() < n_users + 1):
+        raise ValueError("train_ptr must hold n_users + 1 offsets")
+    _want(train_idx32, "train_idx32", torch.int32, None, dev)
+    _want(test_ptr, "test_ptr", torch.int64, (n + 1,), dev)
+    _want(test_sorted32, "test_sorted32", torch.int32, None, dev)
+    if test_sorted32.dim() != 1:
+        raise ValueError("test_sorted32 must be 1-D")
+    return dev, n, int(test_sorted32.numel())
+
+
+def eval_ranks(E, n_users, users32, train_ptr, train_idx32, test_ptr, test_sorted32, scores=None, gt=None, eq=None, fp32=False):
+    """lgcn_eval_ranks, checked: E the propagated table [n_users + m_items, d] fp32 on the device, users32 int32 [n_eval],
+    the train CSR (int64 train_ptr [n_users + 1], int32 ids ascending), the test CSR over the slots (int64 test_ptr
+    [n_eval + 1], test_sorted32 int32 [n_test], ids ascending per slot; test_ptr[n_eval] must be n_test -- the caller's
+    contract, not read back here).  Returns (scores fp32, gt int32, eq int32), each [n_test]; buffers passed in must have
+    exactly that shape.  Everything is validated before anything is launched (ValueError)."""
+    import torch
+    _want(E, "E", torch.float32, None)
+    if E.dim() != 2 or E.device.type != "cuda":
+        raise ValueError("E must be a 2-D device tensor")
+    n_users, d = int(n_users), int(E.shape[1])
+    m_items = int(E.shape[0]) - n_users
+    if d not in (32, 64, 128, 256) or n_users <= 0 or m_items <= 0:
+        raise ValueError(f"E [{tuple(E.shape)}] with n_users={n_users}: d must be 32, 64, 128 or 256 and both sides non-empty")
+    dev, n, n_test = _rank_lists(users32, train_ptr, train_idx32, test_ptr, test_sorted32, n_users)
+    if dev != E.device:
+        raise ValueError(f"users32 must be on {E.device}")
+    if n_test > n * m_items:
+        raise ValueError(f"n_test={n_test} exceeds n_eval * m_items")
+    if scores is None:
+        scores = torch.empty(n_test, dtype=torch.float32, device=dev)
+    if gt is None:
+        gt = torch.empty(n_test, dtype=torch.int32, device=dev)
+    if eq is None:
+        eq = torch.empty(n_test, dtype=torch.int32, device=dev)
+    _want(scores, "scores", torch.float32, (n_test,), dev)
+    _want(gt, "gt", torch.int32, (n_test,), dev)
+    _want(eq, "eq", torch.int32, (n_test,), dev)
+    check(load().lgcn_eval_ranks(tp(E), n_users, m_items, d, tp(users32), n, tp(train_ptr), tp(train_idx32), tp(test_ptr),
+                                 tp(test_sorted32), n_test, tp(scores), tp(gt), tp(eq), EVAL_FP32 if fp32 else 0,
+                                 current_stream()), "lgcn_eval_ranks")
+    return scores, gt, eq
+
+
+def eval_rank_metrics(m_items, users32, train_ptr, train_idx32, test_ptr, test_sorted32, scores, gt, eq, ks, per_user=None, sums=None):
+    """lgcn_eval_rank_metrics, checked: the lists as eval_ranks, its three outputs, ks 1..8 cut-offs in 1..m_items.  Returns
+    (per_user float64 [n_eval, 3 len(ks) + 2] = precision | recall | ndcg | auc | mrr, sums float64 [3 len(ks) + 2])."""
+    import torch
+    m_items = int(m_items)
+    ks = [int(k) for k in ks]
+    if m_items <= 0 or not 1 <= len(ks) <= 8 or any(not 1 <= k <= m_items for k in ks):
+        raise ValueError(f"1..8 cut-offs in 1..m_items={m_items}, got {ks}")
+    dev, n, n_test = _rank_lists(users32, train_ptr, train_idx32, test_ptr, test_sorted32)
+    _want(scores, "scores", torch.float32, (n_test,), dev)
+    _want(gt, "gt", torch.int32, (n_test,), dev)
+    _want(eq, "eq", torch.int32, (n_test,), dev)
+    width = 3 * len(ks) + 2
+    if per_user is None:
+        per_user = torch.empty(n, width, dtype=torch.float64, device=dev)
+    if sums is None:
+        sums = torch.empty(width, dtype=torch.float64, device=dev)
+    _want(per_user, "per_user", torch.float64, (n, width), dev)
+    _want(sums, "sums", torch.float64, (width,), dev)
+    ks_h = torch.tensor(ks, dtype=torch.int32)
+    check(load().lgcn_eval_rank_metrics(n, m_items, tp(users32), tp(train_ptr), tp(train_idx32), tp(test_ptr), tp(test_sorted32),
+                                        n_test, tp(scores), tp(gt), tp(eq), tp(ks_h), len(ks), tp(per_user), tp(sums),
+                                        current_stream()), "lgcn_eval_rank_metrics")
     return per_user, sums
 
 

@@ -89,6 +89,10 @@ def build_parser():
     p.add_argument('--eval_fused', type=int, default=1,
                    help='NEW: 1 = Procedure.Test through the fused HIP kernels (MFMA scores + mask + top-k, metrics on device); '
                         '0 = torch matmul/topk harness')
+    p.add_argument('--rank_metrics', type=int, default=0,
+                   help='NEW: 1 = Procedure.Test ranks through lgcn_eval_ranks / lgcn_eval_rank_metrics: the position of every test item '
+                        'in the full ranking from one item sweep, so any cut-off up to the catalogue size stays on the GPU, and the '
+                        "result also holds 'auc' (utils.AUC) and 'mrr'; 0 (default) = Test as before")
     p.add_argument('--reg_rows', type=str, default='propagated', choices=['propagated', 'ego'],
                    help="NEW: rows the L2 term of bpr_loss is taken on. 'propagated' (default) = this reference (model.py:173: the "
                         "propagated rows of the batch); 'ego' = upstream LightGCN (userEmb0 / posEmb0 / negEmb0, the embedding "

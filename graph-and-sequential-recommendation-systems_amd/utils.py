@@ -383,6 +383,24 @@ def NDCGatK_r(test_data, r, k):
     return np.sum((r[:, :k] * disc).sum(axis=1) / idcg)
 
 
+def AUC(all_item_scores, dataset, test_data):
+    """Area under the ROC curve of ONE user's scores over all items, the test items as positives (utils.py:203-209:
+    roc_auc_score(r_all, all_item_scores)), without sklearn: Mann-Whitney on average ranks, a tie counting one half.
+    0.0 when the test list is empty or holds every item (no pair to compare)."""
+    scores = np.asarray(all_item_scores, dtype=np.float64).reshape(-1)
+    m = int(dataset.m_items)
+    r_all = np.zeros((m,), dtype=bool)
+    r_all[np.asarray(test_data, dtype=np.int64)] = True
+    n = int(r_all.sum())
+    if n == 0 or n == m:
+        return 0.0
+    _, inverse, counts = np.unique(scores, return_inverse=True, return_counts=True)
+    first = np.cumsum(counts) - counts                               # values below each distinct score
+    rank = first + (counts + 1) / 2.0                                # average 1-based rank of a tied group
+    u = rank[inverse.reshape(-1)[r_all]].sum() - n * (n + 1) / 2.0
+    return float(u / (n * (m - n)))
+
+
 def getLabel(groundTruth, predictTopK):
     """0/1 float32 vector: is the j-th predicted item in the ground truth?"""
     truth = groundTruth if isinstance(groundTruth, (list, set, tuple, np.ndarray)) else [groundTruth]

@@ -103,6 +103,7 @@ def configure(argv=None):
     config['gpu_shuffle'] = args.gpu_shuffle
     config['lazy_loss'] = args.lazy_loss
     config['eval_fused'] = args.eval_fused
+    config['rank_metrics'] = args.rank_metrics
     config['gpu_sampler'] = args.gpu_sampler
     config['dense_last'] = args.dense_last
     config['hub_nnz'] = args.hub_nnz

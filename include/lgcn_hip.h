@@ -397,6 +397,41 @@ int lgcn_eval_topk_ex(const float *E, int32_t n_users, int32_t m_items, int32_t 
 int lgcn_eval_metrics_ex(const int32_t *topk_items, int32_t n_eval, int32_t K,
                          const int64_t *test_indptr, const int32_t *test_items_sorted,
                          const int32_t *ks, int32_t n_ks, double *per_user, double *sums, void *stream);
+/* Rank-based evaluation: any cut-off up to m_items, AUC (utils.AUC, utils.py:203-209) and MRR, from one item sweep whose
+ * cost does not depend on a cut-off (additive to ABI 13; the entry points above are unchanged).
+ * For evaluation slot s with user u = users[s], train positives P_u (the sorted CSR), test list T_u (test_indptr over the
+ * n_eval slots, ids ASCENDING per slot, n_test = test_indptr[n_eval] entries in all) and the reference's row
+ * L_u[j] = <E[u], E[n_users + j]> in fp32 accuracy, or -(1<<10) for j in P_u (Procedure.py:177-181), lgcn_eval_ranks writes
+ * per test entry t (three arrays of n_test elements, in the order of test_items_sorted):
+ *   test_scores[t] = L_u[t]                                   (so -1024 when t is also a train positive)
+ *   gt[t] = #{ j not in P_u or T_u : L_u[j] >  test_scores[t] }
+ *   eq[t] = #{ j not in P_u or T_u : L_u[j] == test_scores[t] }
+ * The counts are integers added in any order: bitwise reproducible, whatever the split of the sweep.  flags: LGCN_EVAL_FP32
+ * = every score from the fp32 matrix instructions, else the split bf16 product (d <= 128).
+ * lgcn_eval_rank_metrics derives, per slot, pos[t] = the position of t in L_u sorted best first:
+ *   TIE RULES: a tie between a test item and a non-test item goes AGAINST the test item (the non-test item ranks first: a
+ *   constant table scores nothing); a tie among test items goes to the LOWER id.  The train positives outside T_u sit at
+ *   -1024 and rank above a test item whose score is <= -1024.
+ * and from it hit@K = [pos[t] < K] for any cut-off 1 <= ks[q] <= m_items (ks: HOST pointer, 1..8 cut-offs, any order),
+ * precision / recall / NDCG by the formulas of lgcn_eval_metrics_ex (same additions, same order),
+ *   AUC_u = sum_t (#{j not in T_u : L_u[j] < score[t]} + 1/2 #{j not in T_u : L_u[j] == score[t]}) / (n (m_items - n)),
+ *           = roc_auc_score(r_all, L_u); 0 for a slot with n = 0 or n = m_items,
+ *   MRR_u = 1 / (1 + min_t pos[t]); 0 for an empty list.
+ * per_user [n_eval, 3*n_ks + 2] = precision | recall | ndcg | auc | mrr in float64, sums [3*n_ks + 2] their sums over the
+ * slots in a fixed order.  n_test sizes the temporaries (stream-ordered; nothing synchronises) and bounds every access to
+ * the per-entry arrays: entries at or past n_test are never read or written.
+ * rc 3, nothing launched and no output written: d outside {32, 64, 128, 256}, a negative size, n_test > n_eval * m_items, a
+ * NULL array, an unknown flag, a cut-off outside [1, m_items].                                                          */
+int lgcn_eval_ranks(const float *E, int32_t n_users, int32_t m_items, int32_t d,
+                    const int32_t *users, int32_t n_eval,
+                    const int64_t *train_indptr, const int32_t *train_indices,
+                    const int64_t *test_indptr, const int32_t *test_items_sorted, int64_t n_test,
+                    float *test_scores, int32_t *gt, int32_t *eq, int32_t flags, void *stream);
+int lgcn_eval_rank_metrics(int32_t n_eval, int32_t m_items, const int32_t *users,
+                           const int64_t *train_indptr, const int32_t *train_indices,
+                           const int64_t *test_indptr, const int32_t *test_items_sorted, int64_t n_test,
+                           const float *test_scores, const int32_t *gt, const int32_t *eq,
+                           const int32_t *ks, int32_t n_ks, double *per_user, double *sums, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* Item-item co-occurrence graph (preprocess_instacart_i2i.py:61-170)         */
