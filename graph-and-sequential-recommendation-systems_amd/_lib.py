@@ -120,6 +120,9 @@ SIGNATURES = {
     "lgcn_rs_phase": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     "lgcn_rs_buffer": (C.c_int, [_vp, C.c_int32, C.c_int32, C.POINTER(_vp), C.POINTER(C.c_int32)]),
     "lgcn_ctx_set_dropout": (C.c_int, [_vp, C.c_float, C.c_uint64]),
+    "lgcn_ctx_set_layer_weights": (C.c_int, [_vp, _vp, C.c_int32]),
+    "lgcn_ctx_get_layer_weights": (C.c_int32, [_vp, _vp]),
+    "lgcn_propagate_weighted": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "lgcn_dropout_mask": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_float, C.c_uint64, C.c_int64, _vp, _vp]),
     "lgcn_spmm_csr_drop": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int64, C.c_int, _vp]),
 }

@@ -17,6 +17,9 @@
 //    <= 3B non-zero rows, so the first backward SpMM skips zero rows by bitmap
 //    and gathers the flagged rows from a fp32 copy made once per step (k_g32).
 //  * the last backward SpMM applies Adam in its epilogue (no dense grad buffer).
+//  * with layer weights (lgcn_ctx_set_layer_weights) the mean becomes sum_k w_k X_k and the chain
+//    h_K = w_K G, h_{k-1} = w_{k-1} G + A h_k: Gs is then G unscaled and every backward launch carries its two
+//    coefficients (M_WTS); the weighted forms are compile-time axes, so the kernels of the mean are what they were.
 //  * the scatter-add of per-triplet gradient rows uses 64-bit fixed-point integer
 //    atomics (scale 2^50): integer addition is associative, so the result is
 //    bitwise reproducible and independent of batch sharding.
@@ -504,13 +507,18 @@ struct SpmmArgs {
     int remap;
     const float *selfX;           // M_ADDSELF: Y[row] = selfX[row] + (A X)[row]  (item-item smoothing, model.py:228-229)
     int32_t *cnt; float lam;      // reg_ego: slots of the batch naming each row (zeroed as consumed), decay / B: grad += lam * cnt[row] * P[row]
-    DropArgs dr;                  // edge dropout of the step (dr.on: the DROP instantiation is launched); last, so that every other field keeps its offset
+    DropArgs dr;                  // edge dropout of the step (dr.on: the DROP instantiation is launched); behind the older fields, so that every one of them keeps its offset
+    float w_in, w_add;            // M_WTS launches only (layer weights): Y = w_add * G[row] + w_in * (A X)[row]
 };
 
-enum { M_SPARSE = 1, M_ADDG = 2, M_ADAM = 4, M_ADDSELF = 8 };
+enum { M_SPARSE = 1, M_ADDG = 2, M_ADAM = 4, M_ADDSELF = 8, M_WTS = 16 };
 
 //   M_ADDG  : add Gs[row] where flagged (Horner term)
 //   M_ADAM  : apply torch.optim.Adam to P/M/V with grad = result, else store to Y
+//   M_WTS   : layer weights are set (lgcn_ctx_set_layer_weights): G32 holds the UNSCALED gradient rows and the launch carries the
+//             two coefficients of its Horner step, h_{k-1} = w_{k-1} G + A h_k with h_K = w_K G.  The first backward layer gathers
+//             G itself, so its product takes w_in = w_K and its Horner term w_add = w_{K-1}; every later layer has w_in = 1.
+//             A MODE bit and not a run-time test: the instantiations without it are what they were
 // Adam's operands of one row piece, fetched under the LAST gather batch of a pack (see pack_batch)
 template <int C> struct AdamPre { typename VecF<C>::T p, m, v; bool have; };
 
@@ -521,8 +529,10 @@ __device__ __forceinline__ void spmm_epilogue(const SpmmArgs &a, int64_t row, in
     typedef typename VecF<C>::T V;
     const int64_t off = row * D + l * C;
     if (MODE & M_ADDSELF) acc = row_load<D, C, IL>(a.selfX, row, l) + acc;
+    if (MODE & M_WTS) acc = a.w_in * acc;
     if ((MODE & M_ADDG) && flagged) {      // (the row's bitmap word was fetched before the gathers -- a dependent load here measured +0.3-0.6 % on the step)
         V g = row_load<D, C, IL>(a.G32, row, l);          // = (float)(G64 * 2^-50) / (K+1), converted once by k_g32
+        if (MODE & M_WTS) g = a.w_add * g;               // (there G32 is G unscaled)
         acc = g + acc;
         if ((MODE & M_ADAM) && !(MODE & M_SPARSE) && a.clear) {      // consumed: leave the workspace clean
             // (the bitmap is NOT cleared here: an atomic on words that every row's epilogue reads keeps
@@ -1019,6 +1029,7 @@ struct MeanArgs {
     const float *X0; const void *Xl[LGCN_MAX_LAYERS + 1]; int K;
     float *out; int64_t n4;      // number of 4-element pieces
     int32_t d; int64_t N;        // row width and rows of the tables (fp8 tables: where a piece's row scale lies)
+    float w[LGCN_MAX_LAYERS + 1];   // WTS instantiations only (lgcn_propagate_weighted): out = sum_k w[k] X_k
 };
 // piece i (4 consecutive elements) of an [N,d] table of TI
 template <typename TI> __device__ __forceinline__ f32x4 tab_load4(const void *tab, int64_t i, int d, int64_t N) { return load4((const TI *)tab + i * 4); }
@@ -1030,14 +1041,21 @@ template <> __device__ __forceinline__ f32x4 tab_load4<fp8_t>(const void *tab, i
     return f32x4{a[0] * sc, a[1] * sc, b[0] * sc, b[1] * sc};
 }
 
-template <typename TI>
+template <typename TI, bool WTS = false>
 __global__ void __launch_bounds__(256) k_layer_mean(MeanArgs a) {
     const float div = (float)(a.K + 1);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n4; i += (int64_t)gridDim.x * 256) {
-        f32x4 s = load4(a.X0 + i * 4);
-        for (int k = 1; k < a.K; k++) s += tab_load4<TI>(a.Xl[k], i, a.d, a.N);
-        s += load4(a.out + i * 4);
-        store4(a.out + i * 4, s / div);
+        if constexpr (WTS) {         // the weighted combination, in the same layer order
+            f32x4 s = a.w[0] * load4(a.X0 + i * 4);
+            for (int k = 1; k < a.K; k++) s += a.w[k] * tab_load4<TI>(a.Xl[k], i, a.d, a.N);
+            s += a.w[a.K] * load4(a.out + i * 4);
+            store4(a.out + i * 4, s);
+        } else {
+            f32x4 s = load4(a.X0 + i * 4);
+            for (int k = 1; k < a.K; k++) s += tab_load4<TI>(a.Xl[k], i, a.d, a.N);
+            s += load4(a.out + i * 4);
+            store4(a.out + i * 4, s / div);
+        }
     }
 }
 
@@ -1119,7 +1137,8 @@ struct BprArgs {
     // the slot rows -- it writes them to erows [3][B_local][D] and the PARTIAL dot products / squared norms over its columns to
     // colsum [3][B_local] (pos score, neg score, reg term); the ranks all-reduce colsum; k_cols_finish does the rest.
     int32_t cols_phase; float *erows; float *colsum;
-    DropArgs dr;          // edge dropout of the step (dr.on: k_triplet's DROP instantiation gathers the last layer); last: the other offsets stay
+    DropArgs dr;          // edge dropout of the step (dr.on: k_triplet's DROP instantiation gathers the last layer); behind the older fields: their offsets stay
+    float w[LGCN_MAX_LAYERS + 1];   // WTS instantiations only (layer weights): slot row e = sum_k w[k] X_k[row] instead of the mean
 };
 
 __device__ __forceinline__ float logsigmoid_f(float x) { return fminf(x, 0.f) - log1pf(expf(-fabsf(x))); }
@@ -1273,7 +1292,9 @@ units_gather(const ES &es, int64_t start, int n, int u_first, const GatherSrc &s
 }
 
 // TG: type of the table the last layer gathers from (X_{K-1}; E0 itself when K == 1)
-template <int D, typename TG, typename TI, bool BIG, bool DROP = false>
+// WTS: layer weights (a.w) instead of the mean -- every form of a slot row takes them: the lower layers' rows as they are summed
+// (spare wave or three-wave form), the gathered / hub last layer where wave 0 joins the parts
+template <int D, typename TG, typename TI, bool BIG, bool DROP = false, bool WTS = false>
 __device__ __forceinline__ void triplet_body(const BprArgs &a, const void *Xg, int2 *stage, float (*part)[TripletGeo<TI>::NW][D], float (*base)[D], float (*ego)[D]) {
     constexpr int NW = TripletGeo<TI>::NW;
     typedef Geo<D, TG, false> G;
@@ -1296,7 +1317,11 @@ __device__ __forceinline__ void triplet_body(const BprArgs &a, const void *Xg, i
             const int col = j * LPT + lane;
             float s = a.X0[row * D + col];
             if (a.reg_ego) ego[c][col] = s;
-            for (int k = 1; k < a.K; k++) s += tab_elem<TI>(a.Xl[k], a.N, D, row, col);
+            if constexpr (WTS) {
+                s *= a.w[0];
+                for (int k = 1; k < a.K; k++) s += a.w[k] * tab_elem<TI>(a.Xl[k], a.N, D, row, col);
+            } else
+                for (int k = 1; k < a.K; k++) s += tab_elem<TI>(a.Xl[k], a.N, D, row, col);
             base[c][col] = s;
         }
     };
@@ -1344,7 +1369,8 @@ __device__ __forceinline__ void triplet_body(const BprArgs &a, const void *Xg, i
             float xk = hub ? a.Xhub[rowc * D + col] : 0.f;
 #pragma unroll
             for (int i = 0; i < NW; i++) if (i < units) xk += part[c][(c + i) % NW][col];     // unit 0's wave first
-            e[c][j] = (base[c][col] + xk) / div;
+            if constexpr (WTS) e[c][j] = base[c][col] + a.w[a.K] * xk;
+            else e[c][j] = (base[c][col] + xk) / div;
         }
     }
     if (a.reg_ego) {
@@ -1357,7 +1383,7 @@ __device__ __forceinline__ void triplet_body(const BprArgs &a, const void *Xg, i
     } else triplet_loss_regs<D>(a, b, lane, e[0], e[1], e[2]);
 }
 
-template <int D, typename TI, bool BIG, bool DROP = false>
+template <int D, typename TI, bool BIG, bool DROP = false, bool WTS = false>
 __global__ void __launch_bounds__(64 * TripletGeo<TI>::NW, sizeof(TI) == 4 ? TRIPLET_MIN_WAVES_F32 : TRIPLET_MIN_WAVES) k_triplet(BprArgs a) {
     constexpr int NW = TripletGeo<TI>::NW;
     __shared__ int2 stage_lds[NW][TILE_ST];
@@ -1368,8 +1394,8 @@ __global__ void __launch_bounds__(64 * TripletGeo<TI>::NW, sizeof(TI) == 4 ? TRI
     for (int64_t i = (int64_t)blockIdx.x * (64 * NW) + threadIdx.x; i < a.bitmap_words; i += (int64_t)gridDim.x * (64 * NW))
         a.stale_bitmap[i] = 0u;
     int2 *stage = stage_lds[threadIdx.x >> 6];
-    if (a.K == 1) triplet_body<D, float, TI, BIG, DROP>(a, a.X0, stage, part_lds, base_lds, ego_lds);
-    else triplet_body<D, TI, TI, BIG, DROP>(a, a.Xl[a.K - 1], stage, part_lds, base_lds, ego_lds);
+    if (a.K == 1) triplet_body<D, float, TI, BIG, DROP, WTS>(a, a.X0, stage, part_lds, base_lds, ego_lds);
+    else triplet_body<D, TI, TI, BIG, DROP, WTS>(a, a.Xl[a.K - 1], stage, part_lds, base_lds, ego_lds);
 }
 
 // The same when the last layer was propagated densely (cfg.dense_last): e = mean_k X_k[row] is K+1 row reads per slot,
@@ -1377,7 +1403,7 @@ __global__ void __launch_bounds__(64 * TripletGeo<TI>::NW, sizeof(TI) == 4 ? TRI
 // whose positives concentrate on hub items (a popularity-weighted mean item degree in the thousands: the synthetic Yelp /
 // Amazon shapes) the slots together hold several times the graph's non-zeros -- one more dense SpMM is then far cheaper
 // than per-slot gathers (236 -> ~50 us at B = 8192).  (Until run 56 this was two launches with the slot rows in HBM between.)
-template <int D, typename TI>
+template <int D, typename TI, bool WTS = false>
 __global__ void __launch_bounds__(256) k_triplet_dense(BprArgs a) {
     constexpr int LPT = D < 64 ? D : 64, CPT = D / LPT, TPB = 256 / LPT;     // lanes per triplet, triplets per workgroup
     // last step's row bitmap is dead: zero it here with plain stores (the two bitmaps alternate per step)
@@ -1397,8 +1423,14 @@ __global__ void __launch_bounds__(256) k_triplet_dense(BprArgs a) {
             const int64_t o = rows[c] * D + j * LPT + l;
             float s = a.X0[o];
             e0[c][j] = s;
-            for (int k = 1; k <= a.K; k++) s += tab_elem<TI>(a.Xl[k], a.N, D, rows[c], j * LPT + l);
-            e[c][j] = s / div;
+            if constexpr (WTS) {        // layer weights: e = sum_k w[k] X_k[row]
+                s *= a.w[0];
+                for (int k = 1; k <= a.K; k++) s += a.w[k] * tab_elem<TI>(a.Xl[k], a.N, D, rows[c], j * LPT + l);
+                e[c][j] = s;
+            } else {
+                for (int k = 1; k <= a.K; k++) s += tab_elem<TI>(a.Xl[k], a.N, D, rows[c], j * LPT + l);
+                e[c][j] = s / div;
+            }
         }
     }
     triplet_loss_regs<D>(a, b, l, e[0], e[1], e[2], e0[0], e0[1], e0[2]);
@@ -1876,13 +1908,35 @@ static int launch_spmm_d(const SpmmArgs &a, int x_dtype, int y_dtype, hipStream_
     return 0;
 }
 
+// Layer weights (M_WTS): the four launches of the weighted Horner chain and only the type pairs they can ask for (a sparse input
+// is fp32, Adam writes fp32, a middle layer reads and writes the activation type); no fp8, no dropout
+template <int D, int MODE>
+static int launch_spmm_wts(const SpmmArgs &a, int x_dtype, int y_dtype, hipStream_t st) {
+    static_assert((MODE & M_ADDG) && !(MODE & M_ADDSELF), "the weighted forms are the Horner launches");
+    if (MODE & M_SPARSE) x_dtype = LGCN_F32;
+    if (MODE & M_ADAM) y_dtype = LGCN_F32;
+    if (x_dtype == LGCN_FP8 || y_dtype == LGCN_FP8 || a.dr.on) { lgcn_set_error("layer weights are not implemented for fp8 tables or with edge dropout"); return 3; }
+    if (x_dtype == LGCN_F32 && y_dtype == LGCN_F32) launch_spmm_t<D, float, float, MODE>(a, st);
+    else if constexpr ((MODE & M_SPARSE) != 0) {
+        if constexpr (!(MODE & M_ADAM)) launch_spmm_t<D, float, bf16_t, MODE>(a, st);
+    } else if constexpr ((MODE & M_ADAM) != 0) launch_spmm_t<D, bf16_t, float, MODE>(a, st);
+    else if (x_dtype == LGCN_BF16 && y_dtype == LGCN_BF16) launch_spmm_t<D, bf16_t, bf16_t, MODE>(a, st);
+    else { lgcn_set_error("layer weights: no such launch"); return 3; }
+    return 0;
+}
+template <int D, int MODE>
+static int launch_spmm_dm(const SpmmArgs &a, int x_dtype, int y_dtype, hipStream_t st) {
+    if constexpr ((MODE & M_WTS) != 0) return launch_spmm_wts<D, MODE>(a, x_dtype, y_dtype, st);
+    else return launch_spmm_d<D, MODE>(a, x_dtype, y_dtype, st);
+}
+
 template <int MODE>
 static int launch_spmm(const SpmmArgs &a, int d, int x_dtype, int y_dtype, hipStream_t st) {
     switch (d) {
-    case 32: return launch_spmm_d<32, MODE>(a, x_dtype, y_dtype, st);
-    case 64: return launch_spmm_d<64, MODE>(a, x_dtype, y_dtype, st);
-    case 128: return launch_spmm_d<128, MODE>(a, x_dtype, y_dtype, st);
-    case 256: return launch_spmm_d<256, MODE>(a, x_dtype, y_dtype, st);
+    case 32: return launch_spmm_dm<32, MODE>(a, x_dtype, y_dtype, st);
+    case 64: return launch_spmm_dm<64, MODE>(a, x_dtype, y_dtype, st);
+    case 128: return launch_spmm_dm<128, MODE>(a, x_dtype, y_dtype, st);
+    case 256: return launch_spmm_dm<256, MODE>(a, x_dtype, y_dtype, st);
     }
     lgcn_set_error("embedding dim must be 32, 64, 128 or 256");
     return 3;
@@ -2245,12 +2299,25 @@ extern "C" int lgcn_to_fp8(const float *src, void *dst, int64_t n_rows, int32_t 
     return 0;
 }
 
-extern "C" int lgcn_propagate_mean(const lgcn_graph *g, const float *E0, int K, int d, int act_dtype, void *work,
-                                   float *out, void *stream) {
-    if (!g || !E0 || !out || K < 1 || K > LGCN_MAX_LAYERS) { lgcn_set_error("lgcn_propagate_mean: invalid argument"); return 3; }
-    if (K > 1 && !work) { lgcn_set_error("lgcn_propagate_mean: workspace required for K > 1"); return 3; }
+// Layer weights w_0..w_K: fp32 values taken as they are.  n values for a model of K layers; finite, not all zero.
+static int check_layer_weights(const char *who, const float *w, int n, int K) {
+    char buf[192];
+    bool ok = w && n == K + 1, any = false;
+    for (int k = 0; ok && k < n; k++) { ok = isfinite(w[k]); any = any || w[k] != 0.f; }
+    if (ok && any) return 0;
+    snprintf(buf, sizeof buf, "%s: layer weights must be K + 1 = %d finite fp32 values that are not all zero (got %d)", who, K + 1, n);
+    lgcn_set_error(buf);
+    return 3;
+}
+
+// w: NULL = the mean (lgcn_propagate_mean), else K + 1 layer weights (lgcn_propagate_weighted)
+static int propagate_impl(const char *who, const lgcn_graph *g, const float *E0, int K, int d, int act_dtype, void *work,
+                          const float *w, float *out, void *stream) {
+    char buf[160];
+    if (!g || !E0 || !out || K < 1 || K > LGCN_MAX_LAYERS) { snprintf(buf, sizeof buf, "%s: invalid argument", who); lgcn_set_error(buf); return 3; }
+    if (K > 1 && !work) { snprintf(buf, sizeof buf, "%s: workspace required for K > 1", who); lgcn_set_error(buf); return 3; }
     if (check_dtype(act_dtype)) return 3;
-    if (d > g->d_max) { lgcn_set_error("lgcn_propagate_mean: d exceeds the graph's d_max"); return 3; }
+    if (d > g->d_max) { snprintf(buf, sizeof buf, "%s: d exceeds the graph's d_max", who); lgcn_set_error(buf); return 3; }
     hipStream_t st = (hipStream_t)stream;
     { int rc0 = graph_acquire(g, st); if (rc0) return rc0; }
     const int64_t N = g->n_rows;
@@ -2280,11 +2347,26 @@ extern "C" int lgcn_propagate_mean(const lgcn_graph *g, const float *E0, int K, 
     }
     const int64_t blocks = (m.n4 + 255) / 256;
     const unsigned grid = (unsigned)(blocks < 2048 ? blocks : 2048);
-    if (act_dtype == LGCN_F32) hipLaunchKernelGGL((k_layer_mean<float>), dim3(grid), dim3(256), 0, st, m);
+    if (w) {
+        for (int k = 0; k <= K; k++) m.w[k] = w[k];
+        if (act_dtype == LGCN_F32) hipLaunchKernelGGL((k_layer_mean<float, true>), dim3(grid), dim3(256), 0, st, m);
+        else hipLaunchKernelGGL((k_layer_mean<bf16_t, true>), dim3(grid), dim3(256), 0, st, m);
+    } else if (act_dtype == LGCN_F32) hipLaunchKernelGGL((k_layer_mean<float>), dim3(grid), dim3(256), 0, st, m);
     else if (act_dtype == LGCN_BF16) hipLaunchKernelGGL((k_layer_mean<bf16_t>), dim3(grid), dim3(256), 0, st, m);
     else hipLaunchKernelGGL((k_layer_mean<fp8_t>), dim3(grid), dim3(256), 0, st, m);
     HIP_OK(hipGetLastError());
     return 0;
+}
+extern "C" int lgcn_propagate_mean(const lgcn_graph *g, const float *E0, int K, int d, int act_dtype, void *work,
+                                   float *out, void *stream) {
+    return propagate_impl("lgcn_propagate_mean", g, E0, K, d, act_dtype, work, nullptr, out, stream);
+}
+extern "C" int lgcn_propagate_weighted(const lgcn_graph *g, const float *E0, int K, int d, int act_dtype, void *work,
+                                       const float *w_host, float *out, void *stream) {
+    if (K < 1 || K > LGCN_MAX_LAYERS) { lgcn_set_error("lgcn_propagate_weighted: invalid argument"); return 3; }
+    if (act_dtype == LGCN_FP8) { lgcn_set_error("lgcn_propagate_weighted: layer weights are not implemented for LGCN_FP8 activation storage"); return 3; }
+    if (int rc = check_layer_weights("lgcn_propagate_weighted", w_host, K + 1, K)) return rc;
+    return propagate_impl("lgcn_propagate_weighted", g, E0, K, d, act_dtype, work, w_host, out, stream);
 }
 
 extern "C" int lgcn_apply_perm(const int32_t *S, int s_cols, const int64_t *perm, int64_t T,
@@ -2330,6 +2412,8 @@ struct lgcn_ctx {
     // edge dropout (lgcn_ctx_set_dropout): drop_keep < 1 = on.  dr is the mask of the running step, made by lgcn_train_step from
     // the step counter as it stands BEFORE the step; forward, batch rows and backward all read it (dr.on = 0: off)
     float drop_keep; uint64_t drop_seed; DropArgs dr;
+    // layer weights (lgcn_ctx_set_layer_weights): lw_n = K + 1 values in lw, or 0 = the mean
+    int32_t lw_n; float lw[LGCN_MAX_LAYERS + 1];
 };
 // a multi-step call: nobody but this library touches E0 between its steps
 struct LoopScope {
@@ -2366,6 +2450,7 @@ extern "C" int lgcn_ctx_create(const lgcn_train_config *cfg, lgcn_ctx **out) {
     if (!x) { lgcn_set_error("out of memory"); return 4; }
     x->c = c; x->step = 0; x->N = c.graph->n_rows; x->cnt = nullptr; x->colsum = nullptr;
     x->drop_keep = 1.f; x->drop_seed = 0; x->dr = DropArgs{};
+    x->lw_n = 0; for (int k = 0; k <= LGCN_MAX_LAYERS; k++) x->lw[k] = 0.f;
     x->bm_words = (x->N + 31) / 32; x->flip = 0;
     const size_t stride = table_bytes(x->N, c.d, c.act_dtype);
     for (int k = 0; k <= LGCN_MAX_LAYERS; k++) x->act[k] = nullptr;
@@ -2457,6 +2542,7 @@ extern "C" int lgcn_ctx_set_dropout(lgcn_ctx *ctx, float keep_prob, uint64_t see
     if (!drop_prob_ok(keep_prob)) { lgcn_set_error("lgcn_ctx_set_dropout: dropout keep_prob must be in (0, 1]"); return 3; }
     if (ctx->c.act_dtype == LGCN_FP8) { lgcn_set_error("lgcn_ctx_set_dropout: edge dropout is not implemented for LGCN_FP8 activation storage"); return 3; }
     if (ctx->variant) { lgcn_set_error("lgcn_ctx_set_dropout: edge dropout is not implemented with the optional branches (item-item smoothing / popularity gate)"); return 3; }
+    if (ctx->lw_n && keep_prob < 1.f) { lgcn_set_error("lgcn_ctx_set_dropout: edge dropout is not implemented together with layer weights (lgcn_ctx_set_layer_weights)"); return 3; }
     ctx->drop_keep = keep_prob; ctx->drop_seed = seed; ctx->dr = DropArgs{};
     return 0;
 }
@@ -2465,6 +2551,32 @@ static int refuse_dropout(const lgcn_ctx *x, const char *who) {
     if (!x || !(x->drop_keep < 1.f)) return 0;
     char buf[192];
     snprintf(buf, sizeof buf, "%s: edge dropout (lgcn_ctx_set_dropout) is implemented for the single-GPU step only", who);
+    lgcn_set_error(buf);
+    return 3;
+}
+
+extern "C" int lgcn_ctx_set_layer_weights(lgcn_ctx *ctx, const float *w_host, int32_t n) {
+    if (!ctx) { lgcn_set_error("lgcn_ctx_set_layer_weights: null context"); return 3; }
+    if (!w_host || n == 0) { ctx->lw_n = 0; return 0; }            // back to the mean: the step launches what it always launched
+    if (n < 0 || n > LGCN_MAX_LAYERS + 1) n = -1;                    // (reported as a wrong count)
+    if (int rc = check_layer_weights("lgcn_ctx_set_layer_weights", w_host, n, ctx->c.K)) return rc;
+    if (ctx->c.act_dtype == LGCN_FP8) { lgcn_set_error("lgcn_ctx_set_layer_weights: layer weights are not implemented for LGCN_FP8 activation storage"); return 3; }
+    if (ctx->variant) { lgcn_set_error("lgcn_ctx_set_layer_weights: layer weights are not implemented with the optional branches (item-item smoothing / popularity gate)"); return 3; }
+    if (ctx->drop_keep < 1.f) { lgcn_set_error("lgcn_ctx_set_layer_weights: layer weights are not implemented together with edge dropout (lgcn_ctx_set_dropout)"); return 3; }
+    for (int k = 0; k < n; k++) ctx->lw[k] = w_host[k];
+    ctx->lw_n = n;
+    return 0;
+}
+extern "C" int32_t lgcn_ctx_get_layer_weights(const lgcn_ctx *ctx, float *w_out) {
+    if (!ctx || !ctx->lw_n) return 0;
+    if (w_out) for (int k = 0; k < ctx->lw_n; k++) w_out[k] = ctx->lw[k];
+    return ctx->lw_n;
+}
+// ... nor a weighted form: say so instead of training the mean
+static int refuse_layer_weights(const lgcn_ctx *x, const char *who) {
+    if (!x || !x->lw_n) return 0;
+    char buf[192];
+    snprintf(buf, sizeof buf, "%s: layer weights (lgcn_ctx_set_layer_weights) are implemented for the single-GPU step only", who);
     lgcn_set_error(buf);
     return 3;
 }
@@ -2510,6 +2622,8 @@ static int run_bpr(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const 
     BprArgs a{};
     a.reg_ego = c.reg_ego; a.cnt = (atomics && count_slots) ? x->cnt : nullptr;
     a.dr = x->dr;
+    const bool wts = x->lw_n != 0;
+    for (int k = 0; k < x->lw_n; k++) a.w[k] = x->lw[k];
     a.cols_phase = cols_phase; a.erows = c.contrib; a.colsum = x->colsum;
     a.indptr = c.graph->indptr; a.indices = c.graph->indices; a.vals = c.graph->vals; a.X0 = c.E0; a.K = c.K;
     for (int k = 1; k <= x->fwd_layers; k++) a.Xl[k] = x->act[k];
@@ -2557,8 +2671,17 @@ static int run_bpr(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const 
         } else if (c.dense_last) {
             const int tpb = 256 / (D < 64 ? D : 64);
             const unsigned gd = (unsigned)((B_local + tpb - 1) / tpb);
-            if (c.act_dtype == LGCN_F32) hipLaunchKernelGGL((k_triplet_dense<D, float>), dim3(gd), dim3(256), 0, st, a);
+            if (wts) {
+                if (c.act_dtype == LGCN_F32) hipLaunchKernelGGL((k_triplet_dense<D, float, true>), dim3(gd), dim3(256), 0, st, a);
+                else hipLaunchKernelGGL((k_triplet_dense<D, bf16_t, true>), dim3(gd), dim3(256), 0, st, a);
+            } else if (c.act_dtype == LGCN_F32) hipLaunchKernelGGL((k_triplet_dense<D, float>), dim3(gd), dim3(256), 0, st, a);
             else hipLaunchKernelGGL((k_triplet_dense<D, bf16_t>), dim3(gd), dim3(256), 0, st, a);
+        } else if (wts) {          // layer weights: the weighted slot rows (never with dropout: the setters refuse the pair)
+            if (big_table(x->N, D)) {
+                if (c.act_dtype == LGCN_F32) hipLaunchKernelGGL((k_triplet<D, float, true, false, true>), dim3(B_local), dim3(64 * TripletGeo<float>::NW), 0, st, a);
+                else hipLaunchKernelGGL((k_triplet<D, bf16_t, true, false, true>), dim3(B_local), dim3(64 * TripletGeo<bf16_t>::NW), 0, st, a);
+            } else if (c.act_dtype == LGCN_F32) hipLaunchKernelGGL((k_triplet<D, float, false, false, true>), dim3(B_local), dim3(64 * TripletGeo<float>::NW), 0, st, a);
+            else hipLaunchKernelGGL((k_triplet<D, bf16_t, false, false, true>), dim3(B_local), dim3(64 * TripletGeo<bf16_t>::NW), 0, st, a);
         } else if (a.dr.on) {      // edge dropout: the last layer's gathers take the step's mask
             if (big_table(x->N, D)) {
                 if (c.act_dtype == LGCN_F32) hipLaunchKernelGGL((k_triplet<D, float, true, true>), dim3(B_local), dim3(64 * TripletGeo<float>::NW), 0, st, a);
@@ -2668,7 +2791,7 @@ static SlotArgs slot_args(const lgcn_ctx *x, const int32_t *users, const int32_t
     const lgcn_train_config &c = x->c;
     SlotArgs s{};
     s.users = users; s.pos = pos; s.neg = neg; s.B = B; s.n_users = c.n_users; s.N = x->N;
-    s.G64 = (long long *)c.G64; s.G32 = x->g32; s.div = (float)(c.K + 1);
+    s.G64 = (long long *)c.G64; s.G32 = x->g32; s.div = x->lw_n ? 1.f : (float)(c.K + 1);      // layer weights: G32 = G, the launches scale it
     s.bitmap = c.bitmap + x->flip * x->bm_words; s.gathered = gathered; s.shard = shard; s.world = world;
     s.terms = c.terms; s.loss_out = loss_out; s.decay = c.decay; s.skip_rank = -1;
     s.ent_coeff = c.item_pop ? c.gate_entropy_coeff : 0.f;
@@ -2740,6 +2863,13 @@ static int backward_layer(lgcn_ctx *x, int k, const int32_t *users, const int32_
         }
     }
     const int prev_dt = first ? LGCN_F32 : c.act_dtype;
+    if (x->lw_n) {      // layer weights: h_{k-1} = w_{k-1} G + A h_k, h_K = w_K G (G32 is G unscaled; the first layer gathers it)
+        a.w_in = first ? x->lw[c.K] : 1.f; a.w_add = x->lw[k - 1];
+        if (first && last) return launch_spmm<M_SPARSE | M_ADDG | M_ADAM | M_WTS>(a, c.d, prev_dt, LGCN_F32, st);
+        if (first) return launch_spmm<M_SPARSE | M_ADDG | M_WTS>(a, c.d, prev_dt, c.act_dtype, st);
+        if (last) return launch_spmm<M_ADDG | M_ADAM | M_WTS>(a, c.d, prev_dt, LGCN_F32, st);
+        return launch_spmm<M_ADDG | M_WTS>(a, c.d, prev_dt, c.act_dtype, st);
+    }
     if (first && last) return launch_spmm<M_SPARSE | M_ADDG | M_ADAM>(a, c.d, prev_dt, LGCN_F32, st);
     if (first) return launch_spmm<M_SPARSE | M_ADDG>(a, c.d, prev_dt, c.act_dtype, st);
     if (last) return launch_spmm<M_ADDG | M_ADAM>(a, c.d, prev_dt, LGCN_F32, st);
@@ -2829,6 +2959,7 @@ extern "C" int lgcn_train_step_dp_part1(lgcn_ctx *x, const int32_t *users, const
     int rc = check_batch(x, users, pos, neg, B_global);
     if (rc) return rc;
     if ((rc = refuse_dropout(x, "lgcn_train_step_dp_part1"))) return rc;
+    if ((rc = refuse_layer_weights(x, "lgcn_train_step_dp_part1"))) return rc;
     if (!x->c.contrib) { lgcn_set_error("dp step: cfg.contrib exchange buffer missing"); return 3; }
     if (world < 1 || rank < 0 || rank >= world) { lgcn_set_error("dp step: bad world/rank"); return 3; }
     const int32_t shard = (B_global + world - 1) / world;
@@ -2852,6 +2983,7 @@ extern "C" int lgcn_train_step_dp_dense_part1(lgcn_ctx *x, const int32_t *users,
     int rc = check_batch(x, users, pos, neg, B_global);
     if (rc) return rc;
     if ((rc = refuse_dropout(x, "lgcn_train_step_dp_dense_part1"))) return rc;
+    if ((rc = refuse_layer_weights(x, "lgcn_train_step_dp_dense_part1"))) return rc;
     if (world < 1 || rank < 0 || rank >= world) { lgcn_set_error("dp step: bad world/rank"); return 3; }
     const int32_t shard = (B_global + world - 1) / world;
     const int32_t b_off = rank * shard;
@@ -2896,6 +3028,7 @@ extern "C" int lgcn_train_step_dp_part2(lgcn_ctx *x, const int32_t *users, const
     int rc = check_batch(x, users, pos, neg, B_global);
     if (rc) return rc;
     if ((rc = refuse_dropout(x, "lgcn_train_step_dp_part2"))) return rc;
+    if ((rc = refuse_layer_weights(x, "lgcn_train_step_dp_part2"))) return rc;
     if (!loss_out || world < 1) { lgcn_set_error("dp step part 2: invalid argument"); return 3; }
     const int32_t shard = (B_global + world - 1) / world;
     // gathered == NULL is the dense form: G64, the terms and (popularity gate) gate_total hold the reduced sums of the global batch
@@ -2918,6 +3051,7 @@ extern "C" int lgcn_train_step_cols_part1(lgcn_ctx *x, const int32_t *users, con
     int rc = check_batch(x, users, pos, neg, B);
     if (rc) return rc;
     if ((rc = refuse_dropout(x, "lgcn_train_step_cols_part1"))) return rc;
+    if ((rc = refuse_layer_weights(x, "lgcn_train_step_cols_part1"))) return rc;
     if (x->variant) { lgcn_set_error("column-sharded step: the popularity gate / item-item smoothing mix columns (MLPs over the row): not supported"); return 3; }
     if (!x->c.contrib) { lgcn_set_error("column-sharded step: cfg.contrib (3*max_batch*d floats: the batch's slot rows) missing"); return 3; }
     hipStream_t st = (hipStream_t)stream;
@@ -2932,6 +3066,7 @@ extern "C" int lgcn_train_step_cols_part2(lgcn_ctx *x, const int32_t *users, con
     int rc = check_batch(x, users, pos, neg, B);
     if (rc) return rc;
     if ((rc = refuse_dropout(x, "lgcn_train_step_cols_part2"))) return rc;
+    if ((rc = refuse_layer_weights(x, "lgcn_train_step_cols_part2"))) return rc;
     if (!loss_out) { lgcn_set_error("column-sharded step part 2: loss_out is null"); return 3; }
     hipStream_t st = (hipStream_t)stream;
     if ((rc = run_bpr(x, users, pos, neg, B, 0, B, B, true, false, st, true, 2))) return rc;
@@ -2950,6 +3085,7 @@ extern "C" int lgcn_rs_phase(lgcn_ctx *x, int32_t phase, int32_t k, const int32_
     int rc = check_batch(x, users, pos, neg, B_global);
     if (rc) return rc;
     if ((rc = refuse_dropout(x, "lgcn_rs_phase"))) return rc;
+    if ((rc = refuse_layer_weights(x, "lgcn_rs_phase"))) return rc;
     if (x->variant) { lgcn_set_error("lgcn_rs_phase: the popularity gate / item-item smoothing run on one GPU only"); return 3; }
     const lgcn_train_config &c = x->c;
     hipStream_t st = (hipStream_t)stream;
@@ -3107,7 +3243,7 @@ static int train_epoch_dp_impl(lgcn_ctx *x, lgcn_dp *dp, const int32_t *users, c
 extern "C" int lgcn_train_epoch_dp(lgcn_ctx *x, lgcn_dp *dp, const int32_t *users, const int32_t *pos, const int32_t *neg,
                                    int64_t T, int32_t B_global, int32_t reduce, const int64_t *row_ranges, float *gathered,
                                    float *loss_out, void *stream) {
-    if (refuse_dropout(x, "lgcn_train_epoch_dp")) return 3;         // (every rank's context says the same: nobody waits in a collective)
+    if (refuse_dropout(x, "lgcn_train_epoch_dp") || refuse_layer_weights(x, "lgcn_train_epoch_dp")) return 3;         // (every rank's context says the same: nobody waits in a collective)
     const int rc = train_epoch_dp_impl(x, dp, users, pos, neg, T, B_global, reduce, row_ranges, gathered, loss_out, stream);
     // a rank that leaves the loop early never reaches its next collective: release the loopback ranks waiting for it
     // (RCCL has its own abort / timeout machinery)

@@ -39,9 +39,83 @@ def _act_tables(n_tables, N, d, act_dtype, dev):
     return torch.zeros(n_tables, N, d, dtype=torch.float32 if act_dtype == _lib.F32 else torch.bfloat16, device=dev)
 
 
+def _check_layer_weights(w, K, what):
+    w = np.asarray(w, dtype=np.float64).reshape(-1)
+    if w.size != K + 1:
+        raise ValueError(f"{what}: {w.size} layer weights for --layer {K} (K + 1 = {K + 1} are needed)")
+    with np.errstate(over='ignore'):           # (an overflow becomes inf and is refused below)
+        w32 = w.astype(np.float32)
+    if not np.all(np.isfinite(w32)):
+        raise ValueError(f"{what}: layer weights must be finite, got {w.tolist()}")
+    if not np.any(w32 != 0):
+        raise ValueError(f"{what}: layer weights are all zero")
+    return w32
+
+
+def load_ppr_weights(path, K, degrees=None):
+    """--ppr_weights_path: a .npy of shape [K+1], or [N, K+1] as the reference's compute_ppr.py writes it.  That script's
+    transition matrix is row-stochastic, so every node with a neighbour gets the same row alpha (1-alpha)^k / sum: that row
+    is used.  Rows that differ by more than 1e-6 (fp32 file precision) mean per-node weights, which are not implemented.
+    Rows of isolated nodes (degrees[i] == 0; [1, 0, ...] in the reference's output) are ignored -- the one deviation: they
+    would only scale E0 rows that nothing propagates and no training triplet names."""
+    w = np.load(path)
+    if w.ndim == 1:
+        return _check_layer_weights(w, K, f"--ppr_weights_path {path}")
+    if w.ndim != 2 or w.shape[1] != K + 1:
+        raise ValueError(f"--ppr_weights_path {path}: shape {w.shape} is neither [K+1] nor [N, K+1] for --layer {K}")
+    if degrees is not None:
+        degrees = np.asarray(degrees)
+        if degrees.shape[0] != w.shape[0]:
+            raise ValueError(f"--ppr_weights_path {path}: {w.shape[0]} rows for a graph of {degrees.shape[0]} nodes")
+        w = w[degrees > 0]
+    if w.shape[0] == 0:
+        raise ValueError(f"--ppr_weights_path {path}: no row of a node with a neighbour")
+    if float(np.abs(w.astype(np.float64) - w[0].astype(np.float64)).max()) > 1e-6:
+        raise ValueError(f"--ppr_weights_path {path}: the rows of connected nodes differ: per-node weights are not implemented "
+                         "(one weight vector for all nodes is)")
+    return _check_layer_weights(w[0], K, f"--ppr_weights_path {path}")
+
+
+def resolve_layer_weights(config, K, degrees=None):
+    """(config, K) -> the fp32 [K+1] weights of out = sum_k w_k X_k, or None for the mean (the reference's combination).
+    --layer_weights mean | exp | ppr | "[w_0, ..., w_K]"; the reference's own --use_ppr_weights [--ppr_weights_path FILE]
+    (which it parses and never reads) mean `ppr` / the file's row.  degrees: neighbours per node, for a [N, K+1] file."""
+    spec = config.get('layer_weights', 'mean')
+    spec = 'mean' if spec is None else spec
+    named = spec.strip().lower() if isinstance(spec, str) else None
+    if config.get('use_ppr_weights', False):
+        if named != 'mean':
+            raise ValueError(f"--use_ppr_weights and --layer_weights {spec} both name the layer weights: give one of them")
+        if config.get('ppr_weights_path', None):
+            return load_ppr_weights(config['ppr_weights_path'], K, degrees)
+        named = 'ppr'
+    k = np.arange(K + 1, dtype=np.float64)
+    if named == 'mean':
+        return None
+    if named == 'exp':
+        beta = float(config.get('exp_smooth_beta', 0.5))
+        if not (np.isfinite(beta) and beta >= 0.0):
+            raise ValueError(f"--layer_weights exp: --exp_smooth_beta must be a finite value >= 0, got {beta}")
+        w = beta ** k
+        return _check_layer_weights(w / w.sum(), K, "--layer_weights exp")
+    if named == 'ppr':
+        alpha = float(config.get('ppr_alpha', 0.15))
+        if not (0.0 < alpha <= 1.0):
+            raise ValueError(f"--layer_weights ppr: --ppr_alpha must be in (0, 1], got {alpha}")
+        w = alpha * (1.0 - alpha) ** k
+        return _check_layer_weights(w / w.sum(), K, "--layer_weights ppr")
+    if named is not None:            # a literal list, taken as written: "[0.4,0.3,0.2,0.1]"
+        body = named[1:-1] if named[:1] in '[(' and named[-1:] in '])' else None
+        try:
+            spec = [float(v) for v in body.split(',')]
+        except (ValueError, AttributeError):
+            raise ValueError(f"--layer_weights {spec!r}: expected mean, exp, ppr or a list of K + 1 floats") from None
+    return _check_layer_weights(spec, K, "--layer_weights")
+
+
 class _Propagate(torch.autograd.Function):
-    """computer() with autograd: forward = lgcn_propagate_mean, backward = the Horner
-    chain (1/(K+1)) * sum_k A^k g through lgcn_spmm_csr (A_hat is symmetric)."""
+    """computer() with autograd: forward = lgcn_propagate_mean / _weighted, backward = the Horner
+    chain sum_k w_k A^k g (w_k = 1/(K+1) without --layer_weights) through lgcn_spmm_csr (A_hat is symmetric)."""
 
     @staticmethod
     def forward(ctx, user_w, item_w, model):
@@ -51,6 +125,13 @@ class _Propagate(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         m = ctx.model
+        if m.layer_weights is not None:      # h_K = w_K G, h_{k-1} = w_{k-1} G + A h_k: the chain of the fused step
+            w = [float(v) for v in m.layer_weights]
+            g = grad_out.contiguous().float()
+            h = w[m.n_layers] * g
+            for k in range(m.n_layers, 0, -1):
+                h = w[k - 1] * g + m._spmm(h)
+            return h[:m.n_users], h[m.n_users:], None
         g = (grad_out.contiguous().float() / float(m.n_layers + 1))
         h = g
         for _ in range(m.n_layers):
@@ -165,6 +246,18 @@ class LightGCN(nn.Module):
         if self.dropout and self.has_variants:
             raise _lib.LgcnError("--dropout 1 is not implemented together with --use_pop_gate / --use_item_item "
                                  "(the popularity gate and the item-item smoothing train without edge dropout only)")
+        # weights of the layer combination (--layer_weights, --use_ppr_weights): fp32 [K+1], or None = the reference's mean.
+        # The fused step (lgcn_ctx_set_layer_weights), the autograd path and evaluation (lgcn_propagate_weighted) all use them
+        self.layer_weights = resolve_layer_weights(config, self.n_layers, np.diff(self._adj.indptr))
+        if self.layer_weights is not None:
+            flag = "--use_ppr_weights" if config.get('use_ppr_weights', False) else "--layer_weights"
+            if str(config.get('act_dtype', 'fp32')) == 'fp8':
+                raise _lib.LgcnError(f"{flag} is not implemented together with --act_dtype fp8 (fp32 and bf16 storage only)")
+            if self.has_variants:
+                raise _lib.LgcnError(f"{flag} is not implemented together with --use_pop_gate / --use_item_item "
+                                     "(the optional branches train with the layer mean only)")
+            if self.dropout:
+                raise _lib.LgcnError(f"{flag} is not implemented together with --dropout 1 (edge dropout trains with the layer mean only)")
         self._gate_flat = None      # the eight MLP tensors of the gate in ONE buffer (what the fused step reads / updates)
         self._Graph = None
         self._dev = None            # device-side state (graph, workspace, context)
@@ -384,6 +477,13 @@ class LightGCN(nn.Module):
                 msg = lib.lgcn_last_error()
                 lib.lgcn_ctx_destroy(h)
                 raise _lib.LgcnError(f"lgcn_ctx_set_dropout failed (rc={rc}): {msg.decode() if msg else ''}")
+        if self.layer_weights is not None:
+            w = np.ascontiguousarray(self.layer_weights, dtype=np.float32)
+            rc = lib.lgcn_ctx_set_layer_weights(h, w.ctypes.data_as(C.c_void_p), int(w.size))
+            if rc:
+                msg = lib.lgcn_last_error()
+                lib.lgcn_ctx_destroy(h)
+                raise _lib.LgcnError(f"lgcn_ctx_set_layer_weights failed (rc={rc}): {msg.decode() if msg else ''}")
         st['ctx'], st['max_batch'], st['dp_world'], st['table_ptr'] = h, max_batch, dp_world, self._table.data_ptr()
         st['ctx_rows'] = rows
 
@@ -447,6 +547,12 @@ class LightGCN(nn.Module):
             work = st['eval_work'] = _act_tables(K - 1, N, d, act_dtype, self._table.device)
             st['eval_work_dtype'] = act_dtype
         out = torch.empty(N, d, dtype=torch.float32, device=self._table.device)
+        if self.layer_weights is not None:
+            w = np.ascontiguousarray(self.layer_weights, dtype=np.float32)
+            _lib.check(_lib.load().lgcn_propagate_weighted(
+                st['graph'].handle, _lib.tp(self._table), K, d, act_dtype, _lib.tp(work) if K > 1 else None,
+                w.ctypes.data_as(C.c_void_p), _lib.tp(out), _lib.current_stream()), "lgcn_propagate_weighted")
+            return out
         _lib.check(_lib.load().lgcn_propagate_mean(
             st['graph'].handle, _lib.tp(self._table), K, d, act_dtype, _lib.tp(work) if K > 1 else None,
             _lib.tp(out), _lib.current_stream()), "lgcn_propagate_mean")

@@ -104,6 +104,13 @@ def build_parser():
                         'CLI (one basket per line of train.txt) whenever every user is one line')
     p.add_argument('--i2i_topk', type=int, default=50, help='NEW: neighbours kept per item by --i2i_build (1..256)')
     p.add_argument('--i2i_min_basket', type=int, default=1, help='NEW: --i2i_build skips baskets with fewer items')
+    p.add_argument('--layer_weights', type=str, default='mean',
+                   help="NEW: weights of the layer combination out = sum_k w_k X_k, in the fused step, the autograd path and evaluation. "
+                        "'mean' (default) = the reference: 1/(K+1) each; 'exp' = w_k ~ beta^k with --exp_smooth_beta, normalised; "
+                        "'ppr' = w_k ~ alpha (1-alpha)^k with --ppr_alpha, normalised (--use_ppr_weights means this); or a literal list "
+                        "of K+1 floats such as \"[0.4,0.3,0.2,0.1]\", taken as written. fp32 / bf16 storage, single GPU, default model")
+    p.add_argument('--ppr_alpha', type=float, default=0.15,
+                   help="NEW: teleport probability of --layer_weights ppr (the default of the reference's compute_ppr.py)")
     p.add_argument('--data_path', type=str, default=None,
                    help='NEW: directory that holds <dataset>/train.txt (default: <root>/data)')
     return p

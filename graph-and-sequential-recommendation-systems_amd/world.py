@@ -111,6 +111,8 @@ def configure(argv=None):
     config['i2i_build'] = args.i2i_build
     config['i2i_topk'] = args.i2i_topk
     config['i2i_min_basket'] = args.i2i_min_basket
+    config['layer_weights'] = args.layer_weights
+    config['ppr_alpha'] = args.ppr_alpha
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     return config
 

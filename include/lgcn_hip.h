@@ -162,6 +162,10 @@ int lgcn_spmm_csr_drop(const lgcn_graph *g, const void *X, int x_dtype, void *Y,
  * of act_dtype (may be NULL for K == 1).                                       */
 int lgcn_propagate_mean(const lgcn_graph *g, const float *E0, int K, int d, int act_dtype,
                         void *work, float *out, void *stream);
+/* The same with layer weights: out = sum_k w_host[k] * A^k X_0 for the K + 1 fp32 values w_host[0..K] (host memory), used
+ * as they are (no normalisation).  LGCN_F32 / LGCN_BF16 storage.  rc 3: a non-finite weight, all weights zero, LGCN_FP8.     */
+int lgcn_propagate_weighted(const lgcn_graph *g, const float *E0, int K, int d, int act_dtype,
+                            void *work, const float *w_host, float *out, void *stream);
 
 /* The same permutation from the same stream, produced ON THE DEVICE (d_perm: device int64[n]): one wave twists MT19937 in LDS
  * and aligns the draws to the Fisher-Yates steps as it generates them (64 per pass), then the swaps are resolved as sorted chains +
@@ -264,6 +268,20 @@ void lgcn_ctx_set_lr(lgcn_ctx *ctx, double lr);
  * uses LGCN_FP8 storage or an optional branch (i2i / popularity gate).  While dropout is on, every entry point that splits
  * a step over ranks (lgcn_train_step_dp_* / _cols_*, lgcn_rs_phase, lgcn_train_epoch_dp) returns 3 and says so.          */
 int lgcn_ctx_set_dropout(lgcn_ctx *ctx, float keep_prob, uint64_t seed);
+/* Layer weights in the training step (--layer_weights): the model's output becomes  out = sum_k w_k X_k  (X_0 = E0,
+ * X_k = A_hat X_{k-1}) instead of the mean, for the n = K + 1 fp32 values w_host[0..K] (host memory), used exactly as given.
+ * lgcn_train_step / _i64 / lgcn_train_epoch then form the weighted rows of the batch and run the backward chain
+ *     h_K = w_K G,   h_{k-1} = w_{k-1} G + A_hat h_k,   gradient = h_0        (G = d loss / d out)
+ * with the same launches as the mean (the weights travel as kernel arguments).  reg_ego is untouched by the weights; the
+ * default L2 term is taken on the weighted rows.  w_host == NULL or n == 0 restores the mean: the step then launches exactly
+ * the kernels it launches without this call, with the same arguments.  rc 3 (the error text names the layer weights):
+ * n != K + 1, a non-finite value, all zeros, LGCN_FP8 storage, an optional branch (i2i / popularity gate), dropout on.
+ * While weights are set lgcn_ctx_set_dropout refuses, and every entry point that splits a step over ranks
+ * (lgcn_train_step_dp_* / _cols_*, lgcn_rs_phase, lgcn_train_epoch_dp) returns 3 and says so.                             */
+int lgcn_ctx_set_layer_weights(lgcn_ctx *ctx, const float *w_host, int32_t n);
+/* The weights in force: writes them to w_out (room for LGCN_MAX_LAYERS + 1 floats; may be NULL) and returns their count;
+ * 0 = the mean.                                                                                                          */
+int32_t lgcn_ctx_get_layer_weights(const lgcn_ctx *ctx, float *w_out);
 /* Data parallel, rows mode: 1 = part 1 of a step also adds this rank's OWN gradient rows into its G64 (besides writing
  * them to the exchange block) and part 2 scatters only the other ranks' blocks -- what lgcn_train_epoch_dp does itself;
  * 0 (default) = part 2 scatters every block (one context may then play several ranks, as the emulation tests do). */
