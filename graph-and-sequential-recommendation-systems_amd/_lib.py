@@ -47,6 +47,18 @@ class TrainConfig(C.Structure):
     ]
 
 
+class MfConfig(C.Structure):
+    """Mirror of lgcn_mf_config (include/lgcn_hip.h)."""
+    _fields_ = [
+        ("n_users", C.c_int32), ("m_items", C.c_int32), ("d", C.c_int32),
+        ("E0", _vp), ("adam_m", _vp), ("adam_v", _vp),
+        ("G64", _vp), ("bitmap", _vp), ("terms", _vp),
+        ("err", _vp), ("max_batch", C.c_int32),
+        ("decay", C.c_float),
+        ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/lgcn_hip.h declares
 SIGNATURES = {
     "lgcn_abi_version": (C.c_int, []),
@@ -125,6 +137,14 @@ SIGNATURES = {
     "lgcn_propagate_weighted": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "lgcn_dropout_mask": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_float, C.c_uint64, C.c_int64, _vp, _vp]),
     "lgcn_spmm_csr_drop": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int64, C.c_int, _vp]),
+    "lgcn_mf_create": (C.c_int, [C.POINTER(MfConfig), C.POINTER(_vp)]),
+    "lgcn_mf_destroy": (None, [_vp]),
+    "lgcn_mf_get_step": (C.c_int64, [_vp]),
+    "lgcn_mf_set_step": (None, [_vp, C.c_int64]),
+    "lgcn_mf_set_lr": (None, [_vp, C.c_double]),
+    "lgcn_mf_train_step": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _vp, _vp]),
+    "lgcn_mf_train_epoch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, _vp, _vp]),
+    "lgcn_mf_check": (C.c_int, [_vp, _vp]),
 }
 
 _LIB = None

@@ -716,3 +716,228 @@ class LightGCN(nn.Module):
     @property
     def adam_step(self):
         return _lib.load().lgcn_ctx_get_step(self._dev['ctx']) if self._dev and self._dev.get('ctx') else 0
+
+    def set_adam_step(self, step):
+        """torch Adam's state['step'] of a loaded optimizer state -> the training context (made if need be)."""
+        _lib.load().lgcn_ctx_set_step(self._state(need_ctx=True)['ctx'], int(step))
+
+
+class PureMF(nn.Module):
+    """Matrix factorisation trained with BPR: upstream LightGCN's second model (`--model mf`, the class the reference's
+    register.py:43-44 registers when it exists) and the baseline every LightGCN number is read against.
+
+    Same constructor `(config, dataset)` and state_dict keys as LightGCN; the tables keep nn.Embedding's own N(0, 1) init
+    (upstream PureMF calls no normal_), and live in ONE contiguous [N, d] fp32 table, rows [0, n_users) the users.  No graph
+    is built or loaded.  BPRLoss.stageOne / fused_step / fused_epoch run the two HIP launches of csrc/lgcn_mf.hip
+    (lgcn_mf_train_step / _epoch: loss, gradient rows, dense torch.optim.Adam); there is no CPU fallback.  `bpr_loss` is the
+    plain torch restatement on the parameter views (autograd-capable: what the fused step is cross-checked against).
+
+    `--layer` is ignored.  The fork's optional branches and the LightGCN-only switches are refused at construction."""
+    has_variants = False
+    fused_variants = False
+    use_pop_gate = False
+    dropout = False
+    layer_weights = None
+
+    def __init__(self, config, dataset):
+        super().__init__()
+        self.config = config
+        self.dataset = dataset
+        self.device = world.device
+        self.n_users = dataset.n_users
+        self.m_items = dataset.m_items
+        self.latent_dim = config['latent_dim_rec']
+        no = "is not implemented for --model mf"
+        if config.get('use_pop_gate', False):
+            raise _lib.LgcnError(f"--use_pop_gate {no} (the popularity gate belongs to LightGCN)")
+        if config.get('use_item_item', False):
+            raise _lib.LgcnError(f"--use_item_item {no} (the item-item smoothing belongs to LightGCN)")
+        if int(config.get('dropout', 0)):
+            raise _lib.LgcnError(f"--dropout 1 {no} (there is no graph whose edges could be dropped)")
+        lw = config.get('layer_weights', 'mean')
+        if not (lw is None or (isinstance(lw, str) and lw.strip().lower() == 'mean')):
+            raise _lib.LgcnError(f"--layer_weights {lw} {no} (there are no layers to combine)")
+        if config.get('use_ppr_weights', False):
+            raise _lib.LgcnError(f"--use_ppr_weights {no} (there are no layers to combine)")
+        if str(config.get('act_dtype', 'fp32')) != 'fp32':
+            raise _lib.LgcnError(f"--act_dtype {config.get('act_dtype')} {no} (fp32 tables only)")
+        if self.latent_dim not in (32, 64, 128, 256):
+            raise ValueError("latent_dim_rec must be 32, 64, 128 or 256 for the HIP kernels")
+        if self.n_users + self.m_items >= 2 ** 31:
+            raise ValueError("n_users + m_items must stay below 2^31")
+        # RNG consumption of upstream PureMF: the two nn.Embedding constructors in this order, their own N(0, 1) init kept
+        self.embedding_user = nn.Embedding(self.n_users, self.latent_dim)
+        self.embedding_item = nn.Embedding(self.m_items, self.latent_dim)
+        with torch.no_grad():
+            table = torch.cat([self.embedding_user.weight, self.embedding_item.weight], dim=0).contiguous()
+        self._table = table
+        self._rebind()
+        self._dev = None            # device-side state (Adam moments, workspace, context)
+        self.f = nn.Sigmoid()
+
+    # -- parameters live in one table (as in LightGCN) ---------------------------------
+    def _rebind(self):
+        self.embedding_user.weight.data = self._table[:self.n_users]
+        self.embedding_item.weight.data = self._table[self.n_users:]
+
+    def _apply(self, fn, recurse=True):
+        new = fn(self._table)
+        if new is not self._table:
+            self._table = new
+            self._drop_device_state()
+        self._rebind()
+        for p in (self.embedding_user.weight, self.embedding_item.weight):
+            if p.grad is not None:
+                p.grad = fn(p.grad)
+        return self
+
+    def _check_table(self):
+        u, i = self.embedding_user.weight, self.embedding_item.weight
+        if (u.data_ptr() != self._table.data_ptr()
+                or i.data_ptr() != self._table.data_ptr() + self.n_users * self.latent_dim * 4):
+            with torch.no_grad():
+                self._table[:self.n_users].copy_(u.data)
+                self._table[self.n_users:].copy_(i.data)
+            self._rebind()
+
+    # -- device state -----------------------------------------------------------------
+    def _drop_device_state(self):
+        if self._dev is not None and self._dev.get('ctx'):
+            _lib.load().lgcn_mf_destroy(self._dev['ctx'])
+        self._dev = None
+
+    def __del__(self):
+        try:
+            self._drop_device_state()
+        except Exception:
+            pass
+
+    def _state(self, max_batch=None, need_ctx=False, **_):
+        _lib.require_gpu()
+        if not self._table.is_cuda:
+            raise _lib.LgcnError("model parameters are not on the GPU: call .to(world.device) first")
+        self._check_table()
+        if self._dev is None:
+            self._dev = {'ctx': None, 'max_batch': 0}
+        st = self._dev
+        if need_ctx:
+            max_batch = int(max_batch or self.config.get('bpr_batch_size', 2048))
+            if st['ctx'] is None or st['max_batch'] < max_batch or st.get('table_ptr') != self._table.data_ptr():
+                self._make_ctx(max_batch)
+        return st
+
+    def _make_ctx(self, max_batch):
+        st, dev = self._dev, self._table.device
+        lib = _lib.load()
+        old_step = 0
+        if st['ctx'] is not None:
+            old_step = lib.lgcn_mf_get_step(st['ctx'])
+            lib.lgcn_mf_destroy(st['ctx'])
+            st['ctx'] = None
+        N, d = self.n_users + self.m_items, self.latent_dim
+        if 'adam_m' not in st:
+            st['adam_m'] = torch.zeros(N, d, dtype=torch.float32, device=dev)
+            st['adam_v'] = torch.zeros(N, d, dtype=torch.float32, device=dev)
+        # (a step leaves G64 all zero and one bitmap flagged; a new context starts on fresh ones)
+        st['G64'] = torch.zeros(N, d, dtype=torch.int64, device=dev)
+        st['bitmap'] = torch.zeros(2 * ((N + 31) // 32), dtype=torch.int32, device=dev)
+        st['terms'] = torch.zeros(2 * max_batch, dtype=torch.float32, device=dev)
+        st['err'] = torch.zeros(1, dtype=torch.int32, device=dev)
+        cfg = _lib.MfConfig()
+        cfg.n_users, cfg.m_items, cfg.d = self.n_users, self.m_items, d
+        cfg.E0, cfg.adam_m, cfg.adam_v = self._table.data_ptr(), st['adam_m'].data_ptr(), st['adam_v'].data_ptr()
+        cfg.G64, cfg.bitmap, cfg.terms = st['G64'].data_ptr(), st['bitmap'].data_ptr(), st['terms'].data_ptr()
+        cfg.err, cfg.max_batch = st['err'].data_ptr(), max_batch
+        cfg.decay = float(self.config.get('decay', 1e-4))
+        cfg.lr = float(self.config.get('lr', 1e-3))
+        cfg.beta1, cfg.beta2, cfg.eps = 0.9, 0.999, 1e-8
+        h = C.c_void_p()
+        _lib.check(lib.lgcn_mf_create(C.byref(cfg), C.byref(h)), "lgcn_mf_create")
+        lib.lgcn_mf_set_step(h, old_step)
+        st['ctx'], st['max_batch'], st['table_ptr'] = h, max_batch, self._table.data_ptr()
+
+    # -- reference API --------------------------------------------------------------------
+    def invalidate_cache(self):
+        """Nothing is cached: the scores are taken on the table itself."""
+
+    def propagated_table(self):
+        """The [N, d] fp32 table computer() splits into users / items: the parameters themselves."""
+        return self._table
+
+    def rating_table(self):
+        """What the fused evaluation kernels rank with: the table itself, i.e. the RAW scores U . I^T.  getUsersRating applies
+        a sigmoid, which is monotone and in fp32 merges distinct scores (everything above ~16.6 becomes 1.0), so ranking the
+        raw scores refines upstream's ranking and never contradicts it."""
+        return self._table
+
+    def computer(self):
+        """-> (all_users [n_users, d], all_items [m_items, d]): the two parameter views."""
+        return self.embedding_user.weight, self.embedding_item.weight
+
+    def getUsersRating(self, users):
+        all_users, all_items = self.computer()
+        return self.f(torch.matmul(all_users[users.long()], all_items.t()))
+
+    def getEmbedding(self, users, pos_items, neg_items):
+        all_users, all_items = self.computer()
+        return all_users[users.long()], all_items[pos_items.long()], all_items[neg_items.long()], all_users, all_items
+
+    def bpr_loss(self, users, pos, neg):
+        """Upstream PureMF.bpr_loss in plain torch (autograd-capable): (mean softplus(neg - pos), reg_loss)."""
+        u, pos_e, neg_e, _, _ = self.getEmbedding(users, pos, neg)
+        pos_scores = torch.sum(u * pos_e, dim=1)
+        neg_scores = torch.sum(u * neg_e, dim=1)
+        loss = torch.mean(F.softplus(neg_scores - pos_scores))
+        reg_loss = (0.5 * (u.norm(2).pow(2) + pos_e.norm(2).pow(2) + neg_e.norm(2).pow(2))) / float(u.shape[0])
+        return loss, reg_loss
+
+    def forward(self, users, items):
+        all_users, all_items = self.computer()
+        return self.f(torch.sum(all_users[users.long()] * all_items[items.long()], dim=1))
+
+    # -- fused path (what BPRLoss.stageOne calls) ------------------------------------------
+    _ids = staticmethod(LightGCN._ids)
+
+    def fused_step(self, users, pos, neg, loss_out=None, lr=None):
+        """One BPRLoss.stageOne in the HIP kernels (lgcn_mf_train_step).  Returns a device tensor [3] =
+        (bpr + decay*reg, bpr, reg); no host synchronisation."""
+        dev = self._table.device
+        users, pos, neg = self._ids(users, dev), self._ids(pos, dev), self._ids(neg, dev)
+        B = int(users.numel())
+        st = self._state(max_batch=max(B, int(self.config.get('bpr_batch_size', B))), need_ctx=True)
+        lib = _lib.load()
+        if lr is not None:
+            lib.lgcn_mf_set_lr(st['ctx'], float(lr))
+        if loss_out is None:
+            loss_out = torch.empty(3, dtype=torch.float32, device=dev)
+        _lib.check(lib.lgcn_mf_train_step(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(neg), B, _lib.tp(loss_out),
+                                          _lib.current_stream()), "lgcn_mf_train_step")
+        return loss_out
+
+    def fused_epoch(self, users, pos, neg, batch_size, lr=None):
+        """The loop of main.py:223-225 over already-shuffled device id arrays, one C call (lgcn_mf_train_epoch).
+        Returns a device tensor [steps,3] of per-step (loss, bpr, reg)."""
+        dev = self._table.device
+        users, pos, neg = self._ids(users, dev), self._ids(pos, dev), self._ids(neg, dev)
+        T = int(users.numel())
+        steps = (T + batch_size - 1) // batch_size
+        st = self._state(max_batch=batch_size, need_ctx=True)
+        lib = _lib.load()
+        if lr is not None:
+            lib.lgcn_mf_set_lr(st['ctx'], float(lr))
+        losses = torch.empty(steps, 3, dtype=torch.float32, device=dev)
+        _lib.check(lib.lgcn_mf_train_epoch(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(neg), T, int(batch_size),
+                                           _lib.tp(losses), _lib.current_stream()), "lgcn_mf_train_epoch")
+        return losses
+
+    def check_device_errors(self):
+        if self._dev and self._dev.get('ctx'):
+            _lib.check(_lib.load().lgcn_mf_check(self._dev['ctx'], _lib.current_stream()), "device id check")
+
+    @property
+    def adam_step(self):
+        return _lib.load().lgcn_mf_get_step(self._dev['ctx']) if self._dev and self._dev.get('ctx') else 0
+
+    def set_adam_step(self, step):
+        """torch Adam's state['step'] of a loaded optimizer state -> the training context (made if need be)."""
+        _lib.load().lgcn_mf_set_step(self._state(need_ctx=True)['ctx'], int(step))

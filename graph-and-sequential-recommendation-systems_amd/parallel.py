@@ -132,6 +132,9 @@ class DataParallelBPR:
 
     def __init__(self, recmodel, config, group=None, reduce='rows', shard='batch'):
         from .utils import _AdamView
+        if type(recmodel).__name__ == 'PureMF':
+            raise RuntimeError("--model mf is implemented for single-GPU training only: DataParallelBPR has no matrix-factorisation "
+                               "step (data-parallel MF is out of scope)")
         if getattr(recmodel, 'layer_weights', None) is not None:
             raise RuntimeError("--layer_weights / --use_ppr_weights are implemented for single-GPU training only: DataParallelBPR "
                                "(every reduce / shard mode) has no weighted layer combination")

@@ -89,7 +89,7 @@ class _AdamView(optim.Adam):
                         st['gate_m'][off:off + p.numel()].copy_(s['exp_avg'].reshape(-1))
                         st['gate_v'][off:off + p.numel()].copy_(s['exp_avg_sq'].reshape(-1))
                     off += p.numel()
-        _lib.load().lgcn_ctx_set_step(st['ctx'], step)
+        m.set_adam_step(step)           # (LightGCN and PureMF keep different context types)
         self._sync_from_kernel()
 
     def step(self, closure=None):

@@ -545,6 +545,67 @@ int lgcn_rs_buffer(const lgcn_ctx *ctx, int32_t phase, int32_t k, void **buf, in
  * 1 = id out of range in users/pos/neg.                                        */
 int lgcn_ctx_check(lgcn_ctx *ctx, void *stream);
 
+/* ------------------------------------------------------------------------ */
+/* Device: matrix factorisation (--model mf) -- replaces BPRLoss.stageOne    */
+/*   utils.py:53-64 on upstream LightGCN's PureMF (the model the reference's */
+/*   register.py:43-44 registers "if it exists"):                            */
+/*   = PureMF.bpr_loss (embedding lookups, softplus(neg - pos).mean(), the    */
+/*     L2 term on the looked-up rows) + loss.backward() + torch.optim.Adam    */
+/*     .step on the DENSE gradient of both tables (utils.py:51,62)            */
+/* ------------------------------------------------------------------------ */
+/* No graph and no propagation: the scores are dot products of the tables' own rows.  For a batch of B triplets (u, p, n)
+ * with rows U, P, Nn:   x_b = <U_b, Nn_b> - <U_b, P_b>,   bpr = mean_b softplus(x_b),   reg = 1/2 (|U|^2 + |P|^2 + |Nn|^2) / B,
+ * loss = bpr + decay * reg.  With s_b = sigmoid(x_b) row u receives (s_b (Nn_b - P_b) + decay U_b) / B, row p
+ * (-s_b U_b + decay P_b) / B and row n (s_b U_b + decay Nn_b) / B; repeated ids sum (2^50 fixed point: in any order, bit for
+ * bit).  Adam is torch's dense one: EVERY row is updated every step, rows outside the batch with g = 0.
+ * Two launches per step (k_mf_triplet, k_mf_adam), no host sync, no allocation; after a step G64 is all zero again.      */
+typedef struct lgcn_mf lgcn_mf;   /* opaque */
+
+typedef struct {
+    int32_t n_users;
+    int32_t m_items;            /* N = n_users + m_items < 2^31 */
+    int32_t d;                  /* latent_dim_rec: 32/64/128/256 */
+    /* parameters + Adam state, fp32 [N,d]: rows [0,n_users) = embedding_user.weight,
+     * rows [n_users,N) = embedding_item.weight */
+    float *E0;
+    float *adam_m;
+    float *adam_v;
+    /* workspace, caller-allocated, zero-initialised before the first step */
+    int64_t *G64;               /* [N,d] fixed-point (2^50) accumulator of the batch rows' gradient */
+    uint32_t *bitmap;           /* [2*ceil(N/32)] rows of G64 that are non-zero (two, used alternately) */
+    float *terms;               /* [2*max_batch] per-triplet loss / reg terms */
+    int32_t *err;               /* [1] device error flag */
+    int32_t max_batch;
+    /* hyper-parameters (utils.py:47-51, torch.optim.Adam defaults) */
+    float decay;                /* config['decay'] */
+    double lr, beta1, beta2, eps;
+} lgcn_mf_config;
+
+/* rc 3 (nothing allocated): a null pointer, d outside {32, 64, 128, 256}, n_users or m_items < 1, N >= 2^31, max_batch < 1.
+ * The context owns no device memory. */
+int lgcn_mf_create(const lgcn_mf_config *cfg, lgcn_mf **out);
+void lgcn_mf_destroy(lgcn_mf *mf);
+/* optimizer step counter (torch Adam state['step']) for checkpoint/resume, and the learning rate of the next step */
+int64_t lgcn_mf_get_step(const lgcn_mf *mf);
+void lgcn_mf_set_step(lgcn_mf *mf, int64_t step);
+void lgcn_mf_set_lr(lgcn_mf *mf, double lr);
+
+/* One full stageOne on a batch of B triplets (device int32 ids): replaces PureMF.bpr_loss + backward + Adam.step.
+ * loss_out[0..2] (device) = {bpr + decay*reg, bpr, reg}.  No host sync.  An id outside its table raises the device error
+ * flag (lgcn_mf_check) and its triplet contributes nothing (zero terms, no gradient); the step still divides by B.
+ * rc 3, with nothing launched and nothing written: a null pointer, B < 1, B > max_batch.                                  */
+int lgcn_mf_train_step(lgcn_mf *mf, const int32_t *users, const int32_t *pos, const int32_t *neg,
+                       int32_t B, float *loss_out, void *stream);
+
+/* A whole epoch: the loop of main.py:223-225 over ceil(T/B) consecutive batches of the (already shuffled) device arrays,
+ * the last one short.  loss_out: [3*ceil(T/B)].  Bit for bit the loop of lgcn_mf_train_step.  Same rc 3 cases.           */
+int lgcn_mf_train_epoch(lgcn_mf *mf, const int32_t *users, const int32_t *pos, const int32_t *neg,
+                        int64_t T, int32_t B, float *loss_out, void *stream);
+
+/* reads and clears the device error flag (synchronises the stream): 0 = none,
+ * 1 = id out of range in users/pos/neg.                                        */
+int lgcn_mf_check(lgcn_mf *mf, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
