@@ -145,6 +145,10 @@ SIGNATURES = {
     "lgcn_mf_train_step": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _vp, _vp]),
     "lgcn_mf_train_epoch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, _vp, _vp]),
     "lgcn_mf_check": (C.c_int, [_vp, _vp]),
+    "lgcn_ctx_set_fold_g32": (C.c_int, [_vp, C.c_int]),
+    "lgcn_ctx_folded_steps": (C.c_int64, [_vp]),
+    "lgcn_ctx_copy_arrivals": (C.c_int, [_vp, _vp, C.c_int64]),
+    "lgcn_slot_multiplicity": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int64, _vp, _vp]),
 }
 
 _LIB = None

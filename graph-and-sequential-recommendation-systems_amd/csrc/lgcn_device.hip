@@ -1139,6 +1139,10 @@ struct BprArgs {
     int32_t cols_phase; float *erows; float *colsum;
     DropArgs dr;          // edge dropout of the step (dr.on: k_triplet's DROP instantiation gathers the last layer); behind the older fields: their offsets stay
     float w[LGCN_MAX_LAYERS + 1];   // WTS instantiations only (layer weights): slot row e = sum_k w[k] X_k[row] instead of the mean
+    // The fold of k_g32 into this launch (lgcn_train_epoch's single-GPU steps): mult != NULL.  mult[c * B_local + b]
+    // = slots of THIS batch that name slot (c, b)'s row (k_slot_mult, once per call); the workgroup that completes a row writes
+    // its fp32 copy G32[row] = (float)(G64[row] * 2^-50) / gdiv itself.  arrive: [N] arrival tickets of the shared rows, zero between steps
+    const uint16_t *mult; float *G32; float gdiv; int32_t *arrive;
 };
 
 __device__ __forceinline__ float logsigmoid_f(float x) { return fminf(x, 0.f) - log1pf(expf(-fabsf(x))); }
@@ -1195,6 +1199,49 @@ __device__ __forceinline__ void triplet_loss_regs(const BprArgs &a, int b, int l
     triplet_finish<D>(a, b, l, u, p, n, ps, ns, rr);
 }
 
+#ifndef FOLD_TICKET_ALL
+#define FOLD_TICKET_ALL 0      /* the fold of k_g32: 0 = a row named by ONE slot of the batch is written to G32 directly (no G64 atomics,
+                                  no ticket); 1 = every row goes through G64 and the ticket (A/B form: profiles/fold_g32/README.md) */
+#endif
+// The fold's hand-off for the rows of a triplet that m > 1 slots of the batch name (a.mult): this lane group has just added its
+// three gradient rows (m[c] > 1: into G64[row]).  It drains those atomics ONCE and takes its tickets with ONE instruction -- lane
+// c of the group adds 1 to the arrival counter of slot c's row -- so a triplet pays one drain and one atomic round trip however
+// many of its rows are shared (one of each per slot was slower: the chain sits at the end of every workgroup; profiles/fold_g32/README.md).
+// The group whose ticket on a row is m - 1 is the last one there; every other group's adds were drained before its own ticket,
+// so it reads the complete fixed-point row (agent-scope loads behind an agent acquire: the hand-off of k_spmm's split rows, with
+// atomics as the payload stores; the acquiring wave's own loads need no wait for the invalidate), converts it exactly as k_g32
+// does and leaves the counter zero for the next step.  Nobody waits: a group that is not last just goes on.  A triplet whose
+// positive and negative are one row takes two tickets on it (two lanes, two values).  The lane group is LPT lanes of one wave.
+template <int D>
+__device__ __forceinline__ void fold_close_rows(const BprArgs &a, const int64_t (&rows)[3], const int (&m)[3], int l) {
+    constexpr int LPT = D < 64 ? D : 64, CPL = D / LPT, MIN_SHARED = FOLD_TICKET_ALL ? 1 : 2;
+    typedef __attribute__((address_space(1))) unsigned long long gu64;
+    if (m[0] < MIN_SHARED && m[1] < MIN_SHARED && m[2] < MIN_SHARED) return;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const int ml = l == 0 ? m[0] : (l == 1 ? m[1] : m[2]);
+    const int64_t rl = l == 0 ? rows[0] : (l == 1 ? rows[1] : rows[2]);
+    int ticket = -1;
+    if (l < 3 && ml >= MIN_SHARED) ticket = __hip_atomic_fetch_add(a.arrive + rl, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    bool last[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const int t = LPT == 64 ? __builtin_amdgcn_readlane(ticket, c) : __shfl(ticket, c, LPT);
+        last[c] = m[c] >= MIN_SHARED && t == m[c] - 1;
+    }
+    if (!(last[0] || last[1] || last[2])) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (l < 3 && ml >= MIN_SHARED && ticket == ml - 1) __hip_atomic_store(a.arrive + rl, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // next step
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        if (!last[c]) continue;
+#pragma unroll
+        for (int j = 0; j < CPL; j++) {
+            const long long q = (long long)__hip_atomic_load((gu64 *)(a.G64 + rows[c] * D + j * LPT + l), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            a.G32[rows[c] * D + j * LPT + l] = (float)((double)q * FIXED_INV) / a.gdiv;
+        }
+    }
+}
+
 // loss terms + the three gradient rows of one triplet from its slot rows and its (complete) dot products
 template <int D>
 __device__ __forceinline__ void triplet_finish(const BprArgs &a, int b, int l, const float *u, const float *p, const float *n,
@@ -1212,14 +1259,25 @@ __device__ __forceinline__ void triplet_finish(const BprArgs &a, int b, int l, c
     }
     if (tbad && !a.exchange) return;
     const int64_t rows[3] = {(int64_t)a.users[b], (int64_t)a.pos[b] + a.n_users, (int64_t)a.neg[b] + a.n_users};
+    int mm[3] = {0, 0, 0};
+    if (a.mult) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) mm[c] = (int)a.mult[c * a.B_local + b];
+    }
 #pragma unroll
     for (int c = 0; c < 3; c++) {
+        // the fold of k_g32: m = slots of the batch naming this row (0: no fold, the row is converted by k_g32).  A row that
+        // only this slot names is complete with this one term: its fp32 copy is the one-term sum's, bit for bit
+        const int m = mm[c];
+        const bool direct = !FOLD_TICKET_ALL && m == 1;
 #pragma unroll
         for (int j = 0; j < CPL; j++) {
             float g = c == 0 ? gb * (p[j] - n[j]) + lam * u[j] : (c == 1 ? gb * u[j] + lam * p[j] : (-gb) * u[j] + lam * n[j]);
-            if (a.G64 && !tbad)
-                atomicAdd((unsigned long long *)(a.G64 + rows[c] * D + j * LPT + l),
-                          (unsigned long long)__double2ll_rn((double)g * FIXED_SCALE));
+            if (a.G64 && !tbad) {
+                const long long q = __double2ll_rn((double)g * FIXED_SCALE);
+                if (direct) a.G32[rows[c] * D + j * LPT + l] = (float)((double)q * FIXED_INV) / a.gdiv;
+                else atomicAdd((unsigned long long *)(a.G64 + rows[c] * D + j * LPT + l), (unsigned long long)q);
+            }
             if (a.exchange) a.contrib[((int64_t)c * a.shard + b) * D + j * LPT + l] = tbad ? 0.f : g;
         }
         if (a.G64 && !tbad && l == 0) {
@@ -1228,6 +1286,7 @@ __device__ __forceinline__ void triplet_finish(const BprArgs &a, int b, int l, c
             if (a.item_bitmap && c > 0) { const int64_t it = rows[c] - a.n_users; atomicOr(a.item_bitmap + (it >> 5), 1u << (it & 31)); }
         }
     }
+    if (a.G64 && !tbad && a.mult) fold_close_rows<D>(a, rows, mm, l);
 }
 
 #ifndef TRIPLET_HUB_NNZ
@@ -1808,6 +1867,110 @@ __global__ void __launch_bounds__(256) k_g32(SlotArgs a) {
     const int64_t row = slot_row(s / a.B, s % a.B, a.users, a.pos, a.neg, a.n_users, a.N);
     if (row < 0) return;
     store4(a.G32 + row * D + l * 4, loadv_fixed<4>(a.G64 + row * D + l * 4, a.div));
+}
+
+// Slot multiplicities of a whole multi-step call (the fold of k_g32 into k_triplet).  The call's triplets
+// [0, T) are cut into consecutive batches of B (the last one shorter); for batch i of b_i triplets and its slot
+// s = c * b_i + b, out[3 * i * B + s] = how many slots of THAT batch name slot s's destination row -- 0 for the three
+// slots of a triplet with an out-of-range id (slot_row's rule, which is triplet_bad's).  It depends on the ids alone, so one
+// launch ahead of the loop serves every step.  One workgroup per batch: an open-addressing hash (linear probing) of the
+// batch's row ids in LDS, H slots of key + count with 3 * B <= 3/4 H, so every probe sequence ends within H steps.
+#define SLOT_MULT_HMAX 16384        /* hash slots, 8 bytes each: 128 KiB of a CU's 160 KiB; batches up to B = 4096 */
+#define SLOT_MULT_THREADS 1024
+struct SlotMultArgs {
+    const int32_t *users; const int32_t *pos; const int32_t *neg;
+    int64_t T; int32_t B; int32_t n_users; int64_t N;
+    uint16_t *out; int32_t H;
+};
+__global__ void __launch_bounds__(SLOT_MULT_THREADS) k_slot_mult(SlotMultArgs a) {
+    // One thread per triplet (tid, tid + 1024, ...): its three ids are one round trip and its three rows follow from them.  The
+    // loops are NOT unrolled: the launch runs once per call with a cold instruction cache, and an unrolled body (four triplets
+    // x three rows x two passes, 9 KB of code) took tens of microseconds per launch, as did a slot-by-slot walk with its twelve
+    // dependent id reads (profiles/fold_g32/README.md); the second pass re-reads the ids, which are cache hits by then.
+    extern __shared__ int32_t slot_mult_lds[];          // keys [H] (-1: empty) | counts [H]
+    int32_t *keys = slot_mult_lds, *cnts = slot_mult_lds + a.H;
+    const int64_t t0 = (int64_t)blockIdx.x * a.B;
+    const int bn = (int)((a.T - t0) < a.B ? (a.T - t0) : a.B);
+    const int32_t *users = a.users + t0, *pos = a.pos + t0, *neg = a.neg + t0;
+    const uint32_t mask = (uint32_t)a.H - 1u;
+    for (int i = threadIdx.x; i < a.H; i += SLOT_MULT_THREADS) { keys[i] = -1; cnts[i] = 0; }
+    __syncthreads();
+#pragma unroll 1
+    for (int b = threadIdx.x; b < bn; b += SLOT_MULT_THREADS) {
+        const int32_t r0 = (int32_t)slot_row(0, b, users, pos, neg, a.n_users, a.N);
+        if (r0 < 0) continue;                            // a void triplet: none of its slots counts
+        const int32_t r1 = pos[b] + a.n_users, r2 = neg[b] + a.n_users;
+#pragma unroll 1
+        for (int c = 0; c < 3; c++) {
+            const int32_t row = c == 0 ? r0 : (c == 1 ? r1 : r2);
+            uint32_t h = drop_fmix32((uint32_t)row) & mask;
+            for (int probe = 0; probe < a.H; probe++, h = (h + 1u) & mask) {
+                const int32_t old = atomicCAS(&keys[h], -1, row);
+                if (old == -1 || old == row) { atomicAdd(&cnts[h], 1); break; }
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int b = threadIdx.x; b < bn; b += SLOT_MULT_THREADS) {
+        const int32_t r0 = (int32_t)slot_row(0, b, users, pos, neg, a.n_users, a.N);
+        const int32_t r1 = pos[b] + a.n_users, r2 = neg[b] + a.n_users;
+#pragma unroll 1
+        for (int c = 0; c < 3; c++) {
+            const int32_t row = c == 0 ? r0 : (c == 1 ? r1 : r2);
+            int m = 0;
+            if (r0 >= 0) {
+                uint32_t h = drop_fmix32((uint32_t)row) & mask;
+                for (int probe = 0; probe < a.H; probe++, h = (h + 1u) & mask)
+                    if (keys[h] == row) { m = cnts[h]; break; }
+            }
+            a.out[3 * t0 + (int64_t)c * bn + b] = (uint16_t)m;
+        }
+    }
+}
+// hash slots for batches of B triplets: a power of two with 3 B <= 3/4 H, or 0 where that exceeds the LDS budget
+static int32_t slot_mult_hash(int32_t B) {
+    if (B <= 0) return 0;
+    int64_t H = 64;
+    while (3 * H < 12 * (int64_t)B) H <<= 1;
+    return H <= SLOT_MULT_HMAX ? (int32_t)H : 0;
+}
+// steps whose multiplicities one launch computes (and the context's buffer holds): 1024 steps = 3 * B * 1024 uint16 = 12 MiB at
+// B = 2048, 24 MiB at the largest batch that folds.  LGCN_FOLD_SEGMENT: for tests only (a call longer than a small segment)
+static int64_t fold_segment_steps() {
+    const char *e = getenv("LGCN_FOLD_SEGMENT");
+    const long v = e ? atol(e) : 0;
+    return v > 0 ? (int64_t)v : 1024;
+}
+static int launch_slot_mult(const int32_t *users, const int32_t *pos, const int32_t *neg, int64_t T, int32_t B, int32_t n_users,
+                            int64_t N, uint16_t *out, hipStream_t st) {
+    SlotMultArgs a{};
+    a.users = users; a.pos = pos; a.neg = neg; a.T = T; a.B = B; a.n_users = n_users; a.N = N; a.out = out; a.H = slot_mult_hash(B);
+    const size_t lds = sizeof(int32_t) * 2 * (size_t)a.H;
+    // (once per device, for the largest hash: the call sits on the host path ahead of the first launch of every folded call)
+    static bool attr_set[64] = {};
+    int dev = 0;
+    HIP_OK(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+        HIP_OK(hipFuncSetAttribute((const void *)k_slot_mult, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(int32_t) * 2 * SLOT_MULT_HMAX)));
+        if (dev >= 0 && dev < 64) attr_set[dev] = true;
+    }
+    hipLaunchKernelGGL(k_slot_mult, dim3((unsigned)((T + B - 1) / B)), dim3(SLOT_MULT_THREADS), lds, st, a);
+    return 0;
+}
+extern "C" int lgcn_slot_multiplicity(const int32_t *users, const int32_t *pos, const int32_t *neg, int64_t T, int32_t B,
+                                      int32_t n_users, int64_t N, uint16_t *mult_out, void *stream) {
+    if (T <= 0) return 0;
+    if (!users || !pos || !neg || !mult_out) { lgcn_set_error("lgcn_slot_multiplicity: null argument"); return 3; }
+    if (B <= 0 || n_users <= 0 || N <= n_users || N > 0x7fffffffLL) { lgcn_set_error("lgcn_slot_multiplicity: bad sizes (0 < B, 0 < n_users < N < 2^31)"); return 3; }
+    if (!slot_mult_hash(B)) { lgcn_set_error("lgcn_slot_multiplicity: the row ids of a batch of B triplets do not fit the LDS hash (B <= 4096)"); return 3; }
+    const int64_t seg = fold_segment_steps() * B;          // triplets per launch
+    for (int64_t t = 0; t < T; t += seg) {
+        int rc = launch_slot_mult(users + t, pos + t, neg + t, (T - t) < seg ? (T - t) : seg, B, n_users, N, mult_out + 3 * t, (hipStream_t)stream);
+        if (rc) return rc;
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
 }
 
 // dense data-parallel form: flag the rows of the WHOLE global batch (every rank knows all ids), so the
@@ -2414,6 +2577,13 @@ struct lgcn_ctx {
     float drop_keep; uint64_t drop_seed; DropArgs dr;
     // layer weights (lgcn_ctx_set_layer_weights): lw_n = K + 1 values in lw, or 0 = the mean
     int32_t lw_n; float lw[LGCN_MAX_LAYERS + 1];
+    // the fold of k_g32 into k_triplet (lgcn_ctx_set_fold_g32): lgcn_train_epoch computes the slot multiplicities
+    // of its steps (k_slot_mult) into `mult` and points fold_mult at the running step's slice; NULL everywhere else
+    bool fold_g32;                // the setter's switch (default on)
+    uint16_t *mult; int64_t mult_cap;     // library-owned, grown when a call needs more (elements)
+    const uint16_t *fold_mult;    // multiplicities of the running step's slots, or NULL: the step launches k_g32
+    int32_t *arrive;              // [N] arrival tickets of the rows several slots name (library-owned, zero between steps; allocated by the first call that folds)
+    int64_t folded_steps;         // steps run with the fold since the context was created
 };
 // a multi-step call: nobody but this library touches E0 between its steps
 struct LoopScope {
@@ -2451,6 +2621,7 @@ extern "C" int lgcn_ctx_create(const lgcn_train_config *cfg, lgcn_ctx **out) {
     x->c = c; x->step = 0; x->N = c.graph->n_rows; x->cnt = nullptr; x->colsum = nullptr;
     x->drop_keep = 1.f; x->drop_seed = 0; x->dr = DropArgs{};
     x->lw_n = 0; for (int k = 0; k <= LGCN_MAX_LAYERS; k++) x->lw[k] = 0.f;
+    x->fold_g32 = true; x->mult = nullptr; x->mult_cap = 0; x->fold_mult = nullptr; x->arrive = nullptr; x->folded_steps = 0;
     x->bm_words = (x->N + 31) / 32; x->flip = 0;
     const size_t stride = table_bytes(x->N, c.d, c.act_dtype);
     for (int k = 0; k <= LGCN_MAX_LAYERS; k++) x->act[k] = nullptr;
@@ -2502,6 +2673,7 @@ extern "C" int lgcn_ctx_create(const lgcn_train_config *cfg, lgcn_ctx **out) {
         if (x->g32) (void)hipFree(x->g32);
         if (x->colsum) (void)hipFree(x->colsum);
         if (x->cnt) (void)hipFree(x->cnt);
+        if (x->arrive) (void)hipFree(x->arrive);
         if (x->tvar) (void)hipFree(x->tvar);
         if (x->item_bitmap) (void)hipFree(x->item_bitmap);
         if (x->gate_partials) (void)hipFree(x->gate_partials);
@@ -2520,6 +2692,8 @@ extern "C" void lgcn_ctx_destroy(lgcn_ctx *ctx) {
     if (ctx->g32) (void)hipFree(ctx->g32);
     if (ctx->colsum) (void)hipFree(ctx->colsum);
     if (ctx->cnt) (void)hipFree(ctx->cnt);
+    if (ctx->arrive) (void)hipFree(ctx->arrive);
+    if (ctx->mult) (void)hipFree(ctx->mult);
     if (ctx->tvar) (void)hipFree(ctx->tvar);
     if (ctx->item_bitmap) (void)hipFree(ctx->item_bitmap);
     if (ctx->gate_partials) (void)hipFree(ctx->gate_partials);
@@ -2531,6 +2705,20 @@ extern "C" void lgcn_ctx_destroy(lgcn_ctx *ctx) {
 extern "C" int lgcn_ctx_set_dp_local(lgcn_ctx *ctx, int on) {
     if (!ctx) { lgcn_set_error("lgcn_ctx_set_dp_local: null context"); return 3; }
     ctx->dp_local = on != 0; ctx->dp_rank = -1;
+    return 0;
+}
+extern "C" int lgcn_ctx_set_fold_g32(lgcn_ctx *ctx, int on) {
+    if (!ctx) { lgcn_set_error("lgcn_ctx_set_fold_g32: null context"); return 3; }
+    ctx->fold_g32 = on != 0;
+    return 0;
+}
+extern "C" int64_t lgcn_ctx_folded_steps(const lgcn_ctx *ctx) { return ctx ? ctx->folded_steps : -1; }
+extern "C" int lgcn_ctx_copy_arrivals(const lgcn_ctx *ctx, int32_t *dst_host, int64_t n) {
+    if (!ctx || !dst_host) { lgcn_set_error("lgcn_ctx_copy_arrivals: null argument"); return 3; }
+    if (ctx->variant || n < 0 || n > ctx->N) { lgcn_set_error("lgcn_ctx_copy_arrivals: the context has no arrival array of that size"); return 3; }
+    if (!ctx->arrive) { memset(dst_host, 0, sizeof(int32_t) * (size_t)n); return 0; }       // no call has folded yet: nothing was ever counted
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(dst_host, ctx->arrive, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
     return 0;
 }
 extern "C" int64_t lgcn_ctx_get_step(const lgcn_ctx *ctx) { return ctx ? ctx->step : -1; }
@@ -2636,6 +2824,10 @@ static int run_bpr(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const 
     a.stale_bitmap = c.bitmap + (x->flip ^ 1) * x->bm_words; a.bitmap_words = x->bm_words;
     a.contrib = c.contrib; a.terms = c.terms; a.err = c.err; a.exchange = exchange ? 1 : 0;
     a.terms_off = exchange ? 0 : b_off; a.terms_stride = B_global;
+    if (x->fold_mult && atomics && !exchange && cols_phase == 0 && b_off == 0 && B_local == B_global) {
+        // a step of lgcn_train_epoch with the fold: the launch below also writes the fp32 copies of its gradient rows
+        a.mult = x->fold_mult; a.G32 = x->g32; a.gdiv = x->lw_n ? 1.f : (float)(c.K + 1); a.arrive = x->arrive;
+    }
     if (cols_phase == 2) {      // column shard, after the all-reduce: loss terms + gradient scatter from the stored slot rows
         if (B_local <= 0) return 0;
         DISPATCH_D(c.d, {
@@ -2822,9 +3014,11 @@ static int backward_layer(lgcn_ctx *x, int k, const int32_t *users, const int32_
                           const float *gathered, int32_t shard, float *loss_out, bool fused_finish, hipStream_t st) {
     const lgcn_train_config &c = x->c;
     const bool first = (k == c.K), last = (k == 1);
-    if (first) {        // every contribution is in G64 by now: convert the batch rows once
-        SlotArgs s = slot_args(x, users, pos, neg, B, gathered, shard, 1, loss_out);
-        DISPATCH_D(c.d, hipLaunchKernelGGL((k_g32<D>), dim3(slot_grid(x, B)), dim3(256), 0, st, s));
+    if (first) {        // every contribution is in G64 by now: convert the batch rows once (the fold: k_triplet has done it)
+        if (!x->fold_mult) {
+            SlotArgs s = slot_args(x, users, pos, neg, B, gathered, shard, 1, loss_out);
+            DISPATCH_D(c.d, hipLaunchKernelGGL((k_g32<D>), dim3(slot_grid(x, B)), dim3(256), 0, st, s));
+        }
         if (x->variant && c.i2i) {
             // backward of the smoothing: Gs_items <- Gs_items + (alpha I2I)^T Gs_items, a sparse-input SpMM on the item block; the
             // result is dense, so every item row of Gs counts as non-zero from here on
@@ -2945,11 +3139,45 @@ extern "C" int lgcn_train_epoch(lgcn_ctx *x, const int32_t *users, const int32_t
     if (T <= 0) return 0;
     if (!x) { lgcn_set_error("train epoch: null context"); return 3; }
     LoopScope scope(x);
-    int64_t i = 0;
+    // The fold of k_g32: the call's triplets are all here, so how many slots of each batch name a row is known
+    // before the first step -- one k_slot_mult launch per segment of steps, into the context's buffer -- and k_triplet writes
+    // the fp32 copies of the gradient rows itself.  Not with the optional branches (they run another loss kernel), not with a
+    // hub plan (its rows live in the same table until k_g32), not where a batch's row ids do not fit the LDS hash
+    const bool fold = x->fold_g32 && !x->variant && !x->hub_graph && users && pos && neg &&
+                      B > 0 && B <= x->c.max_batch && x->N <= 0x7fffffffLL && slot_mult_hash(B) != 0;
+    const int64_t seg = fold_segment_steps();
+    if (fold) {
+        if (!x->arrive) {         // the first call that folds: every other path leaves the context's footprint as it was
+            HIP_OK(hipMalloc((void **)&x->arrive, sizeof(int32_t) * (size_t)x->N));
+            HIP_OK(hipMemsetAsync(x->arrive, 0, sizeof(int32_t) * (size_t)x->N, (hipStream_t)stream));
+        }
+        // room for a whole segment of the context's largest batch that folds, whatever this call's length: a longer call
+        // later (an epoch after a few warm-up steps) finds the buffer in place, and only a larger segment grows it
+        const int64_t bmax = x->c.max_batch < 4096 ? x->c.max_batch : 4096;
+        const int64_t need = 3 * (B > bmax ? (int64_t)B : bmax) * seg;
+        if (x->mult_cap < need) {
+            if (x->mult) (void)hipFree(x->mult);
+            x->mult = nullptr; x->mult_cap = 0;
+            HIP_OK(hipMalloc((void **)&x->mult, sizeof(uint16_t) * (size_t)need));
+            x->mult_cap = need;
+        }
+    }
+    int64_t i = 0, seg_t0 = 0;
     for (int64_t t = 0; t < T; t += B, i++) {
         const int32_t b = (int32_t)((T - t) < B ? (T - t) : B);
+        if (fold) {
+            if (i % seg == 0) {       // the next segment's multiplicities (the steps that read the last one's are ahead on the stream)
+                seg_t0 = t;
+                const int64_t Ts = (T - t) < seg * B ? (T - t) : seg * B;
+                int rc = launch_slot_mult(users + t, pos + t, neg + t, Ts, B, x->c.n_users, x->N, x->mult, (hipStream_t)stream);
+                if (rc) return rc;
+            }
+            x->fold_mult = x->mult + 3 * (t - seg_t0);
+        }
         int rc = lgcn_train_step(x, users + t, pos + t, neg + t, b, loss_out + 3 * i, stream);
+        x->fold_mult = nullptr;
         if (rc) return rc;
+        if (fold) x->folded_steps += 1;
     }
     return 0;
 }

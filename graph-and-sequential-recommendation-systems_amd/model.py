@@ -484,6 +484,12 @@ class LightGCN(nn.Module):
                 msg = lib.lgcn_last_error()
                 lib.lgcn_ctx_destroy(h)
                 raise _lib.LgcnError(f"lgcn_ctx_set_layer_weights failed (rc={rc}): {msg.decode() if msg else ''}")
+        if str(self.config.get('fold_g32', 1)).strip().lower() in ('0', 'false', 'off'):      # config['fold_g32'] = 0: fused_epoch launches k_g32 every step again (A/B, tests)
+            rc = lib.lgcn_ctx_set_fold_g32(h, 0)
+            if rc:
+                msg = lib.lgcn_last_error()
+                lib.lgcn_ctx_destroy(h)
+                raise _lib.LgcnError(f"lgcn_ctx_set_fold_g32 failed (rc={rc}): {msg.decode() if msg else ''}")
         st['ctx'], st['max_batch'], st['dp_world'], st['table_ptr'] = h, max_batch, dp_world, self._table.data_ptr()
         st['ctx_rows'] = rows
 

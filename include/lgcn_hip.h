@@ -303,6 +303,29 @@ int lgcn_train_step_i64(lgcn_ctx *ctx, const int64_t *users, const int64_t *pos,
 int lgcn_train_epoch(lgcn_ctx *ctx, const int32_t *users, const int32_t *pos, const int32_t *neg,
                      int64_t T, int32_t B, float *loss_out, void *stream);
 
+/* The fold of the gradient-row conversion into the batch-row launch.  lgcn_train_epoch holds all triplets of
+ * the call before its first step, so it computes once (per segment of 1024 steps) how many slots of each batch name each
+ * destination row; the batch-row kernel then writes the fp32 copy of a gradient row itself -- directly where one slot names
+ * the row, from the workgroup that adds last (an arrival ticket, nobody waits) where several do -- and the step launches no
+ * k_g32.  The results are bit for bit those of the unfolded step.  On by default; it engages in lgcn_train_epoch only, for
+ * the default model (no i2i / popularity gate), without a hub plan (lgcn_ctx_hub_rows() == 0) and for B <= 4096.  Every other
+ * entry point, and lgcn_train_epoch with the switch off, launches what it launched before.                                  */
+int lgcn_ctx_set_fold_g32(lgcn_ctx *ctx, int on);
+/* steps run with the fold since the context was created (tests: did it engage?) */
+int64_t lgcn_ctx_folded_steps(const lgcn_ctx *ctx);
+/* debug: copies the first n entries of the fold's per-row arrival counters to HOST memory after a device synchronise; they
+ * are zero between steps (the array is allocated by the first lgcn_train_epoch call that folds; before that, zeros are
+ * written).  rc 3: no such array (optional branches) or n > N.                                                              */
+int lgcn_ctx_copy_arrivals(const lgcn_ctx *ctx, int32_t *dst_host, int64_t n);
+/* Slot multiplicities of a multi-step call: the triplets [0, T) (device int32 ids) are cut into consecutive batches of B, the
+ * last one shorter; for batch i of b_i triplets and slot s = c * b_i + b (c = 0 user, 1 positive, 2 negative),
+ * mult_out[3 * i * B + s] = the number of slots of batch i whose destination row is slot s's (user u -> row u, item j -> row
+ * n_users + j), counting only triplets whose three ids are in range; the three slots of a triplet with an out-of-range id
+ * get 0.  mult_out: device, 3 * T values of 16 bits (a batch that fits has at most 12 288 slots).  rc 3 where the row ids of
+ * a batch do not fit the kernel's LDS hash (B > 4096) or N >= 2^31.  No host sync.                                          */
+int lgcn_slot_multiplicity(const int32_t *users, const int32_t *pos, const int32_t *neg, int64_t T, int32_t B,
+                           int32_t n_users, int64_t N, uint16_t *mult_out, void *stream);
+
 /* Data-parallel split of the same step (replicated tables, batch sharded):
  *   part 1  forward propagation + per-triplet loss terms and gradient rows for this
  *           rank's shard [rank*S, min((rank+1)*S, B_global)), S = ceil(B_global/world),
