@@ -26,7 +26,11 @@ CORES = multiprocessing.cpu_count() // 2
 
 def sample_epoch_to_device(dataset, device):
     """Sample (utils.UniformSample_original), upload, shuffle (utils.shuffle) -- the
-    semantics of main.py:216-220.  Returns int32 device tensors users, pos, neg [T]."""
+    semantics of main.py:216-220.  Returns int32 device tensors users, pos, neg [T]; with --neg_ratio R > 1 the negatives
+    are [R, T] (column r of the sampler's rows in row r: what LightGCN.fused_epoch hands to lgcn_train_epoch_multi)."""
+    R = int(world.config.get('neg_ratio', 1))
+    if R > 1:
+        return _sample_epoch_multi(dataset, device, R)
     S32 = None
     if (torch.device(device).type == 'cuda' and int(world.config.get('gpu_sampler', 1)) and utils.sample_ext
             and utils.sampler_mode(dataset) == 'cpp'):
@@ -59,6 +63,36 @@ def sample_epoch_to_device(dataset, device):
                                            _lib.tp(neg), _lib.current_stream()), "lgcn_apply_perm")
     return users, pos, neg
 
+
+def _epoch_perm(T, device):
+    """utils.shuffle's permutation of an epoch of T rows, on the device where it can be made there."""
+    permd = None
+    if torch.device(device).type == 'cuda' and int(world.config.get('gpu_shuffle', 1)) and 2 <= T < (1 << 31) - 16:
+        permd = utils.shuffle_indices_device(T, device)
+    if permd is None:
+        permd = torch.from_numpy(utils.shuffle_indices(T)).to(device)
+    return permd
+
+
+def _sample_epoch_multi(dataset, device, R):
+    """--neg_ratio R > 1: the native host sampler with neg_num = R (sampling.cpp:27-56 writes rows of 2 + R ids; bit-exact with
+    the reference), the same epoch permutation as R = 1, lgcn_apply_perm_multi.  The device sampler draws one negative and
+    is not used here.  Returns int32 device tensors users [T], pos [T], negs [R, T]."""
+    if not 1 <= R <= _lib.MAX_NEG_RATIO:
+        raise ValueError(f"--neg_ratio must be in 1..{_lib.MAX_NEG_RATIO}, got {R}")
+    if not (utils.sample_ext and utils.sampler_mode(dataset) == 'cpp'):
+        raise _lib.LgcnError(f"--neg_ratio {R} needs the native sampler (--sampler cpp): the reference's Python sampler draws one "
+                             "negative per positive (--sampler python, or --sampler auto on a dataset with a user without positives)")
+    S = utils.UniformSample_original(dataset, neg_ratio=R)
+    T = len(S)
+    S32 = torch.from_numpy(np.ascontiguousarray(S[:, :2 + R], dtype=np.int32)).to(device)
+    permd = _epoch_perm(T, device)
+    users = torch.empty(T, dtype=torch.int32, device=device)
+    pos = torch.empty_like(users)
+    negs = torch.empty(R, T, dtype=torch.int32, device=device)
+    _lib.check(_lib.load().lgcn_apply_perm_multi(_lib.tp(S32), 2 + R, _lib.tp(permd), T, _lib.tp(users), _lib.tp(pos),
+                                                 _lib.tp(negs), R, _lib.current_stream()), "lgcn_apply_perm_multi")
+    return users, pos, negs
 
 
 def _prefetch_next_epoch(dataset):

@@ -11,6 +11,7 @@ from . import build as _build
 F32, BF16, FP8 = 0, 1, 2
 ABI_VERSION = 13
 MAX_LAYERS = 8
+MAX_NEG_RATIO = 16     # LGCN_MAX_NEG_RATIO: negatives per positive of lgcn_train_step_multi / _epoch_multi
 
 _c_i32p = C.POINTER(C.c_int32)
 _c_i64p = C.POINTER(C.c_int64)
@@ -95,6 +96,10 @@ SIGNATURES = {
     "lgcn_ctx_set_dp_local": (C.c_int, [_vp, C.c_int]),
     "lgcn_train_step": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _vp, _vp]),
     "lgcn_train_epoch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, _vp, _vp]),
+    # several negatives per positive (--neg_ratio)
+    "lgcn_apply_perm_multi": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _vp, _vp, _vp, C.c_int32, _vp]),
+    "lgcn_train_step_multi": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp, _vp]),
+    "lgcn_train_epoch_multi": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int64, C.c_int32, _vp, _vp]),
     "lgcn_dp_block_floats": (C.c_int64, [_vp, C.c_int32, C.c_int32]),
     "lgcn_train_step_dp_part1": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
     "lgcn_train_step_dp_dense_part1": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),

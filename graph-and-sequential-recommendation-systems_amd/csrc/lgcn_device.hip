@@ -2014,6 +2014,62 @@ __global__ void __launch_bounds__(256) k_apply_perm(const int32_t *S, int cols, 
     users[t] = S[j * cols]; pos[t] = S[j * cols + 1]; neg[t] = S[j * cols + 2];
 }
 
+// Several negatives per positive (lgcn_train_step_multi): the slot kernels' siblings over the (2 + R) B slots of a
+// batch of B samples.  Slot s = c * B + b: c = 0 the user, 1 the positive, 2 + r negative r, read from negs + r * neg_stride.
+// The three-slot launches above receive what they always received.
+struct SlotArgsMulti {
+    SlotArgs s;                    // users / pos / B / tables / loss reduction as in the three-slot kernels (s.neg unused)
+    const int32_t *negs; int64_t neg_stride; int32_t R;
+};
+// slot -> destination row (-1: the slot's sample has an out-of-range id among its 2 + R: the whole sample is void)
+__device__ __forceinline__ int64_t slot_row_multi(const SlotArgsMulti &a, int c, int b) {
+    const int u = a.s.users[b], p = a.s.pos[b];
+    bool bad = u < 0 || u >= a.s.n_users || p < 0 || (int64_t)p + a.s.n_users >= a.s.N;
+    int nc = 0;
+    for (int r = 0; r < a.R; r++) {
+        const int n = a.negs[(int64_t)r * a.neg_stride + b];
+        bad = bad || n < 0 || (int64_t)n + a.s.n_users >= a.s.N;
+        if (r == c - 2) nc = n;
+    }
+    if (bad) return -1;
+    return c == 0 ? (int64_t)u : (int64_t)(c == 1 ? p : nc) + a.s.n_users;
+}
+template <int D>
+__global__ void __launch_bounds__(256) k_g32_multi(SlotArgsMulti a) {
+    constexpr int LPR = D / 4, SPB = 256 / LPR;
+    const int64_t s = (int64_t)blockIdx.x * SPB + threadIdx.x / LPR;
+    const int l = threadIdx.x % LPR;
+    if (s >= (int64_t)(2 + a.R) * a.s.B) return;
+    const int64_t row = slot_row_multi(a, (int)(s / a.s.B), (int)(s % a.s.B));
+    if (row < 0) return;
+    store4(a.s.G32 + row * D + l * 4, loadv_fixed<4>(a.s.G64 + row * D + l * 4, a.s.div));
+}
+template <int D>
+__global__ void __launch_bounds__(256) k_finish_multi(SlotArgsMulti a) {
+    constexpr int LPR = D / 4, SPB = 256 / LPR;
+    const int64_t s = (int64_t)blockIdx.x * SPB + threadIdx.x / LPR;
+    const int l = threadIdx.x % LPR;
+    if (s < (int64_t)(2 + a.R) * a.s.B) {
+        const int64_t row = slot_row_multi(a, (int)(s / a.s.B), (int)(s % a.s.B));
+        if (row >= 0) {
+            i64x2 *q = reinterpret_cast<i64x2 *>(a.s.G64 + row * D + l * 4);
+            q[0] = i64x2{0, 0}; q[1] = i64x2{0, 0};
+            if (l == 0) { a.s.bitmap[row >> 5] = 0u; if (a.s.cnt) a.s.cnt[row] = 0; }
+        }
+    }
+    // the per-sample terms are scaled so that the three-slot step's reduction with 1 / B yields the loss (same wave, same order)
+    if (blockIdx.x == 0 && threadIdx.x < 64)
+        reduce_loss_wave(a.s.terms, nullptr, a.s.B, a.s.shard, D, a.s.decay, a.s.loss_out, (int)threadIdx.x, 0.f, 0);
+}
+__global__ void __launch_bounds__(256) k_apply_perm_multi(const int32_t *S, int cols, const int64_t *perm, int64_t T,
+                                                         int32_t *users, int32_t *pos, int32_t *negs, int32_t R) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= T) return;
+    const int64_t j = perm ? perm[t] : t;
+    users[t] = S[j * cols]; pos[t] = S[j * cols + 1];
+    for (int r = 0; r < R; r++) negs[(int64_t)r * T + t] = S[j * cols + 2 + r];
+}
+
 // ---------------------------------------------------------------------------------
 // launch helpers
 // ---------------------------------------------------------------------------------
@@ -2542,6 +2598,17 @@ extern "C" int lgcn_apply_perm(const int32_t *S, int s_cols, const int64_t *perm
     return 0;
 }
 
+extern "C" int lgcn_apply_perm_multi(const int32_t *S, int s_cols, const int64_t *perm, int64_t T,
+                                     int32_t *users, int32_t *pos, int32_t *negs, int32_t R, void *stream) {
+    if (R < 1 || R > LGCN_MAX_NEG_RATIO) { lgcn_set_error("lgcn_apply_perm_multi: the negative ratio R must be in 1..16"); return 3; }
+    if (!S || !users || !pos || !negs || s_cols < 2 + R || T < 0) { lgcn_set_error("lgcn_apply_perm_multi: invalid argument (s_cols >= 2 + R)"); return 3; }
+    if (T == 0) return 0;
+    hipLaunchKernelGGL(k_apply_perm_multi, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       S, s_cols, perm, T, users, pos, negs, R);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------
 // training context
 // ---------------------------------------------------------------------------------
@@ -2584,6 +2651,9 @@ struct lgcn_ctx {
     const uint16_t *fold_mult;    // multiplicities of the running step's slots, or NULL: the step launches k_g32
     int32_t *arrive;              // [N] arrival tickets of the rows several slots name (library-owned, zero between steps; allocated by the first call that folds)
     int64_t folded_steps;         // steps run with the fold since the context was created
+    // several negatives per positive (lgcn_train_step_multi): mn_R > 0 only while such a step runs -- its backward
+    // enumerates (2 + mn_R) B slots (negative column r at mn_negs + r * mn_stride) and the reg_ego epilogue takes decay / (B mn_R)
+    const int32_t *mn_negs; int64_t mn_stride; int32_t mn_R;
 };
 // a multi-step call: nobody but this library touches E0 between its steps
 struct LoopScope {
@@ -2622,6 +2692,7 @@ extern "C" int lgcn_ctx_create(const lgcn_train_config *cfg, lgcn_ctx **out) {
     x->drop_keep = 1.f; x->drop_seed = 0; x->dr = DropArgs{};
     x->lw_n = 0; for (int k = 0; k <= LGCN_MAX_LAYERS; k++) x->lw[k] = 0.f;
     x->fold_g32 = true; x->mult = nullptr; x->mult_cap = 0; x->fold_mult = nullptr; x->arrive = nullptr; x->folded_steps = 0;
+    x->mn_negs = nullptr; x->mn_stride = 0; x->mn_R = 0;
     x->bm_words = (x->N + 31) / 32; x->flip = 0;
     const size_t stride = table_bytes(x->N, c.d, c.act_dtype);
     for (int k = 0; k <= LGCN_MAX_LAYERS; k++) x->act[k] = nullptr;
@@ -3001,6 +3072,17 @@ static unsigned slot_grid(const lgcn_ctx *x, int32_t B) {
     return (unsigned)((3 * (int64_t)B + spb - 1) / spb);
 }
 
+static SlotArgsMulti slot_args_multi(const lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B, float *loss_out) {
+    SlotArgsMulti m{};
+    m.s = slot_args(x, users, pos, nullptr, B, nullptr, B, 1, loss_out);
+    m.negs = x->mn_negs; m.neg_stride = x->mn_stride; m.R = x->mn_R;
+    return m;
+}
+static unsigned slot_grid_multi(const lgcn_ctx *x, int32_t B) {
+    const int spb = 256 / (x->c.d / 4);
+    return (unsigned)(((2 + (int64_t)x->mn_R) * B + spb - 1) / spb);
+}
+
 // buffer the backward layer k writes (k > 1): ping-pong inside the activation workspace (forward
 // activations are dead by then)
 static void *bwd_buffer(const lgcn_ctx *x, int k) {
@@ -3015,7 +3097,10 @@ static int backward_layer(lgcn_ctx *x, int k, const int32_t *users, const int32_
     const lgcn_train_config &c = x->c;
     const bool first = (k == c.K), last = (k == 1);
     if (first) {        // every contribution is in G64 by now: convert the batch rows once (the fold: k_triplet has done it)
-        if (!x->fold_mult) {
+        if (x->mn_R) {      // several negatives per positive: (2 + R) B slots, never folded
+            SlotArgsMulti s = slot_args_multi(x, users, pos, B, loss_out);
+            DISPATCH_D(c.d, hipLaunchKernelGGL((k_g32_multi<D>), dim3(slot_grid_multi(x, B)), dim3(256), 0, st, s));
+        } else if (!x->fold_mult) {
             SlotArgs s = slot_args(x, users, pos, neg, B, gathered, shard, 1, loss_out);
             DISPATCH_D(c.d, hipLaunchKernelGGL((k_g32<D>), dim3(slot_grid(x, B)), dim3(256), 0, st, s));
         }
@@ -3043,6 +3128,7 @@ static int backward_layer(lgcn_ctx *x, int k, const int32_t *users, const int32_
         const double bc2 = 1.0 - pow(c.beta2, (double)x->step);
         a.P = c.E0; a.M = c.adam_m; a.V = c.adam_v;
         a.cnt = x->cnt; a.lam = c.decay / (float)B;
+        if (x->mn_R) a.lam = c.decay / (float)((int64_t)B * x->mn_R);      // the counts are R per user / positive slot, 1 per negative slot
         // inside a multi-step call on replicated tables the epilogue keeps the bf16 copy of E0 current (row-sharded steps
         // update only the owned rows and convert again after the exchange)
         a.Pb = (x->e0b && x->in_loop && fused_finish) ? x->e0b : nullptr;
@@ -3103,6 +3189,11 @@ static int run_backward(lgcn_ctx *x, const int32_t *users, const int32_t *pos, c
         hipLaunchKernelGGL(k_gate_adam, dim3((unsigned)((x->gate_P + 255) / 256)), dim3(256), 0, st, ga);
     }
     if (c.K >= 2) { x->flip ^= 1; return 0; }       // next step flags rows in the other bitmap
+    if (x->mn_R) {
+        SlotArgsMulti sm = slot_args_multi(x, users, pos, B, loss_out);
+        DISPATCH_D(c.d, hipLaunchKernelGGL((k_finish_multi<D>), dim3(slot_grid_multi(x, B)), dim3(256), 0, st, sm));
+        return 0;
+    }
     DISPATCH_D(c.d, hipLaunchKernelGGL((k_finish<D>), dim3(sgrid), dim3(256), 0, st, s));
     if (x->variant && c.i2i) {
         // K = 1 keeps ONE bitmap (k_finish clears the batch rows' words); the smoothing's backward flagged EVERY item row in it
@@ -3178,6 +3269,74 @@ extern "C" int lgcn_train_epoch(lgcn_ctx *x, const int32_t *users, const int32_t
         x->fold_mult = nullptr;
         if (rc) return rc;
         if (fold) x->folded_steps += 1;
+    }
+    return 0;
+}
+
+// Several negatives per positive.  Everything is checked before anything is launched or counted: a refusal leaves
+// the outputs, the step counter and the workspace as they were.
+static int check_multi(const lgcn_ctx *x, const void *u, const void *p, const void *n, const void *loss_out, int32_t R, int32_t B,
+                       int64_t neg_stride, const char *who) {
+    char buf[224];
+    if (!x || !u || !p || !n || !loss_out) { snprintf(buf, sizeof buf, "%s: null argument", who); lgcn_set_error(buf); return 3; }
+    if (R < 1 || R > LGCN_MAX_NEG_RATIO) { snprintf(buf, sizeof buf, "%s: the negative ratio R = %d is out of range (1..%d)", who, (int)R, LGCN_MAX_NEG_RATIO); lgcn_set_error(buf); return 3; }
+    if (!x->c.dense_last) { snprintf(buf, sizeof buf, "%s: a negative ratio above the three-slot step's needs a context with dense_last = 1 (the gathered last layer has no 2 + R slot form)", who); lgcn_set_error(buf); return 3; }
+    if (x->c.act_dtype == LGCN_FP8) { snprintf(buf, sizeof buf, "%s: the negative ratio (several negatives per positive) is not implemented for LGCN_FP8 activation storage", who); lgcn_set_error(buf); return 3; }
+    if (x->variant) { snprintf(buf, sizeof buf, "%s: the negative ratio (several negatives per positive) is not implemented with the optional branches (item-item smoothing / popularity gate)", who); lgcn_set_error(buf); return 3; }
+    if (B <= 0 || B > x->c.max_batch) { snprintf(buf, sizeof buf, "%s: batch size out of range (0 < B <= max_batch)", who); lgcn_set_error(buf); return 3; }
+    if (neg_stride < B) { snprintf(buf, sizeof buf, "%s: neg_stride must be at least B (negative ratio columns would overlap)", who); lgcn_set_error(buf); return 3; }
+    return 0;
+}
+
+static int run_bpr_multi(lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B, hipStream_t st) {
+    const lgcn_train_config &c = x->c;
+    MultiNegArgs a{};
+    a.X0 = c.E0; a.K = c.K;
+    for (int k = 1; k <= x->fwd_layers; k++) a.Xl[k] = x->act[k];
+    a.n_users = c.n_users; a.N = x->N;
+    a.users = users; a.pos = pos; a.negs = x->mn_negs; a.neg_stride = x->mn_stride; a.R = x->mn_R; a.B = B;
+    const float BR = (float)((int64_t)B * x->mn_R);
+    a.inv_BR = 1.0f / BR; a.inv_R = 1.0f / (float)x->mn_R;
+    a.lam = c.decay / (float)B; a.lam_n = c.decay / BR;
+    a.G64 = (long long *)c.G64; a.bitmap = c.bitmap + x->flip * x->bm_words;
+    a.stale_bitmap = c.bitmap + (x->flip ^ 1) * x->bm_words; a.bitmap_words = x->bm_words;
+    a.terms = c.terms; a.terms_stride = B; a.err = c.err;
+    a.reg_ego = c.reg_ego; a.cnt = x->cnt;
+    for (int k = 0; k < x->lw_n; k++) a.w[k] = x->lw[k];
+    return lgcn_multineg_launch(a, c.d, c.act_dtype, x->lw_n != 0, st);
+}
+
+static int train_step_multi(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int64_t neg_stride, int32_t R,
+                            int32_t B, float *loss_out, hipStream_t st) {
+    struct MultiScope {         // the backward's slot kernels and the reg_ego epilogue read these; cleared on every way out
+        lgcn_ctx *x;
+        MultiScope(lgcn_ctx *x_, const int32_t *n, int64_t s, int32_t r) : x(x_) { x->mn_negs = n; x->mn_stride = s; x->mn_R = r; }
+        ~MultiScope() { x->mn_negs = nullptr; x->mn_stride = 0; x->mn_R = 0; }
+    } scope(x, negs, neg_stride, R);
+    int rc;
+    x->dr = make_drop(x->drop_keep, x->drop_seed, x->step, 0);        // ONE mask per step, from the counter before the step
+    if ((rc = run_forward(x, st))) return rc;
+    if ((rc = run_bpr_multi(x, users, pos, B, st))) return rc;
+    if ((rc = run_backward(x, users, pos, negs, B, nullptr, B, 1, loss_out, st))) return rc;
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int lgcn_train_step_multi(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int64_t neg_stride,
+                                     int32_t R, int32_t B, float *loss_out, void *stream) {
+    if (int rc = check_multi(x, users, pos, negs, loss_out, R, B, neg_stride, "lgcn_train_step_multi")) return rc;
+    return train_step_multi(x, users, pos, negs, neg_stride, R, B, loss_out, (hipStream_t)stream);
+}
+
+extern "C" int lgcn_train_epoch_multi(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int32_t R,
+                                      int64_t T, int32_t B, float *loss_out, void *stream) {
+    if (T <= 0) return 0;
+    if (int rc = check_multi(x, users, pos, negs, loss_out, R, B, T < B ? (int64_t)B : T, "lgcn_train_epoch_multi")) return rc;
+    LoopScope scope(x);
+    int64_t i = 0;
+    for (int64_t t = 0; t < T; t += B, i++) {
+        const int32_t b = (int32_t)((T - t) < B ? (T - t) : B);
+        if (int rc = train_step_multi(x, users + t, pos + t, negs + t, T, R, b, loss_out + 3 * i, (hipStream_t)stream)) return rc;
     }
     return 0;
 }

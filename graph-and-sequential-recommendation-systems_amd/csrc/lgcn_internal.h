@@ -3,6 +3,7 @@
 #define LGCN_INTERNAL_H
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>       // types only: RCCL is resolved with dlopen at run time, never linked
+#include "lgcn_hip.h"
 
 extern "C" void lgcn_set_error(const char *msg);   // lgcn_host.cpp
 
@@ -30,4 +31,22 @@ struct lgcn_dp {
 };
 void lgcn_dp_loopback_release(lgcn_dp *dp);      // lgcn_dp_loopback.hip
 void lgcn_dp_loopback_abort(lgcn_dp *dp);        // a rank failed outside a collective: wake every waiter, all later collectives fail
+
+// The batch-row launch for samples with several negatives (lgcn_multineg.hip; lgcn_train_step_multi fills this in).
+// Sample b = (users[b], pos[b], negs[r * neg_stride + b] for r < R); dense-last form: Xl[1..K] are all tables of the storage type.
+struct MultiNegArgs {
+    const float *X0; const void *Xl[LGCN_MAX_LAYERS + 1]; int K;
+    int32_t n_users; int64_t N;
+    const int32_t *users; const int32_t *pos; const int32_t *negs; int64_t neg_stride;
+    int32_t R, B;
+    float inv_BR, inv_R;          // 1 / (B R), 1 / R
+    float lam, lam_n;             // decay / B (user, positive rows), decay / (B R) (a negative's row)
+    long long *G64; uint32_t *bitmap;
+    uint32_t *stale_bitmap; int64_t bitmap_words;      // last step's bitmap: zeroed by the launch (plain stores)
+    float *terms; int32_t terms_stride;                // [2 * terms_stride]: per-sample loss term | reg term
+    int32_t *err;
+    int32_t reg_ego; int32_t *cnt;                     // reg_ego: cnt[row] += R per user / positive slot, 1 per negative slot
+    float w[LGCN_MAX_LAYERS + 1];                      // wts launches only: the layer weights
+};
+int lgcn_multineg_launch(const MultiNegArgs &a, int d, int act_dtype, bool wts, hipStream_t st);
 #endif

@@ -258,6 +258,17 @@ class LightGCN(nn.Module):
                                      "(the optional branches train with the layer mean only)")
             if self.dropout:
                 raise _lib.LgcnError(f"{flag} is not implemented together with --dropout 1 (edge dropout trains with the layer mean only)")
+        # several negatives per positive (--neg_ratio R; lgcn_train_step_multi): the default model, fp32 / bf16 storage
+        self.neg_ratio = int(config.get('neg_ratio', 1))
+        if not 1 <= self.neg_ratio <= _lib.MAX_NEG_RATIO:
+            raise ValueError(f"--neg_ratio must be in 1..{_lib.MAX_NEG_RATIO}, got {self.neg_ratio}")
+        if self.neg_ratio > 1:
+            if str(config.get('act_dtype', 'fp32')) == 'fp8':
+                raise _lib.LgcnError(f"--neg_ratio {self.neg_ratio} is not implemented together with --act_dtype fp8 (fp32 and bf16 storage only)")
+            if self.use_pop_gate or self.use_item_item:
+                raise _lib.LgcnError(f"--neg_ratio {self.neg_ratio} is not implemented together with --use_pop_gate / --use_item_item "
+                                     "(the optional branches train on one negative per positive)")
+        self._neg_ratio_said = False
         self._gate_flat = None      # the eight MLP tensors of the gate in ONE buffer (what the fused step reads / updates)
         self._Graph = None
         self._dev = None            # device-side state (graph, workspace, context)
@@ -418,6 +429,11 @@ class LightGCN(nn.Module):
         variants = self.fused_variants
         if variants:
             dense_last = True       # the optional branches score on the layer mean of EVERY row (model.py:221-229)
+        if self.neg_ratio > 1 and not dense_last:
+            dense_last = True       # the 2 + R slot batch-row kernel reads a dense last layer (the gathered form is not built)
+            if not self._neg_ratio_said:
+                world.cprint(f"[neg_ratio] --neg_ratio {self.neg_ratio}: the last layer is propagated densely (dense_last = 1)")
+                self._neg_ratio_said = True
         st['act'] = _act_tables(max(1, K if dense_last else K - 1), N, d, act_dtype, dev)
         st['G64'] = torch.zeros(N, d, dtype=torch.int64, device=dev)
         st['bitmap'] = torch.zeros(2 * ((N + 31) // 32), dtype=torch.int32, device=dev)
@@ -634,8 +650,30 @@ class LightGCN(nn.Module):
         i_emb = self._fuse_item_embeddings(all_items) if self.use_pop_gate else all_items
         return all_users[users], i_emb[pos_items], i_emb[neg_items], all_users, all_items
 
+    def _bpr_loss_multi(self, users, pos, neg):
+        """bpr_loss for R negatives per positive, neg [B, R] (or [R, B]): the autograd statement of the loss of
+        lgcn_train_step_multi -- bpr = -mean_{b,r} logsigmoid(x_{b,r}), reg = 0.5/B sum_b (|u|^2 + |p|^2 + 1/R sum_r |n_r|^2)."""
+        if self.has_variants:
+            raise _lib.LgcnError("several negatives per positive (--neg_ratio > 1) are implemented for the default model, not with "
+                                 "--use_pop_gate / --use_item_item")
+        B = int(users.shape[0])
+        if neg.shape[0] != B:
+            neg = neg.t()
+        if neg.shape[0] != B:
+            raise ValueError(f"neg must be [B, R] or [R, B] with B = {B}, got {tuple(neg.shape)}")
+        R = int(neg.shape[1])
+        u, pos_e, neg_e, _, _ = self.getEmbedding(users, pos, neg)          # neg_e [B, R, d]
+        x = torch.sum(u * pos_e, dim=1)[:, None] - torch.sum(u[:, None, :] * neg_e, dim=2)
+        bpr = -torch.mean(F.logsigmoid(x))
+        if str(self.config.get('reg_rows', 'propagated')) == 'ego':
+            u, pos_e, neg_e = self.embedding_user.weight[users.long()], self.embedding_item.weight[pos.long()], self.embedding_item.weight[neg.long()]
+        reg_loss = (0.5 * (u.norm(2).pow(2) + pos_e.norm(2).pow(2) + neg_e.norm(2).pow(2) / float(R))) / float(B)
+        return bpr, reg_loss
+
     def bpr_loss(self, users, pos, neg):
         """model.py:162-183 (unfused, autograd-capable): (bpr [- entropy term of the gate], reg_loss)."""
+        if torch.is_tensor(neg) and neg.dim() == 2:
+            return self._bpr_loss_multi(users, pos, neg)
         u, pos_e, neg_e, _, _ = self.getEmbedding(users, pos, neg)
         pos_scores = torch.sum(u * pos_e, dim=1)
         neg_scores = torch.sum(u * neg_e, dim=1)
@@ -665,6 +703,41 @@ class LightGCN(nn.Module):
             t = torch.as_tensor(np.asarray(t))
         return t.to(device=dev, dtype=torch.int32).contiguous()
 
+    @staticmethod
+    def _neg_dim(neg):
+        return neg.dim() if torch.is_tensor(neg) else np.asarray(neg).ndim
+
+    def _negs_rt(self, neg, n, dev):
+        """2-D negatives of n samples -> contiguous int32 [R, n] on the device (negative column r in row r), or None for R == 1.
+        Accepts [n, R] (the sampler's S[:, 2:]; taken when both readings fit) and [R, n] (Procedure.sample_epoch_to_device)."""
+        neg = self._ids(neg, dev)
+        if neg.shape[0] == n:
+            neg = neg.t()
+        elif neg.shape[1] != n:
+            raise ValueError(f"neg must be [{n}, R] or [R, {n}], got {tuple(neg.shape)}")
+        R = int(neg.shape[0])
+        if R == 1:
+            return None
+        if not 1 <= R <= _lib.MAX_NEG_RATIO:
+            raise ValueError(f"the negative ratio (neg_ratio) must be in 1..{_lib.MAX_NEG_RATIO}, got {R} negatives per positive")
+        return neg.contiguous()
+
+    def _fused_step_multi(self, users, pos, negs, loss_out, lr):
+        """fused_step for R > 1 negatives per positive (negs int32 [R, B]): lgcn_train_step_multi."""
+        dev = self._table.device
+        B = int(users.numel())
+        st = self._state(max_batch=max(B, int(self.config.get('bpr_batch_size', B))), need_ctx=True,
+                         dp_world=(self._dev or {}).get('dp_world', 1))
+        lib = _lib.load()
+        if lr is not None:
+            lib.lgcn_ctx_set_lr(st['ctx'], float(lr))
+        if loss_out is None:
+            loss_out = torch.empty(3, dtype=torch.float32, device=dev)
+        _lib.check(lib.lgcn_train_step_multi(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(negs), B, int(negs.shape[0]), B,
+                                             _lib.tp(loss_out), _lib.current_stream()), "lgcn_train_step_multi")
+        self.invalidate_cache()
+        return loss_out
+
     def fused_step(self, users, pos, neg, loss_out=None, lr=None):
         """One BPRLoss.stageOne (utils.py:53-64) in the HIP kernels.  Returns a device
         tensor [3] = (bpr + decay*reg, bpr, reg); no host synchronisation."""
@@ -672,6 +745,13 @@ class LightGCN(nn.Module):
             raise RuntimeError("this configuration of the popularity gate / item-item smoothing is outside the fused step "
                                "(--fused_variants 0, or gate hidden sizes > 64 / d > 128): use BPRLoss.stageOne (autograd path)")
         dev = self._table.device
+        if self._neg_dim(neg) == 2:            # several negatives per positive: neg [B, R] (the sampler's S[:, 2:]) or [R, B]
+            users, pos = self._ids(users, dev), self._ids(pos, dev)
+            B = int(users.numel())
+            negs = self._negs_rt(neg, B, dev)
+            if negs is not None:
+                return self._fused_step_multi(users, pos, negs, loss_out, lr)
+            neg = self._ids(neg, dev).reshape(-1)     # R == 1: the three-slot step, unchanged
         # the reference's call shape: three torch.long device tensors (main.py:217-225) -- narrowed inside the step's own launch
         # sequence (lgcn_train_step_i64) instead of three conversion kernels and allocations here
         as_i64 = all(torch.is_tensor(t) and t.dtype == torch.int64 and t.device == dev and t.is_contiguous() for t in (users, pos, neg))
@@ -702,7 +782,12 @@ class LightGCN(nn.Module):
         if self.has_variants and not self.fused_variants:
             raise RuntimeError("this configuration of the optional branches is outside the fused step: loop BPRLoss.stageOne")
         dev = self._table.device
-        users, pos, neg = self._ids(users, dev), self._ids(pos, dev), self._ids(neg, dev)
+        users, pos = self._ids(users, dev), self._ids(pos, dev)
+        negs = None
+        if self._neg_dim(neg) == 2:            # several negatives per positive: neg [T, R] or [R, T]
+            negs = self._negs_rt(neg, int(users.numel()), dev)
+        if negs is None:                       # R == 1 (1-D, or one column): the three-slot epoch, unchanged
+            neg = self._ids(neg, dev).reshape(-1)
         T = int(users.numel())
         steps = (T + batch_size - 1) // batch_size
         st = self._state(max_batch=batch_size, need_ctx=True, dp_world=(self._dev or {}).get('dp_world', 1))
@@ -710,6 +795,11 @@ class LightGCN(nn.Module):
         if lr is not None:
             lib.lgcn_ctx_set_lr(st['ctx'], float(lr))
         losses = torch.empty(steps, 3, dtype=torch.float32, device=dev)
+        if negs is not None:                   # R > 1: the multi-negative epoch (negative column r at negs + r * T)
+            _lib.check(lib.lgcn_train_epoch_multi(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(negs), int(negs.shape[0]), T,
+                                                  int(batch_size), _lib.tp(losses), _lib.current_stream()), "lgcn_train_epoch_multi")
+            self.invalidate_cache()
+            return losses
         _lib.check(lib.lgcn_train_epoch(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(neg), T, int(batch_size),
                                         _lib.tp(losses), _lib.current_stream()), "lgcn_train_epoch")
         self.invalidate_cache()
@@ -767,6 +857,9 @@ class PureMF(nn.Module):
             raise _lib.LgcnError(f"--use_ppr_weights {no} (there are no layers to combine)")
         if str(config.get('act_dtype', 'fp32')) != 'fp32':
             raise _lib.LgcnError(f"--act_dtype {config.get('act_dtype')} {no} (fp32 tables only)")
+        if int(config.get('neg_ratio', 1)) != 1:
+            raise _lib.LgcnError(f"--neg_ratio {config.get('neg_ratio')} {no} (the matrix-factorisation step trains on triplets, "
+                                 "one negative per positive)")
         if self.latent_dim not in (32, 64, 128, 256):
             raise ValueError("latent_dim_rec must be 32, 64, 128 or 256 for the HIP kernels")
         if self.n_users + self.m_items >= 2 ** 31:

@@ -111,6 +111,11 @@ def build_parser():
                         "of K+1 floats such as \"[0.4,0.3,0.2,0.1]\", taken as written. fp32 / bf16 storage, single GPU, default model")
     p.add_argument('--ppr_alpha', type=float, default=0.15,
                    help="NEW: teleport probability of --layer_weights ppr (the default of the reference's compute_ppr.py)")
+    p.add_argument('--neg_ratio', type=int, default=1,
+                   help='NEW: negatives drawn per sampled positive (1..16). 1 (default) = the reference: triplets. R > 1 trains on '
+                        'samples (u, p, n_1..n_R) in the fused step -- the loss of the flattened B*R triplets, with the user and '
+                        'positive rows read and added once per sample. Native host sampler (--sampler cpp), fp32 / bf16 storage, '
+                        'single GPU, default model, dense last layer')
     p.add_argument('--data_path', type=str, default=None,
                    help='NEW: directory that holds <dataset>/train.txt (default: <root>/data)')
     return p

@@ -113,7 +113,8 @@ def configure(argv=None):
     config['i2i_min_basket'] = args.i2i_min_basket
     config['layer_weights'] = args.layer_weights
     config['ppr_alpha'] = args.ppr_alpha
-    device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
+    config['neg_ratio'] = args.neg_ratio
+    device =torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     return config
 
 

@@ -179,6 +179,12 @@ int lgcn_np_shuffle_perm_device(int64_t n, int64_t *d_perm, void *workspace, int
 int lgcn_apply_perm(const int32_t *S, int s_cols, const int64_t *perm, int64_t T,
                     int32_t *users, int32_t *pos, int32_t *neg, void *stream);
 
+/* The same for rows of 2 + R ids (the sampler's output with neg_num = R): users/pos[T] = S[perm[t], 0..1], and negative
+ * column r of the result, negs + r * T, holds S[perm[t], 2 + r] -- the [R][T] layout lgcn_train_epoch_multi reads.
+ * 1 <= R <= LGCN_MAX_NEG_RATIO, s_cols >= 2 + R.  For R = 1 it writes what lgcn_apply_perm writes.                 */
+int lgcn_apply_perm_multi(const int32_t *S, int s_cols, const int64_t *perm, int64_t T,
+                          int32_t *users, int32_t *pos, int32_t *negs /* [R][T] */, int32_t R, void *stream);
+
 /* ------------------------------------------------------------------------ */
 /* Device: fused training step -- replaces BPRLoss.stageOne   utils.py:53-64  */
 /*   = LightGCN.bpr_loss (model.py:162-183) + loss.backward() (autograd of     */
@@ -302,6 +308,28 @@ int lgcn_train_step_i64(lgcn_ctx *ctx, const int64_t *users, const int64_t *pos,
  * of the (already shuffled) device arrays.  loss_out: [3*ceil(T/B)].           */
 int lgcn_train_epoch(lgcn_ctx *ctx, const int32_t *users, const int32_t *pos, const int32_t *neg,
                      int64_t T, int32_t B, float *loss_out, void *stream);
+
+/* Several negatives per positive (--neg_ratio R).  A batch is B samples (u_b, p_b, n_{b,1..R}); negative column r
+ * of the batch is negs + r * neg_stride (device int32, neg_stride >= B).  With e the rows of the model's output table:
+ *   x_{b,r} = e_u.e_p - e_u.e_{n_r}
+ *   bpr = -1/(B R) sum_b sum_r logsigmoid(x_{b,r})
+ *   reg = 0.5/B sum_b ( |e_u|^2 + |e_p|^2 + 1/R sum_r |e_{n_r}|^2 )      (reg_ego: the same on the tables' own rows)
+ *   loss_out = {bpr + decay * reg, bpr, reg}
+ * -- term for term the loss of lgcn_train_step on the flattened batch of B R triplets (u_b, p_b, n_{b,r}), but the batch-row
+ * launch reads 2 + R slot rows per sample and adds 2 + R gradient rows instead of 3 R.  Forward, backward chain and the Adam
+ * epilogue are those of lgcn_train_step; edge dropout and layer weights set on the context apply.  B <= max_batch.
+ * rc 3, with a message that names the negative ratio and with outputs, step counter and workspace untouched: R outside
+ * 1..LGCN_MAX_NEG_RATIO, neg_stride < B, a context with dense_last = 0, LGCN_FP8 storage, or an optional branch (i2i /
+ * popularity gate).  The data-parallel entry points stay three-slot.                                                          */
+#define LGCN_MAX_NEG_RATIO 16
+int lgcn_train_step_multi(lgcn_ctx *ctx, const int32_t *users, const int32_t *pos,
+                          const int32_t *negs, int64_t neg_stride, int32_t R,
+                          int32_t B, float *loss_out, void *stream);
+/* A whole epoch of such steps: ceil(T/B) consecutive batches of the (already shuffled) arrays, negative column r of the
+ * epoch at negs + r * T (what lgcn_apply_perm_multi writes).  loss_out: [3*ceil(T/B)].  The same refusals.                  */
+int lgcn_train_epoch_multi(lgcn_ctx *ctx, const int32_t *users, const int32_t *pos,
+                           const int32_t *negs /* [R][T]: column r at negs + r*T */, int32_t R,
+                           int64_t T, int32_t B, float *loss_out, void *stream);
 
 /* The fold of the gradient-row conversion into the batch-row launch.  lgcn_train_epoch holds all triplets of
  * the call before its first step, so it computes once (per segment of 1024 steps) how many slots of each batch name each
