@@ -2654,6 +2654,9 @@ struct lgcn_ctx {
     // several negatives per positive (lgcn_train_step_multi): mn_R > 0 only while such a step runs -- its backward
     // enumerates (2 + mn_R) B slots (negative column r at mn_negs + r * mn_stride) and the reg_ego epilogue takes decay / (B mn_R)
     const int32_t *mn_negs; int64_t mn_stride; int32_t mn_R;
+    // the loss of the multi-negative step (lgcn_ctx_set_loss): LGCN_LOSS_BPR launches k_multineg_dense as ever,
+    // LGCN_LOSS_SOFTMAX k_multineg_softmax with the temperature loss_temp; the three-slot and rank-splitting entry points refuse
+    int32_t loss_kind; float loss_temp;
 };
 // a multi-step call: nobody but this library touches E0 between its steps
 struct LoopScope {
@@ -2693,6 +2696,7 @@ extern "C" int lgcn_ctx_create(const lgcn_train_config *cfg, lgcn_ctx **out) {
     x->lw_n = 0; for (int k = 0; k <= LGCN_MAX_LAYERS; k++) x->lw[k] = 0.f;
     x->fold_g32 = true; x->mult = nullptr; x->mult_cap = 0; x->fold_mult = nullptr; x->arrive = nullptr; x->folded_steps = 0;
     x->mn_negs = nullptr; x->mn_stride = 0; x->mn_R = 0;
+    x->loss_kind = LGCN_LOSS_BPR; x->loss_temp = 1.f;
     x->bm_words = (x->N + 31) / 32; x->flip = 0;
     const size_t stride = table_bytes(x->N, c.d, c.act_dtype);
     for (int k = 0; k <= LGCN_MAX_LAYERS; k++) x->act[k] = nullptr;
@@ -2836,6 +2840,31 @@ static int refuse_layer_weights(const lgcn_ctx *x, const char *who) {
     if (!x || !x->lw_n) return 0;
     char buf[192];
     snprintf(buf, sizeof buf, "%s: layer weights (lgcn_ctx_set_layer_weights) are implemented for the single-GPU step only", who);
+    lgcn_set_error(buf);
+    return 3;
+}
+
+extern "C" int lgcn_ctx_set_loss(lgcn_ctx *ctx, int32_t kind, float temperature) {
+    if (!ctx) { lgcn_set_error("lgcn_ctx_set_loss: null context"); return 3; }
+    if (kind == LGCN_LOSS_BPR) { ctx->loss_kind = LGCN_LOSS_BPR; ctx->loss_temp = 1.f; return 0; }      // the step launches what it always launched
+    if (kind != LGCN_LOSS_SOFTMAX) { lgcn_set_error("lgcn_ctx_set_loss: unknown loss kind (LGCN_LOSS_BPR or LGCN_LOSS_SOFTMAX)"); return 3; }
+    if (!(temperature > 0.f) || !isfinite(temperature)) { lgcn_set_error("lgcn_ctx_set_loss: the sampled-softmax loss needs a finite temperature > 0"); return 3; }
+    if (ctx->c.act_dtype == LGCN_FP8) { lgcn_set_error("lgcn_ctx_set_loss: the sampled-softmax loss is not implemented for LGCN_FP8 activation storage"); return 3; }
+    if (ctx->variant) { lgcn_set_error("lgcn_ctx_set_loss: the sampled-softmax loss is not implemented with the optional branches (item-item smoothing / popularity gate)"); return 3; }
+    if (!ctx->c.dense_last) { lgcn_set_error("lgcn_ctx_set_loss: the sampled-softmax loss needs a context with dense_last = 1 (the gathered last layer has no 2 + R slot form)"); return 3; }
+    ctx->loss_kind = LGCN_LOSS_SOFTMAX; ctx->loss_temp = temperature;
+    return 0;
+}
+extern "C" int32_t lgcn_ctx_get_loss(const lgcn_ctx *ctx, float *temperature_out) {
+    if (!ctx) return -1;
+    if (temperature_out) *temperature_out = ctx->loss_temp;
+    return ctx->loss_kind;
+}
+// today's three-slot kernels, and every form that splits a step over ranks, compute BPR: say so instead of training another loss
+static int refuse_softmax(const lgcn_ctx *x, const char *who) {
+    if (!x || x->loss_kind == LGCN_LOSS_BPR) return 0;
+    char buf[224];
+    snprintf(buf, sizeof buf, "%s: the sampled-softmax loss (lgcn_ctx_set_loss) is implemented for lgcn_train_step_multi / lgcn_train_epoch_multi only", who);
     lgcn_set_error(buf);
     return 3;
 }
@@ -3213,6 +3242,7 @@ extern "C" int lgcn_train_step(lgcn_ctx *x, const int32_t *users, const int32_t 
                                int32_t B, float *loss_out, void *stream) {
     int rc = check_batch(x, users, pos, neg, B);
     if (rc) return rc;
+    if ((rc = refuse_softmax(x, "lgcn_train_step"))) return rc;
     if (!loss_out) { lgcn_set_error("train step: loss_out is null"); return 3; }
     hipStream_t st = (hipStream_t)stream;
     x->dr = make_drop(x->drop_keep, x->drop_seed, x->step, 0);        // ONE mask per step, from the counter before the step
@@ -3229,6 +3259,7 @@ extern "C" int lgcn_train_epoch(lgcn_ctx *x, const int32_t *users, const int32_t
                                 int64_t T, int32_t B, float *loss_out, void *stream) {
     if (T <= 0) return 0;
     if (!x) { lgcn_set_error("train epoch: null context"); return 3; }
+    if (int rc = refuse_softmax(x, "lgcn_train_epoch")) return rc;
     LoopScope scope(x);
     // The fold of k_g32: the call's triplets are all here, so how many slots of each batch name a row is known
     // before the first step -- one k_slot_mult launch per segment of steps, into the context's buffer -- and k_triplet writes
@@ -3303,6 +3334,11 @@ static int run_bpr_multi(lgcn_ctx *x, const int32_t *users, const int32_t *pos, 
     a.terms = c.terms; a.terms_stride = B; a.err = c.err;
     a.reg_ego = c.reg_ego; a.cnt = x->cnt;
     for (int k = 0; k < x->lw_n; k++) a.w[k] = x->lw[k];
+    if (x->loss_kind == LGCN_LOSS_SOFTMAX) {       // the same rows, flags and terms; another coefficient per negative
+        SoftmaxArgs s{};
+        s.m = a; s.tau = x->loss_temp; s.inv_tauB = (float)(1.0 / ((double)x->loss_temp * (double)B));
+        return lgcn_softmax_launch(s, c.d, c.act_dtype, x->lw_n != 0, st);
+    }
     return lgcn_multineg_launch(a, c.d, c.act_dtype, x->lw_n != 0, st);
 }
 
@@ -3347,6 +3383,7 @@ extern "C" int lgcn_train_step_dp_part1(lgcn_ctx *x, const int32_t *users, const
     if (rc) return rc;
     if ((rc = refuse_dropout(x, "lgcn_train_step_dp_part1"))) return rc;
     if ((rc = refuse_layer_weights(x, "lgcn_train_step_dp_part1"))) return rc;
+    if ((rc = refuse_softmax(x, "lgcn_train_step_dp_part1"))) return rc;
     if (!x->c.contrib) { lgcn_set_error("dp step: cfg.contrib exchange buffer missing"); return 3; }
     if (world < 1 || rank < 0 || rank >= world) { lgcn_set_error("dp step: bad world/rank"); return 3; }
     const int32_t shard = (B_global + world - 1) / world;
@@ -3371,6 +3408,7 @@ extern "C" int lgcn_train_step_dp_dense_part1(lgcn_ctx *x, const int32_t *users,
     if (rc) return rc;
     if ((rc = refuse_dropout(x, "lgcn_train_step_dp_dense_part1"))) return rc;
     if ((rc = refuse_layer_weights(x, "lgcn_train_step_dp_dense_part1"))) return rc;
+    if ((rc = refuse_softmax(x, "lgcn_train_step_dp_dense_part1"))) return rc;
     if (world < 1 || rank < 0 || rank >= world) { lgcn_set_error("dp step: bad world/rank"); return 3; }
     const int32_t shard = (B_global + world - 1) / world;
     const int32_t b_off = rank * shard;
@@ -3416,6 +3454,7 @@ extern "C" int lgcn_train_step_dp_part2(lgcn_ctx *x, const int32_t *users, const
     if (rc) return rc;
     if ((rc = refuse_dropout(x, "lgcn_train_step_dp_part2"))) return rc;
     if ((rc = refuse_layer_weights(x, "lgcn_train_step_dp_part2"))) return rc;
+    if ((rc = refuse_softmax(x, "lgcn_train_step_dp_part2"))) return rc;
     if (!loss_out || world < 1) { lgcn_set_error("dp step part 2: invalid argument"); return 3; }
     const int32_t shard = (B_global + world - 1) / world;
     // gathered == NULL is the dense form: G64, the terms and (popularity gate) gate_total hold the reduced sums of the global batch
@@ -3439,6 +3478,7 @@ extern "C" int lgcn_train_step_cols_part1(lgcn_ctx *x, const int32_t *users, con
     if (rc) return rc;
     if ((rc = refuse_dropout(x, "lgcn_train_step_cols_part1"))) return rc;
     if ((rc = refuse_layer_weights(x, "lgcn_train_step_cols_part1"))) return rc;
+    if ((rc = refuse_softmax(x, "lgcn_train_step_cols_part1"))) return rc;
     if (x->variant) { lgcn_set_error("column-sharded step: the popularity gate / item-item smoothing mix columns (MLPs over the row): not supported"); return 3; }
     if (!x->c.contrib) { lgcn_set_error("column-sharded step: cfg.contrib (3*max_batch*d floats: the batch's slot rows) missing"); return 3; }
     hipStream_t st = (hipStream_t)stream;
@@ -3454,6 +3494,7 @@ extern "C" int lgcn_train_step_cols_part2(lgcn_ctx *x, const int32_t *users, con
     if (rc) return rc;
     if ((rc = refuse_dropout(x, "lgcn_train_step_cols_part2"))) return rc;
     if ((rc = refuse_layer_weights(x, "lgcn_train_step_cols_part2"))) return rc;
+    if ((rc = refuse_softmax(x, "lgcn_train_step_cols_part2"))) return rc;
     if (!loss_out) { lgcn_set_error("column-sharded step part 2: loss_out is null"); return 3; }
     hipStream_t st = (hipStream_t)stream;
     if ((rc = run_bpr(x, users, pos, neg, B, 0, B, B, true, false, st, true, 2))) return rc;
@@ -3473,6 +3514,7 @@ extern "C" int lgcn_rs_phase(lgcn_ctx *x, int32_t phase, int32_t k, const int32_
     if (rc) return rc;
     if ((rc = refuse_dropout(x, "lgcn_rs_phase"))) return rc;
     if ((rc = refuse_layer_weights(x, "lgcn_rs_phase"))) return rc;
+    if ((rc = refuse_softmax(x, "lgcn_rs_phase"))) return rc;
     if (x->variant) { lgcn_set_error("lgcn_rs_phase: the popularity gate / item-item smoothing run on one GPU only"); return 3; }
     const lgcn_train_config &c = x->c;
     hipStream_t st = (hipStream_t)stream;
@@ -3630,7 +3672,7 @@ static int train_epoch_dp_impl(lgcn_ctx *x, lgcn_dp *dp, const int32_t *users, c
 extern "C" int lgcn_train_epoch_dp(lgcn_ctx *x, lgcn_dp *dp, const int32_t *users, const int32_t *pos, const int32_t *neg,
                                    int64_t T, int32_t B_global, int32_t reduce, const int64_t *row_ranges, float *gathered,
                                    float *loss_out, void *stream) {
-    if (refuse_dropout(x, "lgcn_train_epoch_dp") || refuse_layer_weights(x, "lgcn_train_epoch_dp")) return 3;         // (every rank's context says the same: nobody waits in a collective)
+    if (refuse_dropout(x, "lgcn_train_epoch_dp") || refuse_layer_weights(x, "lgcn_train_epoch_dp") || refuse_softmax(x, "lgcn_train_epoch_dp")) return 3;         // (every rank's context says the same: nobody waits in a collective)
     const int rc = train_epoch_dp_impl(x, dp, users, pos, neg, T, B_global, reduce, row_ranges, gathered, loss_out, stream);
     // a rank that leaves the loop early never reaches its next collective: release the loopback ranks waiting for it
     // (RCCL has its own abort / timeout machinery)

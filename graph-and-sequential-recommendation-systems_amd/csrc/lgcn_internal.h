@@ -49,4 +49,11 @@ struct MultiNegArgs {
     float w[LGCN_MAX_LAYERS + 1];                      // wts launches only: the layer weights
 };
 int lgcn_multineg_launch(const MultiNegArgs &a, int d, int act_dtype, bool wts, hipStream_t st);
+// The same launch under the sampled-softmax loss (lgcn_softmax.hip; lgcn_ctx_set_loss): m as above (inv_BR unused),
+// z_r = -x_r / tau, gb_r = -q_r * inv_tauB with inv_tauB = 1 / (tau B).
+struct SoftmaxArgs {
+    MultiNegArgs m;
+    float tau, inv_tauB;
+};
+int lgcn_softmax_launch(const SoftmaxArgs &a, int d, int act_dtype, bool wts, hipStream_t st);
 #endif

@@ -76,6 +76,18 @@ def load_ppr_weights(path, K, degrees=None):
     return _check_layer_weights(w[0], K, f"--ppr_weights_path {path}")
 
 
+def resolve_loss(config):
+    """--loss bpr | softmax and --softmax_temp -> ('bpr' | 'softmax', temperature).  ValueError: an unknown loss, or a
+    temperature that is not a finite value > 0."""
+    kind = str(config.get('loss', 'bpr')).strip().lower()
+    if kind not in ('bpr', 'softmax'):
+        raise ValueError(f"--loss must be bpr or softmax, got {config.get('loss')!r}")
+    tau = float(config.get('softmax_temp', 1.0))
+    if kind == 'softmax' and not (np.isfinite(tau) and tau > 0.0):
+        raise ValueError(f"--loss softmax: --softmax_temp must be a finite value > 0, got {tau}")
+    return kind, tau
+
+
 def resolve_layer_weights(config, K, degrees=None):
     """(config, K) -> the fp32 [K+1] weights of out = sum_k w_k X_k, or None for the mean (the reference's combination).
     --layer_weights mean | exp | ppr | "[w_0, ..., w_K]"; the reference's own --use_ppr_weights [--ppr_weights_path FILE]
@@ -269,6 +281,16 @@ class LightGCN(nn.Module):
                 raise _lib.LgcnError(f"--neg_ratio {self.neg_ratio} is not implemented together with --use_pop_gate / --use_item_item "
                                      "(the optional branches train on one negative per positive)")
         self._neg_ratio_said = False
+        # the loss of the fused step (--loss bpr | softmax, --softmax_temp; lgcn_ctx_set_loss): softmax = the positive
+        # against all R negatives of its sample in one log-sum-exp; every negative shape then goes to the _multi entry points
+        self.loss_kind, self.softmax_temp = resolve_loss(config)
+        if self.loss_kind == 'softmax':
+            if str(config.get('act_dtype', 'fp32')) == 'fp8':
+                raise _lib.LgcnError("--loss softmax is not implemented together with --act_dtype fp8 (fp32 and bf16 storage only)")
+            if self.use_pop_gate or self.use_item_item:
+                raise _lib.LgcnError("--loss softmax is not implemented together with --use_pop_gate / --use_item_item "
+                                     "(the optional branches train with the BPR loss only)")
+        self._loss_said = False
         self._gate_flat = None      # the eight MLP tensors of the gate in ONE buffer (what the fused step reads / updates)
         self._Graph = None
         self._dev = None            # device-side state (graph, workspace, context)
@@ -434,6 +456,11 @@ class LightGCN(nn.Module):
             if not self._neg_ratio_said:
                 world.cprint(f"[neg_ratio] --neg_ratio {self.neg_ratio}: the last layer is propagated densely (dense_last = 1)")
                 self._neg_ratio_said = True
+        if self.loss_kind == 'softmax' and not dense_last:
+            dense_last = True       # the softmax batch-row kernel is the 2 + R slot form too
+            if not self._loss_said:
+                world.cprint("[loss] --loss softmax: the last layer is propagated densely (dense_last = 1)")
+                self._loss_said = True
         st['act'] = _act_tables(max(1, K if dense_last else K - 1), N, d, act_dtype, dev)
         st['G64'] = torch.zeros(N, d, dtype=torch.int64, device=dev)
         st['bitmap'] = torch.zeros(2 * ((N + 31) // 32), dtype=torch.int32, device=dev)
@@ -500,6 +527,12 @@ class LightGCN(nn.Module):
                 msg = lib.lgcn_last_error()
                 lib.lgcn_ctx_destroy(h)
                 raise _lib.LgcnError(f"lgcn_ctx_set_layer_weights failed (rc={rc}): {msg.decode() if msg else ''}")
+        if self.loss_kind == 'softmax':
+            rc = lib.lgcn_ctx_set_loss(h, _lib.LOSS_SOFTMAX, float(self.softmax_temp))
+            if rc:
+                msg = lib.lgcn_last_error()
+                lib.lgcn_ctx_destroy(h)
+                raise _lib.LgcnError(f"lgcn_ctx_set_loss failed (rc={rc}): {msg.decode() if msg else ''}")
         if str(self.config.get('fold_g32', 1)).strip().lower() in ('0', 'false', 'off'):      # config['fold_g32'] = 0: fused_epoch launches k_g32 every step again (A/B, tests)
             rc = lib.lgcn_ctx_set_fold_g32(h, 0)
             if rc:
@@ -664,7 +697,11 @@ class LightGCN(nn.Module):
         R = int(neg.shape[1])
         u, pos_e, neg_e, _, _ = self.getEmbedding(users, pos, neg)          # neg_e [B, R, d]
         x = torch.sum(u * pos_e, dim=1)[:, None] - torch.sum(u[:, None, :] * neg_e, dim=2)
-        bpr = -torch.mean(F.logsigmoid(x))
+        if self.loss_kind == 'softmax':      # l_b = log(1 + sum_r exp(-x_{b,r} / tau)), one term per sample
+            z = -x / float(self.softmax_temp)
+            bpr = torch.logsumexp(torch.cat([torch.zeros_like(z[:, :1]), z], dim=1), dim=1).sum() / float(B)
+        else:
+            bpr = -torch.mean(F.logsigmoid(x))
         if str(self.config.get('reg_rows', 'propagated')) == 'ego':
             u, pos_e, neg_e = self.embedding_user.weight[users.long()], self.embedding_item.weight[pos.long()], self.embedding_item.weight[neg.long()]
         reg_loss = (0.5 * (u.norm(2).pow(2) + pos_e.norm(2).pow(2) + neg_e.norm(2).pow(2) / float(R))) / float(B)
@@ -674,6 +711,8 @@ class LightGCN(nn.Module):
         """model.py:162-183 (unfused, autograd-capable): (bpr [- entropy term of the gate], reg_loss)."""
         if torch.is_tensor(neg) and neg.dim() == 2:
             return self._bpr_loss_multi(users, pos, neg)
+        if self.loss_kind == 'softmax':          # 1-D negatives: R = 1
+            return self._bpr_loss_multi(users, pos, torch.as_tensor(neg).reshape(-1, 1))
         u, pos_e, neg_e, _, _ = self.getEmbedding(users, pos, neg)
         pos_scores = torch.sum(u * pos_e, dim=1)
         neg_scores = torch.sum(u * neg_e, dim=1)
@@ -716,7 +755,7 @@ class LightGCN(nn.Module):
         elif neg.shape[1] != n:
             raise ValueError(f"neg must be [{n}, R] or [R, {n}], got {tuple(neg.shape)}")
         R = int(neg.shape[0])
-        if R == 1:
+        if R == 1 and self.loss_kind != 'softmax':
             return None
         if not 1 <= R <= _lib.MAX_NEG_RATIO:
             raise ValueError(f"the negative ratio (neg_ratio) must be in 1..{_lib.MAX_NEG_RATIO}, got {R} negatives per positive")
@@ -745,6 +784,8 @@ class LightGCN(nn.Module):
             raise RuntimeError("this configuration of the popularity gate / item-item smoothing is outside the fused step "
                                "(--fused_variants 0, or gate hidden sizes > 64 / d > 128): use BPRLoss.stageOne (autograd path)")
         dev = self._table.device
+        if self.loss_kind == 'softmax' and self._neg_dim(neg) == 1:      # --loss softmax: every shape is a multi step, R = 1 included
+            neg = self._ids(neg, dev).reshape(1, -1)
         if self._neg_dim(neg) == 2:            # several negatives per positive: neg [B, R] (the sampler's S[:, 2:]) or [R, B]
             users, pos = self._ids(users, dev), self._ids(pos, dev)
             B = int(users.numel())
@@ -784,6 +825,8 @@ class LightGCN(nn.Module):
         dev = self._table.device
         users, pos = self._ids(users, dev), self._ids(pos, dev)
         negs = None
+        if self.loss_kind == 'softmax' and self._neg_dim(neg) == 1:      # --loss softmax: the multi epoch at R = 1
+            neg = self._ids(neg, dev).reshape(1, -1)
         if self._neg_dim(neg) == 2:            # several negatives per positive: neg [T, R] or [R, T]
             negs = self._negs_rt(neg, int(users.numel()), dev)
         if negs is None:                       # R == 1 (1-D, or one column): the three-slot epoch, unchanged
@@ -860,6 +903,8 @@ class PureMF(nn.Module):
         if int(config.get('neg_ratio', 1)) != 1:
             raise _lib.LgcnError(f"--neg_ratio {config.get('neg_ratio')} {no} (the matrix-factorisation step trains on triplets, "
                                  "one negative per positive)")
+        if str(config.get('loss', 'bpr')).strip().lower() != 'bpr':
+            raise _lib.LgcnError(f"--loss {config.get('loss')} {no} (the matrix-factorisation step computes the BPR loss)")
         if self.latent_dim not in (32, 64, 128, 256):
             raise ValueError("latent_dim_rec must be 32, 64, 128 or 256 for the HIP kernels")
         if self.n_users + self.m_items >= 2 ** 31:

@@ -144,6 +144,9 @@ class DataParallelBPR:
         if int(getattr(recmodel, 'neg_ratio', 1)) > 1 or int(config.get('neg_ratio', 1)) > 1:
             raise RuntimeError("--neg_ratio > 1 is implemented for single-GPU training only: DataParallelBPR (every reduce / shard "
                                "mode) trains on triplets, one negative per positive")
+        if str(getattr(recmodel, 'loss_kind', 'bpr')) != 'bpr' or str(config.get('loss', 'bpr')).strip().lower() != 'bpr':
+            raise RuntimeError("--loss softmax is implemented for single-GPU training only: DataParallelBPR (every reduce / shard "
+                               "mode) computes the BPR loss")
         if not dist.is_initialized():
             raise RuntimeError("torch.distributed is not initialised")
         # (row-sharded and column-sharded propagation refuse the optional branches: the first was never wired to carry the smoothing's

@@ -114,6 +114,8 @@ def configure(argv=None):
     config['layer_weights'] = args.layer_weights
     config['ppr_alpha'] = args.ppr_alpha
     config['neg_ratio'] = args.neg_ratio
+    config['loss'] = args.loss
+    config['softmax_temp'] = args.softmax_temp
     device =torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     return config
 

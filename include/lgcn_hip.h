@@ -330,6 +330,24 @@ int lgcn_train_step_multi(lgcn_ctx *ctx, const int32_t *users, const int32_t *po
 int lgcn_train_epoch_multi(lgcn_ctx *ctx, const int32_t *users, const int32_t *pos,
                            const int32_t *negs /* [R][T]: column r at negs + r*T */, int32_t R,
                            int64_t T, int32_t B, float *loss_out, void *stream);
+/* The loss of the multi-negative step (--loss).  LGCN_LOSS_BPR (the default) is the definition above.  With
+ * LGCN_LOSS_SOFTMAX the positive competes against all R negatives of its sample inside one log-sum-exp at temperature tau:
+ *   z_{b,r} = -x_{b,r} / tau,   l_b = log(1 + sum_r exp(z_{b,r})),   sm = 1/B sum_b l_b        (one term per sample: 1/B, not 1/(B R))
+ *   loss_out = {sm + decay * reg, sm, reg}      (reg as above)
+ *   gb_r = -q_{b,r} / (tau B),  q_{b,r} = exp(z_{b,r}) / (1 + sum_j exp(z_{b,j}))      (evaluated with the maximum subtracted: no
+ *                                                                                       exp of a positive argument, any finite score)
+ * lgcn_train_step_multi / lgcn_train_epoch_multi then run another batch-row launch (k_multineg_softmax) for every R in
+ * 1..LGCN_MAX_NEG_RATIO; forward, backward chain, Adam epilogue, edge dropout, layer weights and reg_ego are untouched.  At
+ * R = 1, tau = 1 it is the BPR step.  lgcn_ctx_set_loss(ctx, LGCN_LOSS_BPR, anything) restores exactly the launches of a
+ * context that was never told otherwise.  rc 3, with a message that names the loss and nothing changed: an unknown kind, tau
+ * not finite or <= 0, LGCN_FP8 storage, an optional branch (i2i / popularity gate), dense_last = 0.  While the softmax loss is
+ * set every three-slot and every rank-splitting entry point (lgcn_train_step / _i64, lgcn_train_epoch, lgcn_train_step_dp_* /
+ * _cols_*, lgcn_rs_phase, lgcn_train_epoch_dp) returns 3 and says so: their kernels compute BPR.                              */
+#define LGCN_LOSS_BPR 0
+#define LGCN_LOSS_SOFTMAX 1
+int lgcn_ctx_set_loss(lgcn_ctx *ctx, int32_t kind, float temperature);
+/* The loss in force (-1: null context); its temperature goes to temperature_out (may be NULL; 1 under LGCN_LOSS_BPR).       */
+int32_t lgcn_ctx_get_loss(const lgcn_ctx *ctx, float *temperature_out);
 
 /* The fold of the gradient-row conversion into the batch-row launch.  lgcn_train_epoch holds all triplets of
  * the call before its first step, so it computes once (per segment of 1024 steps) how many slots of each batch name each
