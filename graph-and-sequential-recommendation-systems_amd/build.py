@@ -7,6 +7,7 @@ The build itself runs under an exclusive file lock with a per-process temporary
 name, so concurrent builders (ranks of one job on a fresh checkout) cannot
 clobber each other's output."""
 import fcntl
+import glob
 import hashlib
 import os
 import shutil
@@ -15,7 +16,7 @@ import subprocess
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO_DIR = os.path.dirname(PKG_DIR)
 SOURCES = [os.path.join(PKG_DIR, "csrc", f) for f in
-           ("lgcn_device.hip", "lgcn_eval.hip", "lgcn_eval_ranks.hip", "lgcn_sampler.hip", "lgcn_shuffle.hip", "lgcn_ids.hip", "lgcn_i2i.hip", "lgcn_mf.hip", "lgcn_multineg.hip", "lgcn_softmax.hip", "lgcn_dp_loopback.hip", "lgcn_dp.cpp", "lgcn_host.cpp")]
+           ("lgcn_device.hip", "lgcn_eval.hip", "lgcn_eval_ranks.hip", "lgcn_sampler.hip", "lgcn_shuffle.hip", "lgcn_ids.hip", "lgcn_i2i.hip", "lgcn_mf.hip", "lgcn_multineg.hip", "lgcn_dp_loopback.hip", "lgcn_dp.cpp", "lgcn_host.cpp")]
 HEADER = os.path.join(REPO_DIR, "include", "lgcn_hip.h")
 LIB_PATH = os.environ.get("LGCN_LIB_PATH") or os.path.join(PKG_DIR, "liblgcn_hip.so")   # env: pick a tuning variant
 BASE_FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-shared", "-std=c++17"]
@@ -32,9 +33,14 @@ def find_hipcc():
     return None
 
 
+def hashed_files():
+    """Everything the library is compiled from: the sources, the installed header and every internal header under csrc/."""
+    return sources() + [HEADER] + sorted(glob.glob(os.path.join(PKG_DIR, "csrc", "*.h")))
+
+
 def source_hash(extra_flags=()):
     h = hashlib.sha256()
-    for f in sources() + [HEADER]:
+    for f in hashed_files():
         h.update(os.path.basename(f).encode())
         with open(f, "rb") as fh:
             h.update(fh.read())

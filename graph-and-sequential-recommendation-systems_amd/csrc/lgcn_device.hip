@@ -34,25 +34,11 @@
 #include <new>
 #include <vector>
 
-#include "lgcn_hip.h"
-#include "lgcn_internal.h"
+#include "lgcn_device_common.h"
 
-#define HIP_OK(expr)                                                            \
-    do {                                                                        \
-        hipError_t e_ = (expr);                                                 \
-        if (e_ != hipSuccess) {                                                 \
-            char buf_[256];                                                     \
-            snprintf(buf_, sizeof buf_, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-            lgcn_set_error(buf_);                                               \
-            return 10;                                                          \
-        }                                                                       \
-    } while (0)
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) float f32x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __bf16 bf16_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(16))) __bf16 bf16x16;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
@@ -74,8 +60,6 @@ __device__ __forceinline__ float *fp8_scales(void *tab, int64_t n_rows, int D) {
 #ifndef LGCN_GATHER_U
 #define LGCN_GATHER_U 8      /* max row gathers in flight per lane (8 x 16 B raw = 32 VGPRs) */
 #endif
-#define FIXED_SCALE 1125899906842624.0   /* 2^50 */
-#define FIXED_INV   8.8817841970012523e-16 /* 2^-50 */
 
 // C fp32 values per lane (C = 4: 16 B of fp32 / 8 B of bf16; C = 8: 32 B of fp32 / 16 B of bf16)
 template <int C> struct VecF;
@@ -105,11 +89,8 @@ __device__ __forceinline__ f32x4 load4(const float *p) { return loadv<4>(p); }
 __device__ __forceinline__ f32x4 load4(const bf16_t *p) { return loadv<4>(p); }
 __device__ __forceinline__ void store4(float *p, f32x4 v) { storev<4>(p, v); }
 __device__ __forceinline__ void store4(bf16_t *p, f32x4 v) { storev<4>(p, v); }
-// one fp8 element of a table, decoded (k_triplet's lower-layer rows: lane = column)
+// one fp8 element of a table, decoded (k_triplet's lower-layer rows: lane = column): the fp8 form of the header's tab_elem
 __device__ __forceinline__ float fp8_decode(uint8_t b) { return __builtin_amdgcn_cvt_pk_f32_fp8((int)b, false)[0]; }
-template <typename TI> __device__ __forceinline__ float tab_elem(const void *tab, int64_t n_rows, int D, int64_t row, int col);
-template <> __device__ __forceinline__ float tab_elem<float>(const void *tab, int64_t, int D, int64_t row, int col) { return ((const float *)tab)[row * D + col]; }
-template <> __device__ __forceinline__ float tab_elem<bf16_t>(const void *tab, int64_t, int D, int64_t row, int col) { return (float)((const bf16_t *)tab)[row * D + col]; }
 template <> __device__ __forceinline__ float tab_elem<fp8_t>(const void *tab, int64_t n_rows, int D, int64_t row, int col) {
     return fp8_scales(tab, n_rows, D)[row] * fp8_decode(((const uint8_t *)tab)[row * D + fp8_byte_of_col(col, D)]);
 }
@@ -239,7 +220,6 @@ struct GatherSrc {           // what a row gather reads
 // issued as many gathers as the fp32 one and was instruction-bound: +15 % for half the bytes).
 // The conversion to fp32 is kept OUT of the load block: hipcc otherwise waits vmcnt(0) inside every
 // block and the U gathers serialise (measured: bf16 SpMM 2x slower than fp32).
-typedef __attribute__((ext_vector_type(2))) long long i64x2;
 struct fixed4 { i64x2 a, b; };
 template <typename TI, bool SPARSE> struct Raw;
 template <> struct Raw<float, false> {
@@ -1145,12 +1125,6 @@ struct BprArgs {
     const uint16_t *mult; float *G32; float gdiv; int32_t *arrive;
 };
 
-__device__ __forceinline__ float logsigmoid_f(float x) { return fminf(x, 0.f) - log1pf(expf(-fabsf(x))); }
-__device__ __forceinline__ float sigmoid_neg_f(float x) {
-    const float z = expf(-fabsf(x));
-    return x < 0.f ? 1.f / (1.f + z) : z / (1.f + z);
-}
-
 __device__ __forceinline__ bool triplet_bad(const BprArgs &a, int b) {
     const int u = a.users[b], p = a.pos[b], n = a.neg[b];
     return u < 0 || u >= a.n_users || p < 0 || (int64_t)p + a.n_users >= a.N || n < 0 || (int64_t)n + a.n_users >= a.N;
@@ -1667,7 +1641,7 @@ __global__ void __launch_bounds__(256) k_triplet_gate(GateArgs a) {
         for (int j = 0; j < CPT; j++) {
             if (col) {
                 const float du = gb * (f[0][j] - f[1][j]) + a.lam * u[j];
-                if (a.G64) atomicAdd((unsigned long long *)(a.G64 + urow * D + j * LPT + lane), (unsigned long long)__double2ll_rn((double)du * FIXED_SCALE));
+                if (a.G64) fixed_add(a.G64 + urow * D + j * LPT + lane, du);
                 if (a.exchange) a.contrib[((int64_t)0 * a.shard + b) * D + j * LPT + lane] = du;
             }
         }
@@ -1699,7 +1673,7 @@ __global__ void __launch_bounds__(256) k_triplet_gate(GateArgs a) {
                 const float de = g[q] * dF[j] + die, dpv = (1.f - g[q]) * dF[j] + dip;
                 if (col) {
                     DPV[sidx * D + c] = dpv;
-                    if (a.G64) atomicAdd((unsigned long long *)(a.G64 + row * D + c), (unsigned long long)__double2ll_rn((double)de * FIXED_SCALE));
+                    if (a.G64) fixed_add(a.G64 + row * D + c, de);
                     if (a.exchange) a.contrib[((int64_t)(1 + q) * a.shard + b) * D + c] = de;
                 }
             }
@@ -1846,8 +1820,7 @@ __global__ void __launch_bounds__(256) k_scatter(SlotArgs a) {
     const float *src = a.gathered + r * blk + ((int64_t)c * a.shard + i) * D;
 #pragma unroll
     for (int j = 0; j < CPT; j++)
-        atomicAdd((unsigned long long *)(a.G64 + row * D + j * LPT + l),
-                  (unsigned long long)__double2ll_rn((double)src[j * LPT + l] * FIXED_SCALE));
+        fixed_add(a.G64 + row * D + j * LPT + l, src[j * LPT + l]);
     if (l == 0) {
         atomicOr(a.bitmap + (row >> 5), 1u << (row & 31));
         if (a.cnt) atomicAdd(a.cnt + row, 1);
@@ -2172,15 +2145,6 @@ static int launch_spmm_addself(const SpmmArgs &a, int d, hipStream_t st) {
     lgcn_set_error("embedding dim must be 32, 64, 128 or 256");
     return 3;
 }
-
-#define DISPATCH_D(d, CALL)                                                      \
-    switch (d) {                                                                 \
-    case 32: { constexpr int D = 32; CALL; } break;                              \
-    case 64: { constexpr int D = 64; CALL; } break;                              \
-    case 128: { constexpr int D = 128; CALL; } break;                            \
-    case 256: { constexpr int D = 256; CALL; } break;                            \
-    default: lgcn_set_error("embedding dim must be 32, 64, 128 or 256"); return 3; \
-    }
 
 static int check_dtype(int t) {
     if (t != LGCN_F32 && t != LGCN_BF16 && t != LGCN_FP8) { lgcn_set_error("dtype must be LGCN_F32, LGCN_BF16 or LGCN_FP8"); return 3; }
@@ -2654,8 +2618,8 @@ struct lgcn_ctx {
     // several negatives per positive (lgcn_train_step_multi): mn_R > 0 only while such a step runs -- its backward
     // enumerates (2 + mn_R) B slots (negative column r at mn_negs + r * mn_stride) and the reg_ego epilogue takes decay / (B mn_R)
     const int32_t *mn_negs; int64_t mn_stride; int32_t mn_R;
-    // the loss of the multi-negative step (lgcn_ctx_set_loss): LGCN_LOSS_BPR launches k_multineg_dense as ever,
-    // LGCN_LOSS_SOFTMAX k_multineg_softmax with the temperature loss_temp; the three-slot and rank-splitting entry points refuse
+    // the loss of the multi-negative step (lgcn_ctx_set_loss): LGCN_LOSS_BPR launches the BPR instantiations of k_multineg,
+    // LGCN_LOSS_SOFTMAX the softmax ones with the temperature loss_temp; the three-slot and rank-splitting entry points refuse
     int32_t loss_kind; float loss_temp;
 };
 // a multi-step call: nobody but this library touches E0 between its steps
@@ -3334,10 +3298,9 @@ static int run_bpr_multi(lgcn_ctx *x, const int32_t *users, const int32_t *pos, 
     a.terms = c.terms; a.terms_stride = B; a.err = c.err;
     a.reg_ego = c.reg_ego; a.cnt = x->cnt;
     for (int k = 0; k < x->lw_n; k++) a.w[k] = x->lw[k];
+    a.loss = x->loss_kind;
     if (x->loss_kind == LGCN_LOSS_SOFTMAX) {       // the same rows, flags and terms; another coefficient per negative
-        SoftmaxArgs s{};
-        s.m = a; s.tau = x->loss_temp; s.inv_tauB = (float)(1.0 / ((double)x->loss_temp * (double)B));
-        return lgcn_softmax_launch(s, c.d, c.act_dtype, x->lw_n != 0, st);
+        a.tau = x->loss_temp; a.inv_tauB = (float)(1.0 / ((double)x->loss_temp * (double)B));
     }
     return lgcn_multineg_launch(a, c.d, c.act_dtype, x->lw_n != 0, st);
 }

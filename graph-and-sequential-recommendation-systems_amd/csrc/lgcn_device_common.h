@@ -1,0 +1,72 @@
+// lgcn_device_common.h -- what the device translation units of liblgcn_hip.so share (not installed): the error macro of the
+// launchers, the 2^50 fixed point of G64, the vector typedefs, the switch over the embedding dim, and the few device functions
+// that more than one file needs.  ONE definition of each lives here; build.kernel_hash() covers lgcn_device.hip alone, so code
+// that another file needs too belongs in this header, not in a copy.
+#ifndef LGCN_DEVICE_COMMON_H
+#define LGCN_DEVICE_COMMON_H
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "lgcn_hip.h"
+#include "lgcn_internal.h"
+
+#define HIP_OK(expr)                                                            \
+    do {                                                                        \
+        hipError_t e_ = (expr);                                                 \
+        if (e_ != hipSuccess) {                                                 \
+            char buf_[256];                                                     \
+            snprintf(buf_, sizeof buf_, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+            lgcn_set_error(buf_);                                               \
+            return 10;                                                          \
+        }                                                                       \
+    } while (0)
+
+// G64 holds gradient rows as 64-bit fixed point: integer addition is associative, so a row's sum is order-free
+#define FIXED_SCALE 1125899906842624.0   /* 2^50 */
+#define FIXED_INV   8.8817841970012523e-16 /* 2^-50 */
+
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(2))) long long i64x2;
+typedef __bf16 bf16_t;
+
+// runs the statement with D a compile-time constant; any other d is the caller's error 3
+#define DISPATCH_D(d, ...)                                                       \
+    switch (d) {                                                                 \
+    case 32: { constexpr int D = 32; __VA_ARGS__; } break;                       \
+    case 64: { constexpr int D = 64; __VA_ARGS__; } break;                       \
+    case 128: { constexpr int D = 128; __VA_ARGS__; } break;                     \
+    case 256: { constexpr int D = 256; __VA_ARGS__; } break;                     \
+    default: lgcn_set_error("embedding dim must be 32, 64, 128 or 256"); return 3; \
+    }
+
+__device__ __forceinline__ float logsigmoid_f(float x) { return fminf(x, 0.f) - log1pf(expf(-fabsf(x))); }
+__device__ __forceinline__ float sigmoid_neg_f(float x) {
+    const float z = expf(-fabsf(x));
+    return x < 0.f ? 1.f / (1.f + z) : z / (1.f + z);
+}
+
+// element o of a table of the storage type TI, and the same by row and column (lgcn_device.hip adds the fp8 form of tab_elem)
+template <typename TI> __device__ __forceinline__ float tab_at(const void *tab, int64_t o) { return (float)((const TI *)tab)[o]; }
+template <typename TI> __device__ __forceinline__ float tab_elem(const void *tab, int64_t n_rows, int D, int64_t row, int col);
+template <> __device__ __forceinline__ float tab_elem<float>(const void *tab, int64_t, int D, int64_t row, int col) { return tab_at<float>(tab, row * D + col); }
+template <> __device__ __forceinline__ float tab_elem<bf16_t>(const void *tab, int64_t, int D, int64_t row, int col) { return tab_at<bf16_t>(tab, row * D + col); }
+
+// sum / max over the LPT consecutive lanes of a lane group (xor-shuffle tree: every lane ends with the same bits)
+template <int LPT> __device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+    for (int off = 1; off < LPT; off <<= 1) v += __shfl_xor(v, off);
+    return v;
+}
+template <int LPT> __device__ __forceinline__ float group_max(float v) {
+#pragma unroll
+    for (int off = 1; off < LPT; off <<= 1) v = fmaxf(v, __shfl_xor(v, off));
+    return v;
+}
+
+// *g64 += g in the fixed point of G64
+__device__ __forceinline__ void fixed_add(long long *g64, float g) {
+    atomicAdd((unsigned long long *)g64, (unsigned long long)__double2ll_rn((double)g * FIXED_SCALE));
+}
+#endif

@@ -26,10 +26,8 @@
 #include <stdint.h>
 #include <math.h>
 
-#include "lgcn_hip.h"
-#include "lgcn_internal.h"
+#include "lgcn_device_common.h"
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 #define EVAL_KMAX 64

@@ -20,12 +20,10 @@
 #include <stdint.h>
 #include <math.h>
 
-#include "lgcn_hip.h"
-#include "lgcn_internal.h"
+#include "lgcn_device_common.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;

@@ -47,13 +47,9 @@ struct MultiNegArgs {
     int32_t *err;
     int32_t reg_ego; int32_t *cnt;                     // reg_ego: cnt[row] += R per user / positive slot, 1 per negative slot
     float w[LGCN_MAX_LAYERS + 1];                      // wts launches only: the layer weights
+    // the loss (lgcn_ctx_set_loss): LGCN_LOSS_BPR, or LGCN_LOSS_SOFTMAX with z_r = -x_r / tau and gb_r = -q_r * inv_tauB,
+    // inv_tauB = 1 / (tau B) (inv_BR is then unused)
+    int32_t loss; float tau, inv_tauB;
 };
 int lgcn_multineg_launch(const MultiNegArgs &a, int d, int act_dtype, bool wts, hipStream_t st);
-// The same launch under the sampled-softmax loss (lgcn_softmax.hip; lgcn_ctx_set_loss): m as above (inv_BR unused),
-// z_r = -x_r / tau, gb_r = -q_r * inv_tauB with inv_tauB = 1 / (tau B).
-struct SoftmaxArgs {
-    MultiNegArgs m;
-    float tau, inv_tauB;
-};
-int lgcn_softmax_launch(const SoftmaxArgs &a, int d, int act_dtype, bool wts, hipStream_t st);
 #endif

@@ -17,34 +17,13 @@
 //                 and zeroes it, any other row has g = 0; last step's bitmap is zeroed with plain stores (the two bitmaps
 //                 alternate per step, as in the LightGCN step); one extra workgroup reduces the loss terms in the fixed order
 //                 of the LightGCN step's reduction.
-// The Adam arithmetic is that of the LightGCN step's epilogue (lerp, mul / addcmul, sqrt(v) / bc2_sqrt + eps, step_size),
-// restated here so that the file of that step is not touched.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
+// The Adam arithmetic is that of the LightGCN step's epilogue (lerp, mul / addcmul, sqrt(v) / bc2_sqrt + eps, step_size) on
+// 16-byte pieces of a dense stream.
 #include <new>
 
-#include "lgcn_hip.h"
-#include "lgcn_internal.h"
+#include "lgcn_device_common.h"
 
-#define HIP_OK(expr)                                                            \
-    do {                                                                        \
-        hipError_t e_ = (expr);                                                 \
-        if (e_ != hipSuccess) {                                                 \
-            char buf_[256];                                                     \
-            snprintf(buf_, sizeof buf_, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-            lgcn_set_error(buf_);                                               \
-            return 10;                                                          \
-        }                                                                       \
-    } while (0)
-
-#define MF_FIXED_SCALE 1125899906842624.0     /* 2^50, the scale of G64 everywhere in this library */
-#define MF_FIXED_INV   8.8817841970012523e-16 /* 2^-50 */
 #define MF_ADAM_BLOCKS_MAX 16384              /* workgroups of the Adam stream: one 16-byte piece per lane up to here, grid-stride beyond */
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) long long i64x2;
 
 struct lgcn_mf {
     lgcn_mf_config c;
@@ -122,9 +101,9 @@ __global__ void __launch_bounds__(256) k_mf_triplet(MfTripletArgs a) {
         const float du = (s * (n[i] - p[i]) + a.decay * u[i]) / a.Bf;
         const float dp = (a.decay * p[i] - s * u[i]) / a.Bf;
         const float dn = (s * u[i] + a.decay * n[i]) / a.Bf;
-        atomicAdd((unsigned long long *)(gu + i), (unsigned long long)__double2ll_rn((double)du * MF_FIXED_SCALE));
-        atomicAdd((unsigned long long *)(gp + i), (unsigned long long)__double2ll_rn((double)dp * MF_FIXED_SCALE));
-        atomicAdd((unsigned long long *)(gn + i), (unsigned long long)__double2ll_rn((double)dn * MF_FIXED_SCALE));
+        fixed_add(gu + i, du);
+        fixed_add(gp + i, dp);
+        fixed_add(gn + i, dn);
     }
     if (l == 0) {
         atomicOr(a.bitmap + (ru >> 5), 1u << (ru & 31));
@@ -177,8 +156,8 @@ __global__ void __launch_bounds__(256) k_mf_adam(MfAdamArgs a) {
         if ((word >> (row & 31)) & 1u) {               // a row of the batch: its gradient, consumed (G64 is all zero after the step)
             i64x2 *q = reinterpret_cast<i64x2 *>(a.G64 + 4 * i);
             const i64x2 q0 = q[0], q1 = q[1];
-            g[0] = (float)((double)q0.x * MF_FIXED_INV); g[1] = (float)((double)q0.y * MF_FIXED_INV);
-            g[2] = (float)((double)q1.x * MF_FIXED_INV); g[3] = (float)((double)q1.y * MF_FIXED_INV);
+            g[0] = (float)((double)q0.x * FIXED_INV); g[1] = (float)((double)q0.y * FIXED_INV);
+            g[2] = (float)((double)q1.x * FIXED_INV); g[3] = (float)((double)q1.y * FIXED_INV);
             q[0] = i64x2{0, 0}; q[1] = i64x2{0, 0};
         }
         m = m + a.w1 * (g - m);                         // exp_avg.lerp_(grad, 1-beta1)
@@ -192,14 +171,6 @@ __global__ void __launch_bounds__(256) k_mf_adam(MfAdamArgs a) {
         *reinterpret_cast<f32x4 *>(a.V + 4 * i) = v;
     }
 }
-
-#define MF_DISPATCH_D(d, stmt)                                      \
-    switch (d) {                                                    \
-    case 32: { constexpr int D = 32; stmt; break; }                 \
-    case 64: { constexpr int D = 64; stmt; break; }                 \
-    case 128: { constexpr int D = 128; stmt; break; }               \
-    default: { constexpr int D = 256; stmt; break; }                \
-    }
 
 extern "C" int lgcn_mf_create(const lgcn_mf_config *cfg, lgcn_mf **out) {
     if (!cfg || !out) { lgcn_set_error("lgcn_mf_create: null argument"); return 3; }
@@ -243,7 +214,7 @@ static int mf_step(lgcn_mf *x, const int32_t *users, const int32_t *pos, const i
     a.w1 = (float)(1.0 - c.beta1); a.beta2 = (float)c.beta2; a.omb2 = (float)(1.0 - c.beta2); a.eps = (float)c.eps;
     int64_t blocks = (a.n_vec + 255) / 256;
     if (blocks > MF_ADAM_BLOCKS_MAX) blocks = MF_ADAM_BLOCKS_MAX;
-    MF_DISPATCH_D(c.d, {
+    DISPATCH_D(c.d, {
         constexpr int TPB = 256 / (D / 4);
         hipLaunchKernelGGL((k_mf_triplet<D>), dim3((unsigned)(((int64_t)B + TPB - 1) / TPB)), dim3(256), 0, st, t);
         hipLaunchKernelGGL((k_mf_adam<D>), dim3((unsigned)blocks + 1), dim3(256), 0, st, a);

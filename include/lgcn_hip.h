@@ -336,7 +336,7 @@ int lgcn_train_epoch_multi(lgcn_ctx *ctx, const int32_t *users, const int32_t *p
  *   loss_out = {sm + decay * reg, sm, reg}      (reg as above)
  *   gb_r = -q_{b,r} / (tau B),  q_{b,r} = exp(z_{b,r}) / (1 + sum_j exp(z_{b,j}))      (evaluated with the maximum subtracted: no
  *                                                                                       exp of a positive argument, any finite score)
- * lgcn_train_step_multi / lgcn_train_epoch_multi then run another batch-row launch (k_multineg_softmax) for every R in
+ * lgcn_train_step_multi / lgcn_train_epoch_multi then run the softmax form of the batch-row launch (k_multineg) for every R in
  * 1..LGCN_MAX_NEG_RATIO; forward, backward chain, Adam epilogue, edge dropout, layer weights and reg_ego are untouched.  At
  * R = 1, tau = 1 it is the BPR step.  lgcn_ctx_set_loss(ctx, LGCN_LOSS_BPR, anything) restores exactly the launches of a
  * context that was never told otherwise.  rc 3, with a message that names the loss and nothing changed: an unknown kind, tau

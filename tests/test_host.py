@@ -45,6 +45,34 @@ def test_graft_entry_build_checks(pkg):
     assert "lgcn_abi_version() ==" in src and not re.search(r"lgcn_abi_version\(\) == \d", src)
 
 
+def test_source_hash_reads_every_file_the_library_includes(pkg):
+    """build.source_hash() decides whether liblgcn_hip.so is stale, so it has to read everything the library is compiled from:
+    every #include "x" of the sources, and of the headers those reach, names a file among the ones it hashes (an edit to a
+    struct that is passed by value into a kernel must not leave the old library in place)."""
+    b = pkg.build
+    hashed = b.hashed_files()
+    assert set(b.SOURCES) <= set(hashed) and b.HEADER in hashed
+    assert all(os.path.exists(f) for f in hashed)
+    names = {os.path.basename(f) for f in hashed}
+    assert len(names) == len(hashed)                        # the hash names files by basename: no two may share one
+    included = set()
+    for f in hashed:                                        # the sources and the headers themselves
+        for inc in re.findall(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', open(f).read(), flags=re.M):
+            assert os.path.basename(inc) in names, f"{os.path.basename(f)} includes {inc}, which source_hash() does not read"
+            included.add(os.path.basename(inc))
+    assert {"lgcn_internal.h", "lgcn_device_common.h", "lgcn_hip.h"} <= included
+    # and the hash does move with an internal header: the same files with one byte more in one of them
+
+    def digest(extra):
+        h = hashlib.sha256()
+        for f in hashed:
+            h.update(os.path.basename(f).encode())
+            h.update(open(f, "rb").read() + (extra if f.endswith("lgcn_internal.h") else b""))
+        h.update(" ".join(b.BASE_FLAGS).encode())
+        return h.hexdigest()
+    assert digest(b"") == b.source_hash() != digest(b" ")
+
+
 def test_glibc_stream_and_randint(pkg):
     s = pkg.sampling
     s.seed(2020)

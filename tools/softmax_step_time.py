@@ -2,8 +2,8 @@
 """Step time of the sampled-softmax loss (--loss softmax) against the BPR loss of the same multi-negative step:
 Gowalla, K = 3, d = 64, B = 2048 samples per step, fp32 and bf16 storage, R = 1, 4, 16 -- steps/s of the one-C-call epoch
 lgcn_train_epoch_multi for
-  (a) bpr       lgcn_ctx_set_loss(LGCN_LOSS_BPR): k_multineg_dense, the code this feature does not touch -- the baseline;
-  (b) softmax   lgcn_ctx_set_loss(LGCN_LOSS_SOFTMAX, tau): k_multineg_softmax, which reads the negatives' rows twice.
+  (a) bpr       lgcn_ctx_set_loss(LGCN_LOSS_BPR): the BPR form of k_multineg, one pass over the negatives -- the baseline;
+  (b) softmax   lgcn_ctx_set_loss(LGCN_LOSS_SOFTMAX, tau): the softmax form of k_multineg, which reads the negatives' rows twice.
 Both forms run on a context with dense_last = 1 and call the C entry point directly (R = 1 included, where model.fused_epoch
 would take the three-slot epoch under --loss bpr), on the same sampled rows and the same permutation.
 
