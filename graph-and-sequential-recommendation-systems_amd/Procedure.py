@@ -75,17 +75,30 @@ def _epoch_perm(T, device):
 
 
 def _sample_epoch_multi(dataset, device, R):
-    """--neg_ratio R > 1: the native host sampler with neg_num = R (sampling.cpp:27-56 writes rows of 2 + R ids; bit-exact with
-    the reference), the same epoch permutation as R = 1, lgcn_apply_perm_multi.  The device sampler draws one negative and
-    is not used here.  Returns int32 device tensors users [T], pos [T], negs [R, T]."""
+    """--neg_ratio R > 1: the native sampler with neg_num = R (sampling.cpp:27-56 writes rows of 2 + R ids; bit-exact with
+    the reference), the same epoch permutation as R = 1, lgcn_apply_perm_multi.  On a CUDA device with --gpu_sampler 1 the rows
+    are drawn on the device (lgcn_sample_negative_device_multi: the same rows from the same stream, no host loop, no upload)
+    and go to lgcn_apply_perm_multi as they are; otherwise, and for an epoch whose rejections exceed the device stream's margin,
+    the host loop draws them.  Returns int32 device tensors users [T], pos [T], negs [R, T]."""
     if not 1 <= R <= _lib.MAX_NEG_RATIO:
         raise ValueError(f"--neg_ratio must be in 1..{_lib.MAX_NEG_RATIO}, got {R}")
     if not (utils.sample_ext and utils.sampler_mode(dataset) == 'cpp'):
         raise _lib.LgcnError(f"--neg_ratio {R} needs the native sampler (--sampler cpp): the reference's Python sampler draws one "
                              "negative per positive (--sampler python, or --sampler auto on a dataset with a user without positives)")
-    S = utils.UniformSample_original(dataset, neg_ratio=R)
-    T = len(S)
-    S32 = torch.from_numpy(np.ascontiguousarray(S[:, :2 + R], dtype=np.int32)).to(device)
+    S32 = None
+    if torch.device(device).type == 'cuda' and int(world.config.get('gpu_sampler', 1)):
+        try:
+            S32 = utils.sampling.sample_negative_device(dataset.n_users, dataset.m_items, dataset.trainDataSize,
+                                                        utils._pos_csr(dataset), device, neg_num=R)
+        except _lib.LgcnError as e:
+            # rc 5: the margin (R * T/50 + 65536 draws) does not hold this epoch's rejections; the host generator has not moved
+            if "(rc=5)" not in str(e):
+                raise
+            world.cprint("[sampler] GPU sampler margin exceeded (dense dataset): host sampler for this epoch")
+    if S32 is None:
+        S = utils.UniformSample_original(dataset, neg_ratio=R)
+        S32 = torch.from_numpy(np.ascontiguousarray(S[:, :2 + R], dtype=np.int32)).to(device)
+    T = int(S32.shape[0])
     permd = _epoch_perm(T, device)
     users = torch.empty(T, dtype=torch.int32, device=device)
     pos = torch.empty_like(users)

@@ -428,3 +428,372 @@ extern "C" int lgcn_sample_negative_device(int user_num, int item_num, int64_t t
     lgcn_glibc_advance((uint64_t)res[0]);          // the host generator continues where the device stopped
     return 0;
 }
+
+// ---- several negatives per sample (neg_num = R, W = 1 + R draws per sample when nothing is rejected) -----------------------
+// The same design with "triplet t" read as "slot s": sample t owns the slots s = W t + j, j = 0 the positive draw, j = 1..R the
+// negatives, and slot s reads stream position s + delta (delta = rejections before it).  Position p can be a rejection only as a
+// NEGATIVE slot: with x = p - delta, x % W != 0 and the user of sample x / W positive on R[p] % m.  State, segments and events
+// are all counted in slots, so a segment may begin and end inside a sample (one sample can hold up to R events) and nothing is
+// special about a sample boundary.  lgcn_sample_negative_device (above) stays on its own kernels: the rows of the R = 1 path
+// and the margins at which it reports an exhausted stream are pinned by tests, and the W = 2 instance of these kernels computes
+// the same rows (tests/test_gpu_sampler_multi.py compares the two).
+#define SAMP_SEG_MAX_SLOTS (2 * SAMP_SEG_MAX)      /* slots per segment at most: the pair blocks of a segment are those of R = 1 */
+
+struct MultiArgs {
+    SampleArgs a;                     // a.T = samples; a.S rows of 2 + R ids
+    int32_t R, W;
+    long long n_slots;                // W * T
+};
+struct MSegArgs {
+    MultiArgs m;
+    long long seg;                    // slots per segment
+    SampState *st;                    // t_begin / seg_t0 / seg_t1 count SLOTS here
+    uint2 *pairs; int *pair_cnt;
+    SampEvent *events;                // (slot, extra draws consumed once the slot is done)
+};
+
+__global__ void __launch_bounds__(256) k_msamp_pairs(MSegArgs g) {
+    const SampleArgs &a = g.m.a;
+    const int W = g.m.W;
+    const int tid = threadIdx.x;
+    __shared__ int cnt[256];
+    __shared__ int total;
+    __shared__ long long s_s0, s_din;
+    __shared__ int s_skip;
+    if (tid == 0) { s_s0 = g.st->t_begin; s_din = g.st->delta; s_skip = g.st->fail != 0; }     // read once per workgroup (see k_samp_pairs)
+    __syncthreads();
+    const long long s0 = s_s0;
+    if (s0 >= g.m.n_slots || s_skip) return;
+    const long long s1 = min(g.m.n_slots, s0 + g.seg), din = s_din;
+    const long long pbase = s0 + din, plast = s1 - 1 + din + SAMP_DMAX;
+    const long long p = pbase + (long long)blockIdx.x * 256 + tid;
+    int c = 0;
+    int ulo = 0, uhi = -1, cand = 0;
+    if (p <= plast && p < a.n_draws) {
+        cand = (int)(a.R[p] % (uint32_t)a.item_num);
+        // slots that can read p: x = p - d for a d in [din, din + SAMP_DMAX], within the segment; their samples' users
+        long long xhi = p - din, xlo = p - din - SAMP_DMAX;
+        if (xhi > s1 - 1) xhi = s1 - 1;
+        if (xlo < s0) xlo = s0;
+        if (xlo <= xhi) { ulo = (int)(xlo / W / a.per_user); uhi = (int)(xhi / W / a.per_user); }
+        for (int u = ulo; u <= uhi; u++) {
+            const int64_t rs = a.indptr[u];
+            if (is_positive(a.indices + rs, (int)(a.indptr[u + 1] - rs), cand)) c++;
+        }
+    }
+    cnt[tid] = c;
+    if (tid == 0) total = 0;
+    __syncthreads();
+    if (c > 0) {                                              // rare: position order is kept by an explicit prefix
+        int off = 0;
+        for (int i = 0; i < tid; i++) off += cnt[i];
+        atomicAdd(&total, c);
+        uint2 *dst = g.pairs + (long long)blockIdx.x * SAMP_PCAP;
+        for (int u = ulo; u <= uhi; u++) {
+            const int64_t rs = a.indptr[u];
+            if (is_positive(a.indices + rs, (int)(a.indptr[u + 1] - rs), cand)) {
+                if (off < SAMP_PCAP) dst[off] = make_uint2((uint32_t)(p - pbase), (uint32_t)u);
+                off++;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        g.pair_cnt[blockIdx.x] = total;
+        if (total > SAMP_PCAP) atomicExch(&g.st->fail, 1);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_msamp_events(MSegArgs g, int nblocks) {
+    const SampleArgs &a = g.m.a;
+    const int W = g.m.W;
+    __shared__ uint2 pr[SAMP_LDS_PAIRS];
+    __shared__ int part[256];
+    __shared__ int s_first, s_i0, s_end, s_np;
+    __shared__ long long s_scur, s_d;
+    const int tid = threadIdx.x;
+    SampState *st = g.st;
+    const long long s0 = st->t_begin;
+    if (s0 >= g.m.n_slots || st->fail) { if (tid == 0) { st->seg_t0 = st->seg_t1 = 0; st->n_events = 0; } return; }
+    const long long s1 = min(g.m.n_slots, s0 + g.seg), din = st->delta;
+    const long long pbase = s0 + din;
+    // ---- the blocks' pairs, in block (= position) order, into LDS
+    const int per = (nblocks + 255) / 256, b0 = min(nblocks, tid * per), b1 = min(nblocks, b0 + per);
+    int mine = 0;
+    for (int b = b0; b < b1; b++) mine += min(g.pair_cnt[b], SAMP_PCAP);
+    part[tid] = mine;
+    __syncthreads();
+    if (tid == 0) { int run = 0; for (int i = 0; i < 256; i++) { const int v = part[i]; part[i] = run; run += v; } s_np = run; }
+    __syncthreads();
+    const int np = s_np;
+    if (np > SAMP_LDS_PAIRS) {                                // this segment keeps its state: k_msample takes over from it
+        if (tid == 0) { atomicExch(&st->fail, 1); st->seg_t0 = st->seg_t1 = 0; st->n_events = 0; }
+        return;
+    }
+    {
+        int o = part[tid];
+        for (int b = b0; b < b1; b++) {
+            const int n = min(g.pair_cnt[b], SAMP_PCAP);
+            for (int i = 0; i < n; i++) pr[o++] = g.pairs[(long long)b * SAMP_PCAP + i];
+        }
+    }
+    if (tid == 0) { s_scur = s0; s_d = din; s_i0 = 0; s_end = 0; }
+    __syncthreads();
+    int nev = 0;                                               // (thread 0's count)
+    long long seg_end = s1;
+    // every pass either consumes pairs (s_i0 grows) or records an event (nev grows; SAMP_EV_MAX ends the segment)
+    while (true) {
+        const long long scur = s_scur, d = s_d;
+        const int i0 = s_i0;
+        if (s_end || i0 >= np) break;
+        __syncthreads();
+        if (tid == 0) s_first = 0x7fffffff;
+        __syncthreads();
+        const int i1 = min(np, i0 + 1024);
+        for (int i = i0 + tid; i < i1; i += 256) {
+            // live: the position is a negative slot, not yet passed, of a sample of that user under the current delta
+            const long long x = pbase + pr[i].x - d;
+            if (x >= scur && x < s1 && x % W != 0 && (uint32_t)(x / W / a.per_user) == pr[i].y) atomicMin(&s_first, i);
+        }
+        __syncthreads();
+        const int f = s_first;
+        if (tid == 0) {
+            if (f == 0x7fffffff) s_i0 = i1;
+            else {                                              // a rejection event: walk its loop, the only serial part
+                const long long pf = pbase + pr[f].x;           // position of the rejected candidate
+                const long long s = pf - d;                     // its slot
+                const uint32_t u = pr[f].y;
+                long long q = pf + 1;
+                int j = f + 1;
+                bool ok = true;
+                while (true) {                                  // (bounded by n_draws)
+                    if (q >= a.n_draws) { ok = false; break; }
+                    bool rej = false;
+                    if (d + (q - pf) > din + SAMP_DMAX) {       // beyond the range the pairs cover: ask the row itself
+                        const int64_t rs = a.indptr[u];
+                        rej = is_positive(a.indices + rs, (int)(a.indptr[u + 1] - rs), (int)(a.R[q] % (uint32_t)a.item_num));
+                    } else {
+                        while (j < np && pbase + pr[j].x < q) j++;
+                        for (int jj = j; jj < np && pbase + pr[jj].x == q; jj++) rej |= pr[jj].y == u;
+                    }
+                    if (!rej) break;
+                    q++;
+                }
+                if (!ok) { atomicExch(&st->fail, 2); s_end = 1; seg_end = s; }      // (k_msample reports the exhausted stream)
+                else {
+                    const long long d_after = d + (q - pf);
+                    g.events[nev++] = SampEvent{s, d_after};
+                    s_scur = s + 1; s_d = d_after;
+                    // slot s + 1 reads position q + 1 under the new delta: the walk goes on with the pairs behind q, and the
+                    // liveness test alone says which of them are negative slots
+                    while (j < np && pbase + pr[j].x <= q) j++;
+                    s_i0 = j;
+                    if (d_after - din > SAMP_DMAX || nev >= SAMP_EV_MAX - 1) { s_end = 1; seg_end = s + 1; }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        // every draw the slots [s0, seg_end) read lies below seg_end + delta_out; a segment that reaches past the expanded
+        // stream is DISCARDED (see k_samp_events): k_msample checks every draw against n_draws and finishes from the old state
+        if (seg_end + s_d > a.n_draws) {
+            atomicExch(&st->fail, 1);
+            st->seg_t0 = st->seg_t1 = 0; st->n_events = 0;
+        } else {
+            st->seg_t0 = s0; st->seg_t1 = seg_end; st->seg_delta = din; st->n_events = nev;
+            st->t_begin = seg_end; st->delta = s_d;
+        }
+    }
+}
+
+// one thread per slot: consecutive threads read consecutive draws and write consecutive ids of S (the user column apart)
+__global__ void __launch_bounds__(256) k_msamp_emit(MSegArgs g) {
+    const SampleArgs &a = g.m.a;
+    const int W = g.m.W;
+    __shared__ SampEvent ev[SAMP_EV_MAX];
+    const SampState *st = g.st;
+    const long long s0 = st->seg_t0, s1 = st->seg_t1;
+    const long long s = s0 + (long long)blockIdx.x * 256 + threadIdx.x;
+    if (s0 + (long long)blockIdx.x * 256 >= s1) return;
+    const int nev = min(st->n_events, SAMP_EV_MAX);
+    for (int i = threadIdx.x; i < nev; i += 256) ev[i] = g.events[i];
+    __syncthreads();
+    if (s >= s1) return;
+    int lo = 0, hi = nev;                                      // events on a smaller slot
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (ev[mid].t < s) lo = mid + 1; else hi = mid; }
+    const long long d = lo > 0 ? ev[lo - 1].delta_after : st->seg_delta;
+    // an event slot's accepted candidate follows its rejected ones: their number is what the event added to delta
+    const long long nrej = (lo < nev && ev[lo].t == s) ? ev[lo].delta_after - d : 0;
+    const long long t = s / W;
+    const int j = (int)(s - t * W);
+    int32_t *row = a.S + (long long)(W + 1) * t;               // 64-bit: (2 + R) T passes 2^31 at the 200 M-sample shape
+    if (j == 0) {
+        const int u = (int)(t / a.per_user);
+        const int64_t rs = a.indptr[u];
+        row[0] = u;
+        row[1] = a.indices[rs + (int)(a.R[s + d] % (uint32_t)(int)(a.indptr[u + 1] - rs))];
+    } else {
+        row[1 + j] = (int)(a.R[s + d + nrej] % (uint32_t)a.item_num);
+    }
+}
+
+// the finisher (and, alone, the whole job: `init` NULL): k_sample with all R candidates of a sample evaluated by its thread
+__global__ void __launch_bounds__(SAMPLE_THREADS) k_msample(MultiArgs m, const SampState *init) {
+    const SampleArgs &a = m.a;
+    const int W = m.W;
+    __shared__ long long first_rej;      // smallest sample of the window with a rejection in any slot
+    __shared__ long long s_s0, s_delta;
+    __shared__ int s_fail;
+    const int tid = threadIdx.x;
+    if (tid == 0) { s_s0 = init ? init->t_begin : 0; s_delta = init ? init->delta : 0; s_fail = init && init->fail == 2 ? 1 : 0; }
+    __syncthreads();
+    long long window = 2 * SAMPLE_THREADS;
+    // every pass moves s_s0 forward by at least one slot or sets s_fail
+    while (true) {
+        const long long s0 = s_s0, delta = s_delta;
+        if (s0 >= m.n_slots || s_fail) break;
+        const long long t0 = s0 / W;
+        const int j0 = (int)(s0 - t0 * W);                    // > 0: the segments stopped inside sample t0
+        if (tid == 0) first_rej = a.T;
+        __syncthreads();
+        long long t1 = t0, fr = a.T;
+        if (j0 == 0) {
+            t1 = min((long long)a.T, t0 + window);
+            // the W draws of the last sample of the window lie below W t1 + delta
+            if ((long long)W * t1 + delta > a.n_draws) { if (tid == 0) s_fail = 1; __syncthreads(); break; }
+            for (long long t = t0 + tid; t < t1; t += SAMPLE_THREADS) {
+                const int u = (int)(t / a.per_user);
+                const int64_t rs = a.indptr[u];
+                const int deg = (int)(a.indptr[u + 1] - rs);
+                const int32_t *row = a.indices + rs;
+                const long long base = (long long)W * t + delta;
+                bool rej = false;
+                for (int j = 1; j < W; j++) rej |= is_positive(row, deg, (int)(a.R[base + j] % (uint32_t)a.item_num));
+                if (rej) atomicMin(&first_rej, t);
+                else {
+                    int32_t *o = a.S + (long long)(W + 1) * t;
+                    o[0] = u; o[1] = row[(int)(a.R[base] % (uint32_t)deg)];
+                    for (int j = 1; j < W; j++) o[1 + j] = (int)(a.R[base + j] % (uint32_t)a.item_num);
+                }
+            }
+            __syncthreads();
+            fr = first_rej;
+        }
+        if (tid == 0) {
+            if (j0 == 0 && fr >= t1) { s_s0 = (long long)W * t1; }
+            else {                              // one sample, serially over its slots from j0 on: the only serial part
+                const long long ts = j0 == 0 ? fr : t0;
+                const int u = (int)(ts / a.per_user);
+                const int64_t rs = a.indptr[u];
+                const int deg = (int)(a.indptr[u + 1] - rs);
+                const int32_t *row = a.indices + rs;
+                int32_t *o = a.S + (long long)(W + 1) * ts;
+                long long i = (long long)W * ts + j0 + delta;
+                bool ok = true;
+                for (int j = j0; j < W && ok; j++) {
+                    if (i >= a.n_draws) { ok = false; break; }
+                    if (j == 0) { o[0] = u; o[1] = row[(int)(a.R[i++] % (uint32_t)deg)]; continue; }
+                    int cand = (int)(a.R[i++] % (uint32_t)a.item_num);
+                    while (is_positive(row, deg, cand)) {       // (bounded by n_draws)
+                        if (i >= a.n_draws) { ok = false; break; }
+                        cand = (int)(a.R[i++] % (uint32_t)a.item_num);
+                    }
+                    if (ok) o[1 + j] = cand;
+                }
+                if (!ok) s_fail = 1;
+                else {
+                    s_delta = i - (long long)W * (ts + 1);
+                    s_s0 = (long long)W * (ts + 1);
+                }
+            }
+        }
+        // window follows the distance between rejecting samples (2x the last gap, within [2, 64] x threads)
+        const long long gap = (fr < t1 ? fr : t1) - t0 + 1;
+        window = min(max(2 * gap, 2LL * SAMPLE_THREADS), 64LL * SAMPLE_THREADS);
+        __syncthreads();
+    }
+    if (tid == 0) { a.result[0] = m.n_slots + s_delta; a.result[1] = s_fail; }
+}
+
+// W draws per sample + R x (the margin of one negative): rejections scale with R.  R = 1 gives stream_draws(T).
+static inline int64_t stream_draws_multi(int64_t T, int R) { return (int64_t)(1 + R) * T + (int64_t)R * (T / g_margin_div) + g_margin_fixed; }
+static inline int64_t mseg_pair_blocks() { return ((int64_t)SAMP_SEG_MAX_SLOTS + SAMP_DMAX) / 256 + 2; }
+static inline int64_t mseg_workspace_bytes() {
+    return 256 /* state */ + mseg_pair_blocks() * (SAMP_PCAP * 8 + 4) + SAMP_EV_MAX * (int64_t)sizeof(SampEvent) + 256;
+}
+static bool neg_num_ok(int neg_num) {
+    if (neg_num >= 1 && neg_num <= LGCN_MAX_NEG_RATIO) return true;
+    lgcn_set_error("sample_negative_device_multi: the negative ratio neg_num must be in 1..16");
+    return false;
+}
+
+extern "C" int64_t lgcn_sample_negative_device_multi_workspace(int user_num, int64_t train_num, int neg_num) {
+    if (user_num <= 0 || train_num < 0 || !neg_num_ok(neg_num)) return 0;
+    const int64_t T = (int64_t)user_num * (train_num / user_num);
+    const int64_t draws = stream_draws_multi(T, neg_num);
+    const int64_t nblocks = (draws + GLIBC_BLOCK - 1) / GLIBC_BLOCK;
+    return nblocks * GLIBC_BLOCK * 4 + nblocks * 31 * 4 + 256 + mseg_workspace_bytes();
+}
+
+extern "C" int lgcn_sample_negative_device_multi(int user_num, int item_num, int64_t train_num,
+                                                 const int64_t *h_indptr, const int64_t *d_indptr, const int32_t *d_indices,
+                                                 int neg_num, int32_t *d_S, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (!neg_num_ok(neg_num)) return 3;
+    if (user_num <= 0 || item_num <= 0 || train_num < 0 || !h_indptr || !d_indptr || !d_indices || !d_S || !workspace) {
+        lgcn_set_error("sample_negative_device_multi: invalid argument"); return 3;
+    }
+    const int per_user = (int)(train_num / user_num);
+    const int64_t T = (int64_t)user_num * per_user;
+    if (T == 0) return 0;
+    for (int u = 0; u < user_num; u++) {
+        const int64_t deg = h_indptr[u + 1] - h_indptr[u];
+        if (deg <= 0) { lgcn_set_error("sample_negative: a user has no training positives (the reference divides by zero here); use the python-mode sampler for such datasets"); return 2; }
+        if (deg >= item_num) { lgcn_set_error("sample_negative: a user is positive on every item (rejection loop would not end)"); return 2; }
+    }
+    if (workspace_bytes < lgcn_sample_negative_device_multi_workspace(user_num, train_num, neg_num)) { lgcn_set_error("sample_negative_device_multi: workspace too small"); return 3; }
+    const int R = neg_num, W = 1 + R;
+    const int64_t draws = stream_draws_multi(T, R);
+    const int64_t nblocks = (draws + GLIBC_BLOCK - 1) / GLIBC_BLOCK;
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t *Rs = (uint32_t *)workspace;
+    uint32_t *hist = Rs + nblocks * GLIBC_BLOCK;
+    int64_t *result = (int64_t *)(((uintptr_t)(hist + nblocks * 31) + 15) & ~(uintptr_t)15);
+    std::vector<uint32_t> h((size_t)nblocks * 31);
+    lgcn_glibc_block_histories(nblocks, GLIBC_BLOCK, h.data());
+    if (hipMemcpyAsync(hist, h.data(), h.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) { lgcn_set_error("sample_negative_device_multi: history upload failed"); return 10; }
+    hipLaunchKernelGGL(k_glibc_expand, dim3((unsigned)((nblocks + 63) / 64)), dim3(64), 0, st, hist, nblocks, Rs);
+    MultiArgs m{SampleArgs{Rs, nblocks * GLIBC_BLOCK, d_indptr, d_indices, user_num, item_num, per_user, T, d_S, result}, R, W, (long long)W * T};
+    char *seg_ws = (char *)(((uintptr_t)(result + 2) + 255) & ~(uintptr_t)255);
+    MSegArgs g{m, 0, (SampState *)seg_ws, nullptr, nullptr, nullptr};
+    g.pairs = (uint2 *)(seg_ws + 256);
+    g.pair_cnt = (int *)(g.pairs + mseg_pair_blocks() * SAMP_PCAP);
+    g.events = (SampEvent *)(((uintptr_t)(g.pair_cnt + mseg_pair_blocks()) + 15) & ~(uintptr_t)15);
+    // k_msamp_pairs tests a position against the SAMP_DMAX / W / per_user + 1 users whose samples can read it: fewer than at
+    // R = 1, so the rule of the three-slot path (very sparse datasets go to the one-workgroup kernel) holds as it is
+    const bool segments = SAMP_SEGMENTS != 0 && per_user >= 8;
+    if (hipMemsetAsync(g.st, 0, sizeof(SampState), st) != hipSuccess) { lgcn_set_error("sample_negative_device_multi: memset failed"); return 10; }
+    if (segments) {
+        // a segment should end by itself, not on SAMP_DMAX: size it for half that many expected rejections, at R x (deg / items)
+        // rejections per sample = R / W of that per slot
+        const double rate = (double)h_indptr[user_num] / (double)user_num / (double)item_num * R / W;
+        long long seg = rate > 0 ? (long long)(SAMP_DMAX / (2.0 * rate)) : SAMP_SEG_MAX_SLOTS;
+        seg = seg > SAMP_SEG_MAX_SLOTS ? SAMP_SEG_MAX_SLOTS : seg < 8192 ? 8192 : seg / 256 * 256;
+        g.seg = seg;
+        const long long nseg = (m.n_slots + seg - 1) / seg * 5 / 4 + 4;
+        const unsigned pair_blocks = (unsigned)((seg + SAMP_DMAX) / 256 + 1);
+        for (long long s = 0; s < nseg; s++) {
+            hipLaunchKernelGGL(k_msamp_pairs, dim3(pair_blocks), dim3(256), 0, st, g);
+            hipLaunchKernelGGL(k_msamp_events, dim3(1), dim3(256), 0, st, g, (int)pair_blocks);
+            hipLaunchKernelGGL(k_msamp_emit, dim3((unsigned)(seg / 256)), dim3(256), 0, st, g);
+        }
+    }
+    hipLaunchKernelGGL(k_msample, dim3(1), dim3(SAMPLE_THREADS), 0, st, m, (const SampState *)g.st);
+    int64_t res[2] = {0, 1};
+    if (hipMemcpyAsync(res, result, sizeof res, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) { lgcn_set_error("sample_negative_device_multi: kernel failed"); return 10; }
+    if (res[1]) { lgcn_set_error("sample_negative_device_multi: more rejections than the stream margin allows"); return 5; }
+    lgcn_glibc_advance((uint64_t)res[0]);          // the host generator continues where the device stopped
+    return 0;
+}

@@ -79,7 +79,8 @@ def build_parser():
                    help='NEW: graph rows with more non-zeros than this get their last-layer row from a whole-chip SpMM once per '
                         'step instead of from every triplet that names them (0 = library default 131072, < 0 = off)')
     p.add_argument('--gpu_sampler', type=int, default=1,
-                   help='NEW: 1 = the cpp-mode BPR sampler runs on the GPU (same rand() stream, same rows); 0 = on the host')
+                   help='NEW: 1 = the cpp-mode BPR sampler runs on the GPU at every --neg_ratio (same rand() stream, same rows of '
+                        '2 + neg_ratio ids); 0 = on the host')
     p.add_argument('--lazy_loss', type=int, default=0,
                    help='NEW: 1 = BPRLoss.stageOne returns a float-like DeferredLoss that is read from the device only when looked at '
                         '(the reference returns loss.cpu().item(): a host round trip per step); 0 = a Python float, as the reference')

@@ -54,27 +54,59 @@ def sample_negative_ByUser(users, item_num, allPos, neg_num):
     return S
 
 
-_DEVICE_CSR = {}          # id(indptr array) -> (device indptr, device indices, workspace)
+_DEVICE_CSR = {}          # id(indptr array) -> [device indptr, device indices, workspace (the largest asked for so far), ...]
 
 
-def sample_negative_device(user_num, item_num, train_num, allPos, device):
-    """NEW: sample_negative (neg_num = 1) on the GPU -- the same int32 rows from the same rand()
-    stream, returned as a DEVICE tensor [user_num*(train_num//user_num), 3] (no host loop, no upload)."""
+def _device_csr(indptr, indices, device, ws):
+    """The cached device copy of one CSR and a workspace of at least `ws` bytes (it grows with neg_num and the margin)."""
     import torch
-    indptr, indices = _csr_of(allPos)
     key = (indptr.ctypes.data, indices.ctypes.data, str(device))
     ent = _DEVICE_CSR.get(key)
-    lib = _lib.load()
     if ent is None:
-        ws = int(lib.lgcn_sample_negative_device_workspace(int(user_num), int(train_num)))
-        ent = (torch.from_numpy(indptr).to(device), torch.from_numpy(indices).to(device),
-               torch.empty(max(ws, 256), dtype=torch.uint8, device=device), indptr, indices)
+        ent = [torch.from_numpy(indptr).to(device), torch.from_numpy(indices).to(device),
+               torch.empty(max(ws, 256), dtype=torch.uint8, device=device), indptr, indices]
         _DEVICE_CSR.clear()
         _DEVICE_CSR[key] = ent
-    d_ip, d_ix, work = ent[:3]
+    elif ent[2].numel() < ws:
+        ent[2] = torch.empty(ws, dtype=torch.uint8, device=device)
+    return ent[:3]
+
+
+def sample_negative_device(user_num, item_num, train_num, allPos, device, neg_num=1):
+    """NEW: sample_negative on the GPU -- the same int32 rows from the same rand() stream, returned as a DEVICE
+    tensor [user_num*(train_num//user_num), 2+neg_num] (no host loop, no upload).  neg_num = 1 is served by
+    lgcn_sample_negative_device, 2..16 by lgcn_sample_negative_device_multi."""
+    import torch
+    neg_num = int(neg_num)
+    if neg_num != 1:
+        return sample_negative_device_multi(user_num, item_num, train_num, allPos, device, neg_num)
+    indptr, indices = _csr_of(allPos)
+    lib = _lib.load()
+    ws = int(lib.lgcn_sample_negative_device_workspace(int(user_num), int(train_num)))
+    d_ip, d_ix, work = _device_csr(indptr, indices, device, ws)
     T = int(user_num) * (int(train_num) // int(user_num))
     S = torch.empty(T, 3, dtype=torch.int32, device=device)
     _lib.check(lib.lgcn_sample_negative_device(int(user_num), int(item_num), int(train_num), _lib.npp(indptr),
                                                _lib.tp(d_ip), _lib.tp(d_ix), _lib.tp(S), _lib.tp(work), int(work.numel()),
                                                _lib.current_stream()), "sampling.sample_negative_device")
+    return S
+
+
+def sample_negative_device_multi(user_num, item_num, train_num, allPos, device, neg_num):
+    """lgcn_sample_negative_device_multi for any neg_num in 1..16 (at 1 the rows of sample_negative_device, from the
+    slot kernels) -> DEVICE tensor int32 [user_num*(train_num//user_num), 2+neg_num]."""
+    import torch
+    neg_num = int(neg_num)
+    if not 1 <= neg_num <= _lib.MAX_NEG_RATIO:
+        raise ValueError(f"neg_num must be in 1..{_lib.MAX_NEG_RATIO}, got {neg_num}")
+    indptr, indices = _csr_of(allPos)
+    lib = _lib.load()
+    ws = int(lib.lgcn_sample_negative_device_multi_workspace(int(user_num), int(train_num), neg_num))
+    d_ip, d_ix, work = _device_csr(indptr, indices, device, ws)
+    T = int(user_num) * (int(train_num) // int(user_num))
+    S = torch.empty(T, 2 + neg_num, dtype=torch.int32, device=device)
+    _lib.check(lib.lgcn_sample_negative_device_multi(int(user_num), int(item_num), int(train_num), _lib.npp(indptr),
+                                                     _lib.tp(d_ip), _lib.tp(d_ix), neg_num, _lib.tp(S), _lib.tp(work),
+                                                     int(work.numel()), _lib.current_stream()),
+               "sampling.sample_negative_device_multi")
     return S

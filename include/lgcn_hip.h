@@ -80,6 +80,18 @@ int lgcn_sample_negative_device(int user_num, int item_num, int64_t train_num,
  * returns 5 -- host generator untouched -- when an epoch's rejections need more.  A test makes the margin small to
  * drive the segmented path into the end of the stream; values <= 0 restore the defaults.  Affects the workspace size. */
 void lgcn_sampler_test_margin(int64_t divisor, int64_t fixed);
+/* The device sampler for neg_num = R negatives per positive, 1 <= R <= LGCN_MAX_NEG_RATIO: the rows of
+ * lgcn_sample_negative(..., neg_num, S) as d_S int32 [user_num*(train_num/user_num), 2+neg_num] in DEVICE memory, from the
+ * same rand() stream, the host generator left where the host loop leaves it.  Arguments as lgcn_sample_negative_device;
+ * the workspace query takes neg_num (monotone in it; at 1 it is the three-slot query).  The stream margin is
+ * neg_num * (T / divisor) + fixed draws beyond the 1 + neg_num per sample (lgcn_sampler_test_margin sets both calls').
+ * Returns 3 (nothing touched) for an invalid argument, a short workspace or neg_num outside 1..16, 2 (nothing written) for
+ * a user without positives or positive on every item, 5 (generator not advanced) when the margin is exceeded, 10 for a
+ * failed launch or copy.  Synchronises `stream`. */
+int64_t lgcn_sample_negative_device_multi_workspace(int user_num, int64_t train_num, int neg_num);
+int lgcn_sample_negative_device_multi(int user_num, int item_num, int64_t train_num,
+                                      const int64_t *h_indptr, const int64_t *d_indptr, const int32_t *d_indices,
+                                      int neg_num, int32_t *d_S, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* numpy legacy global RandomState stream (MT19937), used by the reference for
  * the fallback sampler and the epoch shuffle.                                 */
