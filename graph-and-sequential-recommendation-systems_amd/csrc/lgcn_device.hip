@@ -2621,6 +2621,11 @@ struct lgcn_ctx {
     // the loss of the multi-negative step (lgcn_ctx_set_loss): LGCN_LOSS_BPR launches the BPR instantiations of k_multineg,
     // LGCN_LOSS_SOFTMAX the softmax ones with the temperature loss_temp; the three-slot and rank-splitting entry points refuse
     int32_t loss_kind; float loss_temp;
+    // the (2 + R) B slot form of the backward is on: a multi-negative step (mn_R >= 1) or an in-batch step (mn_R = 0, no negatives)
+    bool mn_on;
+    // the in-batch softmax (LGCN_LOSS_INBATCH): the workspace of its launches, allocated by the first lgcn_ctx_set_loss
+    // that accepts the loss (ib_cap = max_batch rounded up to 32 rows) and freed with the context; ONE allocation, carved up
+    void *ib_ws; int32_t ib_cap;
 };
 // a multi-step call: nobody but this library touches E0 between its steps
 struct LoopScope {
@@ -2660,7 +2665,7 @@ extern "C" int lgcn_ctx_create(const lgcn_train_config *cfg, lgcn_ctx **out) {
     x->lw_n = 0; for (int k = 0; k <= LGCN_MAX_LAYERS; k++) x->lw[k] = 0.f;
     x->fold_g32 = true; x->mult = nullptr; x->mult_cap = 0; x->fold_mult = nullptr; x->arrive = nullptr; x->folded_steps = 0;
     x->mn_negs = nullptr; x->mn_stride = 0; x->mn_R = 0;
-    x->loss_kind = LGCN_LOSS_BPR; x->loss_temp = 1.f;
+    x->loss_kind = LGCN_LOSS_BPR; x->loss_temp = 1.f; x->mn_on = false; x->ib_ws = nullptr; x->ib_cap = 0;
     x->bm_words = (x->N + 31) / 32; x->flip = 0;
     const size_t stride = table_bytes(x->N, c.d, c.act_dtype);
     for (int k = 0; k <= LGCN_MAX_LAYERS; k++) x->act[k] = nullptr;
@@ -2733,6 +2738,7 @@ extern "C" void lgcn_ctx_destroy(lgcn_ctx *ctx) {
     if (ctx->cnt) (void)hipFree(ctx->cnt);
     if (ctx->arrive) (void)hipFree(ctx->arrive);
     if (ctx->mult) (void)hipFree(ctx->mult);
+    if (ctx->ib_ws) (void)hipFree(ctx->ib_ws);
     if (ctx->tvar) (void)hipFree(ctx->tvar);
     if (ctx->item_bitmap) (void)hipFree(ctx->item_bitmap);
     if (ctx->gate_partials) (void)hipFree(ctx->gate_partials);
@@ -2808,10 +2814,35 @@ static int refuse_layer_weights(const lgcn_ctx *x, const char *who) {
     return 3;
 }
 
+// floats of the in-batch workspace for `cap` rows of dim d: U, P | sbb | uid, pid | mrg | part (the largest part count)
+static size_t inbatch_ws_words(int32_t cap, int d) {
+    return (size_t)cap * (2 * (size_t)d + 1 + 2 + 2 + 2 * (size_t)lgcn_inbatch_parts(cap));
+}
+// accepted under exactly the conditions of LGCN_LOSS_SOFTMAX; the workspace is allocated once, before anything is changed
+static int set_loss_inbatch(lgcn_ctx *ctx, float temperature) {
+    if (!(temperature > 0.f) || !isfinite(temperature)) { lgcn_set_error("lgcn_ctx_set_loss: the in-batch softmax loss (inbatch) needs a finite temperature > 0"); return 3; }
+    if (ctx->c.act_dtype == LGCN_FP8) { lgcn_set_error("lgcn_ctx_set_loss: the in-batch softmax loss (inbatch) is not implemented for LGCN_FP8 activation storage"); return 3; }
+    if (ctx->variant) { lgcn_set_error("lgcn_ctx_set_loss: the in-batch softmax loss (inbatch) is not implemented with the optional branches (item-item smoothing / popularity gate)"); return 3; }
+    if (!ctx->c.dense_last) { lgcn_set_error("lgcn_ctx_set_loss: the in-batch softmax loss (inbatch) needs a context with dense_last = 1 (the gathered last layer has no 2 B slot form)"); return 3; }
+    if (!ctx->ib_ws) {
+        const int32_t cap = lgcn_inbatch_rows(ctx->c.max_batch);
+        void *ws = nullptr;
+        if (hipMalloc(&ws, sizeof(float) * inbatch_ws_words(cap, ctx->c.d)) != hipSuccess) {
+            (void)hipGetLastError();
+            lgcn_set_error("lgcn_ctx_set_loss: cannot allocate the workspace of the in-batch softmax loss (inbatch): 2 * max_batch * d * 4 bytes and a few vectors");
+            return 4;
+        }
+        ctx->ib_ws = ws; ctx->ib_cap = cap;
+    }
+    ctx->loss_kind = LGCN_LOSS_INBATCH; ctx->loss_temp = temperature;
+    return 0;
+}
+
 extern "C" int lgcn_ctx_set_loss(lgcn_ctx *ctx, int32_t kind, float temperature) {
     if (!ctx) { lgcn_set_error("lgcn_ctx_set_loss: null context"); return 3; }
     if (kind == LGCN_LOSS_BPR) { ctx->loss_kind = LGCN_LOSS_BPR; ctx->loss_temp = 1.f; return 0; }      // the step launches what it always launched
-    if (kind != LGCN_LOSS_SOFTMAX) { lgcn_set_error("lgcn_ctx_set_loss: unknown loss kind (LGCN_LOSS_BPR or LGCN_LOSS_SOFTMAX)"); return 3; }
+    if (kind == LGCN_LOSS_INBATCH) return set_loss_inbatch(ctx, temperature);
+    if (kind != LGCN_LOSS_SOFTMAX) { lgcn_set_error("lgcn_ctx_set_loss: unknown loss kind (LGCN_LOSS_BPR, LGCN_LOSS_SOFTMAX or LGCN_LOSS_INBATCH)"); return 3; }
     if (!(temperature > 0.f) || !isfinite(temperature)) { lgcn_set_error("lgcn_ctx_set_loss: the sampled-softmax loss needs a finite temperature > 0"); return 3; }
     if (ctx->c.act_dtype == LGCN_FP8) { lgcn_set_error("lgcn_ctx_set_loss: the sampled-softmax loss is not implemented for LGCN_FP8 activation storage"); return 3; }
     if (ctx->variant) { lgcn_set_error("lgcn_ctx_set_loss: the sampled-softmax loss is not implemented with the optional branches (item-item smoothing / popularity gate)"); return 3; }
@@ -2824,11 +2855,16 @@ extern "C" int32_t lgcn_ctx_get_loss(const lgcn_ctx *ctx, float *temperature_out
     if (temperature_out) *temperature_out = ctx->loss_temp;
     return ctx->loss_kind;
 }
-// today's three-slot kernels, and every form that splits a step over ranks, compute BPR: say so instead of training another loss
-static int refuse_softmax(const lgcn_ctx *x, const char *who) {
+// today's three-slot kernels, and every form that splits a step over ranks, compute BPR: say so instead of training another
+// loss.  The in-batch loss trains through its own two entry points only, so lgcn_train_step_multi / _epoch_multi refuse it too.
+// (Declared in lgcn_internal.h: lgcn_train_step_i64 in lgcn_ids.hip refuses in the same words.)
+int lgcn_refuse_loss(const lgcn_ctx *x, const char *who) {
     if (!x || x->loss_kind == LGCN_LOSS_BPR) return 0;
-    char buf[224];
-    snprintf(buf, sizeof buf, "%s: the sampled-softmax loss (lgcn_ctx_set_loss) is implemented for lgcn_train_step_multi / lgcn_train_epoch_multi only", who);
+    char buf[256];
+    if (x->loss_kind == LGCN_LOSS_INBATCH)
+        snprintf(buf, sizeof buf, "%s: the in-batch softmax loss (inbatch; lgcn_ctx_set_loss) is implemented for lgcn_train_step_inbatch / lgcn_train_epoch_inbatch only", who);
+    else
+        snprintf(buf, sizeof buf, "%s: the sampled-softmax loss (lgcn_ctx_set_loss) is implemented for lgcn_train_step_multi / lgcn_train_epoch_multi only", who);
     lgcn_set_error(buf);
     return 3;
 }
@@ -3090,7 +3126,7 @@ static int backward_layer(lgcn_ctx *x, int k, const int32_t *users, const int32_
     const lgcn_train_config &c = x->c;
     const bool first = (k == c.K), last = (k == 1);
     if (first) {        // every contribution is in G64 by now: convert the batch rows once (the fold: k_triplet has done it)
-        if (x->mn_R) {      // several negatives per positive: (2 + R) B slots, never folded
+        if (x->mn_on) {     // several negatives per positive, or the in-batch loss (R = 0): (2 + R) B slots, never folded
             SlotArgsMulti s = slot_args_multi(x, users, pos, B, loss_out);
             DISPATCH_D(c.d, hipLaunchKernelGGL((k_g32_multi<D>), dim3(slot_grid_multi(x, B)), dim3(256), 0, st, s));
         } else if (!x->fold_mult) {
@@ -3121,7 +3157,7 @@ static int backward_layer(lgcn_ctx *x, int k, const int32_t *users, const int32_
         const double bc2 = 1.0 - pow(c.beta2, (double)x->step);
         a.P = c.E0; a.M = c.adam_m; a.V = c.adam_v;
         a.cnt = x->cnt; a.lam = c.decay / (float)B;
-        if (x->mn_R) a.lam = c.decay / (float)((int64_t)B * x->mn_R);      // the counts are R per user / positive slot, 1 per negative slot
+        if (x->mn_R > 0) a.lam = c.decay / (float)((int64_t)B * x->mn_R);      // the counts are R per user / positive slot, 1 per negative slot
         // inside a multi-step call on replicated tables the epilogue keeps the bf16 copy of E0 current (row-sharded steps
         // update only the owned rows and convert again after the exchange)
         a.Pb = (x->e0b && x->in_loop && fused_finish) ? x->e0b : nullptr;
@@ -3182,7 +3218,7 @@ static int run_backward(lgcn_ctx *x, const int32_t *users, const int32_t *pos, c
         hipLaunchKernelGGL(k_gate_adam, dim3((unsigned)((x->gate_P + 255) / 256)), dim3(256), 0, st, ga);
     }
     if (c.K >= 2) { x->flip ^= 1; return 0; }       // next step flags rows in the other bitmap
-    if (x->mn_R) {
+    if (x->mn_on) {
         SlotArgsMulti sm = slot_args_multi(x, users, pos, B, loss_out);
         DISPATCH_D(c.d, hipLaunchKernelGGL((k_finish_multi<D>), dim3(slot_grid_multi(x, B)), dim3(256), 0, st, sm));
         return 0;
@@ -3206,7 +3242,7 @@ extern "C" int lgcn_train_step(lgcn_ctx *x, const int32_t *users, const int32_t 
                                int32_t B, float *loss_out, void *stream) {
     int rc = check_batch(x, users, pos, neg, B);
     if (rc) return rc;
-    if ((rc = refuse_softmax(x, "lgcn_train_step"))) return rc;
+    if ((rc = lgcn_refuse_loss(x, "lgcn_train_step"))) return rc;
     if (!loss_out) { lgcn_set_error("train step: loss_out is null"); return 3; }
     hipStream_t st = (hipStream_t)stream;
     x->dr = make_drop(x->drop_keep, x->drop_seed, x->step, 0);        // ONE mask per step, from the counter before the step
@@ -3223,7 +3259,7 @@ extern "C" int lgcn_train_epoch(lgcn_ctx *x, const int32_t *users, const int32_t
                                 int64_t T, int32_t B, float *loss_out, void *stream) {
     if (T <= 0) return 0;
     if (!x) { lgcn_set_error("train epoch: null context"); return 3; }
-    if (int rc = refuse_softmax(x, "lgcn_train_epoch")) return rc;
+    if (int rc = lgcn_refuse_loss(x, "lgcn_train_epoch")) return rc;
     LoopScope scope(x);
     // The fold of k_g32: the call's triplets are all here, so how many slots of each batch name a row is known
     // before the first step -- one k_slot_mult launch per segment of steps, into the context's buffer -- and k_triplet writes
@@ -3274,6 +3310,7 @@ static int check_multi(const lgcn_ctx *x, const void *u, const void *p, const vo
                        int64_t neg_stride, const char *who) {
     char buf[224];
     if (!x || !u || !p || !n || !loss_out) { snprintf(buf, sizeof buf, "%s: null argument", who); lgcn_set_error(buf); return 3; }
+    if (x->loss_kind == LGCN_LOSS_INBATCH) return lgcn_refuse_loss(x, who);
     if (R < 1 || R > LGCN_MAX_NEG_RATIO) { snprintf(buf, sizeof buf, "%s: the negative ratio R = %d is out of range (1..%d)", who, (int)R, LGCN_MAX_NEG_RATIO); lgcn_set_error(buf); return 3; }
     if (!x->c.dense_last) { snprintf(buf, sizeof buf, "%s: a negative ratio above the three-slot step's needs a context with dense_last = 1 (the gathered last layer has no 2 + R slot form)", who); lgcn_set_error(buf); return 3; }
     if (x->c.act_dtype == LGCN_FP8) { snprintf(buf, sizeof buf, "%s: the negative ratio (several negatives per positive) is not implemented for LGCN_FP8 activation storage", who); lgcn_set_error(buf); return 3; }
@@ -3309,8 +3346,8 @@ static int train_step_multi(lgcn_ctx *x, const int32_t *users, const int32_t *po
                             int32_t B, float *loss_out, hipStream_t st) {
     struct MultiScope {         // the backward's slot kernels and the reg_ego epilogue read these; cleared on every way out
         lgcn_ctx *x;
-        MultiScope(lgcn_ctx *x_, const int32_t *n, int64_t s, int32_t r) : x(x_) { x->mn_negs = n; x->mn_stride = s; x->mn_R = r; }
-        ~MultiScope() { x->mn_negs = nullptr; x->mn_stride = 0; x->mn_R = 0; }
+        MultiScope(lgcn_ctx *x_, const int32_t *n, int64_t s, int32_t r) : x(x_) { x->mn_negs = n; x->mn_stride = s; x->mn_R = r; x->mn_on = true; }
+        ~MultiScope() { x->mn_negs = nullptr; x->mn_stride = 0; x->mn_R = 0; x->mn_on = false; }
     } scope(x, negs, neg_stride, R);
     int rc;
     x->dr = make_drop(x->drop_keep, x->drop_seed, x->step, 0);        // ONE mask per step, from the counter before the step
@@ -3340,13 +3377,83 @@ extern "C" int lgcn_train_epoch_multi(lgcn_ctx *x, const int32_t *users, const i
     return 0;
 }
 
+// The in-batch sampled softmax: run_forward, the four launches of lgcn_inbatch.hip, run_backward over the 2 B slots
+// (the multi-negative slot kernels with R = 0 and no negatives).  Everything is checked before anything is launched or counted.
+static int check_inbatch(const lgcn_ctx *x, const void *u, const void *p, const void *loss_out, int32_t B, const char *who) {
+    char buf[256];
+    if (!x || !u || !p || !loss_out) { snprintf(buf, sizeof buf, "%s: null argument", who); lgcn_set_error(buf); return 3; }
+    if (x->loss_kind != LGCN_LOSS_INBATCH || !x->ib_ws) {
+        snprintf(buf, sizeof buf, "%s: the in-batch softmax loss (inbatch) is not set on this context (lgcn_ctx_set_loss with LGCN_LOSS_INBATCH)", who);
+        lgcn_set_error(buf); return 3;
+    }
+    if (B <= 0 || B > x->c.max_batch) { snprintf(buf, sizeof buf, "%s: batch size out of range (0 < B <= max_batch)", who); lgcn_set_error(buf); return 3; }
+    return 0;
+}
+
+static int run_inbatch(lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B, hipStream_t st) {
+    const lgcn_train_config &c = x->c;
+    InBatchArgs ia{};
+    MultiNegArgs &a = ia.m;
+    a.X0 = c.E0; a.K = c.K;
+    for (int k = 1; k <= x->fwd_layers; k++) a.Xl[k] = x->act[k];
+    a.n_users = c.n_users; a.N = x->N;
+    a.users = users; a.pos = pos; a.negs = nullptr; a.neg_stride = 0; a.R = 0; a.B = B;
+    a.lam = c.decay / (float)B;
+    a.G64 = (long long *)c.G64; a.bitmap = c.bitmap + x->flip * x->bm_words;
+    a.stale_bitmap = c.bitmap + (x->flip ^ 1) * x->bm_words; a.bitmap_words = x->bm_words;
+    a.terms = c.terms; a.terms_stride = B; a.err = c.err;
+    a.reg_ego = c.reg_ego; a.cnt = x->cnt;
+    for (int k = 0; k < x->lw_n; k++) a.w[k] = x->lw[k];
+    a.loss = LGCN_LOSS_INBATCH; a.tau = x->loss_temp; a.inv_tauB = (float)(1.0 / ((double)x->loss_temp * (double)B));
+    const size_t cap = (size_t)x->ib_cap, d = (size_t)c.d;
+    float *w = (float *)x->ib_ws;
+    ia.cap = x->ib_cap;
+    ia.U = w; ia.P = w + cap * d; ia.sbb = w + 2 * cap * d;
+    ia.uid = (int32_t *)(w + 2 * cap * d + cap); ia.pid = ia.uid + cap;
+    ia.mrg = w + 2 * cap * d + 3 * cap; ia.part = w + 2 * cap * d + 5 * cap;
+    return lgcn_inbatch_launch(ia, c.d, c.act_dtype, x->lw_n != 0, st);
+}
+
+static int train_step_inbatch(lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B, float *loss_out, hipStream_t st) {
+    struct InBatchScope {       // the backward's slot kernels enumerate 2 B slots; cleared on every way out
+        lgcn_ctx *x;
+        explicit InBatchScope(lgcn_ctx *x_) : x(x_) { x->mn_negs = nullptr; x->mn_stride = 0; x->mn_R = 0; x->mn_on = true; }
+        ~InBatchScope() { x->mn_on = false; }
+    } scope(x);
+    int rc;
+    x->dr = make_drop(x->drop_keep, x->drop_seed, x->step, 0);        // ONE mask per step, from the counter before the step
+    if ((rc = run_forward(x, st))) return rc;
+    if ((rc = run_inbatch(x, users, pos, B, st))) return rc;
+    if ((rc = run_backward(x, users, pos, nullptr, B, nullptr, B, 1, loss_out, st))) return rc;
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int lgcn_train_step_inbatch(lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B, float *loss_out, void *stream) {
+    if (int rc = check_inbatch(x, users, pos, loss_out, B, "lgcn_train_step_inbatch")) return rc;
+    return train_step_inbatch(x, users, pos, B, loss_out, (hipStream_t)stream);
+}
+
+extern "C" int lgcn_train_epoch_inbatch(lgcn_ctx *x, const int32_t *users, const int32_t *pos, int64_t T, int32_t B, float *loss_out,
+                                        void *stream) {
+    if (T <= 0) return 0;
+    if (int rc = check_inbatch(x, users, pos, loss_out, B, "lgcn_train_epoch_inbatch")) return rc;
+    LoopScope scope(x);
+    int64_t i = 0;
+    for (int64_t t = 0; t < T; t += B, i++) {
+        const int32_t b = (int32_t)((T - t) < B ? (T - t) : B);
+        if (int rc = train_step_inbatch(x, users + t, pos + t, b, loss_out + 3 * i, (hipStream_t)stream)) return rc;
+    }
+    return 0;
+}
+
 extern "C" int lgcn_train_step_dp_part1(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *neg,
                                         int32_t B_global, int32_t world, int32_t rank, void *stream) {
     int rc = check_batch(x, users, pos, neg, B_global);
     if (rc) return rc;
     if ((rc = refuse_dropout(x, "lgcn_train_step_dp_part1"))) return rc;
     if ((rc = refuse_layer_weights(x, "lgcn_train_step_dp_part1"))) return rc;
-    if ((rc = refuse_softmax(x, "lgcn_train_step_dp_part1"))) return rc;
+    if ((rc = lgcn_refuse_loss(x, "lgcn_train_step_dp_part1"))) return rc;
     if (!x->c.contrib) { lgcn_set_error("dp step: cfg.contrib exchange buffer missing"); return 3; }
     if (world < 1 || rank < 0 || rank >= world) { lgcn_set_error("dp step: bad world/rank"); return 3; }
     const int32_t shard = (B_global + world - 1) / world;
@@ -3371,7 +3478,7 @@ extern "C" int lgcn_train_step_dp_dense_part1(lgcn_ctx *x, const int32_t *users,
     if (rc) return rc;
     if ((rc = refuse_dropout(x, "lgcn_train_step_dp_dense_part1"))) return rc;
     if ((rc = refuse_layer_weights(x, "lgcn_train_step_dp_dense_part1"))) return rc;
-    if ((rc = refuse_softmax(x, "lgcn_train_step_dp_dense_part1"))) return rc;
+    if ((rc = lgcn_refuse_loss(x, "lgcn_train_step_dp_dense_part1"))) return rc;
     if (world < 1 || rank < 0 || rank >= world) { lgcn_set_error("dp step: bad world/rank"); return 3; }
     const int32_t shard = (B_global + world - 1) / world;
     const int32_t b_off = rank * shard;
@@ -3417,7 +3524,7 @@ extern "C" int lgcn_train_step_dp_part2(lgcn_ctx *x, const int32_t *users, const
     if (rc) return rc;
     if ((rc = refuse_dropout(x, "lgcn_train_step_dp_part2"))) return rc;
     if ((rc = refuse_layer_weights(x, "lgcn_train_step_dp_part2"))) return rc;
-    if ((rc = refuse_softmax(x, "lgcn_train_step_dp_part2"))) return rc;
+    if ((rc = lgcn_refuse_loss(x, "lgcn_train_step_dp_part2"))) return rc;
     if (!loss_out || world < 1) { lgcn_set_error("dp step part 2: invalid argument"); return 3; }
     const int32_t shard = (B_global + world - 1) / world;
     // gathered == NULL is the dense form: G64, the terms and (popularity gate) gate_total hold the reduced sums of the global batch
@@ -3441,7 +3548,7 @@ extern "C" int lgcn_train_step_cols_part1(lgcn_ctx *x, const int32_t *users, con
     if (rc) return rc;
     if ((rc = refuse_dropout(x, "lgcn_train_step_cols_part1"))) return rc;
     if ((rc = refuse_layer_weights(x, "lgcn_train_step_cols_part1"))) return rc;
-    if ((rc = refuse_softmax(x, "lgcn_train_step_cols_part1"))) return rc;
+    if ((rc = lgcn_refuse_loss(x, "lgcn_train_step_cols_part1"))) return rc;
     if (x->variant) { lgcn_set_error("column-sharded step: the popularity gate / item-item smoothing mix columns (MLPs over the row): not supported"); return 3; }
     if (!x->c.contrib) { lgcn_set_error("column-sharded step: cfg.contrib (3*max_batch*d floats: the batch's slot rows) missing"); return 3; }
     hipStream_t st = (hipStream_t)stream;
@@ -3457,7 +3564,7 @@ extern "C" int lgcn_train_step_cols_part2(lgcn_ctx *x, const int32_t *users, con
     if (rc) return rc;
     if ((rc = refuse_dropout(x, "lgcn_train_step_cols_part2"))) return rc;
     if ((rc = refuse_layer_weights(x, "lgcn_train_step_cols_part2"))) return rc;
-    if ((rc = refuse_softmax(x, "lgcn_train_step_cols_part2"))) return rc;
+    if ((rc = lgcn_refuse_loss(x, "lgcn_train_step_cols_part2"))) return rc;
     if (!loss_out) { lgcn_set_error("column-sharded step part 2: loss_out is null"); return 3; }
     hipStream_t st = (hipStream_t)stream;
     if ((rc = run_bpr(x, users, pos, neg, B, 0, B, B, true, false, st, true, 2))) return rc;
@@ -3477,7 +3584,7 @@ extern "C" int lgcn_rs_phase(lgcn_ctx *x, int32_t phase, int32_t k, const int32_
     if (rc) return rc;
     if ((rc = refuse_dropout(x, "lgcn_rs_phase"))) return rc;
     if ((rc = refuse_layer_weights(x, "lgcn_rs_phase"))) return rc;
-    if ((rc = refuse_softmax(x, "lgcn_rs_phase"))) return rc;
+    if ((rc = lgcn_refuse_loss(x, "lgcn_rs_phase"))) return rc;
     if (x->variant) { lgcn_set_error("lgcn_rs_phase: the popularity gate / item-item smoothing run on one GPU only"); return 3; }
     const lgcn_train_config &c = x->c;
     hipStream_t st = (hipStream_t)stream;
@@ -3635,7 +3742,7 @@ static int train_epoch_dp_impl(lgcn_ctx *x, lgcn_dp *dp, const int32_t *users, c
 extern "C" int lgcn_train_epoch_dp(lgcn_ctx *x, lgcn_dp *dp, const int32_t *users, const int32_t *pos, const int32_t *neg,
                                    int64_t T, int32_t B_global, int32_t reduce, const int64_t *row_ranges, float *gathered,
                                    float *loss_out, void *stream) {
-    if (refuse_dropout(x, "lgcn_train_epoch_dp") || refuse_layer_weights(x, "lgcn_train_epoch_dp") || refuse_softmax(x, "lgcn_train_epoch_dp")) return 3;         // (every rank's context says the same: nobody waits in a collective)
+    if (refuse_dropout(x, "lgcn_train_epoch_dp") || refuse_layer_weights(x, "lgcn_train_epoch_dp") || lgcn_refuse_loss(x, "lgcn_train_epoch_dp")) return 3;         // (every rank's context says the same: nobody waits in a collective)
     const int rc = train_epoch_dp_impl(x, dp, users, pos, neg, T, B_global, reduce, row_ranges, gathered, loss_out, stream);
     // a rank that leaves the loop early never reaches its next collective: release the loopback ranks waiting for it
     // (RCCL has its own abort / timeout machinery)

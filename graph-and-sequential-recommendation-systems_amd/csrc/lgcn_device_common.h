@@ -65,6 +65,29 @@ template <int LPT> __device__ __forceinline__ float group_max(float v) {
     return v;
 }
 
+// The output-table row of a slot of the dense-last batch-row launches (k_multineg, k_inbatch_rows): e[j] = the row `row` at
+// columns j * LPT + l (mean over the K + 1 layers, or the weighted sum); e0[j] = E0's.  ONE expression for every loss, so a row
+// has the same bits whichever loss reads it.
+template <int D, typename TI, bool WTS>
+__device__ __forceinline__ void slot_row(const MultiNegArgs &a, int64_t row, int l, float *e, float *e0) {
+    constexpr int LPT = D < 64 ? D : 64, CPT = D / LPT;
+    const float div = (float)(a.K + 1);
+#pragma unroll
+    for (int j = 0; j < CPT; j++) {
+        const int64_t o = row * D + j * LPT + l;
+        float s = a.X0[o];
+        e0[j] = s;
+        if constexpr (WTS) {
+            s *= a.w[0];
+            for (int k = 1; k <= a.K; k++) s += a.w[k] * tab_at<TI>(a.Xl[k], o);
+            e[j] = s;
+        } else {
+            for (int k = 1; k <= a.K; k++) s += tab_at<TI>(a.Xl[k], o);
+            e[j] = s / div;
+        }
+    }
+}
+
 // *g64 += g in the fixed point of G64
 __device__ __forceinline__ void fixed_add(long long *g64, float g) {
     atomicAdd((unsigned long long *)g64, (unsigned long long)__double2ll_rn((double)g * FIXED_SCALE));

@@ -20,10 +20,7 @@ __global__ void __launch_bounds__(256) k_ids_to_i32(const int64_t *u, const int6
 extern "C" int lgcn_train_step_i64(lgcn_ctx *ctx, const int64_t *users, const int64_t *pos, const int64_t *neg, int32_t B,
                                    int32_t *ids_scratch, float *loss_out, void *stream) {
     if (!ctx || !users || !pos || !neg || !ids_scratch || B <= 0) { lgcn_set_error("lgcn_train_step_i64: invalid argument"); return 3; }
-    if (lgcn_ctx_get_loss(ctx, nullptr) != LGCN_LOSS_BPR) {       // refused before the scratch buffer is written
-        lgcn_set_error("lgcn_train_step_i64: the sampled-softmax loss (lgcn_ctx_set_loss) is implemented for lgcn_train_step_multi / lgcn_train_epoch_multi only");
-        return 3;
-    }
+    if (int rc = lgcn_refuse_loss(ctx, "lgcn_train_step_i64")) return rc;       // refused before the scratch buffer is written
     hipLaunchKernelGGL(k_ids_to_i32, dim3((unsigned)((3 * (int64_t)B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, users, pos, neg, B, ids_scratch);
     return lgcn_train_step(ctx, ids_scratch, ids_scratch + B, ids_scratch + 2 * (int64_t)B, B, loss_out, stream);
 }

@@ -1,0 +1,347 @@
+// lgcn_inbatch.hip -- the in-batch sampled softmax of the fused LightGCN step (--loss inbatch; lgcn_train_step_inbatch /
+// lgcn_train_epoch_inbatch), gfx950 (wave64).
+//
+// A batch is B samples (u_b, p_b).  With e the rows of the model's output table (layer mean, or the weighted sum):
+//   s_{b,c} = e_{u_b}.e_{p_c}                                  for sound b, c (both ids of the sample in range)
+//   A_b     = { c sound, c != b, p_c != p_b, u_c != u_b }       the competitors of sample b
+//   z_{b,c} = (s_{b,c} - s_{b,b}) / tau,  l_b = log(1 + sum_{c in A_b} exp(z_{b,c})),  sm = 1/B sum_b l_b,  terms[b] = -l_b
+//   q_{b,c} = exp(z_{b,c}) / (1 + sum_j exp(z_{b,j})),  Q_b = sum_c q_{b,c}
+//   W[b,c] = q_{b,c} / (tau B) (c in A_b),  W[b,b] = -Q_b / (tau B),  0 otherwise
+//   g_{u_b} = sum_c W[b,c] e_{p_c} + lam e_{u_b},   g_{p_c} = sum_b W[b,c] e_{u_b} + lam e_{p_c},   lam = decay / B
+//
+// Four launches between the forward and the backward of the step, over a workspace of Bp = B rounded up to 32 rows:
+//   k_inbatch_rows   one lane group of min(D, 64) lanes per sample (the geometry and the id check of k_multineg).  Gathers e_u
+//                    and e_p through slot_row -- the expression every loss uses -- into dense fp32 U[Bp][D], P[Bp][D] (zero
+//                    rows for void samples and for the padding b >= B), writes s_{b,b}, the reg term, the ids (-1: void),
+//                    zeroes the stale bitmap, flags the two rows, counts them and adds the lam terms to G64.
+//   k_inbatch_norm   one wave per (32 users, part of the item sweep).  The score tile is P.U^T on the fp32-input MFMA
+//                    (v_mfma_f32_32x32x2_f32: exact fp32, a k-ordered fmaf chain), so a lane holds ONE user (column) and 16
+//                    items (rows) of the tile: the running (m, r) of the user -- sum of exponentials = exp(m) (1 + r), the
+//                    first maximal term being the 1 -- lives in the lane, the two lane halves are merged with one shuffle and
+//                    one partial per part leaves.  No atomics on floats, no LDS.
+//   k_inbatch_diag   one lane group per sample again: merges the parts in ascending order (m_b = max(0, max z): no exp of a
+//                    positive argument; the term that equals exp(0) stays out of the sum, so a tiny l_b keeps its relative
+//                    accuracy), writes terms[b] and the merged (M_b, 1 + Zm1_b), and adds the diagonal W[b,b] to both rows.
+//   k_inbatch_grad   one wave per (32 owned rows, part of the sweep, role, 128-column block).  Role "users" recomputes the
+//                    tile as P.U^T (user on the lane), role "items" as U.P^T (item on the lane); W is formed elementwise in
+//                    the 16 accumulator registers and register i IS the A operand of the next 32x32x2 MFMA (output row =
+//                    lane & 31 = the owned index, k = lane half = tile rows r and r + 4 of register i): W^T.Other accumulates
+//                    into 32 x 128 fp32 with no lane movement and no LDS.  The partial rows go to G64 with fixed_add, so the
+//                    split of the sweep has no ordering effect.
+// s_{b,c} has the same bits in all three places: the same k order (lane half h walks columns h D/2 .. h D/2 + D/2 - 1 of both
+// operands) and fp32 products commute, so exp(z - M) <= 1 everywhere and q, Q_b are consistent.
+// Operands: up to D = 64 (IB_REG_D) a lane keeps its row of the owned side in registers for the whole sweep and loads the swept
+// side's NEXT tile (and this tile's ids, normalisers and second-product operands) while the score MFMAs of this tile run; above
+// that the rows are streamed from L2 in chunks of 8 columns per lane half (128 floats per operand would not fit beside the
+// 64-register gradient accumulator).  Measured (profiles/inbatch/README.md): the passes are bound by the vector ALU work on
+// the 16 scores of a lane (a division, an expf, the mask compares), not by the matrix pipe.
+// The sweep split: LGCN_INBATCH_PART_TILES = 8 tiles (256 rows) per workgroup -- 64 owner tiles x 8 parts (x 2 roles) at
+// B = 2048.  Ragged B and every D are handled by the zero rows of the workspace and the id -1 of a void row, never by a
+// branch in the MFMA loop.
+#include "lgcn_device_common.h"
+
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+
+// tile row of accumulator register `reg` on lane half h (C/D layout of the 32x32 MFMAs)
+__device__ __forceinline__ int ib_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
+
+// 32 x 32 scores acc[i][j] = sum_k A[i][k] B[j][k]: arow / brow point at this lane's row (lane & 31) of each operand, at column
+// h D/2.  MFMA number t multiplies columns (t, D/2 + t): the k order every score of this file is summed in.
+template <int D>
+__device__ __forceinline__ f32x16 ib_scores(const float *arow, const float *brow) {
+    f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+    for (int s = 0; s < D / 2; s += 8) {
+        const f32x4 a0 = *reinterpret_cast<const f32x4 *>(arow + s), a1 = *reinterpret_cast<const f32x4 *>(arow + s + 4);
+        const f32x4 b0 = *reinterpret_cast<const f32x4 *>(brow + s), b1 = *reinterpret_cast<const f32x4 *>(brow + s + 4);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, b0.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, b0.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, b0.z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, b0.w, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, b1.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, b1.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, b1.z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, b1.w, acc, 0, 0, 0);
+    }
+    return acc;
+}
+
+// The same scores from operands already in registers (D <= 64: D / 2 floats per operand and lane): the owned side is loaded once
+// per workgroup and the swept side's NEXT tile is loaded while this one is multiplied.  Same k order as ib_scores: the same bits.
+template <int D> struct IbRow { f32x4 v[D / 8]; };
+template <int D>
+__device__ __forceinline__ void ib_load(IbRow<D> &r, const float *row) {
+#pragma unroll
+    for (int i = 0; i < D / 8; i++) r.v[i] = *reinterpret_cast<const f32x4 *>(row + 4 * i);
+}
+template <int D>
+__device__ __forceinline__ f32x16 ib_scores_reg(const IbRow<D> &a, const IbRow<D> &b) {
+    f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < D / 8; i++) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[i].x, b.v[i].x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[i].y, b.v[i].y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[i].z, b.v[i].z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[i].w, b.v[i].w, acc, 0, 0, 0);
+    }
+    return acc;
+}
+constexpr int IB_REG_D = 64;      // up to this D the operands of a tile live in registers (and the next tile's are prefetched)
+
+// (m, r) <- (m, r) + (m2, r2), each standing for the sum exp(m) (1 + r) (m = -inf: the empty sum); every exponent is <= 0
+__device__ __forceinline__ void ib_merge(float &m, float &r, float m2, float r2) {
+    if (m2 == -INFINITY) return;
+    if (m == -INFINITY) { m = m2; r = r2; return; }
+    if (m >= m2) r = r + (1.f + r2) * expf(m2 - m);
+    else { r = r2 + (1.f + r) * expf(m - m2); m = m2; }
+}
+
+template <int D, typename TI, bool WTS>
+__global__ void __launch_bounds__(256) k_inbatch_rows(InBatchArgs ia) {
+    const MultiNegArgs &a = ia.m;
+    constexpr int LPT = D < 64 ? D : 64, CPT = D / LPT, SPB = 256 / LPT;     // lanes per sample, samples per workgroup
+    // last step's row bitmap is dead: zero it here with plain stores (the two bitmaps alternate per step)
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.bitmap_words; i += (int64_t)gridDim.x * 256)
+        a.stale_bitmap[i] = 0u;
+    const int b = blockIdx.x * SPB + threadIdx.x / LPT, l = threadIdx.x % LPT;
+    const int Bp = lgcn_inbatch_rows(a.B);
+    if (b >= Bp) return;                        // whole lane groups leave together
+    // every id is checked before anything is addressed with it: lane 0 holds the user, lane 1 the positive
+    int32_t id = 0;
+    bool idbad = false;
+    if (b < a.B) {
+        if (l == 0) { id = a.users[b]; idbad = id < 0 || id >= a.n_users; }
+        else if (l == 1) { id = a.pos[b]; idbad = id < 0 || (int64_t)id + a.n_users >= a.N; }
+    }
+    constexpr unsigned long long GROUP = LPT == 64 ? ~0ull : ((1ull << (LPT & 63)) - 1ull);
+    const int gshift = (threadIdx.x & 63) / LPT * LPT;                          // this group's first lane in the wave
+    const bool bad = b >= a.B || (__ballot(idbad) & (GROUP << gshift)) != 0ull;
+    if (bad) {          // padding, or an out-of-range id: a zero row and a zero column of the score matrix, masked by uid = -1
+#pragma unroll
+        for (int j = 0; j < CPT; j++) { ia.U[(int64_t)b * D + j * LPT + l] = 0.f; ia.P[(int64_t)b * D + j * LPT + l] = 0.f; }
+        if (l == 0) {
+            ia.uid[b] = -1; ia.pid[b] = -1; ia.sbb[b] = 0.f; ia.mrg[2 * b] = 0.f; ia.mrg[2 * b + 1] = 1.f;
+            if (b < a.B) { atomicExch(a.err, 1); a.terms[b] = 0.f; a.terms[a.terms_stride + b] = 0.f; }
+        }
+        return;
+    }
+    const int32_t iu = __shfl(id, 0, LPT), ip = __shfl(id, 1, LPT);
+    const int64_t ru = (int64_t)iu, rp = (int64_t)ip + a.n_users;
+    const bool ego = a.reg_ego != 0;
+    const float lam = ego ? 0.f : a.lam;
+    float u[CPT], p[CPT], t0[CPT];
+    float ps = 0.f, ru2 = 0.f, rp2 = 0.f;
+    slot_row<D, TI, WTS>(a, ru, l, u, t0);
+#pragma unroll
+    for (int j = 0; j < CPT; j++) { const float v = ego ? t0[j] : u[j]; ru2 += v * v; }
+    slot_row<D, TI, WTS>(a, rp, l, p, t0);
+#pragma unroll
+    for (int j = 0; j < CPT; j++) { const float v = ego ? t0[j] : p[j]; ps += u[j] * p[j]; rp2 += v * v; }
+    ps = group_sum<LPT>(ps);
+    const float rr = group_sum<LPT>(ru2 + rp2);
+#pragma unroll
+    for (int j = 0; j < CPT; j++) {
+        ia.U[(int64_t)b * D + j * LPT + l] = u[j];
+        ia.P[(int64_t)b * D + j * LPT + l] = p[j];
+        if (lam != 0.f) {
+            fixed_add(a.G64 + ru * D + j * LPT + l, lam * u[j]);
+            fixed_add(a.G64 + rp * D + j * LPT + l, lam * p[j]);
+        }
+    }
+    if (l == 0) { ia.uid[b] = iu; ia.pid[b] = ip; ia.sbb[b] = ps; a.terms[a.terms_stride + b] = rr; }
+    if (l < 2) {                                // the 2 rows of the sample: one lane each
+        const int64_t myrow = l == 0 ? ru : rp;
+        atomicOr(a.bitmap + (myrow >> 5), 1u << (myrow & 31));
+        if (a.cnt) atomicAdd(a.cnt + myrow, 1);
+    }
+}
+
+template <int D>
+__global__ void __launch_bounds__(64) k_inbatch_norm(InBatchArgs ia) {
+    const int l = threadIdx.x, j = l & 31, h = l >> 5;
+    const int Bp = lgcn_inbatch_rows(ia.m.B), nT = Bp / 32;
+    const int b = blockIdx.x * 32 + j;          // this lane's user (a column of the tile)
+    const int t0 = blockIdx.y * LGCN_INBATCH_PART_TILES, t1 = t0 + LGCN_INBATCH_PART_TILES < nT ? t0 + LGCN_INBATCH_PART_TILES : nT;
+    const int32_t ub = ia.uid[b], pb = ia.pid[b];
+    const float sbb = ia.sbb[b], tau = ia.m.tau;
+    const float *brow = ia.U + (int64_t)b * D + h * (D / 2);
+    float m = -INFINITY, r = 0.f;
+    constexpr int RD = D <= IB_REG_D ? D : 8;   // (the register form's types at a size that costs nothing where it is not used)
+    IbRow<RD> own, cur, nxt;
+    if constexpr (D <= IB_REG_D) { ib_load(own, brow); ib_load(cur, ia.P + (int64_t)(t0 * 32 + j) * D + h * (D / 2)); }
+#pragma unroll 1
+    for (int t = t0; t < t1; t++) {
+        // this tile's ids and the next tile's rows are in flight while this tile is multiplied
+        int32_t ucs[16], pcs[16];
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) { const int c = t * 32 + ib_row(reg, h); ucs[reg] = ia.uid[c]; pcs[reg] = ia.pid[c]; }
+        f32x16 acc;
+        if constexpr (D <= IB_REG_D) {
+            const int tn = t + 1 < t1 ? t + 1 : t;
+            ib_load(nxt, ia.P + (int64_t)(tn * 32 + j) * D + h * (D / 2));
+            acc = ib_scores_reg<RD>(cur, own);
+            cur = nxt;
+        } else {
+            acc = ib_scores<D>(ia.P + (int64_t)(t * 32 + j) * D + h * (D / 2), brow);
+        }
+        float z[16], tmax = -INFINITY;
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) {
+            const int c = t * 32 + ib_row(reg, h);
+            const int32_t uc = ucs[reg], pc = pcs[reg];
+            const bool ok = ub >= 0 && uc >= 0 && c != b && pc != pb && uc != ub;
+            z[reg] = ok ? (acc[reg] - sbb) / tau : -INFINITY;
+            tmax = fmaxf(tmax, z[reg]);
+        }
+        bool excl = false;                      // a new maximum: its first occurrence becomes the 1 of (1 + r)
+        if (tmax > m) { r = (1.f + r) * expf(m - tmax); m = tmax; excl = true; }
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) {
+            if (z[reg] == -INFINITY) continue;
+            if (excl && z[reg] == m) excl = false;
+            else r += expf(z[reg] - m);
+        }
+    }
+    const float m2 = __shfl_xor(m, 32), r2 = __shfl_xor(r, 32);
+    if (h == 0) {                               // half 0 first, then half 1: a fixed order
+        ib_merge(m, r, m2, r2);
+        float *o = ia.part + ((int64_t)blockIdx.y * Bp + b) * 2;
+        o[0] = m; o[1] = r;
+    }
+}
+
+template <int D>
+__global__ void __launch_bounds__(256) k_inbatch_diag(InBatchArgs ia) {
+    const MultiNegArgs &a = ia.m;
+    constexpr int LPT = D < 64 ? D : 64, CPT = D / LPT, SPB = 256 / LPT;
+    const int b = blockIdx.x * SPB + threadIdx.x / LPT, l = threadIdx.x % LPT;
+    if (b >= a.B) return;
+    const int32_t iu = ia.uid[b], ip = ia.pid[b];
+    if (iu < 0) return;                         // void: k_inbatch_rows wrote its zero terms
+    const int Bp = lgcn_inbatch_rows(a.B), NP = lgcn_inbatch_parts(a.B);
+    float m = -INFINITY, r = 0.f;               // every lane of the group merges the same parts in the same order
+    for (int p = 0; p < NP; p++) { const float *q = ia.part + ((int64_t)p * Bp + b) * 2; ib_merge(m, r, q[0], q[1]); }
+    // with the positive's own exp(0): 1 + sum_c exp(z_c) = exp(M) (1 + Zm1), M = max(0, m)
+    float M = 0.f, zm1 = 0.f, Q = 0.f;
+    if (m > 0.f) { M = m; zm1 = r + expf(-m); Q = (1.f + r) / (1.f + zm1); }          // the 1 is the first maximal competitor's term
+    else if (m != -INFINITY) { zm1 = expf(m) * (1.f + r); Q = zm1 / (1.f + zm1); }    // the 1 is the positive's term
+    if (l == 0) { a.terms[b] = -(M + log1pf(zm1)); ia.mrg[2 * b] = M; ia.mrg[2 * b + 1] = 1.f + zm1; }
+    if (Q == 0.f) return;                       // no competitor (B = 1, everything masked): only the regulariser moves the rows
+    const float wd = -(Q * a.inv_tauB);         // W[b,b]
+    const int64_t ru = (int64_t)iu, rp = (int64_t)ip + a.n_users;
+#pragma unroll
+    for (int j = 0; j < CPT; j++) {
+        const int64_t o = (int64_t)b * D + j * LPT + l;
+        fixed_add(a.G64 + ru * D + j * LPT + l, wd * ia.P[o]);
+        fixed_add(a.G64 + rp * D + j * LPT + l, wd * ia.U[o]);
+    }
+}
+
+template <int D>
+__global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
+    constexpr int CB = D < 128 ? D / 32 : 4;    // 32-column blocks of the output this workgroup accumulates
+    const int l = threadIdx.x, j = l & 31, h = l >> 5;
+    const int Bp = lgcn_inbatch_rows(ia.m.B), nT = Bp / 32;
+    const int role = blockIdx.z & 1, col0 = (blockIdx.z >> 1) * 128;        // role 0: the owned rows are users, 1: items
+    const float *own = role == 0 ? ia.U : ia.P, *oth = role == 0 ? ia.P : ia.U;
+    const int o = blockIdx.x * 32 + j;          // this lane's owned index (a column of the score tile)
+    const int t0 = blockIdx.y * LGCN_INBATCH_PART_TILES, t1 = t0 + LGCN_INBATCH_PART_TILES < nT ? t0 + LGCN_INBATCH_PART_TILES : nT;
+    const int32_t uo = ia.uid[o], po = ia.pid[o];
+    const float sbb_o = ia.sbb[o], M_o = ia.mrg[2 * o], den_o = ia.mrg[2 * o + 1];
+    const float tau = ia.m.tau, inv_tauB = ia.m.inv_tauB;
+    const float *brow = own + (int64_t)o * D + h * (D / 2);
+    f32x16 g[CB];
+#pragma unroll
+    for (int cb = 0; cb < CB; cb++)
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) g[cb][reg] = 0.f;
+    constexpr int RD = D <= IB_REG_D ? D : 8;   // (the register form's types at a size that costs nothing where it is not used)
+    IbRow<RD> ownr, cur, nxt;
+    if constexpr (D <= IB_REG_D) { ib_load(ownr, brow); ib_load(cur, oth + (int64_t)(t0 * 32 + j) * D + h * (D / 2)); }
+#pragma unroll 1
+    for (int t = t0; t < t1; t++) {
+        // what the tile needs besides its scores is in flight while the scores are multiplied: the rows' ids, the users' s_bb and
+        // merged (M, 1 + Zm1) under role 1 (under role 0 they are the lane's own), the B operands of the second product and,
+        // in the register form, the next tile's rows
+        int32_t uxs[16], pxs[16];
+        float sbs[16], Ms[16], dens[16], ob[16][CB];
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) {
+            const int x = t * 32 + ib_row(reg, h);          // the other side's index (a row of the tile)
+            uxs[reg] = ia.uid[x]; pxs[reg] = ia.pid[x];
+            // the USER of the pair owns s_bb and the merged (M, 1 + Zm1): the lane's under role 0, the row's under role 1
+            sbs[reg] = role == 0 ? sbb_o : ia.sbb[x];
+            Ms[reg] = role == 0 ? M_o : ia.mrg[2 * x]; dens[reg] = role == 0 ? den_o : ia.mrg[2 * x + 1];
+            if constexpr (D <= IB_REG_D) {
+#pragma unroll
+                for (int cb = 0; cb < CB; cb++) ob[reg][cb] = oth[(int64_t)x * D + col0 + j + cb * 32];
+            }
+        }
+        f32x16 w;
+        if constexpr (D <= IB_REG_D) {
+            const int tn = t + 1 < t1 ? t + 1 : t;
+            ib_load(nxt, oth + (int64_t)(tn * 32 + j) * D + h * (D / 2));
+            w = ib_scores_reg<RD>(cur, ownr);
+            cur = nxt;
+        } else {
+            w = ib_scores<D>(oth + (int64_t)(t * 32 + j) * D + h * (D / 2), brow);
+        }
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) {
+            const int x = t * 32 + ib_row(reg, h);
+            const bool ok = uo >= 0 && uxs[reg] >= 0 && x != o && pxs[reg] != po && uxs[reg] != uo;
+            const float z = (w[reg] - sbs[reg]) / tau;
+            w[reg] = ok ? expf(z - Ms[reg]) / dens[reg] * inv_tauB : 0.f;
+        }
+        // g[owned][col] += sum_x W[x][owned] Other[x][col]: register i of w is the A operand as it stands
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) {
+            const float *orow = oth + (int64_t)(t * 32 + ib_row(reg, h)) * D + col0 + j;
+#pragma unroll
+            for (int cb = 0; cb < CB; cb++) {
+                float bv;
+                if constexpr (D <= IB_REG_D) bv = ob[reg][cb]; else bv = orow[cb * 32];
+                g[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[reg], bv, g[cb], 0, 0, 0);
+            }
+        }
+    }
+    // rows of g: owned index blockIdx.x * 32 + ib_row(reg, h); columns col0 + cb * 32 + j
+#pragma unroll
+    for (int reg = 0; reg < 16; reg++) {
+        const int ob = blockIdx.x * 32 + ib_row(reg, h);
+        const int32_t us = ia.uid[ob];
+        if (us < 0) continue;                   // void or padding: no row to add to (its W is zero)
+        const int64_t row = role == 0 ? (int64_t)us : (int64_t)ia.pid[ob] + ia.m.n_users;
+#pragma unroll
+        for (int cb = 0; cb < CB; cb++) fixed_add(ia.m.G64 + row * D + col0 + cb * 32 + j, g[cb][reg]);
+    }
+}
+
+template <int D>
+static void launch_d(const InBatchArgs &a, int act_dtype, bool wts, hipStream_t st) {
+    constexpr int SPB = 256 / (D < 64 ? D : 64);
+    const int Bp = lgcn_inbatch_rows(a.m.B), NP = lgcn_inbatch_parts(a.m.B);
+    const dim3 rows_grid((unsigned)((Bp + SPB - 1) / SPB)), diag_grid((unsigned)((a.m.B + SPB - 1) / SPB));
+    if (act_dtype == LGCN_F32) {
+        if (wts) hipLaunchKernelGGL((k_inbatch_rows<D, float, true>), rows_grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_inbatch_rows<D, float, false>), rows_grid, dim3(256), 0, st, a);
+    } else {
+        if (wts) hipLaunchKernelGGL((k_inbatch_rows<D, bf16_t, true>), rows_grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_inbatch_rows<D, bf16_t, false>), rows_grid, dim3(256), 0, st, a);
+    }
+    hipLaunchKernelGGL((k_inbatch_norm<D>), dim3((unsigned)(Bp / 32), (unsigned)NP), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((k_inbatch_diag<D>), diag_grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((k_inbatch_grad<D>), dim3((unsigned)(Bp / 32), (unsigned)NP, 2u * (D > 128 ? D / 128 : 1)), dim3(64), 0, st, a);
+}
+
+int lgcn_inbatch_launch(const InBatchArgs &a, int d, int act_dtype, bool wts, hipStream_t st) {
+    if (a.m.B <= 0 || a.m.loss != LGCN_LOSS_INBATCH || !(a.m.tau > 0.f) || !(a.m.inv_tauB > 0.f) ||
+        (act_dtype != LGCN_F32 && act_dtype != LGCN_BF16) || !a.U || !a.P || !a.sbb || !a.uid || !a.pid || !a.part || !a.mrg ||
+        a.cap % 32 != 0 || a.m.B > a.cap || !a.m.users || !a.m.pos || !a.m.G64 || !a.m.terms || a.m.terms_stride < a.m.B) {
+        lgcn_set_error("in-batch softmax rows: bad launch arguments (0 < B <= the workspace's rows, loss inbatch with temperature > 0, "
+                       "fp32 / bf16 tables, a workspace of a multiple of 32 rows)");
+        return 3;
+    }
+    DISPATCH_D(d, launch_d<D>(a, act_dtype, wts, st));
+    return 0;
+}

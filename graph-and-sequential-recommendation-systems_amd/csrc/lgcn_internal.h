@@ -6,6 +6,9 @@
 #include "lgcn_hip.h"
 
 extern "C" void lgcn_set_error(const char *msg);   // lgcn_host.cpp
+// 0 under LGCN_LOSS_BPR; else rc 3 and the message "<who>: the ... loss ... is implemented for ... only" (lgcn_device.hip): ONE wording
+// for every entry point that does not train the loss set on the context
+int lgcn_refuse_loss(const lgcn_ctx *x, const char *who);
 
 // The RCCL entry points the data-parallel path uses.  Resolved once, preferring the librccl that is
 // already mapped into the process (PyTorch-ROCm ships its own copy; two RCCL instances in one process
@@ -52,4 +55,22 @@ struct MultiNegArgs {
     int32_t loss; float tau, inv_tauB;
 };
 int lgcn_multineg_launch(const MultiNegArgs &a, int d, int act_dtype, bool wts, hipStream_t st);
+
+// The in-batch sampled softmax (lgcn_inbatch.hip; lgcn_train_step_inbatch fills this in).  Sample b = (users[b],
+// pos[b]); every user of the batch scores against every positive of the batch.  `m` carries what the batch-row launch of the
+// other losses carries (tables, ids, G64, bitmaps, terms, err, cnt, layer weights, tau, inv_tauB; negs / R / inv_BR / lam_n
+// are unused, loss = LGCN_LOSS_INBATCH).  The workspace is the context's: `cap` rows (a multiple of 32, >= B rounded up to 32).
+#define LGCN_INBATCH_PART_TILES 8      /* 32-row tiles of the swept side one workgroup covers: the sweep split */
+struct InBatchArgs {
+    MultiNegArgs m;
+    float *U, *P;                 // [cap][d] fp32: the users' / positives' output-table rows, zero rows for void samples and padding
+    float *sbb;                   // [cap] s_{b,b}
+    int32_t *uid, *pid;           // [cap] the sample's ids, -1 / -1 for a void sample or padding (uid >= 0 is the sound flag)
+    float *part;                  // [parts][Bp][2] partial (m, r) of a user over one part of the item sweep: sum = exp(m) (1 + r)
+    float *mrg;                   // [cap][2] merged (M, 1 + Zm1) of a user
+    int32_t cap;
+};
+static __host__ __device__ inline int32_t lgcn_inbatch_rows(int32_t B) { return (B + 31) & ~31; }                          // Bp: B padded to whole tiles
+static __host__ __device__ inline int32_t lgcn_inbatch_parts(int32_t B) { return (lgcn_inbatch_rows(B) / 32 + LGCN_INBATCH_PART_TILES - 1) / LGCN_INBATCH_PART_TILES; }
+int lgcn_inbatch_launch(const InBatchArgs &a, int d, int act_dtype, bool wts, hipStream_t st);
 #endif

@@ -40,26 +40,7 @@
 // Everything downstream consumes what the three-slot kernels write: G64 (2^50 fixed point), the row bitmap, cnt, terms, err.
 #include "lgcn_device_common.h"
 
-// e[j] = the output-table row `row` at columns j * LPT + l (mean over the K + 1 layers, or the weighted sum); e0[j] = E0's
-template <int D, typename TI, bool WTS>
-__device__ __forceinline__ void slot_row(const MultiNegArgs &a, int64_t row, int l, float *e, float *e0) {
-    constexpr int LPT = D < 64 ? D : 64, CPT = D / LPT;
-    const float div = (float)(a.K + 1);
-#pragma unroll
-    for (int j = 0; j < CPT; j++) {
-        const int64_t o = row * D + j * LPT + l;
-        float s = a.X0[o];
-        e0[j] = s;
-        if constexpr (WTS) {
-            s *= a.w[0];
-            for (int k = 1; k <= a.K; k++) s += a.w[k] * tab_at<TI>(a.Xl[k], o);
-            e[j] = s;
-        } else {
-            for (int k = 1; k <= a.K; k++) s += tab_at<TI>(a.Xl[k], o);
-            e[j] = s / div;
-        }
-    }
-}
+// (slot_row, the output-table row of a slot, lives in lgcn_device_common.h: the in-batch launch gathers its rows through it too)
 
 // One of the two passes of the softmax loss over the R negatives of a sample (their ids are in lanes 0..R-1 of the group), the
 // rows of negative r + 1 in flight while negative r is worked on.  Score pass (!EMIT): z_r into lane r of zq, the squares into

@@ -77,14 +77,14 @@ def load_ppr_weights(path, K, degrees=None):
 
 
 def resolve_loss(config):
-    """--loss bpr | softmax and --softmax_temp -> ('bpr' | 'softmax', temperature).  ValueError: an unknown loss, or a
-    temperature that is not a finite value > 0."""
+    """--loss bpr | softmax | inbatch and --softmax_temp -> ('bpr' | 'softmax' | 'inbatch', temperature).  ValueError: an unknown
+    loss, or a temperature that is not a finite value > 0."""
     kind = str(config.get('loss', 'bpr')).strip().lower()
-    if kind not in ('bpr', 'softmax'):
-        raise ValueError(f"--loss must be bpr or softmax, got {config.get('loss')!r}")
+    if kind not in ('bpr', 'softmax', 'inbatch'):
+        raise ValueError(f"--loss must be bpr, softmax or inbatch, got {config.get('loss')!r}")
     tau = float(config.get('softmax_temp', 1.0))
-    if kind == 'softmax' and not (np.isfinite(tau) and tau > 0.0):
-        raise ValueError(f"--loss softmax: --softmax_temp must be a finite value > 0, got {tau}")
+    if kind != 'bpr' and not (np.isfinite(tau) and tau > 0.0):
+        raise ValueError(f"--loss {kind}: --softmax_temp must be a finite value > 0, got {tau}")
     return kind, tau
 
 
@@ -284,12 +284,16 @@ class LightGCN(nn.Module):
         # the loss of the fused step (--loss bpr | softmax, --softmax_temp; lgcn_ctx_set_loss): softmax = the positive
         # against all R negatives of its sample in one log-sum-exp; every negative shape then goes to the _multi entry points
         self.loss_kind, self.softmax_temp = resolve_loss(config)
-        if self.loss_kind == 'softmax':
+        # inbatch = every user of the batch against every positive of the batch; the sampled negatives are not used
+        if self.loss_kind != 'bpr':
             if str(config.get('act_dtype', 'fp32')) == 'fp8':
-                raise _lib.LgcnError("--loss softmax is not implemented together with --act_dtype fp8 (fp32 and bf16 storage only)")
+                raise _lib.LgcnError(f"--loss {self.loss_kind} is not implemented together with --act_dtype fp8 (fp32 and bf16 storage only)")
             if self.use_pop_gate or self.use_item_item:
-                raise _lib.LgcnError("--loss softmax is not implemented together with --use_pop_gate / --use_item_item "
+                raise _lib.LgcnError(f"--loss {self.loss_kind} is not implemented together with --use_pop_gate / --use_item_item "
                                      "(the optional branches train with the BPR loss only)")
+        if self.loss_kind == 'inbatch' and self.neg_ratio > 1:
+            raise _lib.LgcnError(f"--loss inbatch is not implemented together with --neg_ratio {self.neg_ratio}: the in-batch loss has no "
+                                 "sampled negatives (the other samples' positives are the negatives); use --neg_ratio 1")
         self._loss_said = False
         self._gate_flat = None      # the eight MLP tensors of the gate in ONE buffer (what the fused step reads / updates)
         self._Graph = None
@@ -456,10 +460,10 @@ class LightGCN(nn.Module):
             if not self._neg_ratio_said:
                 world.cprint(f"[neg_ratio] --neg_ratio {self.neg_ratio}: the last layer is propagated densely (dense_last = 1)")
                 self._neg_ratio_said = True
-        if self.loss_kind == 'softmax' and not dense_last:
-            dense_last = True       # the softmax batch-row kernel is the 2 + R slot form too
+        if self.loss_kind != 'bpr' and not dense_last:
+            dense_last = True       # the softmax batch-row kernel is the 2 + R slot form too, the in-batch launches its 2 B slot form
             if not self._loss_said:
-                world.cprint("[loss] --loss softmax: the last layer is propagated densely (dense_last = 1)")
+                world.cprint(f"[loss] --loss {self.loss_kind}: the last layer is propagated densely (dense_last = 1)")
                 self._loss_said = True
         st['act'] = _act_tables(max(1, K if dense_last else K - 1), N, d, act_dtype, dev)
         st['G64'] = torch.zeros(N, d, dtype=torch.int64, device=dev)
@@ -527,8 +531,8 @@ class LightGCN(nn.Module):
                 msg = lib.lgcn_last_error()
                 lib.lgcn_ctx_destroy(h)
                 raise _lib.LgcnError(f"lgcn_ctx_set_layer_weights failed (rc={rc}): {msg.decode() if msg else ''}")
-        if self.loss_kind == 'softmax':
-            rc = lib.lgcn_ctx_set_loss(h, _lib.LOSS_SOFTMAX, float(self.softmax_temp))
+        if self.loss_kind != 'bpr':
+            rc = lib.lgcn_ctx_set_loss(h, _lib.LOSS_INBATCH if self.loss_kind == 'inbatch' else _lib.LOSS_SOFTMAX, float(self.softmax_temp))
             if rc:
                 msg = lib.lgcn_last_error()
                 lib.lgcn_ctx_destroy(h)
@@ -707,8 +711,49 @@ class LightGCN(nn.Module):
         reg_loss = (0.5 * (u.norm(2).pow(2) + pos_e.norm(2).pow(2) + neg_e.norm(2).pow(2) / float(R))) / float(B)
         return bpr, reg_loss
 
+    def _inbatch_loss(self, users, pos):
+        """bpr_loss under --loss inbatch: the autograd statement of the loss of lgcn_train_step_inbatch -- (sm, reg),
+        sm = 1/B sum_b logsumexp over {0} and z_{b,c} = (s_{b,c} - s_{b,b}) / tau for c != b, p_c != p_b, u_c != u_b."""
+        B = int(users.shape[0])
+        all_users, all_items = self.computer()
+        ul, pl = users.long(), pos.long()
+        u, p = all_users[ul], all_items[pl]
+        s = u @ p.t()
+        z = (s - torch.diagonal(s)[:, None]) / float(self.softmax_temp)
+        keep = (pl[None, :] != pl[:, None]) & (ul[None, :] != ul[:, None])          # (u_c != u_b leaves c = b out too)
+        z = torch.where(keep, z, torch.full_like(z, float('-inf')))
+        sm = torch.logsumexp(torch.cat([torch.zeros_like(z[:, :1]), z], dim=1), dim=1).sum() / float(B)
+        if str(self.config.get('reg_rows', 'propagated')) == 'ego':
+            u, p = self.embedding_user.weight[ul], self.embedding_item.weight[pl]
+        return sm, (0.5 * (u.norm(2).pow(2) + p.norm(2).pow(2))) / float(B)
+
+    def _fused_inbatch(self, users, pos, batch_size, loss_out, lr, epoch):
+        """fused_step / fused_epoch under --loss inbatch: lgcn_train_step_inbatch / lgcn_train_epoch_inbatch on (users, pos)."""
+        dev = self._table.device
+        users, pos = self._ids(users, dev).reshape(-1), self._ids(pos, dev).reshape(-1)
+        T = int(users.numel())
+        st = self._state(max_batch=batch_size if epoch else max(T, int(self.config.get('bpr_batch_size', T))), need_ctx=True,
+                         dp_world=(self._dev or {}).get('dp_world', 1))
+        lib = _lib.load()
+        if lr is not None:
+            lib.lgcn_ctx_set_lr(st['ctx'], float(lr))
+        if epoch:
+            losses = torch.empty((T + batch_size - 1) // batch_size, 3, dtype=torch.float32, device=dev)
+            _lib.check(lib.lgcn_train_epoch_inbatch(st['ctx'], _lib.tp(users), _lib.tp(pos), T, int(batch_size), _lib.tp(losses),
+                                                    _lib.current_stream()), "lgcn_train_epoch_inbatch")
+            self.invalidate_cache()
+            return losses
+        if loss_out is None:
+            loss_out = torch.empty(3, dtype=torch.float32, device=dev)
+        _lib.check(lib.lgcn_train_step_inbatch(st['ctx'], _lib.tp(users), _lib.tp(pos), T, _lib.tp(loss_out), _lib.current_stream()),
+                   "lgcn_train_step_inbatch")
+        self.invalidate_cache()
+        return loss_out
+
     def bpr_loss(self, users, pos, neg):
         """model.py:162-183 (unfused, autograd-capable): (bpr [- entropy term of the gate], reg_loss)."""
+        if self.loss_kind == 'inbatch':          # the sampled negatives are not used
+            return self._inbatch_loss(users, pos)
         if torch.is_tensor(neg) and neg.dim() == 2:
             return self._bpr_loss_multi(users, pos, neg)
         if self.loss_kind == 'softmax':          # 1-D negatives: R = 1
@@ -784,6 +829,8 @@ class LightGCN(nn.Module):
             raise RuntimeError("this configuration of the popularity gate / item-item smoothing is outside the fused step "
                                "(--fused_variants 0, or gate hidden sizes > 64 / d > 128): use BPRLoss.stageOne (autograd path)")
         dev = self._table.device
+        if self.loss_kind == 'inbatch':        # --loss inbatch: (users, pos) only; neg is accepted and ignored
+            return self._fused_inbatch(users, pos, None, loss_out, lr, False)
         if self.loss_kind == 'softmax' and self._neg_dim(neg) == 1:      # --loss softmax: every shape is a multi step, R = 1 included
             neg = self._ids(neg, dev).reshape(1, -1)
         if self._neg_dim(neg) == 2:            # several negatives per positive: neg [B, R] (the sampler's S[:, 2:]) or [R, B]
@@ -823,6 +870,8 @@ class LightGCN(nn.Module):
         if self.has_variants and not self.fused_variants:
             raise RuntimeError("this configuration of the optional branches is outside the fused step: loop BPRLoss.stageOne")
         dev = self._table.device
+        if self.loss_kind == 'inbatch':        # --loss inbatch: (users, pos) only; neg is accepted and ignored
+            return self._fused_inbatch(users, pos, int(batch_size), None, lr, True)
         users, pos = self._ids(users, dev), self._ids(pos, dev)
         negs = None
         if self.loss_kind == 'softmax' and self._neg_dim(neg) == 1:      # --loss softmax: the multi epoch at R = 1

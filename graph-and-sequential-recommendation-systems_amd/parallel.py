@@ -144,8 +144,10 @@ class DataParallelBPR:
         if int(getattr(recmodel, 'neg_ratio', 1)) > 1 or int(config.get('neg_ratio', 1)) > 1:
             raise RuntimeError("--neg_ratio > 1 is implemented for single-GPU training only: DataParallelBPR (every reduce / shard "
                                "mode) trains on triplets, one negative per positive")
-        if str(getattr(recmodel, 'loss_kind', 'bpr')) != 'bpr' or str(config.get('loss', 'bpr')).strip().lower() != 'bpr':
-            raise RuntimeError("--loss softmax is implemented for single-GPU training only: DataParallelBPR (every reduce / shard "
+        kinds = [str(k).strip().lower() for k in (getattr(recmodel, 'loss_kind', 'bpr'), config.get('loss', 'bpr'))]
+        other = next((k for k in kinds if k != 'bpr'), None)      # the loss that is not bpr, the model's first
+        if other is not None:
+            raise RuntimeError(f"--loss {other} is implemented for single-GPU training only: DataParallelBPR (every reduce / shard "
                                "mode) computes the BPR loss")
         if not dist.is_initialized():
             raise RuntimeError("torch.distributed is not initialised")

@@ -117,13 +117,16 @@ def build_parser():
                         'samples (u, p, n_1..n_R) in the fused step -- the loss of the flattened B*R triplets, with the user and '
                         'positive rows read and added once per sample. Native host sampler (--sampler cpp), fp32 / bf16 storage, '
                         'single GPU, default model, dense last layer')
-    p.add_argument('--loss', type=str, default='bpr', choices=['bpr', 'softmax'],
+    p.add_argument('--loss', type=str, default='bpr', choices=['bpr', 'softmax', 'inbatch'],
                    help='NEW: loss of the fused step. bpr (default) = the reference: -mean logsigmoid(x) over the (flattened) triplets. '
                         'softmax = the sampled-softmax loss: the positive competes against all --neg_ratio negatives of its sample in '
                         'one log-sum-exp at --softmax_temp, log(1 + sum_r exp(-x_r / tau)), one term per sample; the "bpr" slot of the '
-                        'reported loss then holds it. fp32 / bf16 storage, single GPU, default model, dense last layer')
+                        'reported loss then holds it. inbatch = the in-batch sampled softmax: every user of the batch scores against every '
+                        'positive of the batch at --softmax_temp and the other samples\' positives are the negatives (the same item, and '
+                        'other positives of the same user, are left out); the sampled negatives are not used, so --neg_ratio must be 1. '
+                        'fp32 / bf16 storage, single GPU, default model, dense last layer')
     p.add_argument('--softmax_temp', type=float, default=1.0,
-                   help='NEW: temperature tau > 0 of --loss softmax (at --neg_ratio 1 and tau = 1 the loss is the BPR loss)')
+                   help='NEW: temperature tau > 0 of --loss softmax (at --neg_ratio 1 and tau = 1 the loss is the BPR loss) and of --loss inbatch')
     p.add_argument('--data_path', type=str, default=None,
                    help='NEW: directory that holds <dataset>/train.txt (default: <root>/data)')
     return p

@@ -361,6 +361,24 @@ int lgcn_ctx_set_loss(lgcn_ctx *ctx, int32_t kind, float temperature);
 /* The loss in force (-1: null context); its temperature goes to temperature_out (may be NULL; 1 under LGCN_LOSS_BPR).       */
 int32_t lgcn_ctx_get_loss(const lgcn_ctx *ctx, float *temperature_out);
 
+/* The in-batch sampled softmax (--loss inbatch).  A batch is B samples (u_b, p_b); every user of the batch scores
+ * against every positive of the batch and the other samples' positives are the negatives.  With e the output-table rows:
+ *   s_{b,c} = e_{u_b}.e_{p_c},   A_b = { c : c != b, p_c != p_b, u_c != u_b }      (the false negatives the batch itself reveals)
+ *   z_{b,c} = (s_{b,c} - s_{b,b}) / tau,   l_b = log(1 + sum_{c in A_b} exp(z_{b,c})),   sm = 1/B sum_b l_b
+ *   reg = 0.5/B sum_b ( |e_u|^2 + |e_p|^2 )      (reg_ego: the same on the tables' own rows)
+ *   loss_out = {sm + decay * reg, sm, reg}
+ * A sample with an out-of-range id is void (err flag, zero terms, no gradient, neither a row nor a column of the score
+ * matrix); B in the normalisation stays B.  lgcn_ctx_set_loss(ctx, LGCN_LOSS_INBATCH, tau) is accepted and refused exactly as
+ * LGCN_LOSS_SOFTMAX is, and allocates the library-owned workspace (two [max_batch, d] fp32 row tables and a few vectors) once.
+ * While it is set, ONLY the two entry points below train: every other training entry point returns 3 and says so, and these
+ * two return 3 unless it is set.  Forward, backward chain (over the 2 B slots), Adam epilogue, edge dropout, layer weights and
+ * reg_ego are those of lgcn_train_step.  Everything is checked before anything is launched or counted.                        */
+#define LGCN_LOSS_INBATCH 2
+int lgcn_train_step_inbatch(lgcn_ctx *ctx, const int32_t *users, const int32_t *pos, int32_t B, float *loss_out, void *stream);
+/* ceil(T/B) consecutive batches of the (already shuffled) arrays; loss_out: [3*ceil(T/B)].                                   */
+int lgcn_train_epoch_inbatch(lgcn_ctx *ctx, const int32_t *users, const int32_t *pos, int64_t T, int32_t B, float *loss_out,
+                             void *stream);
+
 /* The fold of the gradient-row conversion into the batch-row launch.  lgcn_train_epoch holds all triplets of
  * the call before its first step, so it computes once (per segment of 1024 steps) how many slots of each batch name each
  * destination row; the batch-row kernel then writes the fp32 copy of a gradient row itself -- directly where one slot names
