@@ -457,9 +457,10 @@ int lgcn_train_step_cols_part2(lgcn_ctx *ctx, const int32_t *users, const int32_
  * U_b . I^T on the propagated table E[N,d] -- matrix cores, fp32 accumulate, fp32-accurate), train positives
  * set to -(1<<10) (Procedure.py:177-181; CSR with int64 indptr[n_users+1] and ascending int32
  * indices = dataset.allPos), top-K (Procedure.py:183) -- in one kernel, the [users, m_items]
- * score matrix is never materialised.  topk_items [n_eval,K] int32, best first (ties: lower
- * item id first; when the sweep is split over several workgroups per user block -- catalogues of >= 4096 items -- the
- * order of two items whose scores tie EXACTLY at the K-th place is unspecified, as torch.topk's is);
+ * score matrix is never materialised.  topk_items [n_eval,K] int32, ordered by (score descending, item id
+ * ascending).  Every item scoring strictly above the K-th score is returned; WHICH of several items whose scores tie
+ * EXACTLY at the K-th score are returned is unspecified, for every catalogue size (as torch.topk's choice is) -- the
+ * ones returned are distinct and in id order;
  * topk_scores [n_eval,K] or NULL.  1 <= K <= 64 (Procedure.py:183 takes k = max(topks)).          */
 int lgcn_eval_topk(const float *E, int32_t n_users, int32_t m_items, int32_t d,
                    const int32_t *users, int32_t n_eval,
@@ -496,7 +497,7 @@ int lgcn_eval_metrics(const int32_t *topk_items, int32_t n_eval, int32_t K,
 /* Evaluation past K = 64 (the entry points above keep their 1..64 contract).  lgcn_eval_kmax: the largest K the _ex forms
  * take (256; a larger max(topks) stays with the caller's own ranking).  lgcn_eval_topk_ex ranks as lgcn_eval_topk_masked
  * (same semantics, same tie caveat; a user with fewer than K items that are not train positives gets train positives at -(1<<10)
- * in the tail): 1 <= K <= lgcn_eval_kmax(), K <= m_items; topk_items and topk_scores (or NULL) are [n_eval, K] contiguous and
+ * in the tail -- which of them, when more are left than places, is such a tie): 1 <= K <= lgcn_eval_kmax(), K <= m_items; topk_items and topk_scores (or NULL) are [n_eval, K] contiguous and
  * out_capacity is the number of elements each of them holds -- rc 3, and nothing launched, if n_eval * K > out_capacity.
  * masks: as lgcn_eval_topk_masked, or NULL (the cursor over the train CSR).  flags: LGCN_EVAL_FP32 = every score from the fp32
  * matrix instructions (the cross-check, as lgcn_eval_topk_fp32), else the split bf16 product where the sweep supports it.

@@ -127,8 +127,8 @@ def test_eval_topk_ex_large_k_vs_torch(pkg, m_items, d, K):
 @gpu
 @pytest.mark.parametrize("m_items,K", [(300, 256), (5000, 200), (4100, 128)])
 def test_eval_topk_ex_minus_1024_tail(pkg, m_items, K):
-    """Users whose train positives cover all but K/2 items: the K/2 unmasked items first, then train positives at -(1<<10),
-    lower ids first (Procedure.py:181 + torch.topk)."""
+    """Users whose train positives cover all but K/2 items: the K/2 unmasked items first, then train positives at -(1<<10)
+    (Procedure.py:181 + torch.topk) -- any of them, as they tie exactly at the K-th score, listed in id order."""
     d, n_users = 64, 200
     E, users, rows = _problem(m_items, d, n_users=n_users, n_eval=150, seed=5)
     rng = np.random.Generator(np.random.PCG64(9))
@@ -151,7 +151,7 @@ def test_eval_topk_ex_minus_1024_tail(pkg, m_items, K):
             assert np.array_equal(np.sort(got[s, :K // 2]), free)                      # every non-positive, above ...
             assert np.all(scores[s, K // 2:] == -1024.0)                               # ... the train positives at -1024
             assert np.all(np.isin(got[s, K // 2:], rows[u]))
-            assert np.array_equal(got[s, K // 2:], np.sort(got[s, K // 2:]))           # ties: lower id first
+            assert np.array_equal(got[s, K // 2:], np.sort(got[s, K // 2:]))           # equal scores: in id order (which ids: unspecified)
 
 
 @gpu
