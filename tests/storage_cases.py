@@ -1,5 +1,6 @@
-"""What tests/test_storage_restatement.py (CPU) and tests/test_gpu_storage_step.py (GPU) share: the graph, the hand-set table
-rows, the batches, the cases and the bounds of the bf16 / fp8 default fused step.  Test infrastructure like
+"""What tests/test_storage_restatement.py (CPU), tests/test_gpu_storage_step.py and tests/test_gpu_storage_features.py (GPU) share:
+the graph, the hand-set table rows, the batches, the cases and the bounds of the bf16 / fp8 default fused step, and of the fp32 /
+bf16 step with layer weights or edge dropout.  Test infrastructure like
 tests/storage_restatement.py, which holds the arithmetic.
 
 BOUNDS (u = 2^-24; every bound is per element and first order in u; derivations from the kernels' code):
@@ -38,7 +39,29 @@ BOUNDS (u = 2^-24; every bound is per element and first order in u; derivations 
   K = 4           end to end: the first backward table is overwritten inside the step, so g_rec is compared with the float64 chain
       WITHOUT backward storage; allowance = gate_cases.storage_allowance, (K - 1) 2^-8 (M |G|)_i for bf16, and for fp8 the
       half-ulp figure derived the same way: a table h_k errs by 2^-4 |h_k| + 2^-15 rowmax(h_k), rowmax(h_k)_i <= (sum_j |A|^j r)_i
-      with r_i = max_c |Gs|_ic: (K - 1) (2^-4 M |G| + 2^-15 M r 1^T); plus the fp32 part: the chain's deltas pushed through M."""
+      with r_i = max_c |Gs|_ic: (K - 1) (2^-4 M |G| + 2^-15 M r 1^T); plus the fp32 part: the chain's deltas pushed through M.
+
+THE TWO FEATURES (FEATURE_CASES; fp32 and bf16 storage, fp8 is refused with both).  Every term again from the kernels' code:
+  fp32 storage    the stored table IS the fp32 evaluation: compared with delta alone, no half-ulp term (half_ulp = 0).
+  weighted slot row   triplet_body / k_triplet_dense with WTS: s = X_0 w[0]; s += w[k] X_k (k < K); e = s + w[K] X_K.  K + 1
+      products and K additions, no division; a summand passes through its product's rounding and at most K additions, K + 1
+      roundings, one fewer than the mean's K additions + division + the bound's spare one -- so the mean's factor K + 2 is kept
+      (it pays for the products' second-order terms; an fma contraction only removes roundings).  With T_w = sum_k |w[k]| |X_k|:
+      delta_e = (K + 2) u T_w + |w[K]| delta_last  (delta_last: the SpMM bound of the in-kernel / hub-plan last layer).
+  weighted backward   gdiv = 1: G32 = (float)(G64 2^-50) is ONE rounding, Gs = G, delta_Gs = delta_G + u |G|.  spmm_epilogue with
+      M_WTS: acc = w_in (A h); g = w_add G; y = g + acc -- two products and one addition on top of the default's terms:
+      delta = |w_add| delta_Gs + u |w_add G| + |w_in| (first launch: |A| delta_Gs; SpMM bound of A h) + (first launch, the only
+      one with w_in != 1: u |w_in| |A| |h|) + u (|w_add G| + |w_in| |A| |h|).  A zero weight needs no allowance: 0 G is exact
+      and every term it multiplies vanishes from the bound as it does from the launch.
+  dropout         drop_apply stages fl32(val fl32(1 / keep)) or 0: the restatement's matrix holds exactly these fp32 numbers, so
+      the staged weight adds nothing and every bound above is taken with |A_drop| (forward, slot rows) or |A_drop^T|
+      (backward) in the place of |A|: spmm_sum_bound on the masked, scaled CSR.  Dropped entries are stored as explicit zeros
+      and counted in n_i (the kernel may add their exact zero products; that only loosens (2 n_i + 2) u S_i, S_i ignores them).
+      Rows outside the batch's reach are rows outside the reach of the DROPPED graph's transpose: a backward launch on the
+      untransposed or undropped graph writes non-zero rows there, asserted exactly zero.
+  K = 4 with a feature   storage_allowance's argument with the chain's own coefficients: the stored h_{k-1} = w[k-1] G + B h_k
+      (B = the backward's matrix, h_K = w[K] G; the mean: w = 1 / (K + 1)) has |h_{k-1}| <= sum_{j >= k-1} |w[j]| |B|^(j-k+1) |G| and
+      reaches the result through |B|^(k-1): each of the K - 1 tables adds at most 2^-8 sum_j |w[j]| |B|^j |G|."""
 import os
 
 import numpy as np
@@ -66,10 +89,53 @@ K4_CASES = [("bf16", 128, 4, 0, -1, "propagated"), ("fp8", 128, 4, 0, -1, "propa
 EPOCH_CASES = [(mode, d, K, dl, -1, "propagated") for mode in ("bf16", "fp8") for d in (64, 128) for K in (2, 3) for dl in (0, 1)]
 BATCH_SEED = {}                           # seed of a case's batches: 0 unless a condition of test_storage_restatement.py fails there
 
+# ---- the two features: (mode, d, K, dense_last, hub_nnz, reg_rows, feature), feature = ("w", weight set) | ("drop", keep_prob) --
+DROP_SEED = 2020                          # world's default --seed: what model.LightGCN hands to lgcn_ctx_set_dropout
+_GRID = [(mode, d, K, dl) for d in (32, 64, 128, 256) for mode in ("fp32", "bf16") for K in (1, 2, 3) for dl in (0, 1)]
+WEIGHT_CASES = [(mode, d, K, dl, -1, "propagated", ("w", "literal")) for mode, d, K, dl in _GRID]
+WEIGHT_CASES += [("bf16", d, K, 0, -1, "propagated", ("w", name)) for d in (32, 128) for name, K in (("midzero", 3), ("last", 2), ("first", 3))]
+WEIGHT_CASES += [("bf16", 64, 2, 0, 100, "propagated", ("w", "literal")), ("fp32", 256, 3, 0, 100, "propagated", ("w", "literal"))]
+WEIGHT_CASES += [("bf16", 128, 3, 0, -1, "ego", ("w", "literal")), ("fp32", 32, 1, 0, -1, "ego", ("w", "literal"))]
+DROP_CASES = [(mode, d, K, dl, -1, "propagated", ("drop", 0.6)) for mode, d, K, dl in _GRID]
+DROP_CASES += [("bf16", 64, 2, 0, 100, "propagated", ("drop", 0.6)), ("fp32", 128, 3, 0, 100, "propagated", ("drop", 0.6))]
+DROP_CASES += [("bf16", 32, 2, 0, -1, "ego", ("drop", 0.6)), ("fp32", 256, 1, 0, -1, "ego", ("drop", 0.6))]
+DROP_CASES += [("bf16", 128, 2, 0, -1, "propagated", ("drop", 0.9))]
+FEATURE_CASES = WEIGHT_CASES + DROP_CASES
+FEATURE_K4_CASES = [("bf16", 128, 4, 0, -1, "propagated", ("w", "literal")), ("bf16", 128, 4, 0, -1, "propagated", ("drop", 0.6))]
+FEATURE_EPOCH_CASES = [("bf16", d, K, dl, -1, "propagated", f) for f in (("w", "literal"), ("drop", 0.6)) for d in (32, 128) for K in (2, 3) for dl in (0, 1)]
+
+
+def feature(c):
+    """-> (kind, value) of a case: ("w", weight set), ("drop", keep_prob) or (None, None) for the default step."""
+    return c[6] if len(c) > 6 else (None, None)
+
+
+def case_weights(c):
+    """The fp32 layer weights of a case (tests/test_gpu_layer_weights.py weight_set), or None."""
+    kind, v = feature(c)
+    if kind != "w":
+        return None
+    from test_gpu_layer_weights import weight_set
+    return weight_set(v, c[2])
+
+
+def case_keep(c):
+    kind, v = feature(c)
+    return float(v) if kind == "drop" else 1.0
+
+
+def case_graphs(adj, c, step):
+    """(forward CSR, backward CSR) of step `step` (0-based: the step counter before the step) of a case: (A_drop, A_drop^T as
+    the backward launches read it) under dropout, else (A, A)."""
+    from dropout_restatement import dropped_graphs
+    return dropped_graphs(adj, case_keep(c), DROP_SEED, step)
+
 
 def case_id(c):
-    mode, d, K, dl, hub, reg = c
-    return f"{mode}-d{d}-K{K}-dl{dl}" + (f"-hub{hub}" if hub > 0 else "") + ("-ego" if reg == "ego" else "")
+    mode, d, K, dl, hub, reg = c[:6]
+    kind, v = feature(c)
+    feat = "" if kind is None else (f"-w_{v}" if kind == "w" else f"-drop{v}")
+    return f"{mode}-d{d}-K{K}-dl{dl}" + (f"-hub{hub}" if hub > 0 else "") + ("-ego" if reg == "ego" else "") + feat
 
 
 def write_graph(path, seed=11):
@@ -126,12 +192,17 @@ def make_batches(case):
 
 
 def configure(pkg, case, path, batch=64):
-    mode, d, K, dl, hub, reg = case
+    mode, d, K, dl, hub, reg = case[:6]
     w = pkg.world
     w.configure([])
     w.dataset = "storage_step"
     w.config.update({'lightGCN_n_layers': K, 'latent_dim_rec': d, 'bpr_batch_size': batch, 'decay': DECAY, 'lr': LR, 'act_dtype': mode,
                      'dense_last': str(dl), 'hub_nnz': hub, 'reg_rows': reg, 'checkpoint_dir': os.path.join(path, "ckpt")})
+    if case_weights(case) is not None:
+        w.config['layer_weights'] = "[" + ",".join(repr(float(v)) for v in case_weights(case)) + "]"
+    if case_keep(case) < 1.0:
+        assert w.config['seed'] == DROP_SEED
+        w.config.update({'dropout': 1, 'keep_prob': case_keep(case)})
     return w
 
 
@@ -154,6 +225,8 @@ def half_ulp(ref, mode, delta=0.0):
     """Half a storage ulp of the value that is rounded, |v| <= |ref| + delta.  bf16 keeps 8 significant bits: half an ulp of v in
     [2^e, 2^(e+1)) is 2^(e-8) exactly, between 2^-9 |v| and 2^-8 |v| (2^-9 |v| itself is no bound: RNE of 1 + 2^-8 errs by 2^-8)."""
     ref = np.abs(ref) + delta
+    if mode == "fp32":               # the stored table is the fp32 evaluation itself: delta alone
+        return np.zeros_like(ref)
     if mode == "bf16":
         return np.where(ref > 0, 2.0 ** (np.floor(np.log2(np.maximum(ref, 1e-300))) - 8), 0.0)
     return 2.0 ** -4 * ref + ref.max(axis=1, keepdims=True) * 2.0 ** -15
@@ -171,13 +244,19 @@ def np64(t):
     return t.detach().numpy().astype(np.float64) if torch.is_tensor(t) else np.asarray(t, np.float64)
 
 
-def step_deltas(adj, r, K, dense_last, reg_ego):
+def step_deltas(adj, r, K, dense_last, reg_ego, weights=None, adj_bwd=None):
     """The fp32 error bounds of one step's quantities from its float64 restatement r (storage_restatement.step) -> dict:
-    e [3, B, d], x, term, regterm, gb [B], Gs [N, d], bwd_pre {i: [N, d]}, g_final [N, d]  (module docstring)."""
+    e [3, B, d], x, term, regterm, gb [B], Gs [N, d], bwd_pre {i: [N, d]}, g_final [N, d]  (module docstring).  adj: the CSR of
+    the forward (A_drop under dropout), adj_bwd: of the backward (default: adj); weights: the layer weights or None."""
     rows, e, d = r["rows"], np64(r["e"]), r["e"].shape[2]
     flat = rows.reshape(-1)
     d_last = np.zeros_like(e) if dense_last else spmm_delta(adj, np64(r["last_in"]))[flat].reshape(e.shape)
-    de = ((K + 2) * U * np64(r["terms_abs"]) + d_last) / (K + 1)
+    if weights is not None:
+        w = [abs(float(v)) for v in weights]
+        de = (K + 2) * U * np64(r["terms_abs"]) + w[K] * d_last
+    else:
+        de = ((K + 2) * U * np64(r["terms_abs"]) + d_last) / (K + 1)
+    adj = adj if adj_bwd is None else adj_bwd               # (everything below is the backward)
     u, p, n = np.abs(e)
     du, dp, dn = de
     x, term, gb = np64(r["x"]), np64(r["term"]), np64(r["gb"])
@@ -195,12 +274,18 @@ def step_deltas(adj, r, K, dense_last, reg_ego):
     dG = np.zeros(np64(r["G"]).shape)
     np.add.at(dG, flat, dc.reshape(-1, d))
     Gs = np64(r["Gs"])
-    out["Gs"] = dG / (K + 1) + 2 * U * np.abs(Gs)
+    out["Gs"] = dG / (K + 1) + 2 * U * np.abs(Gs) if weights is None else dG + U * np.abs(Gs)
     aabs = abs(adj).astype(np.float64)
     out["bwd_pre"] = {}
     for i in range(K):
         h = np64(r["bwd_in"][i])
-        dl = out["Gs"] + (aabs @ out["Gs"] if i == 0 else 0.0) + spmm_delta(adj, h) + U * (np.abs(Gs) + aabs @ np.abs(h))
+        if weights is None:
+            dl = out["Gs"] + (aabs @ out["Gs"] if i == 0 else 0.0) + spmm_delta(adj, h) + U * (np.abs(Gs) + aabs @ np.abs(h))
+        else:
+            w_add, w_in = w[K - i - 1], (w[K] if i == 0 else 1.0)
+            ah = aabs @ np.abs(h)
+            dl = (w_add * out["Gs"] + U * w_add * np.abs(Gs) + w_in * ((aabs @ out["Gs"] if i == 0 else 0.0) + spmm_delta(adj, h))
+                  + (U * w_in * ah if i == 0 else 0.0) + U * (w_add * np.abs(Gs) + w_in * ah))
         if i == K - 1:
             if reg_ego:
                 dl = dl + 3 * U * np.abs(r["lam"] * np64(r["cnt"])[:, None] * np64(r["E0"]))
@@ -228,6 +313,19 @@ def k4_allowance(adj, G, K, mode):
         return storage_allowance(adj, G, K)
     r = np.repeat(np.abs(G).max(axis=1, keepdims=True), G.shape[1], axis=1)
     return (K - 1) * (2.0 ** -4 * mean_abs_prop(adj, np.abs(G), K) + 2.0 ** -15 * mean_abs_prop(adj, r, K))
+
+
+def feature_k4_allowance(adj_bwd, G, K, weights=None):
+    """bf16 end-to-end allowance of a K-layer backward chain with layer weights (None: the mean's 1 / (K + 1)) on the backward's
+    matrix (module docstring, K = 4 with a feature): (K - 1) 2^-8 sum_j |w[j]| |B|^j |G|."""
+    w = [1.0 / (K + 1)] * (K + 1) if weights is None else [abs(float(v)) for v in weights]
+    a = abs(adj_bwd).astype(np.float64)
+    y = np.abs(G)
+    acc = w[0] * y
+    for j in range(1, K + 1):
+        y = a @ y
+        acc = acc + w[j] * y
+    return (K - 1) * 2.0 ** -8 * acc
 
 
 def bytes_agree(got_b, got_s, ref_b, ref_s):

@@ -1,4 +1,4 @@
-"""float64 restatement of the DEFAULT fused step (run_forward, run_bpr, triplet_body / k_triplet_dense, triplet_finish,
+"""float64 restatement of the fused step (run_forward, run_bpr, triplet_body / k_triplet_dense, triplet_finish,
 backward_layer and the Adam epilogue of csrc/lgcn_device.hip) with every storage point written out, and its float32 twin
 (the same function with dtype = torch.float32 and the real casts).  Test infrastructure: tests/test_storage_restatement.py
 pins it to the oracle, tests/test_gpu_storage_step.py judges the bf16 / fp8 kernels by it.
@@ -16,6 +16,15 @@ Storage points (Q = the rounding of the activation storage mode; `mode` is 'fp32
   backward  straight-through (Q has gradient 1).  Gs = G / (K + 1) in fp32; launch k = K .. 1 computes Gs + A h with h = Gs for
             the first launch and the STORED output of the launch before it otherwise; every launch but the last stores Q(.),
             the last one feeds Adam in fp32.
+
+The two optional axes of step() (None / absent: the default step, bit for bit what it was):
+  weights   --layer_weights, fp32 w_0 .. w_K used as given: slot row e = w[0] E0[row] + sum_{k=1..K-1} w[k] X_k[row] + w[K] X_K[row]
+            in that order (triplet_body / k_triplet_dense with WTS), no division by K + 1; G stays UNSCALED (gdiv = 1, Gs = G);
+            backward launch i (k = K - i) computes w[k-1] G + w_in (A h), w_in = w[K] and h = G for the first launch, w_in = 1 and
+            h = the stored output of the launch before it afterwards (M_WTS).  Storage points and reg_ego as above.
+  dropout   A_fwd = A_drop for the forward links and the slot rows' last layer, A_bwd = A_drop^T for the backward chain; the
+            entries are the fp32 values fl32(val fl32(1 / keep)) where kept, else 0 (drop_apply; exact in float64), built by
+            tests/dropout_restatement.py -- the transpose explicitly, the mask is not symmetric.
 
 Chain of custody: `custody` = {'e0s': .., 'fwd': {k: ..}, 'bwd': {i: ..}} replaces the INPUT of the following link by the given
 (decoded) table wherever one is given, while the link's own output is still recorded -- every link is then restated on the
@@ -85,9 +94,10 @@ def constants(decay, B):
     return float(np.float32(1.0) / np.float32(B)), float(np.float32(decay) / np.float32(B))
 
 
-def forward(A, E0, K, mode, dense_last, rows, custody=None, q=quantise):
+def forward(A, E0, K, mode, dense_last, rows, custody=None, q=quantise, weights=None):
     """-> dict: e0s (layer 1's input), fwd_pre / fwd {k: [N, d]} (before / after storage), last [3, B, d] (X_K on the slot rows),
-    terms [3, B, d, K + 1] (the summands of a slot row, for bounds), e [3, B, d]"""
+    terms_abs [3, B, d] (the absolute sum of a slot row's summands, for bounds), e [3, B, d].  A is the matrix of the forward
+    (A_drop under edge dropout); weights = the K + 1 fp32 layer weights as floats, or None for the mean."""
     cu = custody or {}
     fwd_layers = K if dense_last else K - 1
     out = {"fwd_pre": {}, "fwd": {}}
@@ -102,19 +112,29 @@ def forward(A, E0, K, mode, dense_last, rows, custody=None, q=quantise):
     out["last_in"] = prev
     flat = rows.reshape(-1)
     last = used[K][flat] if dense_last else A[flat] @ prev
+    shape = (3, rows.shape[1], E0.shape[1])
+    if weights is not None:          # triplet_body / k_triplet_dense with WTS: products summed in layer order, no division
+        w = [float(v) for v in weights]
+        assert len(w) == K + 1
+        base = w[0] * E0[flat]
+        for k in range(1, K):
+            base = base + w[k] * used[k][flat]
+        e = base + w[K] * last
+        out["last"], out["e"] = last.reshape(shape), e.reshape(shape)
+        out["terms_abs"] = (sum(abs(w[k]) * used[k][flat].abs() for k in range(K)) + abs(w[K]) * last.abs()).reshape(shape)
+        return out
     base = E0[flat]
     for k in range(1, K):
         base = base + used[k][flat]
     e = (base + last) / float(K + 1)
-    shape = (3, rows.shape[1], E0.shape[1])
     out["last"], out["e"] = last.reshape(shape), e.reshape(shape)
     out["terms_abs"] = (sum(used[k][flat].abs() for k in range(K)) + last.abs()).reshape(shape)
     return out
 
 
-def bpr(e, e0rows, n_rows, rows, K, decay, reg_ego):
+def bpr(e, e0rows, n_rows, rows, K, decay, reg_ego, scaled=True):
     """triplet_loss_regs + triplet_finish on the slot rows e [3, B, d] -> dict: x, term, regterm [B], gb [B], contrib [3, B, d],
-    G [N, d], Gs, cnt [N], loss_out (total, bpr, reg)"""
+    G [N, d], Gs, cnt [N], loss_out (total, bpr, reg).  scaled = False (layer weights: gdiv = 1): Gs = G."""
     B = e.shape[1]
     inv_B, lam = constants(decay, B)
     u, p, n = e[0], e[1], e[2]
@@ -130,19 +150,24 @@ def bpr(e, e0rows, n_rows, rows, K, decay, reg_ego):
     cnt = torch.zeros(n_rows, dtype=e.dtype).index_add(0, flat, torch.ones(flat.numel(), dtype=e.dtype))
     bpr_l = -(term.sum() / float(B))
     reg = (0.5 * regterm.sum()) / float(B)
-    return dict(x=x, term=term, regterm=regterm, gb=gb, contrib=contrib, G=G, Gs=G / float(K + 1), cnt=cnt, lam=lam,
+    return dict(x=x, term=term, regterm=regterm, gb=gb, contrib=contrib, G=G, Gs=G / float(K + 1) if scaled else G, cnt=cnt, lam=lam,
                 loss_out=(bpr_l + float(np.float32(decay)) * reg, bpr_l, reg))
 
 
-def backward(A, Gs, K, mode, custody=None, q=quantise, ego=None):
+def backward(A, Gs, K, mode, custody=None, q=quantise, ego=None, weights=None):
     """The Horner chain.  -> dict: bwd_pre / bwd {i: [N, d]} for launch i = 0 .. K - 2 (before / after storage), g_final [N, d]
-    (what Adam gets).  ego = (lam, cnt, E0) adds lam cnt[row] E0[row] in the last launch."""
+    (what Adam gets).  ego = (lam, cnt, E0) adds lam cnt[row] E0[row] in the last launch.  A is the matrix of the backward
+    (A_drop^T under edge dropout).  weights: launch i (k = K - i) computes w[k-1] G + w_in (A h), w_in = w[K] for the first
+    launch (h = G, unscaled) and 1 afterwards (spmm_epilogue with M_WTS)."""
     cu = (custody or {}).get("bwd", {})
     out = {"bwd_pre": {}, "bwd": {}, "bwd_in": {}}
     h = Gs
     for i in range(K):
         out["bwd_in"][i] = h
-        y = Gs + A @ h
+        if weights is not None:
+            y = float(weights[K - i - 1]) * Gs + (float(weights[K]) * (A @ h) if i == 0 else A @ h)
+        else:
+            y = Gs + A @ h
         if i == K - 1:
             if ego is not None:
                 y = y + (ego[0] * ego[1])[:, None] * ego[2]
@@ -154,15 +179,20 @@ def backward(A, Gs, K, mode, custody=None, q=quantise, ego=None):
     return out
 
 
-def step(A, n_users, K, decay, table, batch, mode, dense_last=False, reg_ego=False, dtype=F64, custody=None, q=quantise, q_bwd=True):
-    """One default fused step at the fp32 parameters `table` (numpy) -> everything the links above return, in `dtype`."""
+def step(A, n_users, K, decay, table, batch, mode, dense_last=False, reg_ego=False, dtype=F64, custody=None, q=quantise, q_bwd=True,
+         weights=None, A_fwd=None, A_bwd=None):
+    """One fused step at the fp32 parameters `table` (numpy) -> everything the links above return, in `dtype`.  The two optional
+    axes: weights = the K + 1 fp32 layer weights, used as given (--layer_weights); A_fwd / A_bwd = dense A_drop and its
+    explicit transpose (--dropout: the forward links and the slot rows' last layer use A_fwd, the backward chain A_bwd; the
+    mask is not symmetric).  Without them: the default step on A, every result what it was."""
     E0 = torch.from_numpy(np.asarray(table, np.float32)).to(dtype)
-    A = A.to(dtype)
+    A_fwd = (A if A_fwd is None else A_fwd).to(dtype)
+    A_bwd = (A if A_bwd is None else A_bwd).to(dtype)
     rows = slots(batch, n_users)
-    f = forward(A, E0, K, mode, dense_last, rows, custody, q)
+    f = forward(A_fwd, E0, K, mode, dense_last, rows, custody, q, weights)
     e0rows = E0[rows.reshape(-1)].reshape(f["e"].shape)
-    b = bpr(f["e"], e0rows, E0.shape[0], rows, K, decay, reg_ego)
-    w = backward(A, b["Gs"], K, mode if q_bwd else "fp32", custody, q, (b["lam"], b["cnt"], E0) if reg_ego else None)
+    b = bpr(f["e"], e0rows, E0.shape[0], rows, K, decay, reg_ego, scaled=weights is None)
+    w = backward(A_bwd, b["Gs"], K, mode if q_bwd else "fp32", custody, q, (b["lam"], b["cnt"], E0) if reg_ego else None, weights)
     return dict(f, **b, **w, rows=rows, E0=E0, e0rows=e0rows)
 
 

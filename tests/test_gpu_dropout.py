@@ -16,6 +16,8 @@ import numpy as np
 import pytest
 import torch
 
+from dropout_restatement import _fmix32, _keep_host, _rows_of, _splitmix64, a_scaled  # noqa: F401  (the hash, restated on the host from DESIGN 4: the mask is "exported and checkable")
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 N_USERS, M_ITEMS = 300, 700
@@ -85,36 +87,6 @@ def _mask(pkg, a, keep, seed, step):
     mk = out.cpu().numpy()
     assert np.isin(mk, (0, 1)).all()                 # every position written
     return mk.astype(bool)
-
-
-# ---- the hash, restated on the host from DESIGN 4 (the mask is "exported and checkable") ----------------------------------
-def _splitmix64(z):
-    M = (1 << 64) - 1
-    z = (z + 0x9E3779B97F4A7C15) & M
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M
-    return z ^ (z >> 31)
-
-
-def _fmix32(h):
-    h = h.astype(np.uint64)
-    M = np.uint64(0xFFFFFFFF)
-    h ^= h >> np.uint64(16); h = (h * np.uint64(0x85EBCA6B)) & M
-    h ^= h >> np.uint64(13); h = (h * np.uint64(0xC2B2AE35)) & M
-    h ^= h >> np.uint64(16)
-    return h
-
-
-def _keep_host(rows, cols, keep, seed, step):
-    k = _splitmix64((_splitmix64(seed & ((1 << 64) - 1)) + step) & ((1 << 64) - 1))
-    k0, k1 = np.uint64(k & 0xFFFFFFFF), np.uint64(k >> 32)
-    i, j = rows.astype(np.uint64), cols.astype(np.uint64)
-    h = _fmix32(_fmix32(i ^ k0) ^ ((j * np.uint64(0x9E3779B1)) & np.uint64(0xFFFFFFFF)) ^ k1)
-    return h < np.uint64(int(np.floor(float(np.float32(keep)) * 4294967296.0)))
-
-
-def _rows_of(a):
-    return np.repeat(np.arange(a.shape[0]), np.diff(a.indptr))
 
 
 def test_mask_statistics_and_structure(pkg, adj):
@@ -255,11 +227,6 @@ class _TorchRef:
         loss.backward()
         self.opt.step()
         return float(loss)
-
-
-def a_scaled(vals, keep):
-    """the survivors' weights as the kernels stage them: fl32(val * fl32(1 / keep)) -- within 1 ulp of val / keep"""
-    return (vals.astype(np.float32) * (np.float32(1.0) / np.float32(keep))).astype(np.float32)
 
 
 def _run_vs_ref(pkg, tmp_path, adj, K, keep, dense_last, reg_rows, hub, tag):

@@ -21,7 +21,11 @@ quantiser restated on the float64 value); the per-triplet log-sigmoid and reg te
 of the GPU's own terms; rows outside the batch's reach (stored backward tables exactly zero, scale 1; g_rec zero to the
 recovery slack); the recovered gradient; Adam (test_gpu_gate_shapes._adam_checks, from the GPU's own p, m, v, g); G64 all zero,
 check_device_errors() clean, the step counter.  Every test prints the largest share of each bound it used
-(profiles/storage_step/README.md)."""
+(profiles/storage_step/README.md).
+
+_judge_step / _run_case / _epoch_vs_steps also serve the cases with layer weights or edge dropout (a seventh field of the case;
+tests/test_gpu_storage_features.py, whose docstring says what a feature changes in the judgement); a case without one is judged
+exactly as before."""
 import numpy as np
 import pytest
 import torch
@@ -54,28 +58,55 @@ def _gpu_model(pkg, case, path):
 
 def _parts(pkg, raw, mode, N, d):
     """A stored table as the GPU holds it -> (decoded float64 torch [N, d], bytes in column order or None, scales or None)"""
-    if mode == "bf16":
+    if mode != "fp8":
         return raw.float().cpu().to(S.F64), None, None
     b, s = table_parts(pkg, raw, N, d)
     return torch.from_numpy(decode(b, s)).to(S.F64), b.copy(), s.copy()
 
 
 def _forward_tables(pkg, m, case, E0):
-    """Q(E0) and X_1 .. X_fwd_layers with the public calls on the model's own graph -> (e0s raw or None, {k: raw})"""
+    """Q(E0) and X_1 .. X_fwd_layers with the public calls on the model's own graph -> (e0s raw or None, {k: raw}).  fp32 storage
+    has no copy of E0 (layer 1 gathers the table itself); under dropout every layer is Graph.spmm_drop with the step's own
+    (keep, seed, step counter)."""
     mode, d, K, dl = case[:4]
     L, g = pkg._lib, m._dev['graph']
     fwd_layers = K if dl else K - 1
+    keep = SC.case_keep(case)
+    ydt = {"fp8": L.FP8, "bf16": L.BF16, "fp32": L.F32}[mode]
     e0s, out = None, {}
-    if K >= 2:
+    if K >= 2 and mode != "fp32":
         e0s = g.to_fp8(E0) if mode == "fp8" else E0.to(torch.bfloat16)
     prev = e0s
     for k in range(1, fwd_layers + 1):
-        if prev is None:
-            out[k] = g.spmm(E0, L.FP8 if mode == "fp8" else L.BF16)
+        if keep < 1.0:
+            out[k] = g.spmm_drop(E0 if prev is None else prev, keep, SC.DROP_SEED, step=m.adam_step, y_dtype=ydt)
+        elif prev is None:
+            out[k] = g.spmm(E0, ydt)
         else:
             out[k] = g.spmm_fp8(prev, d, L.FP8) if mode == "fp8" else g.spmm(prev)
         prev = out[k]
     return e0s, out
+
+
+def _step_graphs(pkg, case, m):
+    """(forward CSR, backward CSR, their dense float64 forms, layer weights) of the step the model is about to run.  Dropout:
+    the mask of the step counter, exported on the model's own graph, IS the host restatement's (tests/dropout_restatement.py)
+    and keeps keep +- 0.05 of the entries; A_drop and its explicit transpose are built from the restatement."""
+    adj, A = _ADJ["adj"], _ADJ["A"]
+    w, keep = SC.case_weights(case), SC.case_keep(case)
+    if w is not None:
+        assert np.array_equal(m.layer_weights, w)
+    if not keep < 1.0:
+        return adj, adj, A, A, w
+    from dropout_restatement import _keep_host, _rows_of
+    g = m._dev['graph']
+    assert np.array_equal(g.indices.cpu().numpy(), adj.indices) and np.array_equal(g.indptr.cpu().numpy(), adj.indptr)
+    mask = g.dropout_mask(keep, SC.DROP_SEED, m.adam_step).cpu().numpy().astype(bool)
+    assert np.array_equal(mask, _keep_host(_rows_of(adj), adj.indices, keep, SC.DROP_SEED, m.adam_step)), "exported mask != host restatement"
+    assert abs(mask.mean() - keep) <= 0.05, mask.mean()
+    fwd, bwd = SC.case_graphs(adj, case, m.adam_step)
+    assert np.array_equal(fwd.data != 0, mask)
+    return fwd, bwd, S.dense_adj(fwd), S.dense_adj(bwd), w
 
 
 def _bwd_buffer(K, k):
@@ -93,9 +124,11 @@ def _state(m):
 
 def _judge_step(pkg, case, m, batch, step_no, tag, end_to_end=False):
     """One fused step from the GPU's own state -> ({link: largest share of its bound}, [(tag, link, share)] beyond 1)."""
-    mode, d, K, dl, hub, reg = case
+    mode, d, K, dl, hub, reg = case[:6]
     ego, N, B = reg == "ego", SC.N_USERS + SC.M_ITEMS, len(batch[0])
-    adj, A, st = _ADJ["adj"], _ADJ["A"], m._dev
+    A, st = _ADJ["A"], m._dev
+    adj, adj_bwd, A_fwd, A_bwd, w = _step_graphs(pkg, case, m)          # adj: the forward's CSR from here on
+    feat = SC.feature(case)[0] is not None
     nbytes = N * d + 4 * N if mode == "fp8" else None
     body = (lambda t: t[:nbytes]) if mode == "fp8" else (lambda t: t)
     before = _state(m)
@@ -125,13 +158,18 @@ def _judge_step(pkg, case, m, batch, step_no, tag, end_to_end=False):
         for i in range(K - 1):
             custody["bwd"][i], b8, s8 = _parts(pkg, act[_bwd_buffer(K, K - i) - 1], mode, N, d)
             stored[("bwd", i)] = (custody["bwd"][i], b8, s8)
-    r = S.step(A, SC.N_USERS, K, SC.DECAY, before["table"], batch, mode, bool(dl), ego, custody=custody, q_bwd=not end_to_end)
-    dl_ = SC.step_deltas(adj, r, K, bool(dl), ego)
+    if feat:
+        r = S.step(A, SC.N_USERS, K, SC.DECAY, before["table"], batch, mode, bool(dl), ego, custody=custody, q_bwd=not end_to_end,
+                   weights=w, A_fwd=A_fwd, A_bwd=A_bwd)
+        dl_ = SC.step_deltas(adj, r, K, bool(dl), ego, w, adj_bwd)
+    else:
+        r = S.step(A, SC.N_USERS, K, SC.DECAY, before["table"], batch, mode, bool(dl), ego, custody=custody, q_bwd=not end_to_end)
+        dl_ = SC.step_deltas(adj, r, K, bool(dl), ego)
     # stored tables
     for (kind, j), (dec, b8, s8) in stored.items():
         ref = SC.np64(r[kind + "_pre"][j])
         if kind == "fwd":
-            delta = SC.spmm_delta(adj, SC.np64(E0.cpu() if (j == 1 and K == 1) else (custody["e0s"] if j == 1 else custody["fwd"][j - 1])))
+            delta = SC.spmm_delta(adj, SC.np64(E0.cpu() if (j == 1 and "e0s" not in custody) else (custody["e0s"] if j == 1 else custody["fwd"][j - 1])))
         else:
             delta = dl_["bwd_pre"][j]
         err = np.abs(SC.np64(dec) - ref)
@@ -141,7 +179,7 @@ def _judge_step(pkg, case, m, batch, step_no, tag, end_to_end=False):
             rb, rs, _ = S.fp8_parts(r[kind + "_pre"][j])
             cond[f"{kind}{j}"] = SC.bytes_agree(b8, s8, rb, rs)
         if kind == "bwd":
-            outside = ~SC.reach(adj, r["rows"], j + 1)
+            outside = ~SC.reach(adj_bwd, r["rows"], j + 1)
             if mode == "fp8":
                 assert not b8[outside].any() and (s8[outside] == 1.0).all(), (tag, "stored backward rows outside the reach", j)
             else:
@@ -164,14 +202,14 @@ def _judge_step(pkg, case, m, batch, step_no, tag, end_to_end=False):
     info = ""
     if end_to_end:
         chain = dl_["bwd_pre"][0]
-        aabs = abs(adj).astype(np.float64)
+        aabs = abs(adj_bwd).astype(np.float64)
         for i in range(1, K):
             chain = (dl_["bwd_pre"][i] if i < K - 1 else dl_["g_final"]) + aabs @ chain
-        allow = SC.k4_allowance(adj, SC.np64(r["G"]), K, mode)
+        allow = SC.feature_k4_allowance(adj_bwd, SC.np64(r["G"]), K, w) if feat else SC.k4_allowance(adj, SC.np64(r["G"]), K, mode)
         bound = chain + slack + allow
         info = f" raw {float(np.abs(g_rec - G).max() / np.abs(G).max()):.1e} allowance-share {_share(np.abs(g_rec - G), allow + slack + 1e-300):.2f}"
     share["grad"] = _share(np.abs(g_rec - G), bound + 1e-300)
-    outside = ~SC.reach(adj, r["rows"], K)
+    outside = ~SC.reach(adj_bwd, r["rows"], K)
     assert not G[outside].any()
     assert (np.abs(g_rec[outside]) <= slack[outside]).all(), (tag, "a row outside the batch's reach has a gradient")
     if B == 1 and K <= 2:
@@ -224,6 +262,10 @@ def test_epoch_equals_single_steps_bitwise(pkg, storage_graph, case):
     E0 afresh: six steps (5 x 64 + 37 triplets) both ways from fresh models -- losses, table and both Adam moments bit for bit.
     The only observer of the epilogue's shadow rows: a shadow one step stale, or laid out otherwise than to_fp8 lays it out,
     changes layer 1 of the next step."""
+    _epoch_vs_steps(pkg, storage_graph, case)
+
+
+def _epoch_vs_steps(pkg, storage_graph, case):
     try:
         B, T = 64, 5 * 64 + 37
         rng = np.random.Generator(np.random.PCG64(7 + case[1] + case[2]))

@@ -205,3 +205,222 @@ def test_k4_allowance_holds_against_the_exact_chain(pkg, storage_graph, case):
         err = np.abs(SC.np64(on["g_final"]) - SC.np64(off["g_final"]))
         assert (err <= allow).all(), float((err / np.maximum(allow, 1e-300)).max())
         assert (err > 0.01 * allow).any()
+
+
+# ---- the two features: layer weights and edge dropout (storage_cases.FEATURE_CASES) ---------------------------------------
+def _rel(a, b):
+    a, b = SC.np64(a), SC.np64(b)
+    return float(np.abs(a - b).max() / np.abs(b).max())
+
+
+def _autograd64(a, table, w, batch, reg, exact_w=None):
+    """One step of test_gpu_layer_weights._WeightedRef in float64 on the CSR `a` (explicit zeros allowed) -> (loss, gradient,
+    table after torch.optim.Adam's first step).  The batch has 64 triplets and decay is fl32(DECAY), so that run_bpr's fp32
+    constants inv_B = fl32(1 / B) and lam = fl32(fl32(decay) / B) ARE the reference's 1 / B and decay / B (a power of two divides
+    exactly) and the two sides differ by float64 rounding alone.  exact_w: weights that are no fp32 numbers (the mean's 1 / (K + 1))."""
+    import test_gpu_layer_weights as LW
+    assert LW.N_USERS == SC.N_USERS and len(batch[0]) == 64
+    ref = LW._WeightedRef(a, table, w, float(np.float32(SC.DECAY)), SC.LR, reg, torch.float64)
+    if exact_w is not None:
+        ref.w = list(exact_w)
+    loss = ref.step(*batch)
+    return loss, ref.E.grad.detach().clone(), ref.table()
+
+
+def _against_autograd(r, table, loss, grad, after):
+    g = SC.np64(r["g_final"])
+    p2 = S.adam(table.astype(np.float64), 0.0 * g, 0.0 * g, g, 1, SC.LR)[0]
+    return abs(float(r["loss_out"][0]) - loss) / abs(loss), _rel(g, grad), _rel(p2, after)
+
+
+# measured on the CPU, the largest over both parametrisations below, relative to the largest element: loss equal in every digit
+# (so: ten float64 roundings, 2.2e-16 each), gradient 1.8e-15, table after Adam 2.2e-16; each bound keeps a factor of 10
+AUTOGRAD_BOUND = {"loss": 2.2e-15, "grad": 1.8e-14, "table": 2.2e-15}
+
+
+def _assert_autograd(errs, what):
+    for (k, bound), e in zip(AUTOGRAD_BOUND.items(), errs):
+        assert e <= bound, (what, k, e)
+
+
+@pytest.mark.parametrize("K", [1, 2, 3, 4])
+@pytest.mark.parametrize("name", ["exp", "midzero", "last", "first"])
+def test_weights_identity_quantiser_is_float64_autograd(pkg, storage_graph, K, name):
+    """weights = w, mode fp32, on the storage graph (d = 64, the first batch): loss, gradient and the table after one Adam step
+    against torch autograd in float64 through test_gpu_layer_weights._WeightedRef's algebra (out = sum_k w_k X_k), both reg_rows
+    and both dense_last.  float64 against float64; measured: loss equal, gradient 1.8e-15, table 2.2e-16 (AUTOGRAD_BOUND keeps a
+    factor of 10)."""
+    from test_gpu_layer_weights import weight_set
+    case = ("fp32", 64, K, 0, -1, "propagated")
+    adj, A, table = _inputs(pkg, case, storage_graph)
+    batch = SC.make_batches(case)[0]
+    w = weight_set(name, K)
+    worst = [0.0, 0.0, 0.0]
+    for reg in ("propagated", "ego"):
+        loss, grad, after = _autograd64(adj, table, w, batch, reg)
+        for dl in (False, True):
+            r = S.step(A, SC.N_USERS, K, SC.DECAY, table, batch, "fp32", dl, reg == "ego", weights=w)
+            assert torch.equal(r["Gs"], r["G"])                                    # unscaled
+            errs = _against_autograd(r, table, loss, grad, after)
+            _assert_autograd(errs, (K, name, reg, dl))
+            worst = [max(a, b) for a, b in zip(worst, errs)]
+    print(f"[storage_restatement] weights K={K} {name}: loss {worst[0]:.1e} grad {worst[1]:.1e} table {worst[2]:.1e}")
+
+
+@pytest.mark.parametrize("K", [1, 2, 3, 4])
+def test_uniform_weights_are_the_mean(pkg, storage_graph, K):
+    """weights = 1 / (K + 1) (the float64 quotient) give the mean restatement: slot rows, loss and gradient to float64 rounding
+    (measured 4.9e-16 relative at most; asserted 5e-15), with storage on (bf16 forward tables are the same numbers: Q sits behind A X)."""
+    case = ("bf16", 64, K, 0, -1, "propagated")
+    adj, A, table = _inputs(pkg, case, storage_graph)
+    batch = SC.make_batches(case)[1]
+    for dl in (False, True):
+        for reg in (False, True):
+            a = S.step(A, SC.N_USERS, K, SC.DECAY, table, batch, "bf16", dl, reg, q_bwd=False)
+            b = S.step(A, SC.N_USERS, K, SC.DECAY, table, batch, "bf16", dl, reg, q_bwd=False, weights=[1.0 / (K + 1)] * (K + 1))
+            for k in a["fwd"]:
+                assert torch.equal(a["fwd"][k], b["fwd"][k])
+            errs = (_rel(b["e"], a["e"]), abs(float(b["loss_out"][0]) - float(a["loss_out"][0])) / abs(float(a["loss_out"][0])), _rel(b["g_final"], a["g_final"]))
+            print(f"[storage_restatement] uniform K={K} dl={dl} ego={reg}: e {errs[0]:.1e} loss {errs[1]:.1e} grad {errs[2]:.1e}")
+            assert max(errs) <= 5e-15, errs
+
+
+def test_stored_weights_are_symmetric_and_keep_one_is_the_default_step(pkg, storage_graph):
+    """(1) A_hat's fp32 values are symmetric bit for bit, so the matrix the backward launches read (the weight stored at (i, j)
+    under keep(j, i)) IS the explicit transpose of A_drop, and the two are not equal; (2) keep = 1 -- a_scaled and _keep_host
+    evaluated, not short-cut -- gives A itself and the default restatement bit for bit, every output."""
+    import dropout_restatement as DR
+    import scipy.sparse as sp
+    case = ("bf16", 64, 3, 0, -1, "propagated")
+    adj, A, table = _inputs(pkg, case, storage_graph)
+    assert (adj != adj.T).nnz == 0
+    fwd, bwd = DR.dropped_graphs(adj, 0.6, SC.DROP_SEED, 2)
+    assert (bwd != fwd.T.tocsr()).nnz == 0 and (bwd != fwd).nnz > 0.3 * adj.nnz
+    kept = fwd.data != 0
+    assert abs(kept.mean() - 0.6) < 0.05 and np.array_equal(fwd.data[kept], DR.a_scaled(adj.data, 0.6)[kept])
+    rows = DR._rows_of(adj)
+    assert DR._keep_host(rows, adj.indices, 1.0, SC.DROP_SEED, 2).all() and np.array_equal(DR.a_scaled(adj.data, 1.0), adj.data)
+    one = S.dense_adj(sp.csr_matrix((np.where(DR._keep_host(rows, adj.indices, 1.0, SC.DROP_SEED, 2), DR.a_scaled(adj.data, 1.0), np.float32(0)),
+                                     adj.indices, adj.indptr), shape=adj.shape))
+    for batch in SC.make_batches(case)[:2]:
+        a = S.step(A, SC.N_USERS, 3, SC.DECAY, table, batch, "bf16")
+        b = S.step(A, SC.N_USERS, 3, SC.DECAY, table, batch, "bf16", A_fwd=one, A_bwd=one.t().contiguous())
+        for k in ("e", "G", "Gs", "g_final", "term", "regterm", "terms_abs"):
+            assert torch.equal(a[k], b[k]), k
+        for k in ("fwd", "fwd_pre", "bwd", "bwd_pre"):
+            assert all(torch.equal(a[k][j], b[k][j]) for j in a[k]), k
+        assert all(float(x) == float(y) for x, y in zip(a["loss_out"], b["loss_out"]))
+
+
+@pytest.mark.parametrize("K", [1, 2, 3])
+def test_dropout_identity_quantiser_is_float64_autograd(pkg, storage_graph, K):
+    """A_fwd = A_drop, A_bwd = A_drop^T from _keep_host (keep 0.6, step 1), mode fp32: loss, gradient and table after Adam against
+    torch autograd in float64 over the sparse A_drop (test_gpu_dropout._TorchRef's algebra: the layer mean), both reg_rows and
+    both dense_last, within AUTOGRAD_BOUND (measured: loss equal, gradient 4.4e-16, table 3.0e-17).  And the transpose is REQUIRED: the same
+    restatement with A_bwd = A_fwd misses the gradient by more than 1e-2 of its largest element (measured 0.257 at least),
+    twelve orders of magnitude beyond the bound -- so a kernel that forgets dr.tr cannot pass the GPU test."""
+    case = ("fp32", 64, K, 0, -1, "propagated")
+    adj, A, table = _inputs(pkg, case, storage_graph)
+    batch = SC.make_batches(case)[0]
+    fwd, bwd = SC.case_graphs(adj, case + (("drop", 0.6),), 1)
+    Af, Ab = S.dense_adj(fwd), S.dense_adj(bwd)
+    for reg in ("propagated", "ego"):
+        loss, grad, after = _autograd64(fwd, table, np.ones(K + 1, np.float32), batch, reg, exact_w=[1.0 / (K + 1)] * (K + 1))
+        for dl in (False, True):
+            r = S.step(A, SC.N_USERS, K, SC.DECAY, table, batch, "fp32", dl, reg == "ego", A_fwd=Af, A_bwd=Ab)
+            errs = _against_autograd(r, table, loss, grad, after)
+            print(f"[storage_restatement] dropout K={K} {reg} dl={dl}: loss {errs[0]:.1e} grad {errs[1]:.1e} table {errs[2]:.1e}")
+            _assert_autograd(errs, (K, reg, dl))
+            wrong = S.step(A, SC.N_USERS, K, SC.DECAY, table, batch, "fp32", dl, reg == "ego", A_fwd=Af, A_bwd=Af)
+            miss = _rel(wrong["g_final"], grad)
+            print(f"[storage_restatement] dropout K={K} {reg} dl={dl}: untransposed backward misses by {miss:.2e}")
+            assert miss > 1e-2
+            plain = S.step(A, SC.N_USERS, K, SC.DECAY, table, batch, "fp32", dl, reg == "ego")
+            assert _rel(plain["g_final"], grad) > 1e-2                            # (and so does the undropped step)
+
+
+def _feature_trajectory(adj, A, case, table):
+    """_trajectory for a case with a feature -> per step (fp32 table before it, batch, float64 restatement, weights, (forward CSR,
+    backward CSR), their dense forms)."""
+    mode, d, K, dl, hub, reg = case[:6]
+    w = SC.case_weights(case)
+    p = table.astype(np.float64)
+    m, v = np.zeros_like(p), np.zeros_like(p)
+    out = []
+    for i, batch in enumerate(SC.make_batches(case)):
+        fwd, bwd = SC.case_graphs(adj, case, i)
+        Af, Ab = (A, A) if fwd is adj else (S.dense_adj(fwd), S.dense_adj(bwd))
+        r = S.step(A, SC.N_USERS, K, SC.DECAY, p, batch, mode, bool(dl), reg == "ego", weights=w, A_fwd=Af, A_bwd=Ab)
+        out.append((p.astype(np.float32), batch, r, w, (fwd, bwd), (Af, Ab)))
+        p, m, v = S.adam(p, m, v, SC.np64(r["g_final"]), i + 1, SC.LR)
+        p, m, v = (t.astype(np.float32).astype(np.float64) for t in (p, m, v))
+    return out
+
+
+def test_feature_batches_hold_every_row_form():
+    """test_graph_and_table_conditions' conditions on the batches, for the cases with a feature."""
+    for c in SC.FEATURE_CASES + SC.FEATURE_K4_CASES:
+        for (u, p, n) in SC.make_batches(c)[:3]:
+            assert np.bincount(p).max() >= 6 and (p == n).any() and (u == SC.HUB_USER).sum() >= 2
+            assert (p == SC.HUB_ITEM).any() and (n == SC.HUB_ITEM).any() and (n == SC.ISOLATED_ITEM).any()
+    ids = [SC.case_id(c) for c in SC.CASES + SC.K4_CASES + SC.FEATURE_CASES + SC.FEATURE_K4_CASES]
+    assert len(set(ids)) == len(ids)
+
+
+@pytest.mark.parametrize("case", SC.FEATURE_CASES + SC.FEATURE_K4_CASES, ids=SC.case_id)
+def test_feature_case_conditions_and_twin(pkg, storage_graph, case):
+    """test_case_conditions_and_twin for the cases with layer weights or dropout, per step of the case's float64 trajectory: no
+    sigmoid is saturated; every bf16 table that is not zero by construction (weights `first`: the backward tables are 0 G + 0 A G)
+    rounds elements both ways; rows outside the reach of the backward's own graph exist for K <= 2 (one-triplet batch); under
+    dropout the kept share is keep +- 0.05 and the long rows lose entries; and the float32 twin, restated link by link on the
+    float64 chain's stored tables, stays within every derived bound, so the bounds admit an honest fp32 evaluation."""
+    mode, d, K, dl, hub, reg = case[:6]
+    adj, A, table = _inputs(pkg, case, storage_graph)
+    for i, (p, batch, r, w, (fwd, bwd), (Af, Ab)) in enumerate(_feature_trajectory(adj, A, case, table)):
+        s = torch.sigmoid(-r["x"])
+        assert 0.01 < float(s.min()) and float(s.max()) < 0.99, (i, float(s.min()), float(s.max()), "change the case's batch seed (BATCH_SEED)")
+        if SC.case_keep(case) < 1.0:
+            kept = fwd.data != 0
+            assert abs(kept.mean() - SC.case_keep(case)) <= 0.05
+            hub_row = slice(adj.indptr[SC.HUB_USER], adj.indptr[SC.HUB_USER + 1])
+            assert 0 < (~kept[hub_row]).sum() < SC.HUB_USER_DEG and (bwd != fwd).nnz > 0
+        stored = [(r["fwd_pre"][k], r["fwd"][k]) for k in r["fwd"]] + [(r["bwd_pre"][j], r["bwd"][j]) for j in r["bwd"]]
+        for pre, q in stored:
+            live = pre != 0
+            if mode == "bf16" and bool(live.any()):
+                up = float((q > pre)[live].double().mean())
+                assert 0.1 < up < 0.9, (i, up)
+            elif mode == "bf16":
+                assert w is not None and SC.feature(case)[1] == "first"
+        if K <= 2 and len(batch[0]) == 1:
+            assert not SC.reach(bwd, r["rows"], K).all()
+        custody = {"e0s": r["e0s"].float(), "fwd": {k: t.float() for k, t in r["fwd"].items()}, "bwd": {j: t.float() for j, t in r["bwd"].items()}}
+        t = S.step(A, SC.N_USERS, K, SC.DECAY, p, batch, mode, bool(dl), reg == "ego", dtype=S.F32, custody=custody, weights=w, A_fwd=Af, A_bwd=Ab)
+        dl_ = SC.step_deltas(fwd, r, K, bool(dl), reg == "ego", w, bwd)
+        for key in ("term", "regterm", "gb"):
+            assert (np.abs(SC.np64(t[key]) - SC.np64(r[key])) <= dl_[key]).all(), (i, key)
+        assert (np.abs(SC.np64(t["g_final"]) - SC.np64(r["g_final"])) <= dl_["g_final"]).all(), i
+        pairs = [(t["fwd_pre"][k], r["fwd_pre"][k], SC.spmm_delta(fwd, SC.np64(r["e0s"] if k == 1 else r["fwd"][k - 1]))) for k in r["fwd"]]
+        pairs += [(t["bwd_pre"][j], r["bwd_pre"][j], dl_["bwd_pre"][j]) for j in r["bwd"]]
+        for got, ref, delta in pairs:
+            assert (np.abs(SC.np64(S.quantise(got, mode)) - SC.np64(ref)) <= SC.stored_bound(SC.np64(ref), delta, mode)).all(), i
+
+
+@pytest.mark.parametrize("case", SC.FEATURE_K4_CASES, ids=SC.case_id)
+def test_feature_k4_allowance_holds_against_the_exact_chain(pkg, storage_graph, case):
+    """test_k4_allowance_holds_against_the_exact_chain with the chain's own coefficients and the backward's own matrix."""
+    mode, d, K, dl, hub, reg = case[:6]
+    adj, A, table = _inputs(pkg, case, storage_graph)
+    w = SC.case_weights(case)
+    for i, batch in enumerate(SC.make_batches(case)):
+        fwd, bwd = SC.case_graphs(adj, case, i)
+        kw = dict(weights=w, A_fwd=S.dense_adj(fwd), A_bwd=S.dense_adj(bwd))
+        on = S.step(A, SC.N_USERS, K, SC.DECAY, table, batch, mode, **kw)
+        off = S.step(A, SC.N_USERS, K, SC.DECAY, table, batch, mode, q_bwd=False, **kw)
+        assert torch.equal(on["G"], off["G"])
+        allow = SC.feature_k4_allowance(bwd, SC.np64(off["G"]), K, w)
+        err = np.abs(SC.np64(on["g_final"]) - SC.np64(off["g_final"]))
+        assert (err <= allow).all(), float((err / np.maximum(allow, 1e-300)).max())
+        assert (err > 0.01 * allow).any()
+    uni = SC.feature_k4_allowance(adj, SC.np64(off["G"]), K)
+    assert np.allclose(uni, SC.k4_allowance(adj, SC.np64(off["G"]), K, "bf16"), rtol=1e-12, atol=0)          # the mean's coefficients: storage_allowance
