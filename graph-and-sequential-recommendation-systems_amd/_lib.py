@@ -14,6 +14,7 @@ MAX_LAYERS = 8
 MAX_NEG_RATIO = 16     # LGCN_MAX_NEG_RATIO: negatives per positive of lgcn_train_step_multi / _epoch_multi
 
 LOSS_BPR, LOSS_SOFTMAX, LOSS_INBATCH = 0, 1, 2     # LGCN_LOSS_*: lgcn_ctx_set_loss
+SCORE_DOT, SCORE_COSINE = 0, 1                     # LGCN_SCORE_*: lgcn_ctx_set_inbatch_scores
 
 _c_i32p =C.POINTER(C.c_int32)
 _c_i64p = C.POINTER(C.c_int64)
@@ -110,6 +111,9 @@ SIGNATURES = {
     # the in-batch sampled softmax (--loss inbatch)
     "lgcn_train_step_inbatch": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, _vp]),
     "lgcn_train_epoch_inbatch": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int32, _vp, _vp]),
+    # its score options (--score, --inbatch_logq)
+    "lgcn_ctx_set_inbatch_scores": (C.c_int, [_vp, C.c_int, _vp]),
+    "lgcn_ctx_get_inbatch_scores": (C.c_int, [_vp, C.POINTER(_vp)]),
     "lgcn_dp_block_floats": (C.c_int64, [_vp, C.c_int32, C.c_int32]),
     "lgcn_train_step_dp_part1": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
     "lgcn_train_step_dp_dense_part1": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),

@@ -2626,6 +2626,8 @@ struct lgcn_ctx {
     // the in-batch softmax (LGCN_LOSS_INBATCH): the workspace of its launches, allocated by the first lgcn_ctx_set_loss
     // that accepts the loss (ib_cap = max_batch rounded up to 32 rows) and freed with the context; ONE allocation, carved up
     void *ib_ws; int32_t ib_cap;
+    // its score options (lgcn_ctx_set_inbatch_scores): independent of loss_kind, (LGCN_SCORE_DOT, NULL) by default
+    int32_t ib_score; const float *ib_logq;
 };
 // a multi-step call: nobody but this library touches E0 between its steps
 struct LoopScope {
@@ -2666,6 +2668,7 @@ extern "C" int lgcn_ctx_create(const lgcn_train_config *cfg, lgcn_ctx **out) {
     x->fold_g32 = true; x->mult = nullptr; x->mult_cap = 0; x->fold_mult = nullptr; x->arrive = nullptr; x->folded_steps = 0;
     x->mn_negs = nullptr; x->mn_stride = 0; x->mn_R = 0;
     x->loss_kind = LGCN_LOSS_BPR; x->loss_temp = 1.f; x->mn_on = false; x->ib_ws = nullptr; x->ib_cap = 0;
+    x->ib_score = LGCN_SCORE_DOT; x->ib_logq = nullptr;
     x->bm_words = (x->N + 31) / 32; x->flip = 0;
     const size_t stride = table_bytes(x->N, c.d, c.act_dtype);
     for (int k = 0; k <= LGCN_MAX_LAYERS; k++) x->act[k] = nullptr;
@@ -2814,9 +2817,10 @@ static int refuse_layer_weights(const lgcn_ctx *x, const char *who) {
     return 3;
 }
 
-// floats of the in-batch workspace for `cap` rows of dim d: U, P | sbb | uid, pid | mrg | part (the largest part count)
+// floats of the in-batch workspace for `cap` rows of dim d: U, P | sbb | uid, pid | mrg | part (the largest part count) |
+// invu, invp, lqb (the score options)
 static size_t inbatch_ws_words(int32_t cap, int d) {
-    return (size_t)cap * (2 * (size_t)d + 1 + 2 + 2 + 2 * (size_t)lgcn_inbatch_parts(cap));
+    return (size_t)cap * (2 * (size_t)d + 1 + 2 + 2 + 2 * (size_t)lgcn_inbatch_parts(cap) + 3);
 }
 // accepted under exactly the conditions of LGCN_LOSS_SOFTMAX; the workspace is allocated once, before anything is changed
 static int set_loss_inbatch(lgcn_ctx *ctx, float temperature) {
@@ -2849,6 +2853,18 @@ extern "C" int lgcn_ctx_set_loss(lgcn_ctx *ctx, int32_t kind, float temperature)
     if (!ctx->c.dense_last) { lgcn_set_error("lgcn_ctx_set_loss: the sampled-softmax loss needs a context with dense_last = 1 (the gathered last layer has no 2 + R slot form)"); return 3; }
     ctx->loss_kind = LGCN_LOSS_SOFTMAX; ctx->loss_temp = temperature;
     return 0;
+}
+extern "C" int lgcn_ctx_set_inbatch_scores(lgcn_ctx *ctx, int score, const float *item_logq) {
+    if (!ctx) { lgcn_set_error("lgcn_ctx_set_inbatch_scores: null context"); return 3; }
+    if (score != LGCN_SCORE_DOT && score != LGCN_SCORE_COSINE) {
+        lgcn_set_error("lgcn_ctx_set_inbatch_scores: unknown score kind (LGCN_SCORE_DOT or LGCN_SCORE_COSINE)"); return 3; }
+    ctx->ib_score = score; ctx->ib_logq = item_logq;
+    return 0;
+}
+extern "C" int lgcn_ctx_get_inbatch_scores(const lgcn_ctx *ctx, const float **item_logq) {
+    if (!ctx) return -1;
+    if (item_logq) *item_logq = ctx->ib_logq;
+    return ctx->ib_score;
 }
 extern "C" int32_t lgcn_ctx_get_loss(const lgcn_ctx *ctx, float *temperature_out) {
     if (!ctx) return -1;
@@ -3411,6 +3427,7 @@ static int run_inbatch(lgcn_ctx *x, const int32_t *users, const int32_t *pos, in
     ia.U = w; ia.P = w + cap * d; ia.sbb = w + 2 * cap * d;
     ia.uid = (int32_t *)(w + 2 * cap * d + cap); ia.pid = ia.uid + cap;
     ia.mrg = w + 2 * cap * d + 3 * cap; ia.part = w + 2 * cap * d + 5 * cap;
+    ia.score = x->ib_score; ia.item_logq = x->ib_logq;
     return lgcn_inbatch_launch(ia, c.d, c.act_dtype, x->lw_n != 0, st);
 }
 

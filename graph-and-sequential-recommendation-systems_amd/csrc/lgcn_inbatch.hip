@@ -38,9 +38,27 @@
 // The sweep split: LGCN_INBATCH_PART_TILES = 8 tiles (256 rows) per workgroup -- 64 owner tiles x 8 parts (x 2 roles) at
 // B = 2048.  Ragged B and every D are handled by the zero rows of the workspace and the id -1 of a void row, never by a
 // branch in the MFMA loop.
+//
+// Two options (lgcn_ctx_set_inbatch_scores), compile-time axes COS / LQ of the same four launches; the (false, false)
+// instantiations are the kernels above and hold no other code:
+//   COS  s_{b,c} = e^_{u_b}.e^_{p_c}, e^ = e inv(e), inv(e) = 1 / |e| (0 for |e| = 0; sqrtf of the fp32 sum of squares and an IEEE
+//        division).  k_inbatch_rows writes U^, P^ into U, P, inv into invu / invp and takes s_bb from the normalised values; the
+//        reg term and lam e stay on the raw rows.  The chain through the normalisation is a projection,
+//        g_o = inv_o (sum_x W[x,o] other^_x - t_o own^_o), t_o = sum_x W[x,o] s[x,o]: k_inbatch_grad sums t_o over the 16
+//        accumulator registers in which it forms W from the scores (per lane, the two halves added with one shuffle) and applies
+//        the projection to its partial rows in the epilogue -- it is linear, so the parts of the sweep still meet order-free in
+//        G64; k_inbatch_diag adds the diagonal's inv_u W[b,b] (p^_b - s_bb u^_b) and its mirror.
+//   LQ   z_{b,c} = (s_{b,c} - s_{b,b}) / tau - (lq_{p_c} - lq_{p_b}): k_inbatch_rows gathers lq[p_b] into lqb (after the id check;
+//        0 for void rows and padding), the two tile passes load the lane's and the tile rows' lq where s_bb and the ids are
+//        loaded; fl(lq_c - lq_b) has the same bits in all three places.
 #include "lgcn_device_common.h"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+
+// the three [cap] vectors of the score options, carved behind `part` in the context's workspace
+__device__ __forceinline__ float *ib_invu(const InBatchArgs &ia) { return ia.part + 2 * (int64_t)ia.cap * lgcn_inbatch_parts(ia.cap); }
+__device__ __forceinline__ float *ib_invp(const InBatchArgs &ia) { return ib_invu(ia) + ia.cap; }
+__device__ __forceinline__ float *ib_lqb(const InBatchArgs &ia) { return ib_invu(ia) + 2 * (int64_t)ia.cap; }
 
 // tile row of accumulator register `reg` on lane half h (C/D layout of the 32x32 MFMAs)
 __device__ __forceinline__ int ib_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
@@ -96,7 +114,7 @@ __device__ __forceinline__ void ib_merge(float &m, float &r, float m2, float r2)
     else { r = r2 + (1.f + r) * expf(m - m2); m = m2; }
 }
 
-template <int D, typename TI, bool WTS>
+template <int D, typename TI, bool WTS, bool COS, bool LQ>
 __global__ void __launch_bounds__(256) k_inbatch_rows(InBatchArgs ia) {
     const MultiNegArgs &a = ia.m;
     constexpr int LPT = D < 64 ? D : 64, CPT = D / LPT, SPB = 256 / LPT;     // lanes per sample, samples per workgroup
@@ -121,6 +139,8 @@ __global__ void __launch_bounds__(256) k_inbatch_rows(InBatchArgs ia) {
         for (int j = 0; j < CPT; j++) { ia.U[(int64_t)b * D + j * LPT + l] = 0.f; ia.P[(int64_t)b * D + j * LPT + l] = 0.f; }
         if (l == 0) {
             ia.uid[b] = -1; ia.pid[b] = -1; ia.sbb[b] = 0.f; ia.mrg[2 * b] = 0.f; ia.mrg[2 * b + 1] = 1.f;
+            if constexpr (COS) { ib_invu(ia)[b] = 0.f; ib_invp(ia)[b] = 0.f; }
+            if constexpr (LQ) ib_lqb(ia)[b] = 0.f;
             if (b < a.B) { atomicExch(a.err, 1); a.terms[b] = 0.f; a.terms[a.terms_stride + b] = 0.f; }
         }
         return;
@@ -139,16 +159,41 @@ __global__ void __launch_bounds__(256) k_inbatch_rows(InBatchArgs ia) {
     for (int j = 0; j < CPT; j++) { const float v = ego ? t0[j] : p[j]; ps += u[j] * p[j]; rp2 += v * v; }
     ps = group_sum<LPT>(ps);
     const float rr = group_sum<LPT>(ru2 + rp2);
+    if constexpr (COS) {
+        // |e| = sqrtf of the fp32 sum of squares, inv = 1 / |e| by an IEEE division (0 for a row of norm 0): two roundings.
+        // U, P and s_bb are those of the rows over their norms; the reg term and lam e stay on the rows themselves
+        float nu = 0.f, np = 0.f;
 #pragma unroll
-    for (int j = 0; j < CPT; j++) {
-        ia.U[(int64_t)b * D + j * LPT + l] = u[j];
-        ia.P[(int64_t)b * D + j * LPT + l] = p[j];
-        if (lam != 0.f) {
-            fixed_add(a.G64 + ru * D + j * LPT + l, lam * u[j]);
-            fixed_add(a.G64 + rp * D + j * LPT + l, lam * p[j]);
+        for (int j = 0; j < CPT; j++) { nu += u[j] * u[j]; np += p[j] * p[j]; }
+        nu = group_sum<LPT>(nu); np = group_sum<LPT>(np);
+        const float inv_u = nu > 0.f ? 1.f / sqrtf(nu) : 0.f, inv_p = np > 0.f ? 1.f / sqrtf(np) : 0.f;
+        ps = 0.f;
+#pragma unroll
+        for (int j = 0; j < CPT; j++) {
+            const float uh = u[j] * inv_u, ph = p[j] * inv_p;
+            ps += uh * ph;
+            ia.U[(int64_t)b * D + j * LPT + l] = uh;
+            ia.P[(int64_t)b * D + j * LPT + l] = ph;
+            if (lam != 0.f) {
+                fixed_add(a.G64 + ru * D + j * LPT + l, lam * u[j]);
+                fixed_add(a.G64 + rp * D + j * LPT + l, lam * p[j]);
+            }
+        }
+        ps = group_sum<LPT>(ps);
+        if (l == 0) { ib_invu(ia)[b] = inv_u; ib_invp(ia)[b] = inv_p; }
+    } else {
+#pragma unroll
+        for (int j = 0; j < CPT; j++) {
+            ia.U[(int64_t)b * D + j * LPT + l] = u[j];
+            ia.P[(int64_t)b * D + j * LPT + l] = p[j];
+            if (lam != 0.f) {
+                fixed_add(a.G64 + ru * D + j * LPT + l, lam * u[j]);
+                fixed_add(a.G64 + rp * D + j * LPT + l, lam * p[j]);
+            }
         }
     }
     if (l == 0) { ia.uid[b] = iu; ia.pid[b] = ip; ia.sbb[b] = ps; a.terms[a.terms_stride + b] = rr; }
+    if constexpr (LQ) { if (l == 0) ib_lqb(ia)[b] = ia.item_logq[ip]; }          // (ip passed the id check above)
     if (l < 2) {                                // the 2 rows of the sample: one lane each
         const int64_t myrow = l == 0 ? ru : rp;
         atomicOr(a.bitmap + (myrow >> 5), 1u << (myrow & 31));
@@ -156,7 +201,7 @@ __global__ void __launch_bounds__(256) k_inbatch_rows(InBatchArgs ia) {
     }
 }
 
-template <int D>
+template <int D, bool LQ>
 __global__ void __launch_bounds__(64) k_inbatch_norm(InBatchArgs ia) {
     const int l = threadIdx.x, j = l & 31, h = l >> 5;
     const int Bp = lgcn_inbatch_rows(ia.m.B), nT = Bp / 32;
@@ -164,6 +209,8 @@ __global__ void __launch_bounds__(64) k_inbatch_norm(InBatchArgs ia) {
     const int t0 = blockIdx.y * LGCN_INBATCH_PART_TILES, t1 = t0 + LGCN_INBATCH_PART_TILES < nT ? t0 + LGCN_INBATCH_PART_TILES : nT;
     const int32_t ub = ia.uid[b], pb = ia.pid[b];
     const float sbb = ia.sbb[b], tau = ia.m.tau;
+    float lqb = 0.f;                            // log Q of the lane's own positive
+    if constexpr (LQ) lqb = ib_lqb(ia)[b];
     const float *brow = ia.U + (int64_t)b * D + h * (D / 2);
     float m = -INFINITY, r = 0.f;
     constexpr int RD = D <= IB_REG_D ? D : 8;   // (the register form's types at a size that costs nothing where it is not used)
@@ -175,6 +222,11 @@ __global__ void __launch_bounds__(64) k_inbatch_norm(InBatchArgs ia) {
         int32_t ucs[16], pcs[16];
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) { const int c = t * 32 + ib_row(reg, h); ucs[reg] = ia.uid[c]; pcs[reg] = ia.pid[c]; }
+        float lqs[LQ ? 16 : 1];
+        if constexpr (LQ) {
+#pragma unroll
+            for (int reg = 0; reg < 16; reg++) lqs[reg] = ib_lqb(ia)[t * 32 + ib_row(reg, h)];
+        }
         f32x16 acc;
         if constexpr (D <= IB_REG_D) {
             const int tn = t + 1 < t1 ? t + 1 : t;
@@ -190,7 +242,8 @@ __global__ void __launch_bounds__(64) k_inbatch_norm(InBatchArgs ia) {
             const int c = t * 32 + ib_row(reg, h);
             const int32_t uc = ucs[reg], pc = pcs[reg];
             const bool ok = ub >= 0 && uc >= 0 && c != b && pc != pb && uc != ub;
-            z[reg] = ok ? (acc[reg] - sbb) / tau : -INFINITY;
+            if constexpr (LQ) z[reg] = ok ? (acc[reg] - sbb) / tau - (lqs[reg] - lqb) : -INFINITY;
+            else z[reg] = ok ? (acc[reg] - sbb) / tau : -INFINITY;
             tmax = fmaxf(tmax, z[reg]);
         }
         bool excl = false;                      // a new maximum: its first occurrence becomes the 1 of (1 + r)
@@ -210,7 +263,7 @@ __global__ void __launch_bounds__(64) k_inbatch_norm(InBatchArgs ia) {
     }
 }
 
-template <int D>
+template <int D, bool COS>
 __global__ void __launch_bounds__(256) k_inbatch_diag(InBatchArgs ia) {
     const MultiNegArgs &a = ia.m;
     constexpr int LPT = D < 64 ? D : 64, CPT = D / LPT, SPB = 256 / LPT;
@@ -232,12 +285,18 @@ __global__ void __launch_bounds__(256) k_inbatch_diag(InBatchArgs ia) {
 #pragma unroll
     for (int j = 0; j < CPT; j++) {
         const int64_t o = (int64_t)b * D + j * LPT + l;
-        fixed_add(a.G64 + ru * D + j * LPT + l, wd * ia.P[o]);
-        fixed_add(a.G64 + rp * D + j * LPT + l, wd * ia.U[o]);
+        if constexpr (COS) {                    // the diagonal through the normalisation: inv W[b,b] (other^ - s_bb own^)
+            const float uh = ia.U[o], ph = ia.P[o], sbb = ia.sbb[b];
+            fixed_add(a.G64 + ru * D + j * LPT + l, ib_invu(ia)[b] * (wd * (ph - sbb * uh)));
+            fixed_add(a.G64 + rp * D + j * LPT + l, ib_invp(ia)[b] * (wd * (uh - sbb * ph)));
+        } else {
+            fixed_add(a.G64 + ru * D + j * LPT + l, wd * ia.P[o]);
+            fixed_add(a.G64 + rp * D + j * LPT + l, wd * ia.U[o]);
+        }
     }
 }
 
-template <int D>
+template <int D, bool COS, bool LQ>
 __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
     constexpr int CB = D < 128 ? D / 32 : 4;    // 32-column blocks of the output this workgroup accumulates
     const int l = threadIdx.x, j = l & 31, h = l >> 5;
@@ -249,6 +308,9 @@ __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
     const int32_t uo = ia.uid[o], po = ia.pid[o];
     const float sbb_o = ia.sbb[o], M_o = ia.mrg[2 * o], den_o = ia.mrg[2 * o + 1];
     const float tau = ia.m.tau, inv_tauB = ia.m.inv_tauB;
+    float lq_o = 0.f;                           // log Q of the owned sample's positive
+    if constexpr (LQ) lq_o = ib_lqb(ia)[o];
+    float tproj = 0.f;                          // cosine: sum_x W[x][o] s[x][o] over this lane's 16 rows of every tile
     const float *brow = own + (int64_t)o * D + h * (D / 2);
     f32x16 g[CB];
 #pragma unroll
@@ -264,7 +326,7 @@ __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
         // merged (M, 1 + Zm1) under role 1 (under role 0 they are the lane's own), the B operands of the second product and,
         // in the register form, the next tile's rows
         int32_t uxs[16], pxs[16];
-        float sbs[16], Ms[16], dens[16], ob[16][CB];
+        float sbs[16], Ms[16], dens[16], ob[16][CB], lqd[LQ ? 16 : 1];
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {
             const int x = t * 32 + ib_row(reg, h);          // the other side's index (a row of the tile)
@@ -272,6 +334,8 @@ __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
             // the USER of the pair owns s_bb and the merged (M, 1 + Zm1): the lane's under role 0, the row's under role 1
             sbs[reg] = role == 0 ? sbb_o : ia.sbb[x];
             Ms[reg] = role == 0 ? M_o : ia.mrg[2 * x]; dens[reg] = role == 0 ? den_o : ia.mrg[2 * x + 1];
+            // lq of the pair's ITEM less lq of the pair's user's own positive: the row's less the lane's under role 0
+            if constexpr (LQ) { const float lq_x = ib_lqb(ia)[x]; lqd[reg] = role == 0 ? lq_x - lq_o : lq_o - lq_x; }
             if constexpr (D <= IB_REG_D) {
 #pragma unroll
                 for (int cb = 0; cb < CB; cb++) ob[reg][cb] = oth[(int64_t)x * D + col0 + j + cb * 32];
@@ -290,8 +354,15 @@ __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
         for (int reg = 0; reg < 16; reg++) {
             const int x = t * 32 + ib_row(reg, h);
             const bool ok = uo >= 0 && uxs[reg] >= 0 && x != o && pxs[reg] != po && uxs[reg] != uo;
-            const float z = (w[reg] - sbs[reg]) / tau;
-            w[reg] = ok ? expf(z - Ms[reg]) / dens[reg] * inv_tauB : 0.f;
+            float z;
+            if constexpr (LQ) z = (w[reg] - sbs[reg]) / tau - lqd[reg]; else z = (w[reg] - sbs[reg]) / tau;
+            if constexpr (COS) {
+                const float s = w[reg];
+                w[reg] = ok ? expf(z - Ms[reg]) / dens[reg] * inv_tauB : 0.f;
+                tproj += w[reg] * s;
+            } else {
+                w[reg] = ok ? expf(z - Ms[reg]) / dens[reg] * inv_tauB : 0.f;
+            }
         }
         // g[owned][col] += sum_x W[x][owned] Other[x][col]: register i of w is the A operand as it stands
 #pragma unroll
@@ -305,33 +376,54 @@ __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
             }
         }
     }
+    if constexpr (COS) tproj += __shfl_xor(tproj, 32);      // both lane halves: lane r and lane r + 32 hold owned row r's scalar
     // rows of g: owned index blockIdx.x * 32 + ib_row(reg, h); columns col0 + cb * 32 + j
 #pragma unroll
     for (int reg = 0; reg < 16; reg++) {
         const int ob = blockIdx.x * 32 + ib_row(reg, h);
+        float t_row = 0.f;
+        if constexpr (COS) t_row = __shfl(tproj, ib_row(reg, h));             // (every lane takes part: before the skip)
         const int32_t us = ia.uid[ob];
         if (us < 0) continue;                   // void or padding: no row to add to (its W is zero)
         const int64_t row = role == 0 ? (int64_t)us : (int64_t)ia.pid[ob] + ia.m.n_users;
+        if constexpr (COS) {
+            // the chain through the normalisation, per part (it is linear): inv_o (sum_x W own-side^ - t own^), DESIGN 4.20
+            const float inv_o = (role == 0 ? ib_invu(ia) : ib_invp(ia))[ob];
 #pragma unroll
-        for (int cb = 0; cb < CB; cb++) fixed_add(ia.m.G64 + row * D + col0 + cb * 32 + j, g[cb][reg]);
+            for (int cb = 0; cb < CB; cb++) {
+                const float oh = own[(int64_t)ob * D + col0 + cb * 32 + j];
+                fixed_add(ia.m.G64 + row * D + col0 + cb * 32 + j, inv_o * (g[cb][reg] - t_row * oh));
+            }
+        } else {
+#pragma unroll
+            for (int cb = 0; cb < CB; cb++) fixed_add(ia.m.G64 + row * D + col0 + cb * 32 + j, g[cb][reg]);
+        }
     }
 }
 
-template <int D>
+template <int D, bool COS, bool LQ>
 static void launch_d(const InBatchArgs &a, int act_dtype, bool wts, hipStream_t st) {
     constexpr int SPB = 256 / (D < 64 ? D : 64);
     const int Bp = lgcn_inbatch_rows(a.m.B), NP = lgcn_inbatch_parts(a.m.B);
     const dim3 rows_grid((unsigned)((Bp + SPB - 1) / SPB)), diag_grid((unsigned)((a.m.B + SPB - 1) / SPB));
     if (act_dtype == LGCN_F32) {
-        if (wts) hipLaunchKernelGGL((k_inbatch_rows<D, float, true>), rows_grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_inbatch_rows<D, float, false>), rows_grid, dim3(256), 0, st, a);
+        if (wts) hipLaunchKernelGGL((k_inbatch_rows<D, float, true, COS, LQ>), rows_grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_inbatch_rows<D, float, false, COS, LQ>), rows_grid, dim3(256), 0, st, a);
     } else {
-        if (wts) hipLaunchKernelGGL((k_inbatch_rows<D, bf16_t, true>), rows_grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_inbatch_rows<D, bf16_t, false>), rows_grid, dim3(256), 0, st, a);
+        if (wts) hipLaunchKernelGGL((k_inbatch_rows<D, bf16_t, true, COS, LQ>), rows_grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_inbatch_rows<D, bf16_t, false, COS, LQ>), rows_grid, dim3(256), 0, st, a);
     }
-    hipLaunchKernelGGL((k_inbatch_norm<D>), dim3((unsigned)(Bp / 32), (unsigned)NP), dim3(64), 0, st, a);
-    hipLaunchKernelGGL((k_inbatch_diag<D>), diag_grid, dim3(256), 0, st, a);
-    hipLaunchKernelGGL((k_inbatch_grad<D>), dim3((unsigned)(Bp / 32), (unsigned)NP, 2u * (D > 128 ? D / 128 : 1)), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((k_inbatch_norm<D, LQ>), dim3((unsigned)(Bp / 32), (unsigned)NP), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((k_inbatch_diag<D, COS>), diag_grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((k_inbatch_grad<D, COS, LQ>), dim3((unsigned)(Bp / 32), (unsigned)NP, 2u * (D > 128 ? D / 128 : 1)), dim3(64), 0, st, a);
+}
+
+// the two options are compile-time axes: (dot, no logq) are the instantiations a context that was never told launches
+template <int D>
+static void launch_opts(const InBatchArgs &a, int act_dtype, bool wts, hipStream_t st) {
+    const bool cosine = a.score == LGCN_SCORE_COSINE, lq = a.item_logq != nullptr;
+    if (cosine) { if (lq) launch_d<D, true, true>(a, act_dtype, wts, st); else launch_d<D, true, false>(a, act_dtype, wts, st); }
+    else { if (lq) launch_d<D, false, true>(a, act_dtype, wts, st); else launch_d<D, false, false>(a, act_dtype, wts, st); }
 }
 
 int lgcn_inbatch_launch(const InBatchArgs &a, int d, int act_dtype, bool wts, hipStream_t st) {
@@ -342,6 +434,10 @@ int lgcn_inbatch_launch(const InBatchArgs &a, int d, int act_dtype, bool wts, hi
                        "fp32 / bf16 tables, a workspace of a multiple of 32 rows)");
         return 3;
     }
-    DISPATCH_D(d, launch_d<D>(a, act_dtype, wts, st));
+    if (a.score != LGCN_SCORE_DOT && a.score != LGCN_SCORE_COSINE) {
+        lgcn_set_error("in-batch softmax rows: bad launch arguments (score dot or cosine)");
+        return 3;
+    }
+    DISPATCH_D(d, launch_opts<D>(a, act_dtype, wts, st));
     return 0;
 }

@@ -69,6 +69,11 @@ struct InBatchArgs {
     float *part;                  // [parts][Bp][2] partial (m, r) of a user over one part of the item sweep: sum = exp(m) (1 + r)
     float *mrg;                   // [cap][2] merged (M, 1 + Zm1) of a user
     int32_t cap;
+    // the score options (lgcn_ctx_set_inbatch_scores), behind everything the default launches read.  Their three
+    // [cap] vectors lie behind `part` (the largest part count): invu, invp = 1 / |e_u|, 1 / |e_p| of the sample under cosine, lqb =
+    // item_logq[p_b] under logq; 0 for a void sample and for padding (and inv = 0 for a row of norm 0)
+    int32_t score;                // LGCN_SCORE_DOT, or LGCN_SCORE_COSINE: U, P then hold the rows over their norms
+    const float *item_logq;       // [m_items] log Q(item), or NULL: no correction
 };
 static __host__ __device__ inline int32_t lgcn_inbatch_rows(int32_t B) { return (B + 31) & ~31; }                          // Bp: B padded to whole tiles
 static __host__ __device__ inline int32_t lgcn_inbatch_parts(int32_t B) { return (lgcn_inbatch_rows(B) / 32 + LGCN_INBATCH_PART_TILES - 1) / LGCN_INBATCH_PART_TILES; }

@@ -88,6 +88,41 @@ def resolve_loss(config):
     return kind, tau
 
 
+def _unit_rows(x):
+    """x [n, d] -> its rows over their norms; a row of norm 0 stays 0 (the inv(e) of DESIGN 4.20)."""
+    n = x.norm(dim=1, keepdim=True)
+    return x * torch.where(n > 0, 1.0 / n, torch.zeros_like(n))
+
+
+def resolve_inbatch_scores(config, loss_kind):
+    """--score dot | cosine and --inbatch_logq 0 | 1 -> ('dot' | 'cosine', bool).  Both are options of --loss inbatch:
+    LgcnError naming the flag under any other loss; ValueError for a value that is neither."""
+    score = str(config.get('score', 'dot')).strip().lower()
+    if score not in ('dot', 'cosine'):
+        raise ValueError(f"--score must be dot or cosine, got {config.get('score')!r}")
+    lq = str(config.get('inbatch_logq', 0)).strip().lower()
+    if lq not in ('0', '1', 'false', 'true'):
+        raise ValueError(f"--inbatch_logq must be 0 or 1, got {config.get('inbatch_logq')!r}")
+    lq = lq in ('1', 'true')
+    if loss_kind != 'inbatch':
+        if score == 'cosine':
+            raise _lib.LgcnError(f"--score cosine is implemented for --loss inbatch only, not for --loss {loss_kind} "
+                                 "(cosine scores for the sampled softmax are not implemented)")
+        if lq:
+            raise _lib.LgcnError(f"--inbatch_logq 1 is implemented for --loss inbatch only, not for --loss {loss_kind} "
+                                 "(the correction is for negatives that arrive in proportion to item popularity)")
+    return score, lq
+
+
+def item_logq(items_D):
+    """The logQ vector of --inbatch_logq 1: log of the train degree (zeros already 1 in the loader) in float64, rounded once to
+    fp32.  The -log E that would make it a log-probability is common to all items and cancels in z, so it is not applied."""
+    deg = np.asarray(items_D, np.float64).reshape(-1)
+    if not (np.isfinite(deg).all() and (deg > 0).all()):
+        raise ValueError("--inbatch_logq 1: the item degrees must be finite and > 0 (the loader sets empty items to 1)")
+    return np.log(deg).astype(np.float32)
+
+
 def resolve_layer_weights(config, K, degrees=None):
     """(config, K) -> the fp32 [K+1] weights of out = sum_k w_k X_k, or None for the mean (the reference's combination).
     --layer_weights mean | exp | ppr | "[w_0, ..., w_K]"; the reference's own --use_ppr_weights [--ppr_weights_path FILE]
@@ -295,11 +330,17 @@ class LightGCN(nn.Module):
             raise _lib.LgcnError(f"--loss inbatch is not implemented together with --neg_ratio {self.neg_ratio}: the in-batch loss has no "
                                  "sampled negatives (the other samples' positives are the negatives); use --neg_ratio 1")
         self._loss_said = False
+        # the two options of the in-batch step (--score dot | cosine, --inbatch_logq 0 | 1; lgcn_ctx_set_inbatch_scores)
+        self.score_kind, self.inbatch_logq = resolve_inbatch_scores(config, self.loss_kind)
+        self._item_logq = None      # fp32 [m_items] log(items_D), rounded once from float64 (None: --inbatch_logq 0)
+        if self.inbatch_logq:
+            self._item_logq = torch.from_numpy(item_logq(dataset.items_D))
         self._gate_flat = None      # the eight MLP tensors of the gate in ONE buffer (what the fused step reads / updates)
         self._Graph = None
         self._dev = None            # device-side state (graph, workspace, context)
         self._cache = None          # propagated embeddings memoised between invalidate_cache() calls
         self._rating_cache = None
+        self._cosine_cache = None   # --score cosine: the row-normalised propagated table evaluation ranks with, memoised likewise
         self.f = nn.Sigmoid()
 
     # -- parameters live in one table ------------------------------------------------
@@ -395,6 +436,7 @@ class LightGCN(nn.Module):
         self._dev = None
         self._cache = None
         self._rating_cache = None
+        self._cosine_cache = None
 
     def __del__(self):
         try:
@@ -537,6 +579,15 @@ class LightGCN(nn.Module):
                 msg = lib.lgcn_last_error()
                 lib.lgcn_ctx_destroy(h)
                 raise _lib.LgcnError(f"lgcn_ctx_set_loss failed (rc={rc}): {msg.decode() if msg else ''}")
+        if self.score_kind != 'dot' or self.inbatch_logq:      # (a context that is never told runs the launches it always ran)
+            if self.inbatch_logq and (st.get('item_logq') is None or st['item_logq'].device != dev):
+                st['item_logq'] = self._item_logq.to(device=dev, dtype=torch.float32).contiguous()      # uploaded once
+            rc = lib.lgcn_ctx_set_inbatch_scores(h, _lib.SCORE_COSINE if self.score_kind == 'cosine' else _lib.SCORE_DOT,
+                                                 _lib.tp(st['item_logq']) if self.inbatch_logq else None)
+            if rc:
+                msg = lib.lgcn_last_error()
+                lib.lgcn_ctx_destroy(h)
+                raise _lib.LgcnError(f"lgcn_ctx_set_inbatch_scores failed (rc={rc}): {msg.decode() if msg else ''}")
         if str(self.config.get('fold_g32', 1)).strip().lower() in ('0', 'false', 'off'):      # config['fold_g32'] = 0: fused_epoch launches k_g32 every step again (A/B, tests)
             rc = lib.lgcn_ctx_set_fold_g32(h, 0)
             if rc:
@@ -622,6 +673,7 @@ class LightGCN(nn.Module):
         """Hook probed by main.py:190-191 before each Test."""
         self._cache = None
         self._rating_cache = None
+        self._cosine_cache = None
 
     def train(self, mode=True):
         self.invalidate_cache()
@@ -651,6 +703,11 @@ class LightGCN(nn.Module):
     def rating_table(self):
         """What getUsersRating scores with (model.py:114-123): the propagated users and the FINAL item
         embeddings (popularity-gated when the gate is on).  This is what the fused evaluation kernels read."""
+        if self.score_kind == 'cosine':          # --score cosine (DESIGN 4.20): evaluation ranks what was trained, the rows over their norms
+            if getattr(self, '_cosine_cache', None) is None:
+                with torch.no_grad():
+                    self._cosine_cache = _unit_rows(self.propagated_table()).contiguous()
+            return self._cosine_cache
         if not self.use_pop_gate:
             return self.propagated_table()
         if getattr(self, '_rating_cache', None) is None:
@@ -679,6 +736,8 @@ class LightGCN(nn.Module):
 
     def getUsersRating(self, users):
         all_users, all_items = self.computer()
+        if self.score_kind == 'cosine':          # U^ P^^T: what --loss inbatch --score cosine trains
+            return torch.matmul(_unit_rows(all_users[users]), _unit_rows(all_items).t())
         i_emb = self._fuse_item_embeddings(all_items) if self.use_pop_gate else all_items
         return torch.matmul(all_users[users], i_emb.t())
 
@@ -718,8 +777,13 @@ class LightGCN(nn.Module):
         all_users, all_items = self.computer()
         ul, pl = users.long(), pos.long()
         u, p = all_users[ul], all_items[pl]
-        s = u @ p.t()
+        # --score cosine: the rows over their norms (F.normalize; a row of norm 0 scores 0).  The reg term stays on the rows
+        # (eps below every fp32 norm whose square does not underflow: F.normalize then IS e / |e|, and a zero row stays zero)
+        s = F.normalize(u, dim=1, eps=1e-37) @ F.normalize(p, dim=1, eps=1e-37).t() if self.score_kind == 'cosine' else u @ p.t()
         z = (s - torch.diagonal(s)[:, None]) / float(self.softmax_temp)
+        if self.inbatch_logq:                    # --inbatch_logq 1: z_{b,c} -= lq_{p_c} - lq_{p_b}
+            lq = self._item_logq.to(device=z.device, dtype=z.dtype)[pl]
+            z = z - (lq[None, :] - lq[:, None])
         keep = (pl[None, :] != pl[:, None]) & (ul[None, :] != ul[:, None])          # (u_c != u_b leaves c = b out too)
         z = torch.where(keep, z, torch.full_like(z, float('-inf')))
         sm = torch.logsumexp(torch.cat([torch.zeros_like(z[:, :1]), z], dim=1), dim=1).sum() / float(B)
@@ -954,6 +1018,10 @@ class PureMF(nn.Module):
                                  "one negative per positive)")
         if str(config.get('loss', 'bpr')).strip().lower() != 'bpr':
             raise _lib.LgcnError(f"--loss {config.get('loss')} {no} (the matrix-factorisation step computes the BPR loss)")
+        if str(config.get('score', 'dot')).strip().lower() != 'dot':
+            raise _lib.LgcnError(f"--score {config.get('score')} {no} (an option of LightGCN's --loss inbatch)")
+        if str(config.get('inbatch_logq', 0)).strip().lower() not in ('0', 'false'):
+            raise _lib.LgcnError(f"--inbatch_logq {config.get('inbatch_logq')} {no} (an option of LightGCN's --loss inbatch)")
         if self.latent_dim not in (32, 64, 128, 256):
             raise ValueError("latent_dim_rec must be 32, 64, 128 or 256 for the HIP kernels")
         if self.n_users + self.m_items >= 2 ** 31:

@@ -127,6 +127,13 @@ def build_parser():
                         'fp32 / bf16 storage, single GPU, default model, dense last layer')
     p.add_argument('--softmax_temp', type=float, default=1.0,
                    help='NEW: temperature tau > 0 of --loss softmax (at --neg_ratio 1 and tau = 1 the loss is the BPR loss) and of --loss inbatch')
+    p.add_argument('--score', type=str, default='dot', choices=['dot', 'cosine'],
+                   help='NEW: how --loss inbatch forms its scores. dot (default) = the inner product of the output rows. cosine = the inner '
+                        'product of the rows over their norms, trained through the normalisation; evaluation then ranks by cosine too. The '
+                        'scores lie in [-1, 1], so cosine wants --softmax_temp well below 1 (0.1 .. 0.2). --loss inbatch only')
+    p.add_argument('--inbatch_logq', type=int, default=0, choices=[0, 1],
+                   help='NEW: 1 = subtract log Q(item) = log(train degree) from every in-batch logit (the logQ correction: in-batch '
+                        'negatives arrive in proportion to item popularity). 0 (default) = no correction. --loss inbatch only')
     p.add_argument('--data_path', type=str, default=None,
                    help='NEW: directory that holds <dataset>/train.txt (default: <root>/data)')
     return p

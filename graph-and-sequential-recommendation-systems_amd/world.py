@@ -116,6 +116,8 @@ def configure(argv=None):
     config['neg_ratio'] = args.neg_ratio
     config['loss'] = args.loss
     config['softmax_temp'] = args.softmax_temp
+    config['score'] = args.score
+    config['inbatch_logq'] = args.inbatch_logq
     device =torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     return config
 

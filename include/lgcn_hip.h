@@ -379,6 +379,24 @@ int lgcn_train_step_inbatch(lgcn_ctx *ctx, const int32_t *users, const int32_t *
 int lgcn_train_epoch_inbatch(lgcn_ctx *ctx, const int32_t *users, const int32_t *pos, int64_t T, int32_t B, float *loss_out,
                              void *stream);
 
+/* Two options of the in-batch step (--score, --inbatch_logq), read by the two entry points above only:
+ *   score:      LGCN_SCORE_DOT     e^ = e
+ *               LGCN_SCORE_COSINE  e^ = e inv(e),  inv(e) = 1 / |e| if |e| > 0 else 0   (|e| = sqrtf of the fp32 sum of squares)
+ *               s_{b,c} = e^_{u_b}.e^_{p_c}
+ *   item_logq:  lq, one finite fp32 per item (log of the item's sampling probability up to a constant: the constant cancels),
+ *               or NULL = no correction;   z_{b,c} = (s_{b,c} - s_{b,b}) / tau - (lq_{p_c} - lq_{p_b})
+ * l_b, sm, q, W are those of the in-batch loss, from this z.  Under cosine the gradient goes through the normalisation:
+ *   g_{u_b} = inv(e_u) ( sum_c W[b,c] e^_{p_c} - (sum_c W[b,c] s_{b,c}) e^_{u_b} ) + lam e_{u_b}     (c over A_b and b itself)
+ * and its mirror for the items; the reg term and lam e stay on the raw rows, and a row of norm 0 scores 0 and receives no score
+ * gradient.  The state is independent of lgcn_ctx_set_loss; a context that is never told holds (LGCN_SCORE_DOT, NULL) and runs
+ * the launches it always ran.  item_logq is caller-owned DEVICE memory, [m_items], alive while the context trains.
+ * Returns 3 (nothing changed) for a null context or an unknown score kind.                                                    */
+#define LGCN_SCORE_DOT 0
+#define LGCN_SCORE_COSINE 1
+int lgcn_ctx_set_inbatch_scores(lgcn_ctx *ctx, int score, const float *item_logq);
+/* The score kind in force (-1: null context); the logq vector goes to item_logq (may be NULL).                                */
+int lgcn_ctx_get_inbatch_scores(const lgcn_ctx *ctx, const float **item_logq);
+
 /* The fold of the gradient-row conversion into the batch-row launch.  lgcn_train_epoch holds all triplets of
  * the call before its first step, so it computes once (per segment of 1024 steps) how many slots of each batch name each
  * destination row; the batch-row kernel then writes the fp32 copy of a gradient row itself -- directly where one slot names
