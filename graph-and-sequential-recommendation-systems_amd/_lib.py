@@ -114,6 +114,11 @@ SIGNATURES = {
     # its score options (--score, --inbatch_logq)
     "lgcn_ctx_set_inbatch_scores": (C.c_int, [_vp, C.c_int, _vp]),
     "lgcn_ctx_get_inbatch_scores": (C.c_int, [_vp, C.POINTER(_vp)]),
+    # mixed negatives for the in-batch step (--inbatch_mix)
+    "lgcn_ctx_set_inbatch_mix": (C.c_int, [_vp, C.c_int32]),
+    "lgcn_ctx_get_inbatch_mix": (C.c_int32, [_vp]),
+    "lgcn_train_step_inbatch_mix": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp, _vp]),
+    "lgcn_train_epoch_inbatch_mix": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int64, C.c_int32, _vp, _vp]),
     "lgcn_dp_block_floats": (C.c_int64, [_vp, C.c_int32, C.c_int32]),
     "lgcn_train_step_dp_part1": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
     "lgcn_train_step_dp_dense_part1": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),

@@ -2628,6 +2628,9 @@ struct lgcn_ctx {
     void *ib_ws; int32_t ib_cap;
     // its score options (lgcn_ctx_set_inbatch_scores): independent of loss_kind, (LGCN_SCORE_DOT, NULL) by default
     int32_t ib_score; const float *ib_logq;
+    // mixed negatives (lgcn_ctx_set_inbatch_mix): ib_mix = R_max (0: off).  While it is on, ib_ws is large enough for
+    // both carvings: the plain step's (the one above, unchanged) and the mixed step's with (1 + R_max) ib_cap item rows
+    int32_t ib_mix;
 };
 // a multi-step call: nobody but this library touches E0 between its steps
 struct LoopScope {
@@ -2668,7 +2671,7 @@ extern "C" int lgcn_ctx_create(const lgcn_train_config *cfg, lgcn_ctx **out) {
     x->fold_g32 = true; x->mult = nullptr; x->mult_cap = 0; x->fold_mult = nullptr; x->arrive = nullptr; x->folded_steps = 0;
     x->mn_negs = nullptr; x->mn_stride = 0; x->mn_R = 0;
     x->loss_kind = LGCN_LOSS_BPR; x->loss_temp = 1.f; x->mn_on = false; x->ib_ws = nullptr; x->ib_cap = 0;
-    x->ib_score = LGCN_SCORE_DOT; x->ib_logq = nullptr;
+    x->ib_score = LGCN_SCORE_DOT; x->ib_logq = nullptr; x->ib_mix = 0;
     x->bm_words = (x->N + 31) / 32; x->flip = 0;
     const size_t stride = table_bytes(x->N, c.d, c.act_dtype);
     for (int k = 0; k <= LGCN_MAX_LAYERS; k++) x->act[k] = nullptr;
@@ -2866,6 +2869,42 @@ extern "C" int lgcn_ctx_get_inbatch_scores(const lgcn_ctx *ctx, const float **it
     if (item_logq) *item_logq = ctx->ib_logq;
     return ctx->ib_score;
 }
+// floats of the mixed carving for `cap` rows, Rm negatives per sample: U | P | sbb | uid | pid | mrg | part | xinvu | xinvp | xlq
+// with icap = (1 + Rm) cap item rows; never smaller than the plain carving, which lives in the same allocation
+static size_t inbatch_mix_ws_words(int32_t cap, int d, int32_t Rm) {
+    const size_t icap = (size_t)(1 + Rm) * (size_t)cap;
+    const size_t w = (size_t)cap * d + icap * d + 2 * (size_t)cap + icap + 2 * (size_t)cap +
+                     2 * (size_t)cap * (size_t)lgcn_inbatch_mix_parts(cap, Rm) + (size_t)cap + 2 * icap;
+    const size_t plain = inbatch_ws_words(cap, d);
+    return w > plain ? w : plain;
+}
+extern "C" int lgcn_ctx_set_inbatch_mix(lgcn_ctx *ctx, int32_t R_max) {
+    if (!ctx) { lgcn_set_error("lgcn_ctx_set_inbatch_mix: null context"); return 3; }
+    if (R_max == 0) { ctx->ib_mix = 0; return 0; }      // off: the workspace stays (the plain step carves the same allocation)
+    if (R_max < 1 || R_max > LGCN_MAX_NEG_RATIO) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "lgcn_ctx_set_inbatch_mix: R_max = %d is out of range (0 = off, or 1..%d)", (int)R_max, LGCN_MAX_NEG_RATIO);
+        lgcn_set_error(buf); return 3;
+    }
+    if (ctx->loss_kind != LGCN_LOSS_INBATCH || !ctx->ib_ws) {
+        lgcn_set_error("lgcn_ctx_set_inbatch_mix: mixed negatives need the in-batch softmax loss (inbatch) set on the context first (lgcn_ctx_set_loss with LGCN_LOSS_INBATCH)");
+        return 3;
+    }
+    if (R_max > ctx->ib_mix) {      // grow only: the new block first, so a failure changes nothing
+        HIP_OK(hipDeviceSynchronize());     // steps in flight still read the old block
+        void *ws = nullptr;
+        if (hipMalloc(&ws, sizeof(float) * inbatch_mix_ws_words(ctx->ib_cap, ctx->c.d, R_max)) != hipSuccess) {
+            (void)hipGetLastError();
+            lgcn_set_error("lgcn_ctx_set_inbatch_mix: cannot allocate the workspace of the mixed in-batch step: (2 + R_max) * max_batch * d * 4 bytes and a few vectors");
+            return 4;
+        }
+        (void)hipFree(ctx->ib_ws);
+        ctx->ib_ws = ws;
+    }
+    ctx->ib_mix = R_max;
+    return 0;
+}
+extern "C" int32_t lgcn_ctx_get_inbatch_mix(const lgcn_ctx *ctx) { return ctx ? ctx->ib_mix : -1; }
 extern "C" int32_t lgcn_ctx_get_loss(const lgcn_ctx *ctx, float *temperature_out) {
     if (!ctx) return -1;
     if (temperature_out) *temperature_out = ctx->loss_temp;
@@ -3460,6 +3499,95 @@ extern "C" int lgcn_train_epoch_inbatch(lgcn_ctx *x, const int32_t *users, const
     for (int64_t t = 0; t < T; t += B, i++) {
         const int32_t b = (int32_t)((T - t) < B ? (T - t) : B);
         if (int rc = train_step_inbatch(x, users + t, pos + t, b, loss_out + 3 * i, (hipStream_t)stream)) return rc;
+    }
+    return 0;
+}
+
+// Mixed negatives for the in-batch softmax: the same four launches with the pool's (1 + R) Bp item rows, then
+// run_backward over the (2 + R) B slots with mn_R = R.  Everything is checked before anything is launched or counted.
+static int check_inbatch_mix(const lgcn_ctx *x, const void *u, const void *p, const void *n, const void *loss_out, int32_t R, int32_t B,
+                             int64_t neg_stride, const char *who) {
+    char buf[256];
+    if (!x || !u || !p || !n || !loss_out) { snprintf(buf, sizeof buf, "%s: null argument", who); lgcn_set_error(buf); return 3; }
+    if (x->loss_kind != LGCN_LOSS_INBATCH || !x->ib_ws) {
+        snprintf(buf, sizeof buf, "%s: the in-batch softmax loss (inbatch) is not set on this context (lgcn_ctx_set_loss with LGCN_LOSS_INBATCH)", who);
+        lgcn_set_error(buf); return 3;
+    }
+    if (x->ib_mix < 1) { snprintf(buf, sizeof buf, "%s: mixed negatives are not set on this context (lgcn_ctx_set_inbatch_mix)", who); lgcn_set_error(buf); return 3; }
+    if (R < 1 || R > x->ib_mix) {
+        snprintf(buf, sizeof buf, "%s: the negative ratio R = %d is out of range (1..%d, the R_max of lgcn_ctx_set_inbatch_mix)", who, (int)R, (int)x->ib_mix);
+        lgcn_set_error(buf); return 3;
+    }
+    if (B <= 0 || B > x->c.max_batch) { snprintf(buf, sizeof buf, "%s: batch size out of range (0 < B <= max_batch)", who); lgcn_set_error(buf); return 3; }
+    if (neg_stride < B) { snprintf(buf, sizeof buf, "%s: neg_stride must be at least B (negative ratio columns would overlap)", who); lgcn_set_error(buf); return 3; }
+    return 0;
+}
+
+static int run_inbatch_mix(lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B, hipStream_t st) {
+    const lgcn_train_config &c = x->c;
+    InBatchArgs ia{};
+    MultiNegArgs &a = ia.m;
+    a.X0 = c.E0; a.K = c.K;
+    for (int k = 1; k <= x->fwd_layers; k++) a.Xl[k] = x->act[k];
+    a.n_users = c.n_users; a.N = x->N;
+    a.users = users; a.pos = pos; a.negs = x->mn_negs; a.neg_stride = x->mn_stride; a.R = x->mn_R; a.B = B;
+    const float BR = (float)((int64_t)B * x->mn_R);
+    a.inv_BR = 1.0f / BR; a.inv_R = 1.0f / (float)x->mn_R;
+    a.lam = c.decay / (float)B; a.lam_n = c.decay / BR;
+    a.G64 = (long long *)c.G64; a.bitmap = c.bitmap + x->flip * x->bm_words;
+    a.stale_bitmap = c.bitmap + (x->flip ^ 1) * x->bm_words; a.bitmap_words = x->bm_words;
+    a.terms = c.terms; a.terms_stride = B; a.err = c.err;
+    a.reg_ego = c.reg_ego; a.cnt = x->cnt;
+    for (int k = 0; k < x->lw_n; k++) a.w[k] = x->lw[k];
+    a.loss = LGCN_LOSS_INBATCH; a.tau = x->loss_temp; a.inv_tauB = (float)(1.0 / ((double)x->loss_temp * (double)B));
+    const size_t cap = (size_t)x->ib_cap, d = (size_t)c.d, icap = (size_t)(1 + x->ib_mix) * cap;
+    float *w = (float *)x->ib_ws;
+    ia.cap = x->ib_cap; ia.mix = 1; ia.icap = (int32_t)icap;
+    ia.U = w; w += cap * d;
+    ia.P = w; w += icap * d;
+    ia.sbb = w; w += cap;
+    ia.uid = (int32_t *)w; w += cap;
+    ia.pid = (int32_t *)w; w += icap;
+    ia.mrg = w; w += 2 * cap;
+    ia.part = w; w += 2 * cap * (size_t)lgcn_inbatch_mix_parts(x->ib_cap, x->ib_mix);
+    ia.xinvu = w; w += cap;
+    ia.xinvp = w; w += icap;
+    ia.xlq = w;
+    ia.score = x->ib_score; ia.item_logq = x->ib_logq;
+    return lgcn_inbatch_launch(ia, c.d, c.act_dtype, x->lw_n != 0, st);
+}
+
+static int train_step_inbatch_mix(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int64_t neg_stride, int32_t R,
+                                  int32_t B, float *loss_out, hipStream_t st) {
+    struct MixScope {           // the backward's slot kernels and the reg_ego epilogue read these; cleared on every way out
+        lgcn_ctx *x;
+        MixScope(lgcn_ctx *x_, const int32_t *n, int64_t s, int32_t r) : x(x_) { x->mn_negs = n; x->mn_stride = s; x->mn_R = r; x->mn_on = true; }
+        ~MixScope() { x->mn_negs = nullptr; x->mn_stride = 0; x->mn_R = 0; x->mn_on = false; }
+    } scope(x, negs, neg_stride, R);
+    int rc;
+    x->dr = make_drop(x->drop_keep, x->drop_seed, x->step, 0);        // ONE mask per step, from the counter before the step
+    if ((rc = run_forward(x, st))) return rc;
+    if ((rc = run_inbatch_mix(x, users, pos, B, st))) return rc;
+    if ((rc = run_backward(x, users, pos, negs, B, nullptr, B, 1, loss_out, st))) return rc;
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int lgcn_train_step_inbatch_mix(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int64_t neg_stride,
+                                           int32_t R, int32_t B, float *loss_out, void *stream) {
+    if (int rc = check_inbatch_mix(x, users, pos, negs, loss_out, R, B, neg_stride, "lgcn_train_step_inbatch_mix")) return rc;
+    return train_step_inbatch_mix(x, users, pos, negs, neg_stride, R, B, loss_out, (hipStream_t)stream);
+}
+
+extern "C" int lgcn_train_epoch_inbatch_mix(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int32_t R,
+                                            int64_t T, int32_t B, float *loss_out, void *stream) {
+    if (T <= 0) return 0;
+    if (int rc = check_inbatch_mix(x, users, pos, negs, loss_out, R, B, T < B ? (int64_t)B : T, "lgcn_train_epoch_inbatch_mix")) return rc;
+    LoopScope scope(x);
+    int64_t i = 0;
+    for (int64_t t = 0; t < T; t += B, i++) {
+        const int32_t b = (int32_t)((T - t) < B ? (T - t) : B);
+        if (int rc = train_step_inbatch_mix(x, users + t, pos + t, negs + t, T, R, b, loss_out + 3 * i, (hipStream_t)stream)) return rc;
     }
     return 0;
 }

@@ -51,6 +51,21 @@
 //   LQ   z_{b,c} = (s_{b,c} - s_{b,b}) / tau - (lq_{p_c} - lq_{p_b}): k_inbatch_rows gathers lq[p_b] into lqb (after the id check;
 //        0 for void rows and padding), the two tile passes load the lane's and the tile rows' lq where s_bb and the ids are
 //        loaded; fl(lq_c - lq_b) has the same bits in all three places.
+//
+// Mixed negative sampling (lgcn_train_step_inbatch_mix), a third compile-time axis MIX of the same four launches; the
+// MIX = false instantiations are the kernels above.  A sample carries R negatives n_{b,1..R}; the B R negatives of the sound samples
+// are a pool shared by the whole batch, extra columns of every sample's score row in the same log-sum-exp:
+//   z_{b,(c,r)} = (e^_{u_b}.e^_{n_{c,r}} - s_{b,b}) / tau - (lq_{n_{c,r}} - lq_{p_b}),  masked only where n_{c,r} = p_b
+//   g_{n_{c,r}} = sum_b W[b,(c,r)] e^_{u_b} + lam / R e_{n_{c,r}}  (through its own normalisation under cosine), no diagonal
+// The item side grows from Bp to (1 + R) Bp rows: pool row (r, c) is row Bp (1 + r) + c of P and of pid (id -1 and a zero row where
+// sample c is void or padding), its lq / inv in the launch's own vectors over the same rows.
+//   k_inbatch_rows  the negatives' ids sit in lanes 2 .. R + 1 of the group and are checked in the same ballot; the R rows are streamed
+//                   through slot_row one at a time (the register count does not grow with R), written to the pool region, regularised
+//                   (lam / R e to G64, 1 / R |e|^2 to the reg term) and flagged / counted as k_multineg counts them (R, R, 1).
+//   k_inbatch_norm  sweeps (1 + R) Bp / 32 item tiles; the mask rule follows the tile's kind, which is uniform: no divergence.
+//   k_inbatch_diag  merges the larger number of parts.
+//   k_inbatch_grad  role "users" owns Bp / 32 tiles and sweeps all item tiles, role "items" owns (1 + R) Bp / 32 tiles and sweeps the
+//                   user tiles: both extents differ, so the grid is flat (the users' workgroups first).
 #include "lgcn_device_common.h"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -59,6 +74,11 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 __device__ __forceinline__ float *ib_invu(const InBatchArgs &ia) { return ia.part + 2 * (int64_t)ia.cap * lgcn_inbatch_parts(ia.cap); }
 __device__ __forceinline__ float *ib_invp(const InBatchArgs &ia) { return ib_invu(ia) + ia.cap; }
 __device__ __forceinline__ float *ib_lqb(const InBatchArgs &ia) { return ib_invu(ia) + 2 * (int64_t)ia.cap; }
+
+// the same three vectors of a mixed launch: its own pointers, the item-side ones over the (1 + R) Bp item rows
+template <bool MIX> __device__ __forceinline__ float *ibx_invu(const InBatchArgs &ia) { if constexpr (MIX) return ia.xinvu; else return ib_invu(ia); }
+template <bool MIX> __device__ __forceinline__ float *ibx_invp(const InBatchArgs &ia) { if constexpr (MIX) return ia.xinvp; else return ib_invp(ia); }
+template <bool MIX> __device__ __forceinline__ float *ibx_lq(const InBatchArgs &ia) { if constexpr (MIX) return ia.xlq; else return ib_lqb(ia); }
 
 // tile row of accumulator register `reg` on lane half h (C/D layout of the 32x32 MFMAs)
 __device__ __forceinline__ int ib_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
@@ -114,7 +134,7 @@ __device__ __forceinline__ void ib_merge(float &m, float &r, float m2, float r2)
     else { r = r2 + (1.f + r) * expf(m - m2); m = m2; }
 }
 
-template <int D, typename TI, bool WTS, bool COS, bool LQ>
+template <int D, typename TI, bool WTS, bool COS, bool LQ, bool MIX>
 __global__ void __launch_bounds__(256) k_inbatch_rows(InBatchArgs ia) {
     const MultiNegArgs &a = ia.m;
     constexpr int LPT = D < 64 ? D : 64, CPT = D / LPT, SPB = 256 / LPT;     // lanes per sample, samples per workgroup
@@ -130,6 +150,9 @@ __global__ void __launch_bounds__(256) k_inbatch_rows(InBatchArgs ia) {
     if (b < a.B) {
         if (l == 0) { id = a.users[b]; idbad = id < 0 || id >= a.n_users; }
         else if (l == 1) { id = a.pos[b]; idbad = id < 0 || (int64_t)id + a.n_users >= a.N; }
+        if constexpr (MIX) {                    // lanes 2 .. R + 1 hold the sample's negatives (R <= 16: inside the smallest group)
+            if (l >= 2 && l < 2 + a.R) { id = a.negs[(int64_t)(l - 2) * a.neg_stride + b]; idbad = id < 0 || (int64_t)id + a.n_users >= a.N; }
+        }
     }
     constexpr unsigned long long GROUP = LPT == 64 ? ~0ull : ((1ull << (LPT & 63)) - 1ull);
     const int gshift = (threadIdx.x & 63) / LPT * LPT;                          // this group's first lane in the wave
@@ -139,9 +162,21 @@ __global__ void __launch_bounds__(256) k_inbatch_rows(InBatchArgs ia) {
         for (int j = 0; j < CPT; j++) { ia.U[(int64_t)b * D + j * LPT + l] = 0.f; ia.P[(int64_t)b * D + j * LPT + l] = 0.f; }
         if (l == 0) {
             ia.uid[b] = -1; ia.pid[b] = -1; ia.sbb[b] = 0.f; ia.mrg[2 * b] = 0.f; ia.mrg[2 * b + 1] = 1.f;
-            if constexpr (COS) { ib_invu(ia)[b] = 0.f; ib_invp(ia)[b] = 0.f; }
-            if constexpr (LQ) ib_lqb(ia)[b] = 0.f;
+            if constexpr (COS) { ibx_invu<MIX>(ia)[b] = 0.f; ibx_invp<MIX>(ia)[b] = 0.f; }
+            if constexpr (LQ) ibx_lq<MIX>(ia)[b] = 0.f;
             if (b < a.B) { atomicExch(a.err, 1); a.terms[b] = 0.f; a.terms[a.terms_stride + b] = 0.f; }
+        }
+        if constexpr (MIX) {                    // no pool column either: R zero rows with id -1
+            for (int r = 0; r < a.R; r++) {
+                const int64_t x = (int64_t)Bp * (1 + r) + b;
+#pragma unroll
+                for (int j = 0; j < CPT; j++) ia.P[x * D + j * LPT + l] = 0.f;
+                if (l == 0) {
+                    ia.pid[x] = -1;
+                    if constexpr (COS) ia.xinvp[x] = 0.f;
+                    if constexpr (LQ) ia.xlq[x] = 0.f;
+                }
+            }
         }
         return;
     }
@@ -158,7 +193,40 @@ __global__ void __launch_bounds__(256) k_inbatch_rows(InBatchArgs ia) {
 #pragma unroll
     for (int j = 0; j < CPT; j++) { const float v = ego ? t0[j] : p[j]; ps += u[j] * p[j]; rp2 += v * v; }
     ps = group_sum<LPT>(ps);
-    const float rr = group_sum<LPT>(ru2 + rp2);
+    float rr = group_sum<LPT>(ru2 + rp2);
+    if constexpr (MIX) {
+        // the sample's R negatives become pool rows Bp (1 + r) + b of P (normalised under cosine), streamed one at a time
+        const float lam_n = ego ? 0.f : a.lam_n;
+        float srn = 0.f;
+#pragma unroll 1
+        for (int r = 0; r < a.R; r++) {
+            const int32_t in = __shfl(id, 2 + r, LPT);
+            const int64_t rn = (int64_t)in + a.n_users, x = (int64_t)Bp * (1 + r) + b;
+            float n[CPT], n0[CPT];
+            slot_row<D, TI, WTS>(a, rn, l, n, n0);
+            float inv_n = 1.f;
+            if constexpr (COS) {
+                float nn = 0.f;
+#pragma unroll
+                for (int j = 0; j < CPT; j++) nn += n[j] * n[j];
+                nn = group_sum<LPT>(nn);
+                inv_n = nn > 0.f ? 1.f / sqrtf(nn) : 0.f;
+            }
+#pragma unroll
+            for (int j = 0; j < CPT; j++) {
+                const float v = ego ? n0[j] : n[j];
+                srn += v * v;
+                if constexpr (COS) ia.P[x * D + j * LPT + l] = n[j] * inv_n; else ia.P[x * D + j * LPT + l] = n[j];
+                if (lam_n != 0.f) fixed_add(a.G64 + rn * D + j * LPT + l, lam_n * n[j]);
+            }
+            if (l == 0) {
+                ia.pid[x] = in;
+                if constexpr (COS) ia.xinvp[x] = inv_n;
+                if constexpr (LQ) ia.xlq[x] = ia.item_logq[in];         // (in passed the id check above)
+            }
+        }
+        rr = group_sum<LPT>(ru2 + rp2 + srn * a.inv_R);
+    }
     if constexpr (COS) {
         // |e| = sqrtf of the fp32 sum of squares, inv = 1 / |e| by an IEEE division (0 for a row of norm 0): two roundings.
         // U, P and s_bb are those of the rows over their norms; the reg term and lam e stay on the rows themselves
@@ -180,7 +248,7 @@ __global__ void __launch_bounds__(256) k_inbatch_rows(InBatchArgs ia) {
             }
         }
         ps = group_sum<LPT>(ps);
-        if (l == 0) { ib_invu(ia)[b] = inv_u; ib_invp(ia)[b] = inv_p; }
+        if (l == 0) { ibx_invu<MIX>(ia)[b] = inv_u; ibx_invp<MIX>(ia)[b] = inv_p; }
     } else {
 #pragma unroll
         for (int j = 0; j < CPT; j++) {
@@ -193,24 +261,32 @@ __global__ void __launch_bounds__(256) k_inbatch_rows(InBatchArgs ia) {
         }
     }
     if (l == 0) { ia.uid[b] = iu; ia.pid[b] = ip; ia.sbb[b] = ps; a.terms[a.terms_stride + b] = rr; }
-    if constexpr (LQ) { if (l == 0) ib_lqb(ia)[b] = ia.item_logq[ip]; }          // (ip passed the id check above)
-    if (l < 2) {                                // the 2 rows of the sample: one lane each
+    if constexpr (LQ) { if (l == 0) ibx_lq<MIX>(ia)[b] = ia.item_logq[ip]; }          // (ip passed the id check above)
+    if constexpr (MIX) {
+        if (l < 2 + a.R) {                      // the 2 + R rows of the sample: one lane each, counted as k_multineg counts them
+            const int64_t myrow = l == 0 ? ru : (int64_t)id + a.n_users;
+            atomicOr(a.bitmap + (myrow >> 5), 1u << (myrow & 31));
+            if (a.cnt) atomicAdd(a.cnt + myrow, l < 2 ? a.R : 1);
+        }
+    } else if (l < 2) {                         // the 2 rows of the sample: one lane each
         const int64_t myrow = l == 0 ? ru : rp;
         atomicOr(a.bitmap + (myrow >> 5), 1u << (myrow & 31));
         if (a.cnt) atomicAdd(a.cnt + myrow, 1);
     }
 }
 
-template <int D, bool LQ>
+template <int D, bool LQ, bool MIX>
 __global__ void __launch_bounds__(64) k_inbatch_norm(InBatchArgs ia) {
     const int l = threadIdx.x, j = l & 31, h = l >> 5;
-    const int Bp = lgcn_inbatch_rows(ia.m.B), nT = Bp / 32;
+    const int Bp = lgcn_inbatch_rows(ia.m.B);
+    int nT = Bp / 32;                           // item tiles of the sweep
+    if constexpr (MIX) nT = (1 + ia.m.R) * nT;  // ... the pool's behind the batch's own
     const int b = blockIdx.x * 32 + j;          // this lane's user (a column of the tile)
     const int t0 = blockIdx.y * LGCN_INBATCH_PART_TILES, t1 = t0 + LGCN_INBATCH_PART_TILES < nT ? t0 + LGCN_INBATCH_PART_TILES : nT;
     const int32_t ub = ia.uid[b], pb = ia.pid[b];
     const float sbb = ia.sbb[b], tau = ia.m.tau;
     float lqb = 0.f;                            // log Q of the lane's own positive
-    if constexpr (LQ) lqb = ib_lqb(ia)[b];
+    if constexpr (LQ) lqb = ibx_lq<MIX>(ia)[b];
     const float *brow = ia.U + (int64_t)b * D + h * (D / 2);
     float m = -INFINITY, r = 0.f;
     constexpr int RD = D <= IB_REG_D ? D : 8;   // (the register form's types at a size that costs nothing where it is not used)
@@ -220,12 +296,18 @@ __global__ void __launch_bounds__(64) k_inbatch_norm(InBatchArgs ia) {
     for (int t = t0; t < t1; t++) {
         // this tile's ids and the next tile's rows are in flight while this tile is multiplied
         int32_t ucs[16], pcs[16];
+        bool pool = false;                      // the tile's kind (uniform): a pool tile has no users and its own mask rule
+        if constexpr (MIX) pool = t >= Bp / 32;
 #pragma unroll
-        for (int reg = 0; reg < 16; reg++) { const int c = t * 32 + ib_row(reg, h); ucs[reg] = ia.uid[c]; pcs[reg] = ia.pid[c]; }
+        for (int reg = 0; reg < 16; reg++) {
+            const int c = t * 32 + ib_row(reg, h);
+            if constexpr (MIX) ucs[reg] = pool ? 0 : ia.uid[c]; else ucs[reg] = ia.uid[c];
+            pcs[reg] = ia.pid[c];
+        }
         float lqs[LQ ? 16 : 1];
         if constexpr (LQ) {
 #pragma unroll
-            for (int reg = 0; reg < 16; reg++) lqs[reg] = ib_lqb(ia)[t * 32 + ib_row(reg, h)];
+            for (int reg = 0; reg < 16; reg++) lqs[reg] = ibx_lq<MIX>(ia)[t * 32 + ib_row(reg, h)];
         }
         f32x16 acc;
         if constexpr (D <= IB_REG_D) {
@@ -241,7 +323,8 @@ __global__ void __launch_bounds__(64) k_inbatch_norm(InBatchArgs ia) {
         for (int reg = 0; reg < 16; reg++) {
             const int c = t * 32 + ib_row(reg, h);
             const int32_t uc = ucs[reg], pc = pcs[reg];
-            const bool ok = ub >= 0 && uc >= 0 && c != b && pc != pb && uc != ub;
+            bool ok = ub >= 0 && uc >= 0 && c != b && pc != pb && uc != ub;
+            if constexpr (MIX) { if (pool) ok = ub >= 0 && pc >= 0 && pc != pb; }
             if constexpr (LQ) z[reg] = ok ? (acc[reg] - sbb) / tau - (lqs[reg] - lqb) : -INFINITY;
             else z[reg] = ok ? (acc[reg] - sbb) / tau : -INFINITY;
             tmax = fmaxf(tmax, z[reg]);
@@ -263,7 +346,7 @@ __global__ void __launch_bounds__(64) k_inbatch_norm(InBatchArgs ia) {
     }
 }
 
-template <int D, bool COS>
+template <int D, bool COS, bool MIX>
 __global__ void __launch_bounds__(256) k_inbatch_diag(InBatchArgs ia) {
     const MultiNegArgs &a = ia.m;
     constexpr int LPT = D < 64 ? D : 64, CPT = D / LPT, SPB = 256 / LPT;
@@ -271,7 +354,9 @@ __global__ void __launch_bounds__(256) k_inbatch_diag(InBatchArgs ia) {
     if (b >= a.B) return;
     const int32_t iu = ia.uid[b], ip = ia.pid[b];
     if (iu < 0) return;                         // void: k_inbatch_rows wrote its zero terms
-    const int Bp = lgcn_inbatch_rows(a.B), NP = lgcn_inbatch_parts(a.B);
+    const int Bp = lgcn_inbatch_rows(a.B);
+    int NP = lgcn_inbatch_parts(a.B);
+    if constexpr (MIX) NP = lgcn_inbatch_mix_parts(a.B, a.R);
     float m = -INFINITY, r = 0.f;               // every lane of the group merges the same parts in the same order
     for (int p = 0; p < NP; p++) { const float *q = ia.part + ((int64_t)p * Bp + b) * 2; ib_merge(m, r, q[0], q[1]); }
     // with the positive's own exp(0): 1 + sum_c exp(z_c) = exp(M) (1 + Zm1), M = max(0, m)
@@ -287,8 +372,8 @@ __global__ void __launch_bounds__(256) k_inbatch_diag(InBatchArgs ia) {
         const int64_t o = (int64_t)b * D + j * LPT + l;
         if constexpr (COS) {                    // the diagonal through the normalisation: inv W[b,b] (other^ - s_bb own^)
             const float uh = ia.U[o], ph = ia.P[o], sbb = ia.sbb[b];
-            fixed_add(a.G64 + ru * D + j * LPT + l, ib_invu(ia)[b] * (wd * (ph - sbb * uh)));
-            fixed_add(a.G64 + rp * D + j * LPT + l, ib_invp(ia)[b] * (wd * (uh - sbb * ph)));
+            fixed_add(a.G64 + ru * D + j * LPT + l, ibx_invu<MIX>(ia)[b] * (wd * (ph - sbb * uh)));
+            fixed_add(a.G64 + rp * D + j * LPT + l, ibx_invp<MIX>(ia)[b] * (wd * (uh - sbb * ph)));
         } else {
             fixed_add(a.G64 + ru * D + j * LPT + l, wd * ia.P[o]);
             fixed_add(a.G64 + rp * D + j * LPT + l, wd * ia.U[o]);
@@ -296,20 +381,36 @@ __global__ void __launch_bounds__(256) k_inbatch_diag(InBatchArgs ia) {
     }
 }
 
-template <int D, bool COS, bool LQ>
+template <int D, bool COS, bool LQ, bool MIX>
 __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
     constexpr int CB = D < 128 ? D / 32 : 4;    // 32-column blocks of the output this workgroup accumulates
     const int l = threadIdx.x, j = l & 31, h = l >> 5;
-    const int Bp = lgcn_inbatch_rows(ia.m.B), nT = Bp / 32;
-    const int role = blockIdx.z & 1, col0 = (blockIdx.z >> 1) * 128;        // role 0: the owned rows are users, 1: items
+    const int Bp = lgcn_inbatch_rows(ia.m.B);
+    int nT = Bp / 32;                           // tiles of the swept side
+    int role = blockIdx.z & 1, col0 = (blockIdx.z >> 1) * 128;              // role 0: the owned rows are users, 1: items
+    int bx = blockIdx.x, by = blockIdx.y;       // the owned tile, the part of the sweep
+    bool pool_o = false;                        // mixed: the owned tile is a pool tile (role 1 only; uniform)
+    if constexpr (MIX) {
+        // the two roles differ in both extents -- users: Bp / 32 owned tiles x the parts of the (1 + R) Bp / 32 item tiles; items:
+        // (1 + R) Bp / 32 owned tiles x the parts of the Bp / 32 user tiles -- so the grid is flat: the users' workgroups first
+        const int nTI = (1 + ia.m.R) * nT, nb0 = nT * lgcn_inbatch_mix_parts(ia.m.B, ia.m.R);
+        const int i = (int)blockIdx.x;
+        col0 = blockIdx.z * 128;
+        if (i < nb0) { role = 0; bx = i % nT; by = i / nT; nT = nTI; }
+        else { role = 1; bx = (i - nb0) % nTI; by = (i - nb0) / nTI; pool_o = bx >= nT; }
+    }
     const float *own = role == 0 ? ia.U : ia.P, *oth = role == 0 ? ia.P : ia.U;
-    const int o = blockIdx.x * 32 + j;          // this lane's owned index (a column of the score tile)
-    const int t0 = blockIdx.y * LGCN_INBATCH_PART_TILES, t1 = t0 + LGCN_INBATCH_PART_TILES < nT ? t0 + LGCN_INBATCH_PART_TILES : nT;
-    const int32_t uo = ia.uid[o], po = ia.pid[o];
-    const float sbb_o = ia.sbb[o], M_o = ia.mrg[2 * o], den_o = ia.mrg[2 * o + 1];
+    const int o = bx * 32 + j;                  // this lane's owned index (a column of the score tile)
+    const int t0 = by * LGCN_INBATCH_PART_TILES, t1 = t0 + LGCN_INBATCH_PART_TILES < nT ? t0 + LGCN_INBATCH_PART_TILES : nT;
+    int32_t uo, po = ia.pid[o];
+    float sbb_o, M_o, den_o;
+    if constexpr (MIX) {                        // an owned item index may lie in the pool: no user, no s_bb, no merged pair there
+        uo = pool_o ? 0 : ia.uid[o];
+        sbb_o = role == 0 ? ia.sbb[o] : 0.f; M_o = role == 0 ? ia.mrg[2 * o] : 0.f; den_o = role == 0 ? ia.mrg[2 * o + 1] : 1.f;
+    } else { uo = ia.uid[o]; sbb_o = ia.sbb[o]; M_o = ia.mrg[2 * o]; den_o = ia.mrg[2 * o + 1]; }
     const float tau = ia.m.tau, inv_tauB = ia.m.inv_tauB;
     float lq_o = 0.f;                           // log Q of the owned sample's positive
-    if constexpr (LQ) lq_o = ib_lqb(ia)[o];
+    if constexpr (LQ) lq_o = ibx_lq<MIX>(ia)[o];
     float tproj = 0.f;                          // cosine: sum_x W[x][o] s[x][o] over this lane's 16 rows of every tile
     const float *brow = own + (int64_t)o * D + h * (D / 2);
     f32x16 g[CB];
@@ -327,15 +428,18 @@ __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
         // in the register form, the next tile's rows
         int32_t uxs[16], pxs[16];
         float sbs[16], Ms[16], dens[16], ob[16][CB], lqd[LQ ? 16 : 1];
+        bool pool = false;                      // mixed: the pairs of this tile are (user, pool column) -- uniform
+        if constexpr (MIX) pool = pool_o || (role == 0 && t >= Bp / 32);
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {
             const int x = t * 32 + ib_row(reg, h);          // the other side's index (a row of the tile)
-            uxs[reg] = ia.uid[x]; pxs[reg] = ia.pid[x];
+            if constexpr (MIX) uxs[reg] = (role == 0 && pool) ? 0 : ia.uid[x]; else uxs[reg] = ia.uid[x];
+            pxs[reg] = ia.pid[x];
             // the USER of the pair owns s_bb and the merged (M, 1 + Zm1): the lane's under role 0, the row's under role 1
             sbs[reg] = role == 0 ? sbb_o : ia.sbb[x];
             Ms[reg] = role == 0 ? M_o : ia.mrg[2 * x]; dens[reg] = role == 0 ? den_o : ia.mrg[2 * x + 1];
             // lq of the pair's ITEM less lq of the pair's user's own positive: the row's less the lane's under role 0
-            if constexpr (LQ) { const float lq_x = ib_lqb(ia)[x]; lqd[reg] = role == 0 ? lq_x - lq_o : lq_o - lq_x; }
+            if constexpr (LQ) { const float lq_x = ibx_lq<MIX>(ia)[x]; lqd[reg] = role == 0 ? lq_x - lq_o : lq_o - lq_x; }
             if constexpr (D <= IB_REG_D) {
 #pragma unroll
                 for (int cb = 0; cb < CB; cb++) ob[reg][cb] = oth[(int64_t)x * D + col0 + j + cb * 32];
@@ -353,7 +457,9 @@ __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {
             const int x = t * 32 + ib_row(reg, h);
-            const bool ok = uo >= 0 && uxs[reg] >= 0 && x != o && pxs[reg] != po && uxs[reg] != uo;
+            bool ok = uo >= 0 && uxs[reg] >= 0 && x != o && pxs[reg] != po && uxs[reg] != uo;
+            // a pool pair: a sound user, a pool column that exists, another item than the user's positive
+            if constexpr (MIX) { if (pool) ok = (role == 0 ? uo >= 0 && pxs[reg] >= 0 : uxs[reg] >= 0 && po >= 0) && pxs[reg] != po; }
             float z;
             if constexpr (LQ) z = (w[reg] - sbs[reg]) / tau - lqd[reg]; else z = (w[reg] - sbs[reg]) / tau;
             if constexpr (COS) {
@@ -380,15 +486,18 @@ __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
     // rows of g: owned index blockIdx.x * 32 + ib_row(reg, h); columns col0 + cb * 32 + j
 #pragma unroll
     for (int reg = 0; reg < 16; reg++) {
-        const int ob = blockIdx.x * 32 + ib_row(reg, h);
+        const int ob = bx * 32 + ib_row(reg, h);
         float t_row = 0.f;
         if constexpr (COS) t_row = __shfl(tproj, ib_row(reg, h));             // (every lane takes part: before the skip)
-        const int32_t us = ia.uid[ob];
+        int32_t us;
+        if constexpr (MIX) us = role == 0 ? ia.uid[ob] : ia.pid[ob]; else us = ia.uid[ob];        // (a pool row has only its item id)
         if (us < 0) continue;                   // void or padding: no row to add to (its W is zero)
-        const int64_t row = role == 0 ? (int64_t)us : (int64_t)ia.pid[ob] + ia.m.n_users;
+        int64_t row;
+        if constexpr (MIX) row = role == 0 ? (int64_t)us : (int64_t)us + ia.m.n_users;
+        else row = role == 0 ? (int64_t)us : (int64_t)ia.pid[ob] + ia.m.n_users;
         if constexpr (COS) {
             // the chain through the normalisation, per part (it is linear): inv_o (sum_x W own-side^ - t own^), DESIGN 4.20
-            const float inv_o = (role == 0 ? ib_invu(ia) : ib_invp(ia))[ob];
+            const float inv_o = (role == 0 ? ibx_invu<MIX>(ia) : ibx_invp<MIX>(ia))[ob];
 #pragma unroll
             for (int cb = 0; cb < CB; cb++) {
                 const float oh = own[(int64_t)ob * D + col0 + cb * 32 + j];
@@ -401,29 +510,37 @@ __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
     }
 }
 
-template <int D, bool COS, bool LQ>
+template <int D, bool COS, bool LQ, bool MIX>
 static void launch_d(const InBatchArgs &a, int act_dtype, bool wts, hipStream_t st) {
     constexpr int SPB = 256 / (D < 64 ? D : 64);
     const int Bp = lgcn_inbatch_rows(a.m.B), NP = lgcn_inbatch_parts(a.m.B);
     const dim3 rows_grid((unsigned)((Bp + SPB - 1) / SPB)), diag_grid((unsigned)((a.m.B + SPB - 1) / SPB));
     if (act_dtype == LGCN_F32) {
-        if (wts) hipLaunchKernelGGL((k_inbatch_rows<D, float, true, COS, LQ>), rows_grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_inbatch_rows<D, float, false, COS, LQ>), rows_grid, dim3(256), 0, st, a);
+        if (wts) hipLaunchKernelGGL((k_inbatch_rows<D, float, true, COS, LQ, MIX>), rows_grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_inbatch_rows<D, float, false, COS, LQ, MIX>), rows_grid, dim3(256), 0, st, a);
     } else {
-        if (wts) hipLaunchKernelGGL((k_inbatch_rows<D, bf16_t, true, COS, LQ>), rows_grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_inbatch_rows<D, bf16_t, false, COS, LQ>), rows_grid, dim3(256), 0, st, a);
+        if (wts) hipLaunchKernelGGL((k_inbatch_rows<D, bf16_t, true, COS, LQ, MIX>), rows_grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_inbatch_rows<D, bf16_t, false, COS, LQ, MIX>), rows_grid, dim3(256), 0, st, a);
     }
-    hipLaunchKernelGGL((k_inbatch_norm<D, LQ>), dim3((unsigned)(Bp / 32), (unsigned)NP), dim3(64), 0, st, a);
-    hipLaunchKernelGGL((k_inbatch_diag<D, COS>), diag_grid, dim3(256), 0, st, a);
-    hipLaunchKernelGGL((k_inbatch_grad<D, COS, LQ>), dim3((unsigned)(Bp / 32), (unsigned)NP, 2u * (D > 128 ? D / 128 : 1)), dim3(64), 0, st, a);
+    if constexpr (MIX) {
+        // the item sweep is (1 + R) times as long; the gradient's grid is flat (users' workgroups, then the items')
+        const int nT = Bp / 32, nTI = (1 + a.m.R) * nT, NPX = lgcn_inbatch_mix_parts(a.m.B, a.m.R);
+        hipLaunchKernelGGL((k_inbatch_norm<D, LQ, true>), dim3((unsigned)nT, (unsigned)NPX), dim3(64), 0, st, a);
+        hipLaunchKernelGGL((k_inbatch_diag<D, COS, true>), diag_grid, dim3(256), 0, st, a);
+        hipLaunchKernelGGL((k_inbatch_grad<D, COS, LQ, true>), dim3((unsigned)(nT * NPX + nTI * NP), 1u, (unsigned)(D > 128 ? D / 128 : 1)), dim3(64), 0, st, a);
+    } else {
+        hipLaunchKernelGGL((k_inbatch_norm<D, LQ, false>), dim3((unsigned)(Bp / 32), (unsigned)NP), dim3(64), 0, st, a);
+        hipLaunchKernelGGL((k_inbatch_diag<D, COS, false>), diag_grid, dim3(256), 0, st, a);
+        hipLaunchKernelGGL((k_inbatch_grad<D, COS, LQ, false>), dim3((unsigned)(Bp / 32), (unsigned)NP, 2u * (D > 128 ? D / 128 : 1)), dim3(64), 0, st, a);
+    }
 }
 
 // the two options are compile-time axes: (dot, no logq) are the instantiations a context that was never told launches
-template <int D>
+template <int D, bool MIX>
 static void launch_opts(const InBatchArgs &a, int act_dtype, bool wts, hipStream_t st) {
     const bool cosine = a.score == LGCN_SCORE_COSINE, lq = a.item_logq != nullptr;
-    if (cosine) { if (lq) launch_d<D, true, true>(a, act_dtype, wts, st); else launch_d<D, true, false>(a, act_dtype, wts, st); }
-    else { if (lq) launch_d<D, false, true>(a, act_dtype, wts, st); else launch_d<D, false, false>(a, act_dtype, wts, st); }
+    if (cosine) { if (lq) launch_d<D, true, true, MIX>(a, act_dtype, wts, st); else launch_d<D, true, false, MIX>(a, act_dtype, wts, st); }
+    else { if (lq) launch_d<D, false, true, MIX>(a, act_dtype, wts, st); else launch_d<D, false, false, MIX>(a, act_dtype, wts, st); }
 }
 
 int lgcn_inbatch_launch(const InBatchArgs &a, int d, int act_dtype, bool wts, hipStream_t st) {
@@ -438,6 +555,16 @@ int lgcn_inbatch_launch(const InBatchArgs &a, int d, int act_dtype, bool wts, hi
         lgcn_set_error("in-batch softmax rows: bad launch arguments (score dot or cosine)");
         return 3;
     }
-    DISPATCH_D(d, launch_opts<D>(a, act_dtype, wts, st));
+    if (a.mix) {        // the mixed step: the pool's rows must fit the item side of the workspace
+        const int64_t rows = (1 + (int64_t)a.m.R) * lgcn_inbatch_rows(a.m.B);
+        if (a.m.R < 1 || a.m.R > LGCN_MAX_NEG_RATIO || !a.m.negs || a.m.neg_stride < a.m.B || rows > a.icap || !a.xinvu || !a.xinvp || !a.xlq) {
+            lgcn_set_error("in-batch softmax rows: bad launch arguments (mixed negatives: negative ratio 1..16 within the workspace's item rows, "
+                           "neg_stride >= B)");
+            return 3;
+        }
+        DISPATCH_D(d, (launch_opts<D, true>(a, act_dtype, wts, st)));
+        return 0;
+    }
+    DISPATCH_D(d, (launch_opts<D, false>(a, act_dtype, wts, st)));
     return 0;
 }

@@ -74,8 +74,18 @@ struct InBatchArgs {
     // item_logq[p_b] under logq; 0 for a void sample and for padding (and inv = 0 for a row of norm 0)
     int32_t score;                // LGCN_SCORE_DOT, or LGCN_SCORE_COSINE: U, P then hold the rows over their norms
     const float *item_logq;       // [m_items] log Q(item), or NULL: no correction
+    // mixed negatives (lgcn_train_step_inbatch_mix), behind everything the other launches read.  mix != 0: m.negs /
+    // neg_stride / R / inv_R / lam_n are set, the item side has (1 + R) Bp rows -- pool row (r, c) is row Bp (1 + r) + c of P and
+    // of pid (-1: sample c is void or padding), part holds lgcn_inbatch_mix_parts(B, R) parts -- and the three vectors of the
+    // score options are these, the item-side ones over the same (1 + R) Bp rows
+    int32_t mix, icap;            // icap: item rows of P / pid / xinvp / xlq in the workspace (>= (1 + R) Bp)
+    float *xinvu, *xinvp, *xlq;
 };
 static __host__ __device__ inline int32_t lgcn_inbatch_rows(int32_t B) { return (B + 31) & ~31; }                          // Bp: B padded to whole tiles
 static __host__ __device__ inline int32_t lgcn_inbatch_parts(int32_t B) { return (lgcn_inbatch_rows(B) / 32 + LGCN_INBATCH_PART_TILES - 1) / LGCN_INBATCH_PART_TILES; }
+// parts of the (1 + R) Bp-row item sweep of a mixed step
+static __host__ __device__ inline int32_t lgcn_inbatch_mix_parts(int32_t B, int32_t R) {
+    return ((1 + R) * (lgcn_inbatch_rows(B) / 32) + LGCN_INBATCH_PART_TILES - 1) / LGCN_INBATCH_PART_TILES;
+}
 int lgcn_inbatch_launch(const InBatchArgs &a, int d, int act_dtype, bool wts, hipStream_t st);
 #endif

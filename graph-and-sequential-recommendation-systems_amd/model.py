@@ -123,6 +123,33 @@ def item_logq(items_D):
     return np.log(deg).astype(np.float32)
 
 
+def resolve_inbatch_mix(config, loss_kind):
+    """--inbatch_mix 0 | 1 -> bool.  An option of --loss inbatch (DESIGN 4.21): LgcnError naming the flag under any other loss;
+    ValueError for a value that is neither."""
+    mix = str(config.get('inbatch_mix', 0)).strip().lower()
+    if mix not in ('0', '1', 'false', 'true'):
+        raise ValueError(f"--inbatch_mix must be 0 or 1, got {config.get('inbatch_mix')!r}")
+    mix = mix in ('1', 'true')
+    if mix and loss_kind != 'inbatch':
+        raise _lib.LgcnError(f"--inbatch_mix 1 is implemented for --loss inbatch only, not for --loss {loss_kind} "
+                             "(it adds the sampled negatives to the in-batch score matrix)")
+    return mix
+
+
+def item_logq_mix(items_D, B, R):
+    """The logQ vector of --inbatch_logq 1 under --inbatch_mix 1: the log of the expected number of times item i stands among a
+    sample's competitors -- (B - 1) in-batch positives drawn in proportion to the train degree and B R pool ids drawn uniformly --
+    lq_i = log((B - 1) deg_i / sum deg + B R / m_items), B = --bpr_batch, in float64, rounded once to fp32.  The ragged last
+    batch of an epoch uses the same vector."""
+    deg = np.asarray(items_D, np.float64).reshape(-1)
+    if not (np.isfinite(deg).all() and (deg > 0).all()):
+        raise ValueError("--inbatch_logq 1: the item degrees must be finite and > 0 (the loader sets empty items to 1)")
+    B, R = int(B), int(R)
+    if B < 1 or R < 1:
+        raise ValueError(f"--inbatch_mix 1: the batch size and the negative ratio must be >= 1, got {B}, {R}")
+    return np.log((B - 1) * deg / deg.sum() + float(B) * R / deg.size).astype(np.float32)
+
+
 def resolve_layer_weights(config, K, degrees=None):
     """(config, K) -> the fp32 [K+1] weights of out = sum_k w_k X_k, or None for the mean (the reference's combination).
     --layer_weights mean | exp | ppr | "[w_0, ..., w_K]"; the reference's own --use_ppr_weights [--ppr_weights_path FILE]
@@ -326,14 +353,19 @@ class LightGCN(nn.Module):
             if self.use_pop_gate or self.use_item_item:
                 raise _lib.LgcnError(f"--loss {self.loss_kind} is not implemented together with --use_pop_gate / --use_item_item "
                                      "(the optional branches train with the BPR loss only)")
-        if self.loss_kind == 'inbatch' and self.neg_ratio > 1:
+        # mixed negatives (--inbatch_mix 1; lgcn_train_step_inbatch_mix): the sampled negatives of the batch as shared
+        # extra columns of the in-batch score matrix; --neg_ratio 1..16 is then legal
+        self.inbatch_mix = resolve_inbatch_mix(config, self.loss_kind)
+        if self.loss_kind == 'inbatch' and self.neg_ratio > 1 and not self.inbatch_mix:
             raise _lib.LgcnError(f"--loss inbatch is not implemented together with --neg_ratio {self.neg_ratio}: the in-batch loss has no "
                                  "sampled negatives (the other samples' positives are the negatives); use --neg_ratio 1")
         self._loss_said = False
         # the two options of the in-batch step (--score dot | cosine, --inbatch_logq 0 | 1; lgcn_ctx_set_inbatch_scores)
         self.score_kind, self.inbatch_logq = resolve_inbatch_scores(config, self.loss_kind)
         self._item_logq = None      # fp32 [m_items] log(items_D), rounded once from float64 (None: --inbatch_logq 0)
-        if self.inbatch_logq:
+        if self.inbatch_logq and self.inbatch_mix:      # the log of the mixture's expected count
+            self._item_logq = torch.from_numpy(item_logq_mix(dataset.items_D, int(config.get('bpr_batch_size', 2048)), self.neg_ratio))
+        elif self.inbatch_logq:
             self._item_logq = torch.from_numpy(item_logq(dataset.items_D))
         self._gate_flat = None      # the eight MLP tensors of the gate in ONE buffer (what the fused step reads / updates)
         self._Graph = None
@@ -588,6 +620,12 @@ class LightGCN(nn.Module):
                 msg = lib.lgcn_last_error()
                 lib.lgcn_ctx_destroy(h)
                 raise _lib.LgcnError(f"lgcn_ctx_set_inbatch_scores failed (rc={rc}): {msg.decode() if msg else ''}")
+        if self.inbatch_mix:                     # (a context that is never told keeps the workspace and the launches it always had)
+            rc = lib.lgcn_ctx_set_inbatch_mix(h, int(self.neg_ratio))
+            if rc:
+                msg = lib.lgcn_last_error()
+                lib.lgcn_ctx_destroy(h)
+                raise _lib.LgcnError(f"lgcn_ctx_set_inbatch_mix failed (rc={rc}): {msg.decode() if msg else ''}")
         if str(self.config.get('fold_g32', 1)).strip().lower() in ('0', 'false', 'off'):      # config['fold_g32'] = 0: fused_epoch launches k_g32 every step again (A/B, tests)
             rc = lib.lgcn_ctx_set_fold_g32(h, 0)
             if rc:
@@ -791,6 +829,69 @@ class LightGCN(nn.Module):
             u, p = self.embedding_user.weight[ul], self.embedding_item.weight[pl]
         return sm, (0.5 * (u.norm(2).pow(2) + p.norm(2).pow(2))) / float(B)
 
+    def _inbatch_mix_loss(self, users, pos, neg):
+        """bpr_loss under --loss inbatch --inbatch_mix 1: the autograd statement of the loss of lgcn_train_step_inbatch_mix (DESIGN
+        4.21) -- logsumexp over the masked [B, 1 + B + B R] logits: the positive's 0, the in-batch columns of _inbatch_loss and the
+        pool columns (c, r), masked where n_{c,r} = p_b only.  neg: [B], [B, R] or [R, B]."""
+        B = int(users.shape[0])
+        neg = torch.as_tensor(neg)
+        neg = neg.reshape(B, 1) if neg.dim() == 1 else (neg if neg.shape[0] == B else neg.t())
+        if neg.dim() != 2 or neg.shape[0] != B:
+            raise ValueError(f"neg must be [B], [B, R] or [R, B] with B = {B}, got {tuple(neg.shape)}")
+        R = int(neg.shape[1])
+        all_users, all_items = self.computer()
+        ul, pl, nl = users.long(), pos.long(), neg.long().to(users.device).t().reshape(-1)      # pool column r B + c = n_{c,r}
+        u, p, n = all_users[ul], all_items[pl], all_items[nl]
+        cos = self.score_kind == 'cosine'
+        uh = F.normalize(u, dim=1, eps=1e-37) if cos else u
+        items = torch.cat([p, n], dim=0)
+        s = uh @ (F.normalize(items, dim=1, eps=1e-37) if cos else items).t()          # [B, B + B R]
+        z = (s - torch.diagonal(s[:, :B])[:, None]) / float(self.softmax_temp)
+        if self.inbatch_logq:
+            lq = self._item_logq.to(device=z.device, dtype=z.dtype)
+            z = z - (torch.cat([lq[pl], lq[nl]])[None, :] - lq[pl][:, None])
+        keep = torch.cat([(pl[None, :] != pl[:, None]) & (ul[None, :] != ul[:, None]), nl[None, :] != pl[:, None]], dim=1)
+        z = torch.where(keep, z, torch.full_like(z, float('-inf')))
+        sm = torch.logsumexp(torch.cat([torch.zeros_like(z[:, :1]), z], dim=1), dim=1).sum() / float(B)
+        if str(self.config.get('reg_rows', 'propagated')) == 'ego':
+            u, p, n = self.embedding_user.weight[ul], self.embedding_item.weight[pl], self.embedding_item.weight[nl]
+        return sm, (0.5 * (u.norm(2).pow(2) + p.norm(2).pow(2) + n.norm(2).pow(2) / float(R))) / float(B)
+
+    def _fused_inbatch_mix(self, users, pos, neg, batch_size, loss_out, lr, epoch):
+        """fused_step / fused_epoch under --inbatch_mix 1: lgcn_train_step_inbatch_mix / lgcn_train_epoch_inbatch_mix on (users,
+        pos, neg); neg 1-D (R = 1), [n, R] or [R, n]."""
+        dev = self._table.device
+        users, pos = self._ids(users, dev).reshape(-1), self._ids(pos, dev).reshape(-1)
+        T = int(users.numel())
+        neg = self._ids(neg, dev)
+        if neg.dim() == 1:
+            neg = neg.reshape(1, -1)
+        elif neg.shape[0] == T:
+            neg = neg.t()
+        if neg.dim() != 2 or neg.shape[1] != T:
+            raise ValueError(f"neg must be [{T}], [{T}, R] or [R, {T}], got {tuple(neg.shape)}")
+        negs = neg.contiguous()
+        R = int(negs.shape[0])
+        if not 1 <= R <= self.neg_ratio:
+            raise ValueError(f"--inbatch_mix 1: the batch carries {R} negatives per positive, --neg_ratio is {self.neg_ratio}")
+        st = self._state(max_batch=batch_size if epoch else max(T, int(self.config.get('bpr_batch_size', T))), need_ctx=True,
+                         dp_world=(self._dev or {}).get('dp_world', 1))
+        lib = _lib.load()
+        if lr is not None:
+            lib.lgcn_ctx_set_lr(st['ctx'], float(lr))
+        if epoch:
+            losses = torch.empty((T + batch_size - 1) // batch_size, 3, dtype=torch.float32, device=dev)
+            _lib.check(lib.lgcn_train_epoch_inbatch_mix(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(negs), R, T, int(batch_size),
+                                                        _lib.tp(losses), _lib.current_stream()), "lgcn_train_epoch_inbatch_mix")
+            self.invalidate_cache()
+            return losses
+        if loss_out is None:
+            loss_out = torch.empty(3, dtype=torch.float32, device=dev)
+        _lib.check(lib.lgcn_train_step_inbatch_mix(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(negs), T, R, T, _lib.tp(loss_out),
+                                                   _lib.current_stream()), "lgcn_train_step_inbatch_mix")
+        self.invalidate_cache()
+        return loss_out
+
     def _fused_inbatch(self, users, pos, batch_size, loss_out, lr, epoch):
         """fused_step / fused_epoch under --loss inbatch: lgcn_train_step_inbatch / lgcn_train_epoch_inbatch on (users, pos)."""
         dev = self._table.device
@@ -816,6 +917,8 @@ class LightGCN(nn.Module):
 
     def bpr_loss(self, users, pos, neg):
         """model.py:162-183 (unfused, autograd-capable): (bpr [- entropy term of the gate], reg_loss)."""
+        if self.loss_kind == 'inbatch' and self.inbatch_mix:      # the sampled negatives are the batch's shared pool
+            return self._inbatch_mix_loss(users, pos, neg)
         if self.loss_kind == 'inbatch':          # the sampled negatives are not used
             return self._inbatch_loss(users, pos)
         if torch.is_tensor(neg) and neg.dim() == 2:
@@ -893,6 +996,8 @@ class LightGCN(nn.Module):
             raise RuntimeError("this configuration of the popularity gate / item-item smoothing is outside the fused step "
                                "(--fused_variants 0, or gate hidden sizes > 64 / d > 128): use BPRLoss.stageOne (autograd path)")
         dev = self._table.device
+        if self.loss_kind == 'inbatch' and self.inbatch_mix:
+            return self._fused_inbatch_mix(users, pos, neg, None, loss_out, lr, False)
         if self.loss_kind == 'inbatch':        # --loss inbatch: (users, pos) only; neg is accepted and ignored
             return self._fused_inbatch(users, pos, None, loss_out, lr, False)
         if self.loss_kind == 'softmax' and self._neg_dim(neg) == 1:      # --loss softmax: every shape is a multi step, R = 1 included
@@ -934,6 +1039,8 @@ class LightGCN(nn.Module):
         if self.has_variants and not self.fused_variants:
             raise RuntimeError("this configuration of the optional branches is outside the fused step: loop BPRLoss.stageOne")
         dev = self._table.device
+        if self.loss_kind == 'inbatch' and self.inbatch_mix:
+            return self._fused_inbatch_mix(users, pos, neg, int(batch_size), None, lr, True)
         if self.loss_kind == 'inbatch':        # --loss inbatch: (users, pos) only; neg is accepted and ignored
             return self._fused_inbatch(users, pos, int(batch_size), None, lr, True)
         users, pos = self._ids(users, dev), self._ids(pos, dev)
@@ -1022,6 +1129,8 @@ class PureMF(nn.Module):
             raise _lib.LgcnError(f"--score {config.get('score')} {no} (an option of LightGCN's --loss inbatch)")
         if str(config.get('inbatch_logq', 0)).strip().lower() not in ('0', 'false'):
             raise _lib.LgcnError(f"--inbatch_logq {config.get('inbatch_logq')} {no} (an option of LightGCN's --loss inbatch)")
+        if str(config.get('inbatch_mix', 0)).strip().lower() not in ('0', 'false'):
+            raise _lib.LgcnError(f"--inbatch_mix {config.get('inbatch_mix')} {no} (an option of LightGCN's --loss inbatch)")
         if self.latent_dim not in (32, 64, 128, 256):
             raise ValueError("latent_dim_rec must be 32, 64, 128 or 256 for the HIP kernels")
         if self.n_users + self.m_items >= 2 ** 31:

@@ -141,6 +141,9 @@ class DataParallelBPR:
         if getattr(recmodel, 'dropout', False):
             raise RuntimeError("--dropout 1 is implemented for single-GPU training only: DataParallelBPR (every reduce / shard mode) "
                                "has no edge-dropout form")
+        if getattr(recmodel, 'inbatch_mix', False) or str(config.get('inbatch_mix', 0)).strip().lower() in ('1', 'true'):
+            raise RuntimeError("--inbatch_mix 1 is implemented for single-GPU training only: DataParallelBPR (every reduce / shard "
+                               "mode) computes the BPR loss")
         if int(getattr(recmodel, 'neg_ratio', 1)) > 1 or int(config.get('neg_ratio', 1)) > 1:
             raise RuntimeError("--neg_ratio > 1 is implemented for single-GPU training only: DataParallelBPR (every reduce / shard "
                                "mode) trains on triplets, one negative per positive")

@@ -134,6 +134,12 @@ def build_parser():
     p.add_argument('--inbatch_logq', type=int, default=0, choices=[0, 1],
                    help='NEW: 1 = subtract log Q(item) = log(train degree) from every in-batch logit (the logQ correction: in-batch '
                         'negatives arrive in proportion to item popularity). 0 (default) = no correction. --loss inbatch only')
+    p.add_argument('--inbatch_mix', type=int, default=0, choices=[0, 1],
+                   help='NEW: 1 = mixed negative sampling for --loss inbatch: the --neg_ratio sampled negatives of all samples of the batch '
+                        'are a pool shared by the whole batch, extra columns of every sample\'s score row in the same log-sum-exp '
+                        '(--neg_ratio 1..16 is then legal); with --inbatch_logq 1 the correction is the log of the mixture, '
+                        'log((B - 1) deg / sum deg + B R / m_items) with B = --bpr_batch. 0 (default) = in-batch negatives only. '
+                        '--loss inbatch only')
     p.add_argument('--data_path', type=str, default=None,
                    help='NEW: directory that holds <dataset>/train.txt (default: <root>/data)')
     return p

@@ -118,6 +118,7 @@ def configure(argv=None):
     config['softmax_temp'] = args.softmax_temp
     config['score'] = args.score
     config['inbatch_logq'] = args.inbatch_logq
+    config['inbatch_mix'] = args.inbatch_mix
     device =torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     return config
 

@@ -397,6 +397,32 @@ int lgcn_ctx_set_inbatch_scores(lgcn_ctx *ctx, int score, const float *item_logq
 /* The score kind in force (-1: null context); the logq vector goes to item_logq (may be NULL).                                */
 int lgcn_ctx_get_inbatch_scores(const lgcn_ctx *ctx, const float **item_logq);
 
+/* Mixed negative sampling for the in-batch step (--inbatch_mix).  A sample carries R sampled negatives
+ * n_{b,1..R} (the layouts of lgcn_train_step_multi / lgcn_train_epoch_multi); the B R negatives of the sound samples are a pool
+ * SHARED by the whole batch: extra columns of every sample's score row, in the same log-sum-exp.
+ *   N_b         = { (c, r) : c sound, n_{c,r} != p_b }        (nothing else is masked; the train graph is not consulted)
+ *   z_{b,(c,r)} = (e^_{u_b}.e^_{n_{c,r}} - s_{b,b}) / tau - (lq_{n_{c,r}} - lq_{p_b})
+ *   l_b = log(1 + sum_{c in A_b} exp z_{b,c} + sum_{(c,r) in N_b} exp z_{b,(c,r)}),   sm = 1/B sum_b l_b
+ *   g_{n_{c,r}} = sum_b W[b,(c,r)] e^_{u_b} + lam/R e_{n_{c,r}}   (cosine: through the pool row's own normalisation)
+ *   reg = 0.5/B sum_b ( |e_u|^2 + |e_p|^2 + 1/R sum_r |e_{n_{b,r}}|^2 )
+ * An item that is a positive of the batch and named by the pool, or named twice by the pool, counts once per occurrence.  A
+ * sample is sound when all 2 + R ids are in range; a void sample contributes no row, no in-batch column and no pool column.
+ * At B = 1 the loss is LGCN_LOSS_SOFTMAX's at the same R and tau; with an empty pool it is the in-batch loss above.
+ * lgcn_ctx_set_inbatch_mix(ctx, R_max): 0 = off (the default); 1..LGCN_MAX_NEG_RATIO while LGCN_LOSS_INBATCH is set allocates the
+ * library-owned workspace again, for (1 + R_max) item rows per sample -- never inside a step.  Returns 3 (nothing changed) for
+ * a null context, R_max out of range, or a context whose loss is not LGCN_LOSS_INBATCH; 4 if the workspace cannot be allocated.
+ * The two entry points return 3, naming the cause, before anything is launched or counted: loss not inbatch, mixing not set,
+ * R < 1 or R > R_max, neg_stride < B, a null pointer, B > max_batch.  lgcn_train_step_inbatch on the same context stays the
+ * step it is on a context that was never told (bit for bit); every other entry point refuses as before.                      */
+int lgcn_ctx_set_inbatch_mix(lgcn_ctx *ctx, int32_t R_max);
+/* R_max in force (0: off; -1: null context).                                                                                  */
+int32_t lgcn_ctx_get_inbatch_mix(const lgcn_ctx *ctx);
+int lgcn_train_step_inbatch_mix(lgcn_ctx *ctx, const int32_t *users, const int32_t *pos, const int32_t *negs, int64_t neg_stride,
+                                int32_t R, int32_t B, float *loss_out, void *stream);
+/* negs: [R][T]; ceil(T/B) consecutive batches; loss_out: [3*ceil(T/B)].                                                       */
+int lgcn_train_epoch_inbatch_mix(lgcn_ctx *ctx, const int32_t *users, const int32_t *pos, const int32_t *negs, int32_t R,
+                                 int64_t T, int32_t B, float *loss_out, void *stream);
+
 /* The fold of the gradient-row conversion into the batch-row launch.  lgcn_train_epoch holds all triplets of
  * the call before its first step, so it computes once (per segment of 1024 steps) how many slots of each batch name each
  * destination row; the batch-row kernel then writes the fp32 copy of a gradient row itself -- directly where one slot names
