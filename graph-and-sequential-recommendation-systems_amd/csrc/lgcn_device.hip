@@ -2615,14 +2615,13 @@ struct lgcn_ctx {
     const uint16_t *fold_mult;    // multiplicities of the running step's slots, or NULL: the step launches k_g32
     int32_t *arrive;              // [N] arrival tickets of the rows several slots name (library-owned, zero between steps; allocated by the first call that folds)
     int64_t folded_steps;         // steps run with the fold since the context was created
-    // several negatives per positive (lgcn_train_step_multi): mn_R > 0 only while such a step runs -- its backward
-    // enumerates (2 + mn_R) B slots (negative column r at mn_negs + r * mn_stride) and the reg_ego epilogue takes decay / (B mn_R)
-    const int32_t *mn_negs; int64_t mn_stride; int32_t mn_R;
+    // the (2 + R) B slot form of the running step (SlotScope): on only while a multi-negative step (R >= 1), an
+    // in-batch step (R = 0, no negatives) or a mixed one (R >= 1) runs -- its backward enumerates (2 + R) B slots (negative column
+    // r at negs + r * stride) and, with R > 0, the reg_ego epilogue takes decay / (B R)
+    struct SlotForm { const int32_t *negs; int64_t stride; int32_t R; bool on; } mn;
     // the loss of the multi-negative step (lgcn_ctx_set_loss): LGCN_LOSS_BPR launches the BPR instantiations of k_multineg,
     // LGCN_LOSS_SOFTMAX the softmax ones with the temperature loss_temp; the three-slot and rank-splitting entry points refuse
     int32_t loss_kind; float loss_temp;
-    // the (2 + R) B slot form of the backward is on: a multi-negative step (mn_R >= 1) or an in-batch step (mn_R = 0, no negatives)
-    bool mn_on;
     // the in-batch softmax (LGCN_LOSS_INBATCH): the workspace of its launches, allocated by the first lgcn_ctx_set_loss
     // that accepts the loss (ib_cap = max_batch rounded up to 32 rows) and freed with the context; ONE allocation, carved up
     void *ib_ws; int32_t ib_cap;
@@ -2637,6 +2636,12 @@ struct LoopScope {
     lgcn_ctx *x;
     explicit LoopScope(lgcn_ctx *x_) : x(x_) { x->in_loop = true; x->e0b_fresh = false; }
     ~LoopScope() { x->in_loop = false; x->e0b_fresh = false; }
+};
+// a slot-form step: the loss launch, the backward's slot kernels and the reg_ego epilogue read x->mn; cleared on every way out
+struct SlotScope {
+    lgcn_ctx *x;
+    SlotScope(lgcn_ctx *x_, const int32_t *negs, int64_t stride, int32_t R) : x(x_) { x->mn = {negs, stride, R, true}; }
+    ~SlotScope() { x->mn = {}; }
 };
 
 extern "C" int lgcn_ctx_create(const lgcn_train_config *cfg, lgcn_ctx **out) {
@@ -2669,8 +2674,8 @@ extern "C" int lgcn_ctx_create(const lgcn_train_config *cfg, lgcn_ctx **out) {
     x->drop_keep = 1.f; x->drop_seed = 0; x->dr = DropArgs{};
     x->lw_n = 0; for (int k = 0; k <= LGCN_MAX_LAYERS; k++) x->lw[k] = 0.f;
     x->fold_g32 = true; x->mult = nullptr; x->mult_cap = 0; x->fold_mult = nullptr; x->arrive = nullptr; x->folded_steps = 0;
-    x->mn_negs = nullptr; x->mn_stride = 0; x->mn_R = 0;
-    x->loss_kind = LGCN_LOSS_BPR; x->loss_temp = 1.f; x->mn_on = false; x->ib_ws = nullptr; x->ib_cap = 0;
+    x->mn = {};
+    x->loss_kind = LGCN_LOSS_BPR; x->loss_temp = 1.f; x->ib_ws = nullptr; x->ib_cap = 0;
     x->ib_score = LGCN_SCORE_DOT; x->ib_logq = nullptr; x->ib_mix = 0;
     x->bm_words = (x->N + 31) / 32; x->flip = 0;
     const size_t stride = table_bytes(x->N, c.d, c.act_dtype);
@@ -2820,41 +2825,58 @@ static int refuse_layer_weights(const lgcn_ctx *x, const char *who) {
     return 3;
 }
 
-// floats of the in-batch workspace for `cap` rows of dim d: U, P | sbb | uid, pid | mrg | part (the largest part count) |
-// invu, invp, lqb (the score options)
-static size_t inbatch_ws_words(int32_t cap, int d) {
-    return (size_t)cap * (2 * (size_t)d + 1 + 2 + 2 + 2 * (size_t)lgcn_inbatch_parts(cap) + 3);
+// THE carving of the in-batch workspace for `cap` rows of dim d, in floats from its start:
+//   U | P | sbb | uid | pid | mrg | part | invu | invp | lq      with icap = (1 + R_max) cap item rows in P, pid, invp and lq
+// R_max = 0 is the plain step's carving, R_max >= 1 the mixed step's; both live in ONE allocation of `words` floats, which is
+// never smaller than the plain carving's.  The plain kernels do not take the three score vectors as arguments: ib_invu() in
+// lgcn_inbatch.hip finds them at part + 2 cap lgcn_inbatch_parts(cap), which is where `invu` lands here -- `part` holds exactly
+// that many floats under R_max = 0 and invu, invp, lq ([cap] each) are the next blocks
+struct InBatchWs {
+    size_t U, P, sbb, uid, pid, mrg, part, invu, invp, lq, words, icap;
+    InBatchWs(int32_t cap_, int d, int32_t R_max) {
+        const size_t cap = (size_t)cap_;
+        const size_t parts = (size_t)(R_max ? lgcn_inbatch_mix_parts(cap_, R_max) : lgcn_inbatch_parts(cap_));
+        size_t at = 0;
+        auto take = [&at](size_t n) { const size_t o = at; at += n; return o; };
+        icap = (size_t)(1 + R_max) * cap;
+        U = take(cap * d); P = take(icap * d); sbb = take(cap); uid = take(cap); pid = take(icap); mrg = take(2 * cap);
+        part = take(2 * cap * parts); invu = take(cap); invp = take(icap); lq = take(icap);
+        words = at;
+        if (R_max) words = std::max(words, InBatchWs(cap_, d, 0).words);
+    }
+};
+
+// the conditions of the two softmax losses (`what`: the loss as the messages name it, `slots`: its slot form)
+static int refuse_loss_config(const lgcn_ctx *ctx, float temperature, const char *what, const char *slots) {
+    char buf[256];
+    const char *fmt = nullptr;
+    if (!(temperature > 0.f) || !isfinite(temperature)) fmt = "lgcn_ctx_set_loss: %s needs a finite temperature > 0";
+    else if (ctx->c.act_dtype == LGCN_FP8) fmt = "lgcn_ctx_set_loss: %s is not implemented for LGCN_FP8 activation storage";
+    else if (ctx->variant) fmt = "lgcn_ctx_set_loss: %s is not implemented with the optional branches (item-item smoothing / popularity gate)";
+    else if (!ctx->c.dense_last) fmt = "lgcn_ctx_set_loss: %s needs a context with dense_last = 1 (the gathered last layer has no %s slot form)";
+    if (!fmt) return 0;
+    snprintf(buf, sizeof buf, fmt, what, slots);
+    lgcn_set_error(buf);
+    return 3;
 }
-// accepted under exactly the conditions of LGCN_LOSS_SOFTMAX; the workspace is allocated once, before anything is changed
-static int set_loss_inbatch(lgcn_ctx *ctx, float temperature) {
-    if (!(temperature > 0.f) || !isfinite(temperature)) { lgcn_set_error("lgcn_ctx_set_loss: the in-batch softmax loss (inbatch) needs a finite temperature > 0"); return 3; }
-    if (ctx->c.act_dtype == LGCN_FP8) { lgcn_set_error("lgcn_ctx_set_loss: the in-batch softmax loss (inbatch) is not implemented for LGCN_FP8 activation storage"); return 3; }
-    if (ctx->variant) { lgcn_set_error("lgcn_ctx_set_loss: the in-batch softmax loss (inbatch) is not implemented with the optional branches (item-item smoothing / popularity gate)"); return 3; }
-    if (!ctx->c.dense_last) { lgcn_set_error("lgcn_ctx_set_loss: the in-batch softmax loss (inbatch) needs a context with dense_last = 1 (the gathered last layer has no 2 B slot form)"); return 3; }
-    if (!ctx->ib_ws) {
+
+extern "C" int lgcn_ctx_set_loss(lgcn_ctx *ctx, int32_t kind, float temperature) {
+    if (!ctx) { lgcn_set_error("lgcn_ctx_set_loss: null context"); return 3; }
+    if (kind == LGCN_LOSS_BPR) { ctx->loss_kind = LGCN_LOSS_BPR; ctx->loss_temp = 1.f; return 0; }      // the step launches what it always launched
+    if (kind != LGCN_LOSS_SOFTMAX && kind != LGCN_LOSS_INBATCH) { lgcn_set_error("lgcn_ctx_set_loss: unknown loss kind (LGCN_LOSS_BPR, LGCN_LOSS_SOFTMAX or LGCN_LOSS_INBATCH)"); return 3; }
+    const bool inbatch = kind == LGCN_LOSS_INBATCH;
+    if (int rc = refuse_loss_config(ctx, temperature, inbatch ? "the in-batch softmax loss (inbatch)" : "the sampled-softmax loss", inbatch ? "2 B" : "2 + R")) return rc;
+    if (inbatch && !ctx->ib_ws) {       // the workspace is allocated once, before anything is changed
         const int32_t cap = lgcn_inbatch_rows(ctx->c.max_batch);
         void *ws = nullptr;
-        if (hipMalloc(&ws, sizeof(float) * inbatch_ws_words(cap, ctx->c.d)) != hipSuccess) {
+        if (hipMalloc(&ws, sizeof(float) * InBatchWs(cap, ctx->c.d, 0).words) != hipSuccess) {
             (void)hipGetLastError();
             lgcn_set_error("lgcn_ctx_set_loss: cannot allocate the workspace of the in-batch softmax loss (inbatch): 2 * max_batch * d * 4 bytes and a few vectors");
             return 4;
         }
         ctx->ib_ws = ws; ctx->ib_cap = cap;
     }
-    ctx->loss_kind = LGCN_LOSS_INBATCH; ctx->loss_temp = temperature;
-    return 0;
-}
-
-extern "C" int lgcn_ctx_set_loss(lgcn_ctx *ctx, int32_t kind, float temperature) {
-    if (!ctx) { lgcn_set_error("lgcn_ctx_set_loss: null context"); return 3; }
-    if (kind == LGCN_LOSS_BPR) { ctx->loss_kind = LGCN_LOSS_BPR; ctx->loss_temp = 1.f; return 0; }      // the step launches what it always launched
-    if (kind == LGCN_LOSS_INBATCH) return set_loss_inbatch(ctx, temperature);
-    if (kind != LGCN_LOSS_SOFTMAX) { lgcn_set_error("lgcn_ctx_set_loss: unknown loss kind (LGCN_LOSS_BPR, LGCN_LOSS_SOFTMAX or LGCN_LOSS_INBATCH)"); return 3; }
-    if (!(temperature > 0.f) || !isfinite(temperature)) { lgcn_set_error("lgcn_ctx_set_loss: the sampled-softmax loss needs a finite temperature > 0"); return 3; }
-    if (ctx->c.act_dtype == LGCN_FP8) { lgcn_set_error("lgcn_ctx_set_loss: the sampled-softmax loss is not implemented for LGCN_FP8 activation storage"); return 3; }
-    if (ctx->variant) { lgcn_set_error("lgcn_ctx_set_loss: the sampled-softmax loss is not implemented with the optional branches (item-item smoothing / popularity gate)"); return 3; }
-    if (!ctx->c.dense_last) { lgcn_set_error("lgcn_ctx_set_loss: the sampled-softmax loss needs a context with dense_last = 1 (the gathered last layer has no 2 + R slot form)"); return 3; }
-    ctx->loss_kind = LGCN_LOSS_SOFTMAX; ctx->loss_temp = temperature;
+    ctx->loss_kind = kind; ctx->loss_temp = temperature;
     return 0;
 }
 extern "C" int lgcn_ctx_set_inbatch_scores(lgcn_ctx *ctx, int score, const float *item_logq) {
@@ -2868,15 +2890,6 @@ extern "C" int lgcn_ctx_get_inbatch_scores(const lgcn_ctx *ctx, const float **it
     if (!ctx) return -1;
     if (item_logq) *item_logq = ctx->ib_logq;
     return ctx->ib_score;
-}
-// floats of the mixed carving for `cap` rows, Rm negatives per sample: U | P | sbb | uid | pid | mrg | part | xinvu | xinvp | xlq
-// with icap = (1 + Rm) cap item rows; never smaller than the plain carving, which lives in the same allocation
-static size_t inbatch_mix_ws_words(int32_t cap, int d, int32_t Rm) {
-    const size_t icap = (size_t)(1 + Rm) * (size_t)cap;
-    const size_t w = (size_t)cap * d + icap * d + 2 * (size_t)cap + icap + 2 * (size_t)cap +
-                     2 * (size_t)cap * (size_t)lgcn_inbatch_mix_parts(cap, Rm) + (size_t)cap + 2 * icap;
-    const size_t plain = inbatch_ws_words(cap, d);
-    return w > plain ? w : plain;
 }
 extern "C" int lgcn_ctx_set_inbatch_mix(lgcn_ctx *ctx, int32_t R_max) {
     if (!ctx) { lgcn_set_error("lgcn_ctx_set_inbatch_mix: null context"); return 3; }
@@ -2893,7 +2906,7 @@ extern "C" int lgcn_ctx_set_inbatch_mix(lgcn_ctx *ctx, int32_t R_max) {
     if (R_max > ctx->ib_mix) {      // grow only: the new block first, so a failure changes nothing
         HIP_OK(hipDeviceSynchronize());     // steps in flight still read the old block
         void *ws = nullptr;
-        if (hipMalloc(&ws, sizeof(float) * inbatch_mix_ws_words(ctx->ib_cap, ctx->c.d, R_max)) != hipSuccess) {
+        if (hipMalloc(&ws, sizeof(float) * InBatchWs(ctx->ib_cap, ctx->c.d, R_max).words) != hipSuccess) {
             (void)hipGetLastError();
             lgcn_set_error("lgcn_ctx_set_inbatch_mix: cannot allocate the workspace of the mixed in-batch step: (2 + R_max) * max_batch * d * 4 bytes and a few vectors");
             return 4;
@@ -3159,12 +3172,12 @@ static unsigned slot_grid(const lgcn_ctx *x, int32_t B) {
 static SlotArgsMulti slot_args_multi(const lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B, float *loss_out) {
     SlotArgsMulti m{};
     m.s = slot_args(x, users, pos, nullptr, B, nullptr, B, 1, loss_out);
-    m.negs = x->mn_negs; m.neg_stride = x->mn_stride; m.R = x->mn_R;
+    m.negs = x->mn.negs; m.neg_stride = x->mn.stride; m.R = x->mn.R;
     return m;
 }
 static unsigned slot_grid_multi(const lgcn_ctx *x, int32_t B) {
     const int spb = 256 / (x->c.d / 4);
-    return (unsigned)(((2 + (int64_t)x->mn_R) * B + spb - 1) / spb);
+    return (unsigned)(((2 + (int64_t)x->mn.R) * B + spb - 1) / spb);
 }
 
 // buffer the backward layer k writes (k > 1): ping-pong inside the activation workspace (forward
@@ -3181,7 +3194,7 @@ static int backward_layer(lgcn_ctx *x, int k, const int32_t *users, const int32_
     const lgcn_train_config &c = x->c;
     const bool first = (k == c.K), last = (k == 1);
     if (first) {        // every contribution is in G64 by now: convert the batch rows once (the fold: k_triplet has done it)
-        if (x->mn_on) {     // several negatives per positive, or the in-batch loss (R = 0): (2 + R) B slots, never folded
+        if (x->mn.on) {     // several negatives per positive, or the in-batch loss (R = 0): (2 + R) B slots, never folded
             SlotArgsMulti s = slot_args_multi(x, users, pos, B, loss_out);
             DISPATCH_D(c.d, hipLaunchKernelGGL((k_g32_multi<D>), dim3(slot_grid_multi(x, B)), dim3(256), 0, st, s));
         } else if (!x->fold_mult) {
@@ -3212,7 +3225,7 @@ static int backward_layer(lgcn_ctx *x, int k, const int32_t *users, const int32_
         const double bc2 = 1.0 - pow(c.beta2, (double)x->step);
         a.P = c.E0; a.M = c.adam_m; a.V = c.adam_v;
         a.cnt = x->cnt; a.lam = c.decay / (float)B;
-        if (x->mn_R > 0) a.lam = c.decay / (float)((int64_t)B * x->mn_R);      // the counts are R per user / positive slot, 1 per negative slot
+        if (x->mn.R > 0) a.lam = c.decay / (float)((int64_t)B * x->mn.R);      // the counts are R per user / positive slot, 1 per negative slot
         // inside a multi-step call on replicated tables the epilogue keeps the bf16 copy of E0 current (row-sharded steps
         // update only the owned rows and convert again after the exchange)
         a.Pb = (x->e0b && x->in_loop && fused_finish) ? x->e0b : nullptr;
@@ -3273,7 +3286,7 @@ static int run_backward(lgcn_ctx *x, const int32_t *users, const int32_t *pos, c
         hipLaunchKernelGGL(k_gate_adam, dim3((unsigned)((x->gate_P + 255) / 256)), dim3(256), 0, st, ga);
     }
     if (c.K >= 2) { x->flip ^= 1; return 0; }       // next step flags rows in the other bitmap
-    if (x->mn_on) {
+    if (x->mn.on) {
         SlotArgsMulti sm = slot_args_multi(x, users, pos, B, loss_out);
         DISPATCH_D(c.d, hipLaunchKernelGGL((k_finish_multi<D>), dim3(slot_grid_multi(x, B)), dim3(256), 0, st, sm));
         return 0;
@@ -3284,6 +3297,67 @@ static int run_backward(lgcn_ctx *x, const int32_t *users, const int32_t *pos, c
         // and zeroed nothing of G64 beyond the batch rows, which k_finish has just done: clear the whole bitmap
         HIP_OK(hipMemsetAsync(c.bitmap + x->flip * x->bm_words, 0, sizeof(uint32_t) * (size_t)x->bm_words, st));
     }
+    return 0;
+}
+
+// What the batch-row launch of every slot-form step takes (lgcn_multineg.hip, lgcn_inbatch.hip), from the context and the slot
+// form of the running step (x->mn).  Without negatives (the plain in-batch step) inv_BR, inv_R and lam_n stay 0; under
+// LGCN_LOSS_BPR tau and inv_tauB do
+static MultiNegArgs multineg_args(const lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B) {
+    const lgcn_train_config &c = x->c;
+    MultiNegArgs a{};
+    a.X0 = c.E0; a.K = c.K;
+    for (int k = 1; k <= x->fwd_layers; k++) a.Xl[k] = x->act[k];
+    a.n_users = c.n_users; a.N = x->N;
+    a.users = users; a.pos = pos; a.negs = x->mn.negs; a.neg_stride = x->mn.stride; a.R = x->mn.R; a.B = B;
+    a.lam = c.decay / (float)B;
+    if (x->mn.R > 0) {
+        const float BR = (float)((int64_t)B * x->mn.R);
+        a.inv_BR = 1.0f / BR; a.inv_R = 1.0f / (float)x->mn.R; a.lam_n = c.decay / BR;
+    }
+    a.G64 = (long long *)c.G64; a.bitmap = c.bitmap + x->flip * x->bm_words;
+    a.stale_bitmap = c.bitmap + (x->flip ^ 1) * x->bm_words; a.bitmap_words = x->bm_words;
+    a.terms = c.terms; a.terms_stride = B; a.err = c.err;
+    a.reg_ego = c.reg_ego; a.cnt = x->cnt;
+    for (int k = 0; k < x->lw_n; k++) a.w[k] = x->lw[k];
+    a.loss = x->loss_kind;
+    if (x->loss_kind != LGCN_LOSS_BPR) {       // the same rows, flags and terms; another coefficient per negative
+        a.tau = x->loss_temp; a.inv_tauB = (float)(1.0 / ((double)x->loss_temp * (double)B));
+    }
+    return a;
+}
+
+// The four launches of lgcn_inbatch.hip: the plain step on the plain carving of the workspace, a step with
+// negatives on the mixed carving for the context's R_max, with the pool's (1 + R_max) cap item rows
+static int run_inbatch(lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B, hipStream_t st) {
+    const lgcn_train_config &c = x->c;
+    const bool mix = x->mn.R > 0;
+    const InBatchWs ws(x->ib_cap, c.d, mix ? x->ib_mix : 0);
+    float *w = (float *)x->ib_ws;
+    InBatchArgs ia{};
+    ia.m = multineg_args(x, users, pos, B);
+    ia.cap = x->ib_cap;
+    ia.U = w + ws.U; ia.P = w + ws.P; ia.sbb = w + ws.sbb;
+    ia.uid = (int32_t *)(w + ws.uid); ia.pid = (int32_t *)(w + ws.pid);
+    ia.mrg = w + ws.mrg; ia.part = w + ws.part;
+    if (mix) { ia.mix = 1; ia.icap = (int32_t)ws.icap; ia.xinvu = w + ws.invu; ia.xinvp = w + ws.invp; ia.xlq = w + ws.lq; }
+    ia.score = x->ib_score; ia.item_logq = x->ib_logq;
+    return lgcn_inbatch_launch(ia, c.d, c.act_dtype, x->lw_n != 0, st);
+}
+
+// One training step on one GPU: the drop mask, the forward layers, the loss launch of the step's form -- three slots (BPR or
+// the optional branches) unless a SlotScope is open, else the batch-row launch of the context's loss -- and the backward
+static int run_step(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *neg, int32_t B, float *loss_out, hipStream_t st) {
+    const lgcn_train_config &c = x->c;
+    int rc;
+    x->dr = make_drop(x->drop_keep, x->drop_seed, x->step, 0);        // ONE mask per step, from the counter before the step
+    if ((rc = run_forward(x, st))) return rc;
+    if (!x->mn.on) rc = x->variant ? run_variant_loss(x, users, pos, neg, B, 0, B, B, true, false, st) : run_bpr(x, users, pos, neg, B, 0, B, B, true, false, st);
+    else if (x->loss_kind == LGCN_LOSS_INBATCH) rc = run_inbatch(x, users, pos, B, st);
+    else rc = lgcn_multineg_launch(multineg_args(x, users, pos, B), c.d, c.act_dtype, x->lw_n != 0, st);
+    if (rc) return rc;
+    if ((rc = run_backward(x, users, pos, neg, B, nullptr, B, 1, loss_out, st))) return rc;
+    HIP_OK(hipGetLastError());
     return 0;
 }
 
@@ -3299,15 +3373,7 @@ extern "C" int lgcn_train_step(lgcn_ctx *x, const int32_t *users, const int32_t 
     if (rc) return rc;
     if ((rc = lgcn_refuse_loss(x, "lgcn_train_step"))) return rc;
     if (!loss_out) { lgcn_set_error("train step: loss_out is null"); return 3; }
-    hipStream_t st = (hipStream_t)stream;
-    x->dr = make_drop(x->drop_keep, x->drop_seed, x->step, 0);        // ONE mask per step, from the counter before the step
-    if ((rc = run_forward(x, st))) return rc;
-    if (x->variant) rc = run_variant_loss(x, users, pos, neg, B, 0, B, B, true, false, st);
-    else rc = run_bpr(x, users, pos, neg, B, 0, B, B, true, false, st);
-    if (rc) return rc;
-    if ((rc = run_backward(x, users, pos, neg, B, nullptr, B, 1, loss_out, st))) return rc;
-    HIP_OK(hipGetLastError());
-    return 0;
+    return run_step(x, users, pos, neg, B, loss_out, (hipStream_t)stream);
 }
 
 extern "C" int lgcn_train_epoch(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *neg,
@@ -3359,237 +3425,83 @@ extern "C" int lgcn_train_epoch(lgcn_ctx *x, const int32_t *users, const int32_t
     return 0;
 }
 
-// Several negatives per positive.  Everything is checked before anything is launched or counted: a refusal leaves
-// the outputs, the step counter and the workspace as they were.
-static int check_multi(const lgcn_ctx *x, const void *u, const void *p, const void *n, const void *loss_out, int32_t R, int32_t B,
-                       int64_t neg_stride, const char *who) {
-    char buf[224];
-    if (!x || !u || !p || !n || !loss_out) { snprintf(buf, sizeof buf, "%s: null argument", who); lgcn_set_error(buf); return 3; }
-    if (x->loss_kind == LGCN_LOSS_INBATCH) return lgcn_refuse_loss(x, who);
-    if (R < 1 || R > LGCN_MAX_NEG_RATIO) { snprintf(buf, sizeof buf, "%s: the negative ratio R = %d is out of range (1..%d)", who, (int)R, LGCN_MAX_NEG_RATIO); lgcn_set_error(buf); return 3; }
-    if (!x->c.dense_last) { snprintf(buf, sizeof buf, "%s: a negative ratio above the three-slot step's needs a context with dense_last = 1 (the gathered last layer has no 2 + R slot form)", who); lgcn_set_error(buf); return 3; }
-    if (x->c.act_dtype == LGCN_FP8) { snprintf(buf, sizeof buf, "%s: the negative ratio (several negatives per positive) is not implemented for LGCN_FP8 activation storage", who); lgcn_set_error(buf); return 3; }
-    if (x->variant) { snprintf(buf, sizeof buf, "%s: the negative ratio (several negatives per positive) is not implemented with the optional branches (item-item smoothing / popularity gate)", who); lgcn_set_error(buf); return 3; }
-    if (B <= 0 || B > x->c.max_batch) { snprintf(buf, sizeof buf, "%s: batch size out of range (0 < B <= max_batch)", who); lgcn_set_error(buf); return 3; }
-    if (neg_stride < B) { snprintf(buf, sizeof buf, "%s: neg_stride must be at least B (negative ratio columns would overlap)", who); lgcn_set_error(buf); return 3; }
+// The slot-form steps: several negatives per positive under BPR or the sampled softmax (SLOT_MULTI), the
+// in-batch softmax over (users, pos) alone (SLOT_INBATCH; 4.19, 4.20: R = 0, no negatives) and the in-batch softmax with the
+// batch's sampled negatives as a shared pool (SLOT_MIX; 4.21).  Everything is checked before anything is launched or counted: a
+// refusal leaves the outputs, the step counter and the workspace as they were.
+enum SlotKind { SLOT_MULTI, SLOT_INBATCH, SLOT_MIX };
+static int check_slot_step(const lgcn_ctx *x, SlotKind kind, const void *u, const void *p, const void *n, const void *loss_out,
+                           int32_t R, int32_t B, int64_t neg_stride, const char *who) {
+    char buf[256];
+    auto refuse = [&](const char *fmt, int v0 = 0, int v1 = 0) { snprintf(buf, sizeof buf, fmt, who, v0, v1); lgcn_set_error(buf); return 3; };
+    const bool negs = kind != SLOT_INBATCH;
+    if (!x || !u || !p || (negs && !n) || !loss_out) return refuse("%s: null argument");
+    if (kind == SLOT_MULTI) {
+        if (x->loss_kind == LGCN_LOSS_INBATCH) return lgcn_refuse_loss(x, who);
+        if (R < 1 || R > LGCN_MAX_NEG_RATIO) return refuse("%s: the negative ratio R = %d is out of range (1..%d)", R, LGCN_MAX_NEG_RATIO);
+        if (!x->c.dense_last) return refuse("%s: a negative ratio above the three-slot step's needs a context with dense_last = 1 (the gathered last layer has no 2 + R slot form)");
+        if (x->c.act_dtype == LGCN_FP8) return refuse("%s: the negative ratio (several negatives per positive) is not implemented for LGCN_FP8 activation storage");
+        if (x->variant) return refuse("%s: the negative ratio (several negatives per positive) is not implemented with the optional branches (item-item smoothing / popularity gate)");
+    } else {
+        if (x->loss_kind != LGCN_LOSS_INBATCH || !x->ib_ws) return refuse("%s: the in-batch softmax loss (inbatch) is not set on this context (lgcn_ctx_set_loss with LGCN_LOSS_INBATCH)");
+        if (kind == SLOT_MIX && x->ib_mix < 1) return refuse("%s: mixed negatives are not set on this context (lgcn_ctx_set_inbatch_mix)");
+        if (kind == SLOT_MIX && (R < 1 || R > x->ib_mix)) return refuse("%s: the negative ratio R = %d is out of range (1..%d, the R_max of lgcn_ctx_set_inbatch_mix)", R, x->ib_mix);
+    }
+    if (B <= 0 || B > x->c.max_batch) return refuse("%s: batch size out of range (0 < B <= max_batch)");
+    if (negs && neg_stride < B) return refuse("%s: neg_stride must be at least B (negative ratio columns would overlap)");
     return 0;
 }
 
-static int run_bpr_multi(lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B, hipStream_t st) {
-    const lgcn_train_config &c = x->c;
-    MultiNegArgs a{};
-    a.X0 = c.E0; a.K = c.K;
-    for (int k = 1; k <= x->fwd_layers; k++) a.Xl[k] = x->act[k];
-    a.n_users = c.n_users; a.N = x->N;
-    a.users = users; a.pos = pos; a.negs = x->mn_negs; a.neg_stride = x->mn_stride; a.R = x->mn_R; a.B = B;
-    const float BR = (float)((int64_t)B * x->mn_R);
-    a.inv_BR = 1.0f / BR; a.inv_R = 1.0f / (float)x->mn_R;
-    a.lam = c.decay / (float)B; a.lam_n = c.decay / BR;
-    a.G64 = (long long *)c.G64; a.bitmap = c.bitmap + x->flip * x->bm_words;
-    a.stale_bitmap = c.bitmap + (x->flip ^ 1) * x->bm_words; a.bitmap_words = x->bm_words;
-    a.terms = c.terms; a.terms_stride = B; a.err = c.err;
-    a.reg_ego = c.reg_ego; a.cnt = x->cnt;
-    for (int k = 0; k < x->lw_n; k++) a.w[k] = x->lw[k];
-    a.loss = x->loss_kind;
-    if (x->loss_kind == LGCN_LOSS_SOFTMAX) {       // the same rows, flags and terms; another coefficient per negative
-        a.tau = x->loss_temp; a.inv_tauB = (float)(1.0 / ((double)x->loss_temp * (double)B));
-    }
-    return lgcn_multineg_launch(a, c.d, c.act_dtype, x->lw_n != 0, st);
+static int slot_step(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int64_t neg_stride, int32_t R,
+                     int32_t B, float *loss_out, void *stream) {
+    SlotScope scope(x, negs, neg_stride, R);
+    return run_step(x, users, pos, negs, B, loss_out, (hipStream_t)stream);
 }
-
-static int train_step_multi(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int64_t neg_stride, int32_t R,
-                            int32_t B, float *loss_out, hipStream_t st) {
-    struct MultiScope {         // the backward's slot kernels and the reg_ego epilogue read these; cleared on every way out
-        lgcn_ctx *x;
-        MultiScope(lgcn_ctx *x_, const int32_t *n, int64_t s, int32_t r) : x(x_) { x->mn_negs = n; x->mn_stride = s; x->mn_R = r; x->mn_on = true; }
-        ~MultiScope() { x->mn_negs = nullptr; x->mn_stride = 0; x->mn_R = 0; x->mn_on = false; }
-    } scope(x, negs, neg_stride, R);
-    int rc;
-    x->dr = make_drop(x->drop_keep, x->drop_seed, x->step, 0);        // ONE mask per step, from the counter before the step
-    if ((rc = run_forward(x, st))) return rc;
-    if ((rc = run_bpr_multi(x, users, pos, B, st))) return rc;
-    if ((rc = run_backward(x, users, pos, negs, B, nullptr, B, 1, loss_out, st))) return rc;
-    HIP_OK(hipGetLastError());
+// T samples in batches of B (a short last one), negative column r at negs + r * T (or no negatives); stops at the first failure
+static int slot_epoch(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int32_t R, int64_t T, int32_t B,
+                      float *loss_out, void *stream) {
+    LoopScope scope(x);
+    int64_t i = 0;
+    for (int64_t t = 0; t < T; t += B, i++) {
+        const int32_t b = (int32_t)((T - t) < B ? (T - t) : B);
+        if (int rc = slot_step(x, users + t, pos + t, negs ? negs + t : nullptr, negs ? T : 0, R, b, loss_out + 3 * i, stream)) return rc;
+    }
     return 0;
 }
 
 extern "C" int lgcn_train_step_multi(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int64_t neg_stride,
                                      int32_t R, int32_t B, float *loss_out, void *stream) {
-    if (int rc = check_multi(x, users, pos, negs, loss_out, R, B, neg_stride, "lgcn_train_step_multi")) return rc;
-    return train_step_multi(x, users, pos, negs, neg_stride, R, B, loss_out, (hipStream_t)stream);
+    if (int rc = check_slot_step(x, SLOT_MULTI, users, pos, negs, loss_out, R, B, neg_stride, "lgcn_train_step_multi")) return rc;
+    return slot_step(x, users, pos, negs, neg_stride, R, B, loss_out, stream);
 }
-
 extern "C" int lgcn_train_epoch_multi(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int32_t R,
                                       int64_t T, int32_t B, float *loss_out, void *stream) {
     if (T <= 0) return 0;
-    if (int rc = check_multi(x, users, pos, negs, loss_out, R, B, T < B ? (int64_t)B : T, "lgcn_train_epoch_multi")) return rc;
-    LoopScope scope(x);
-    int64_t i = 0;
-    for (int64_t t = 0; t < T; t += B, i++) {
-        const int32_t b = (int32_t)((T - t) < B ? (T - t) : B);
-        if (int rc = train_step_multi(x, users + t, pos + t, negs + t, T, R, b, loss_out + 3 * i, (hipStream_t)stream)) return rc;
-    }
-    return 0;
-}
-
-// The in-batch sampled softmax: run_forward, the four launches of lgcn_inbatch.hip, run_backward over the 2 B slots
-// (the multi-negative slot kernels with R = 0 and no negatives).  Everything is checked before anything is launched or counted.
-static int check_inbatch(const lgcn_ctx *x, const void *u, const void *p, const void *loss_out, int32_t B, const char *who) {
-    char buf[256];
-    if (!x || !u || !p || !loss_out) { snprintf(buf, sizeof buf, "%s: null argument", who); lgcn_set_error(buf); return 3; }
-    if (x->loss_kind != LGCN_LOSS_INBATCH || !x->ib_ws) {
-        snprintf(buf, sizeof buf, "%s: the in-batch softmax loss (inbatch) is not set on this context (lgcn_ctx_set_loss with LGCN_LOSS_INBATCH)", who);
-        lgcn_set_error(buf); return 3;
-    }
-    if (B <= 0 || B > x->c.max_batch) { snprintf(buf, sizeof buf, "%s: batch size out of range (0 < B <= max_batch)", who); lgcn_set_error(buf); return 3; }
-    return 0;
-}
-
-static int run_inbatch(lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B, hipStream_t st) {
-    const lgcn_train_config &c = x->c;
-    InBatchArgs ia{};
-    MultiNegArgs &a = ia.m;
-    a.X0 = c.E0; a.K = c.K;
-    for (int k = 1; k <= x->fwd_layers; k++) a.Xl[k] = x->act[k];
-    a.n_users = c.n_users; a.N = x->N;
-    a.users = users; a.pos = pos; a.negs = nullptr; a.neg_stride = 0; a.R = 0; a.B = B;
-    a.lam = c.decay / (float)B;
-    a.G64 = (long long *)c.G64; a.bitmap = c.bitmap + x->flip * x->bm_words;
-    a.stale_bitmap = c.bitmap + (x->flip ^ 1) * x->bm_words; a.bitmap_words = x->bm_words;
-    a.terms = c.terms; a.terms_stride = B; a.err = c.err;
-    a.reg_ego = c.reg_ego; a.cnt = x->cnt;
-    for (int k = 0; k < x->lw_n; k++) a.w[k] = x->lw[k];
-    a.loss = LGCN_LOSS_INBATCH; a.tau = x->loss_temp; a.inv_tauB = (float)(1.0 / ((double)x->loss_temp * (double)B));
-    const size_t cap = (size_t)x->ib_cap, d = (size_t)c.d;
-    float *w = (float *)x->ib_ws;
-    ia.cap = x->ib_cap;
-    ia.U = w; ia.P = w + cap * d; ia.sbb = w + 2 * cap * d;
-    ia.uid = (int32_t *)(w + 2 * cap * d + cap); ia.pid = ia.uid + cap;
-    ia.mrg = w + 2 * cap * d + 3 * cap; ia.part = w + 2 * cap * d + 5 * cap;
-    ia.score = x->ib_score; ia.item_logq = x->ib_logq;
-    return lgcn_inbatch_launch(ia, c.d, c.act_dtype, x->lw_n != 0, st);
-}
-
-static int train_step_inbatch(lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B, float *loss_out, hipStream_t st) {
-    struct InBatchScope {       // the backward's slot kernels enumerate 2 B slots; cleared on every way out
-        lgcn_ctx *x;
-        explicit InBatchScope(lgcn_ctx *x_) : x(x_) { x->mn_negs = nullptr; x->mn_stride = 0; x->mn_R = 0; x->mn_on = true; }
-        ~InBatchScope() { x->mn_on = false; }
-    } scope(x);
-    int rc;
-    x->dr = make_drop(x->drop_keep, x->drop_seed, x->step, 0);        // ONE mask per step, from the counter before the step
-    if ((rc = run_forward(x, st))) return rc;
-    if ((rc = run_inbatch(x, users, pos, B, st))) return rc;
-    if ((rc = run_backward(x, users, pos, nullptr, B, nullptr, B, 1, loss_out, st))) return rc;
-    HIP_OK(hipGetLastError());
-    return 0;
+    if (int rc = check_slot_step(x, SLOT_MULTI, users, pos, negs, loss_out, R, B, T < B ? (int64_t)B : T, "lgcn_train_epoch_multi")) return rc;
+    return slot_epoch(x, users, pos, negs, R, T, B, loss_out, stream);
 }
 
 extern "C" int lgcn_train_step_inbatch(lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B, float *loss_out, void *stream) {
-    if (int rc = check_inbatch(x, users, pos, loss_out, B, "lgcn_train_step_inbatch")) return rc;
-    return train_step_inbatch(x, users, pos, B, loss_out, (hipStream_t)stream);
+    if (int rc = check_slot_step(x, SLOT_INBATCH, users, pos, nullptr, loss_out, 0, B, 0, "lgcn_train_step_inbatch")) return rc;
+    return slot_step(x, users, pos, nullptr, 0, 0, B, loss_out, stream);
 }
-
 extern "C" int lgcn_train_epoch_inbatch(lgcn_ctx *x, const int32_t *users, const int32_t *pos, int64_t T, int32_t B, float *loss_out,
                                         void *stream) {
     if (T <= 0) return 0;
-    if (int rc = check_inbatch(x, users, pos, loss_out, B, "lgcn_train_epoch_inbatch")) return rc;
-    LoopScope scope(x);
-    int64_t i = 0;
-    for (int64_t t = 0; t < T; t += B, i++) {
-        const int32_t b = (int32_t)((T - t) < B ? (T - t) : B);
-        if (int rc = train_step_inbatch(x, users + t, pos + t, b, loss_out + 3 * i, (hipStream_t)stream)) return rc;
-    }
-    return 0;
-}
-
-// Mixed negatives for the in-batch softmax: the same four launches with the pool's (1 + R) Bp item rows, then
-// run_backward over the (2 + R) B slots with mn_R = R.  Everything is checked before anything is launched or counted.
-static int check_inbatch_mix(const lgcn_ctx *x, const void *u, const void *p, const void *n, const void *loss_out, int32_t R, int32_t B,
-                             int64_t neg_stride, const char *who) {
-    char buf[256];
-    if (!x || !u || !p || !n || !loss_out) { snprintf(buf, sizeof buf, "%s: null argument", who); lgcn_set_error(buf); return 3; }
-    if (x->loss_kind != LGCN_LOSS_INBATCH || !x->ib_ws) {
-        snprintf(buf, sizeof buf, "%s: the in-batch softmax loss (inbatch) is not set on this context (lgcn_ctx_set_loss with LGCN_LOSS_INBATCH)", who);
-        lgcn_set_error(buf); return 3;
-    }
-    if (x->ib_mix < 1) { snprintf(buf, sizeof buf, "%s: mixed negatives are not set on this context (lgcn_ctx_set_inbatch_mix)", who); lgcn_set_error(buf); return 3; }
-    if (R < 1 || R > x->ib_mix) {
-        snprintf(buf, sizeof buf, "%s: the negative ratio R = %d is out of range (1..%d, the R_max of lgcn_ctx_set_inbatch_mix)", who, (int)R, (int)x->ib_mix);
-        lgcn_set_error(buf); return 3;
-    }
-    if (B <= 0 || B > x->c.max_batch) { snprintf(buf, sizeof buf, "%s: batch size out of range (0 < B <= max_batch)", who); lgcn_set_error(buf); return 3; }
-    if (neg_stride < B) { snprintf(buf, sizeof buf, "%s: neg_stride must be at least B (negative ratio columns would overlap)", who); lgcn_set_error(buf); return 3; }
-    return 0;
-}
-
-static int run_inbatch_mix(lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B, hipStream_t st) {
-    const lgcn_train_config &c = x->c;
-    InBatchArgs ia{};
-    MultiNegArgs &a = ia.m;
-    a.X0 = c.E0; a.K = c.K;
-    for (int k = 1; k <= x->fwd_layers; k++) a.Xl[k] = x->act[k];
-    a.n_users = c.n_users; a.N = x->N;
-    a.users = users; a.pos = pos; a.negs = x->mn_negs; a.neg_stride = x->mn_stride; a.R = x->mn_R; a.B = B;
-    const float BR = (float)((int64_t)B * x->mn_R);
-    a.inv_BR = 1.0f / BR; a.inv_R = 1.0f / (float)x->mn_R;
-    a.lam = c.decay / (float)B; a.lam_n = c.decay / BR;
-    a.G64 = (long long *)c.G64; a.bitmap = c.bitmap + x->flip * x->bm_words;
-    a.stale_bitmap = c.bitmap + (x->flip ^ 1) * x->bm_words; a.bitmap_words = x->bm_words;
-    a.terms = c.terms; a.terms_stride = B; a.err = c.err;
-    a.reg_ego = c.reg_ego; a.cnt = x->cnt;
-    for (int k = 0; k < x->lw_n; k++) a.w[k] = x->lw[k];
-    a.loss = LGCN_LOSS_INBATCH; a.tau = x->loss_temp; a.inv_tauB = (float)(1.0 / ((double)x->loss_temp * (double)B));
-    const size_t cap = (size_t)x->ib_cap, d = (size_t)c.d, icap = (size_t)(1 + x->ib_mix) * cap;
-    float *w = (float *)x->ib_ws;
-    ia.cap = x->ib_cap; ia.mix = 1; ia.icap = (int32_t)icap;
-    ia.U = w; w += cap * d;
-    ia.P = w; w += icap * d;
-    ia.sbb = w; w += cap;
-    ia.uid = (int32_t *)w; w += cap;
-    ia.pid = (int32_t *)w; w += icap;
-    ia.mrg = w; w += 2 * cap;
-    ia.part = w; w += 2 * cap * (size_t)lgcn_inbatch_mix_parts(x->ib_cap, x->ib_mix);
-    ia.xinvu = w; w += cap;
-    ia.xinvp = w; w += icap;
-    ia.xlq = w;
-    ia.score = x->ib_score; ia.item_logq = x->ib_logq;
-    return lgcn_inbatch_launch(ia, c.d, c.act_dtype, x->lw_n != 0, st);
-}
-
-static int train_step_inbatch_mix(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int64_t neg_stride, int32_t R,
-                                  int32_t B, float *loss_out, hipStream_t st) {
-    struct MixScope {           // the backward's slot kernels and the reg_ego epilogue read these; cleared on every way out
-        lgcn_ctx *x;
-        MixScope(lgcn_ctx *x_, const int32_t *n, int64_t s, int32_t r) : x(x_) { x->mn_negs = n; x->mn_stride = s; x->mn_R = r; x->mn_on = true; }
-        ~MixScope() { x->mn_negs = nullptr; x->mn_stride = 0; x->mn_R = 0; x->mn_on = false; }
-    } scope(x, negs, neg_stride, R);
-    int rc;
-    x->dr = make_drop(x->drop_keep, x->drop_seed, x->step, 0);        // ONE mask per step, from the counter before the step
-    if ((rc = run_forward(x, st))) return rc;
-    if ((rc = run_inbatch_mix(x, users, pos, B, st))) return rc;
-    if ((rc = run_backward(x, users, pos, negs, B, nullptr, B, 1, loss_out, st))) return rc;
-    HIP_OK(hipGetLastError());
-    return 0;
+    if (int rc = check_slot_step(x, SLOT_INBATCH, users, pos, nullptr, loss_out, 0, B, 0, "lgcn_train_epoch_inbatch")) return rc;
+    return slot_epoch(x, users, pos, nullptr, 0, T, B, loss_out, stream);
 }
 
 extern "C" int lgcn_train_step_inbatch_mix(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int64_t neg_stride,
                                            int32_t R, int32_t B, float *loss_out, void *stream) {
-    if (int rc = check_inbatch_mix(x, users, pos, negs, loss_out, R, B, neg_stride, "lgcn_train_step_inbatch_mix")) return rc;
-    return train_step_inbatch_mix(x, users, pos, negs, neg_stride, R, B, loss_out, (hipStream_t)stream);
+    if (int rc = check_slot_step(x, SLOT_MIX, users, pos, negs, loss_out, R, B, neg_stride, "lgcn_train_step_inbatch_mix")) return rc;
+    return slot_step(x, users, pos, negs, neg_stride, R, B, loss_out, stream);
 }
-
 extern "C" int lgcn_train_epoch_inbatch_mix(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int32_t R,
                                             int64_t T, int32_t B, float *loss_out, void *stream) {
     if (T <= 0) return 0;
-    if (int rc = check_inbatch_mix(x, users, pos, negs, loss_out, R, B, T < B ? (int64_t)B : T, "lgcn_train_epoch_inbatch_mix")) return rc;
-    LoopScope scope(x);
-    int64_t i = 0;
-    for (int64_t t = 0; t < T; t += B, i++) {
-        const int32_t b = (int32_t)((T - t) < B ? (T - t) : B);
-        if (int rc = train_step_inbatch_mix(x, users + t, pos + t, negs + t, T, R, b, loss_out + 3 * i, (hipStream_t)stream)) return rc;
-    }
-    return 0;
+    if (int rc = check_slot_step(x, SLOT_MIX, users, pos, negs, loss_out, R, B, T < B ? (int64_t)B : T, "lgcn_train_epoch_inbatch_mix")) return rc;
+    return slot_epoch(x, users, pos, negs, R, T, B, loss_out, stream);
 }
 
 extern "C" int lgcn_train_step_dp_part1(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *neg,

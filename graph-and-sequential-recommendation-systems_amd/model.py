@@ -857,63 +857,23 @@ class LightGCN(nn.Module):
             u, p, n = self.embedding_user.weight[ul], self.embedding_item.weight[pl], self.embedding_item.weight[nl]
         return sm, (0.5 * (u.norm(2).pow(2) + p.norm(2).pow(2) + n.norm(2).pow(2) / float(R))) / float(B)
 
-    def _fused_inbatch_mix(self, users, pos, neg, batch_size, loss_out, lr, epoch):
-        """fused_step / fused_epoch under --inbatch_mix 1: lgcn_train_step_inbatch_mix / lgcn_train_epoch_inbatch_mix on (users,
-        pos, neg); neg 1-D (R = 1), [n, R] or [R, n]."""
+    def _fused_inbatch(self, users, pos, neg, batch_size, loss_out, lr):
+        """fused_step (batch_size None) / fused_epoch under --loss inbatch: lgcn_train_step_inbatch / lgcn_train_epoch_inbatch on
+        (users, pos), neg accepted and ignored; under --inbatch_mix 1 lgcn_train_step_inbatch_mix / lgcn_train_epoch_inbatch_mix
+        on (users, pos, neg), neg 1-D (R = 1), [n, R] or [R, n]."""
         dev = self._table.device
         users, pos = self._ids(users, dev).reshape(-1), self._ids(pos, dev).reshape(-1)
         T = int(users.numel())
-        neg = self._ids(neg, dev)
-        if neg.dim() == 1:
-            neg = neg.reshape(1, -1)
-        elif neg.shape[0] == T:
-            neg = neg.t()
-        if neg.dim() != 2 or neg.shape[1] != T:
-            raise ValueError(f"neg must be [{T}], [{T}, R] or [R, {T}], got {tuple(neg.shape)}")
-        negs = neg.contiguous()
+        u, p = _lib.tp(users), _lib.tp(pos)
+        if not self.inbatch_mix:
+            if batch_size is None:
+                return self._fused_call("lgcn_train_step_inbatch", (u, p, T), T, None, loss_out, lr)
+            return self._fused_call("lgcn_train_epoch_inbatch", (u, p, T, batch_size), T, batch_size, None, lr)
+        negs = self._negs_rn(neg, T, dev, mixed=True)
         R = int(negs.shape[0])
-        if not 1 <= R <= self.neg_ratio:
-            raise ValueError(f"--inbatch_mix 1: the batch carries {R} negatives per positive, --neg_ratio is {self.neg_ratio}")
-        st = self._state(max_batch=batch_size if epoch else max(T, int(self.config.get('bpr_batch_size', T))), need_ctx=True,
-                         dp_world=(self._dev or {}).get('dp_world', 1))
-        lib = _lib.load()
-        if lr is not None:
-            lib.lgcn_ctx_set_lr(st['ctx'], float(lr))
-        if epoch:
-            losses = torch.empty((T + batch_size - 1) // batch_size, 3, dtype=torch.float32, device=dev)
-            _lib.check(lib.lgcn_train_epoch_inbatch_mix(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(negs), R, T, int(batch_size),
-                                                        _lib.tp(losses), _lib.current_stream()), "lgcn_train_epoch_inbatch_mix")
-            self.invalidate_cache()
-            return losses
-        if loss_out is None:
-            loss_out = torch.empty(3, dtype=torch.float32, device=dev)
-        _lib.check(lib.lgcn_train_step_inbatch_mix(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(negs), T, R, T, _lib.tp(loss_out),
-                                                   _lib.current_stream()), "lgcn_train_step_inbatch_mix")
-        self.invalidate_cache()
-        return loss_out
-
-    def _fused_inbatch(self, users, pos, batch_size, loss_out, lr, epoch):
-        """fused_step / fused_epoch under --loss inbatch: lgcn_train_step_inbatch / lgcn_train_epoch_inbatch on (users, pos)."""
-        dev = self._table.device
-        users, pos = self._ids(users, dev).reshape(-1), self._ids(pos, dev).reshape(-1)
-        T = int(users.numel())
-        st = self._state(max_batch=batch_size if epoch else max(T, int(self.config.get('bpr_batch_size', T))), need_ctx=True,
-                         dp_world=(self._dev or {}).get('dp_world', 1))
-        lib = _lib.load()
-        if lr is not None:
-            lib.lgcn_ctx_set_lr(st['ctx'], float(lr))
-        if epoch:
-            losses = torch.empty((T + batch_size - 1) // batch_size, 3, dtype=torch.float32, device=dev)
-            _lib.check(lib.lgcn_train_epoch_inbatch(st['ctx'], _lib.tp(users), _lib.tp(pos), T, int(batch_size), _lib.tp(losses),
-                                                    _lib.current_stream()), "lgcn_train_epoch_inbatch")
-            self.invalidate_cache()
-            return losses
-        if loss_out is None:
-            loss_out = torch.empty(3, dtype=torch.float32, device=dev)
-        _lib.check(lib.lgcn_train_step_inbatch(st['ctx'], _lib.tp(users), _lib.tp(pos), T, _lib.tp(loss_out), _lib.current_stream()),
-                   "lgcn_train_step_inbatch")
-        self.invalidate_cache()
-        return loss_out
+        if batch_size is None:
+            return self._fused_call("lgcn_train_step_inbatch_mix", (u, p, _lib.tp(negs), T, R, T), T, None, loss_out, lr)
+        return self._fused_call("lgcn_train_epoch_inbatch_mix", (u, p, _lib.tp(negs), R, T, batch_size), T, batch_size, None, lr)
 
     def bpr_loss(self, users, pos, neg):
         """model.py:162-183 (unfused, autograd-capable): (bpr [- entropy term of the gate], reg_loss)."""
@@ -958,36 +918,55 @@ class LightGCN(nn.Module):
     def _neg_dim(neg):
         return neg.dim() if torch.is_tensor(neg) else np.asarray(neg).ndim
 
-    def _negs_rt(self, neg, n, dev):
-        """2-D negatives of n samples -> contiguous int32 [R, n] on the device (negative column r in row r), or None for R == 1.
-        Accepts [n, R] (the sampler's S[:, 2:]; taken when both readings fit) and [R, n] (Procedure.sample_epoch_to_device)."""
+    def _negs_rn(self, neg, n, dev, mixed=False):
+        """Negatives of n samples -> contiguous int32 [R, n] on the device (negative column r in row r).  Accepts [n, R] (the
+        sampler's S[:, 2:]; taken when both readings fit) and [R, n] (Procedure.sample_epoch_to_device).  The multi-negative
+        path passes 2-D negatives and gets None for R == 1 unless the loss is softmax (the three-slot step); the mixed
+        in-batch path also takes 1-D as R = 1 and holds R to --neg_ratio."""
         neg = self._ids(neg, dev)
-        if neg.shape[0] == n:
+        if mixed and neg.dim() == 1:
+            neg = neg.reshape(1, -1)
+        elif neg.shape[0] == n:
             neg = neg.t()
-        elif neg.shape[1] != n:
-            raise ValueError(f"neg must be [{n}, R] or [R, {n}], got {tuple(neg.shape)}")
+        if neg.dim() != 2 or neg.shape[1] != n:
+            raise ValueError(f"neg must be [{n}], [{n}, R] or [R, {n}], got {tuple(neg.shape)}" if mixed else
+                             f"neg must be [{n}, R] or [R, {n}], got {tuple(neg.shape)}")
         R = int(neg.shape[0])
-        if R == 1 and self.loss_kind != 'softmax':
+        if mixed:
+            if not 1 <= R <= self.neg_ratio:
+                raise ValueError(f"--inbatch_mix 1: the batch carries {R} negatives per positive, --neg_ratio is {self.neg_ratio}")
+        elif R == 1 and self.loss_kind != 'softmax':
             return None
-        if not 1 <= R <= _lib.MAX_NEG_RATIO:
+        elif not 1 <= R <= _lib.MAX_NEG_RATIO:
             raise ValueError(f"the negative ratio (neg_ratio) must be in 1..{_lib.MAX_NEG_RATIO}, got {R} negatives per positive")
         return neg.contiguous()
 
-    def _fused_step_multi(self, users, pos, negs, loss_out, lr):
-        """fused_step for R > 1 negatives per positive (negs int32 [R, B]): lgcn_train_step_multi."""
+    def _fused_call(self, entry, args, T, batch_size=None, loss_out=None, lr=None):
+        """What every fused step and epoch does around its C call: the state for max_batch (an epoch's batch_size; a step's T, or
+        --bpr_batch if that is larger), the learning rate, the output -- loss_out [3] of a step, [steps, 3] of an epoch --,
+        `entry`(ctx, *args, output, stream), its check, the cache.  args: the entry point's arguments between the context and
+        the output, or a function of the state that returns them.  Returns the output."""
         dev = self._table.device
-        B = int(users.numel())
-        st = self._state(max_batch=max(B, int(self.config.get('bpr_batch_size', B))), need_ctx=True,
+        epoch = batch_size is not None
+        st = self._state(max_batch=batch_size if epoch else max(T, int(self.config.get('bpr_batch_size', T))), need_ctx=True,
                          dp_world=(self._dev or {}).get('dp_world', 1))
         lib = _lib.load()
         if lr is not None:
             lib.lgcn_ctx_set_lr(st['ctx'], float(lr))
-        if loss_out is None:
+        if epoch:
+            loss_out = torch.empty((T + batch_size - 1) // batch_size, 3, dtype=torch.float32, device=dev)
+        elif loss_out is None:
             loss_out = torch.empty(3, dtype=torch.float32, device=dev)
-        _lib.check(lib.lgcn_train_step_multi(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(negs), B, int(negs.shape[0]), B,
-                                             _lib.tp(loss_out), _lib.current_stream()), "lgcn_train_step_multi")
+        if callable(args):
+            args = args(st)
+        _lib.check(getattr(lib, entry)(st['ctx'], *args, _lib.tp(loss_out), _lib.current_stream()), entry.replace("_i64", ""))
         self.invalidate_cache()
         return loss_out
+
+    def _fused_step_multi(self, users, pos, negs, loss_out, lr):
+        """fused_step for R > 1 negatives per positive (negs int32 [R, B]): lgcn_train_step_multi."""
+        B = int(users.numel())
+        return self._fused_call("lgcn_train_step_multi", (_lib.tp(users), _lib.tp(pos), _lib.tp(negs), B, int(negs.shape[0]), B), B, None, loss_out, lr)
 
     def fused_step(self, users, pos, neg, loss_out=None, lr=None):
         """One BPRLoss.stageOne (utils.py:53-64) in the HIP kernels.  Returns a device
@@ -996,16 +975,13 @@ class LightGCN(nn.Module):
             raise RuntimeError("this configuration of the popularity gate / item-item smoothing is outside the fused step "
                                "(--fused_variants 0, or gate hidden sizes > 64 / d > 128): use BPRLoss.stageOne (autograd path)")
         dev = self._table.device
-        if self.loss_kind == 'inbatch' and self.inbatch_mix:
-            return self._fused_inbatch_mix(users, pos, neg, None, loss_out, lr, False)
-        if self.loss_kind == 'inbatch':        # --loss inbatch: (users, pos) only; neg is accepted and ignored
-            return self._fused_inbatch(users, pos, None, loss_out, lr, False)
+        if self.loss_kind == 'inbatch':        # --loss inbatch: (users, pos) only, neg is accepted and ignored; the pool under --inbatch_mix 1
+            return self._fused_inbatch(users, pos, neg, None, loss_out, lr)
         if self.loss_kind == 'softmax' and self._neg_dim(neg) == 1:      # --loss softmax: every shape is a multi step, R = 1 included
             neg = self._ids(neg, dev).reshape(1, -1)
         if self._neg_dim(neg) == 2:            # several negatives per positive: neg [B, R] (the sampler's S[:, 2:]) or [R, B]
             users, pos = self._ids(users, dev), self._ids(pos, dev)
-            B = int(users.numel())
-            negs = self._negs_rt(neg, B, dev)
+            negs = self._negs_rn(neg, int(users.numel()), dev)
             if negs is not None:
                 return self._fused_step_multi(users, pos, negs, loss_out, lr)
             neg = self._ids(neg, dev).reshape(-1)     # R == 1: the three-slot step, unchanged
@@ -1015,23 +991,15 @@ class LightGCN(nn.Module):
         if not as_i64:
             users, pos, neg = self._ids(users, dev), self._ids(pos, dev), self._ids(neg, dev)
         B = int(users.numel())
-        st = self._state(max_batch=max(B, int(self.config.get('bpr_batch_size', B))), need_ctx=True,
-                         dp_world=(self._dev or {}).get('dp_world', 1))
-        lib = _lib.load()
-        if lr is not None:
-            lib.lgcn_ctx_set_lr(st['ctx'], float(lr))
-        if loss_out is None:
-            loss_out = torch.empty(3, dtype=torch.float32, device=dev)
-        if as_i64:
+        ids = (_lib.tp(users), _lib.tp(pos), _lib.tp(neg), B)
+        if not as_i64:
+            return self._fused_call("lgcn_train_step", ids, B, None, loss_out, lr)
+
+        def with_scratch(st):
             if st.get('ids32') is None or st['ids32'].numel() < 3 * B:
                 st['ids32'] = torch.empty(3 * max(B, st['max_batch']), dtype=torch.int32, device=dev)
-            _lib.check(lib.lgcn_train_step_i64(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(neg), B, _lib.tp(st['ids32']),
-                                               _lib.tp(loss_out), _lib.current_stream()), "lgcn_train_step")
-        else:
-            _lib.check(lib.lgcn_train_step(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(neg), B,
-                                           _lib.tp(loss_out), _lib.current_stream()), "lgcn_train_step")
-        self.invalidate_cache()
-        return loss_out
+            return (*ids, _lib.tp(st['ids32']))
+        return self._fused_call("lgcn_train_step_i64", with_scratch, B, None, loss_out, lr)
 
     def fused_epoch(self, users, pos, neg, batch_size, lr=None):
         """The loop of main.py:223-225 over already-shuffled device id arrays, one C call.
@@ -1039,34 +1007,21 @@ class LightGCN(nn.Module):
         if self.has_variants and not self.fused_variants:
             raise RuntimeError("this configuration of the optional branches is outside the fused step: loop BPRLoss.stageOne")
         dev = self._table.device
-        if self.loss_kind == 'inbatch' and self.inbatch_mix:
-            return self._fused_inbatch_mix(users, pos, neg, int(batch_size), None, lr, True)
-        if self.loss_kind == 'inbatch':        # --loss inbatch: (users, pos) only; neg is accepted and ignored
-            return self._fused_inbatch(users, pos, int(batch_size), None, lr, True)
+        if self.loss_kind == 'inbatch':        # --loss inbatch: (users, pos) only, neg is accepted and ignored; the pool under --inbatch_mix 1
+            return self._fused_inbatch(users, pos, neg, int(batch_size), None, lr)
         users, pos = self._ids(users, dev), self._ids(pos, dev)
+        T = int(users.numel())
         negs = None
         if self.loss_kind == 'softmax' and self._neg_dim(neg) == 1:      # --loss softmax: the multi epoch at R = 1
             neg = self._ids(neg, dev).reshape(1, -1)
         if self._neg_dim(neg) == 2:            # several negatives per positive: neg [T, R] or [R, T]
-            negs = self._negs_rt(neg, int(users.numel()), dev)
-        if negs is None:                       # R == 1 (1-D, or one column): the three-slot epoch, unchanged
-            neg = self._ids(neg, dev).reshape(-1)
-        T = int(users.numel())
-        steps = (T + batch_size - 1) // batch_size
-        st = self._state(max_batch=batch_size, need_ctx=True, dp_world=(self._dev or {}).get('dp_world', 1))
-        lib = _lib.load()
-        if lr is not None:
-            lib.lgcn_ctx_set_lr(st['ctx'], float(lr))
-        losses = torch.empty(steps, 3, dtype=torch.float32, device=dev)
+            negs = self._negs_rn(neg, T, dev)
         if negs is not None:                   # R > 1: the multi-negative epoch (negative column r at negs + r * T)
-            _lib.check(lib.lgcn_train_epoch_multi(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(negs), int(negs.shape[0]), T,
-                                                  int(batch_size), _lib.tp(losses), _lib.current_stream()), "lgcn_train_epoch_multi")
-            self.invalidate_cache()
-            return losses
-        _lib.check(lib.lgcn_train_epoch(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(neg), T, int(batch_size),
-                                        _lib.tp(losses), _lib.current_stream()), "lgcn_train_epoch")
-        self.invalidate_cache()
-        return losses
+            return self._fused_call("lgcn_train_epoch_multi", (_lib.tp(users), _lib.tp(pos), _lib.tp(negs), int(negs.shape[0]), T, int(batch_size)),
+                                    T, batch_size, None, lr)
+        neg = self._ids(neg, dev).reshape(-1)  # R == 1 (1-D, or one column): the three-slot epoch, unchanged
+        return self._fused_call("lgcn_train_epoch", (_lib.tp(users), _lib.tp(pos), _lib.tp(neg), T, int(batch_size)), T, batch_size, None, lr)
+
 
     def check_device_errors(self):
         if self._dev and self._dev.get('ctx'):

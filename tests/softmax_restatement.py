@@ -1,5 +1,5 @@
 """float64 restatement of the fused step under the sampled-softmax loss (--loss softmax; lgcn_ctx_set_loss,
-csrc/lgcn_softmax.hip), in the manner of tests/multineg_restatement.py, whose propagate, adam, make_batches and
+csrc/lgcn_multineg.hip), in the manner of tests/multineg_restatement.py, whose propagate, adam, make_batches and
 graph (tests/storage_cases.py) it uses.  Test infrastructure: tests/test_softmax_host.py pins it (torch autograd, the BPR
 restatement at R = 1 and tau = 1); tests/test_gpu_softmax.py judges the device against it.
 

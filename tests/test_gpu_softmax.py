@@ -1,4 +1,4 @@
-"""The sampled-softmax loss in the fused step (--loss softmax; lgcn_ctx_set_loss, csrc/lgcn_softmax.hip) on the GPU
+"""The sampled-softmax loss in the fused step (--loss softmax; lgcn_ctx_set_loss, csrc/lgcn_multineg.hip) on the GPU
 (-m gpu), on the graph, table rows and batch shapes of tests/storage_cases.py with the batches of tests/multineg_restatement.py,
 against the float64 restatement tests/softmax_restatement.py.  Every step is judged from the GPU's OWN state before the step.
 

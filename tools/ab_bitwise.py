@@ -15,6 +15,13 @@ Cases (cases()):
             (partial lane groups, a partial last workgroup), reg_rows propagated / ego, loss bpr / softmax at tau 0.2 and 1.0;
             loss x R x reg_rows in full at d = 64, every value of every axis at every d (check_coverage); one batch per d with an
             out-of-range negative, and the saturating batch of tests/softmax_restatement.py (m > 0 in the softmax normalisation).
+  inbatch   lgcn_train_step_inbatch: d 32/64/128/256, fp32 / bf16 tables, mean / layer weights, K 1/3, B 1/7/67 (B = 7: 25 padding
+            rows of the 32-row tile; B = 67: three tiles, the last one partial), reg_rows propagated / ego, score dot / cosine,
+            logQ off / on; every value of every axis at every d (check_coverage); one batch with an out-of-range positive (a void
+            sample) and one lgcn_train_epoch_inbatch over T = 2 B + 3 (a short last batch).
+  inbatch_mix  lgcn_train_step_inbatch_mix on a context set to R_max = 16: the axes of inbatch and R 1/2/16 (R < R_max against
+            the one allocation); one batch with an out-of-range negative, one lgcn_train_epoch_inbatch_mix over T = 2 B + 3, and
+            one mixed step followed by plain lgcn_train_step_inbatch steps on the same context.
   mf        lgcn_mf_train_step: d 32/64/128/256, B 1/7/67.
   step      the three-slot lgcn_train_step at d = 64: gathered and dense_last forms, fp32 / bf16 / fp8 tables, and one case each
             with edge dropout, layer weights, the popularity gate and item-item smoothing."""
@@ -33,6 +40,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STEPS = 3
 DS, MODES, WTS, KS, RS, BS, REGS = (32, 64, 128, 256), ("fp32", "bf16"), (False, True), (1, 3), (1, 2, 5, 16), (1, 7, 67), ("propagated", "ego")
 LOSSES = (("bpr", 1.0), ("softmax", 0.2), ("softmax", 1.0))
+SCORES, LOGQS, MIX_RS, MIX_RMAX, IB_TAU = ("dot", "cosine"), (False, True), (1, 2, 16), 16, 0.2
+IB_KINDS = ("inbatch", "inbatch_mix")
 
 
 def cases():
@@ -52,6 +61,15 @@ def cases():
         out.append(dict(kind="multi", d=d, mode=MODES[i % 2], wts=False, K=1, R=5, B=7, reg="propagated", loss=loss, tau=tau, void=3))
     for mode in MODES:                                      # tests/test_gpu_softmax.py::test_saturation_batch's construction
         out.append(dict(kind="multi", d=256, mode=mode, wts=False, K=1, R=4, B=8, reg="propagated", loss="softmax", tau=0.05, saturate=True))
+    for kind in IB_KINDS:
+        for j, d in enumerate(DS):                          # six cases per d that show every value of every axis (R: inbatch_mix only)
+            for i in range(6):
+                out.append(dict(kind=kind, d=d, mode=MODES[(i + j) % 2], wts=WTS[(i // 2) % 2], K=KS[(i // 3) % 2], B=BS[i % 3], reg=REGS[((i + 1) // 2) % 2],
+                                score=SCORES[(i + i // 3) % 2], logq=LOGQS[(i // 2 + j) % 2], R=MIX_RS[(i + i // 3 + j) % 3]))
+        base = dict(kind=kind, d=64, mode="fp32", wts=False, K=3, B=7, reg="propagated", score="cosine", logq=True, R=2)
+        out.append(dict(base, void=3))                      # an out-of-range positive (inbatch) / negative (inbatch_mix)
+        out.append(dict(base, mode="bf16", epoch=True))     # the epoch entry point over T = 2 B + 3
+    out.append(dict(base, B=67, then_plain=True))           # a mixed step, then plain steps on the same context
     out += [dict(kind="mf", d=d, B=B) for d in DS for B in BS]
     for dl in (0, 1):
         out += [dict(kind="step", d=64, mode=mode, K=3, dl=dl, B=67, cfg={}) for mode in ("fp32", "bf16", "fp8")]
@@ -70,6 +88,14 @@ def check_coverage(cs):
             assert {c[key] for c in at} == set(values), (d, key)
         assert {(c["loss"], c["tau"]) for c in at} == set(LOSSES), d
     assert {(c["loss"], c["tau"], c["R"], c["reg"]) for c in multi if c["d"] == 64} == set((l, t, R, g) for (l, t), R, g in itertools.product(LOSSES, RS, REGS))
+    for kind in IB_KINDS:
+        plain = [c for c in cs if c["kind"] == kind and not (c.get("void") or c.get("epoch") or c.get("then_plain"))]
+        for d in DS:
+            at = [c for c in plain if c["d"] == d]
+            for key, values in (("mode", MODES), ("wts", WTS), ("K", KS), ("B", BS), ("reg", REGS), ("score", SCORES), ("logq", LOGQS)) + ((("R", MIX_RS),) if kind == "inbatch_mix" else ()):
+                assert {c[key] for c in at} == set(values), (kind, d, key)
+        for tag, n in (("void", 1), ("epoch", 1), ("then_plain", int(kind == "inbatch_mix"))):
+            assert sum(1 for c in cs if c["kind"] == kind and c.get(tag)) == n, (kind, tag)
 
 
 def name(c):
@@ -77,6 +103,10 @@ def name(c):
         tag = "-void" if c.get("void") else "-saturate" if c.get("saturate") else ""
         return (f"multi-d{c['d']}-{c['mode']}-{'wts' if c['wts'] else 'mean'}-K{c['K']}-R{c['R']}-B{c['B']}-{c['reg']}-{c['loss']}"
                 + (f"{c['tau']}" if c["loss"] == "softmax" else "") + tag)
+    if c["kind"] in IB_KINDS:
+        tag = "-void" if c.get("void") else "-epoch" if c.get("epoch") else "-then-plain" if c.get("then_plain") else ""
+        return (f"{c['kind']}-d{c['d']}-{c['mode']}-{'wts' if c['wts'] else 'mean'}-K{c['K']}-B{c['B']}-{c['reg']}-{c['score']}-{'logq' if c['logq'] else 'nologq'}"
+                + (f"-R{c['R']}of{MIX_RMAX}" if c["kind"] == "inbatch_mix" else "") + tag)
     if c["kind"] == "mf":
         return f"mf-d{c['d']}-B{c['B']}"
     return f"step-d{c['d']}-{c['mode']}-K{c['K']}-dl{c['dl']}" + "".join(f"-{k}" for k in c["cfg"] if k in ("dropout", "layer_weights", "use_pop_gate", "use_item_item"))
@@ -101,6 +131,11 @@ def child(out_path):
         B = c["B"]
         if c["kind"] == "mf":
             w = SC.configure(pkg, ("fp32", c["d"], 1, 1, -1, "propagated"), path, 64)
+        elif c["kind"] in IB_KINDS:
+            w = SC.configure(pkg, (c["mode"], c["d"], c["K"], 1, -1, c["reg"]), path, 64)
+            w.config.update({'loss': 'inbatch', 'softmax_temp': IB_TAU, 'score': c["score"], 'inbatch_logq': int(c["logq"])}, **({'layer_weights': 'exp'} if c["wts"] else {}))
+            if c["kind"] == "inbatch_mix":
+                w.config.update({'inbatch_mix': 1, 'neg_ratio': MIX_RMAX})
         elif c["kind"] == "multi":
             w = SC.configure(pkg, (c["mode"], c["d"], c["K"], 1, -1, c["reg"]), path, 64)
             w.config.update({'neg_ratio': c["R"], 'loss': c["loss"], 'softmax_temp': c["tau"]}, **({'layer_weights': 'exp'} if c["wts"] else {}))
@@ -120,17 +155,31 @@ def child(out_path):
             assert (zs > 100.0).any() and (zs < -100.0).all(1).any(), "the saturating batch no longer reaches the m > 0 branch"
         m = m.to(dev)
         m.train()
-        losses = []
-        for _ in range(STEPS):
-            u, p = rng.integers(1, SC.N_USERS, B), rng.integers(1, SC.M_ITEMS, B)
-            n = rng.integers(1, SC.M_ITEMS, (B, c["R"]) if c["kind"] == "multi" else B)
+        losses, held = [], []
+        T = 2 * B + 3 if c.get("epoch") else B              # an epoch case: ONE call of three batches, the last one short
+        for step in range(1 if c.get("epoch") else STEPS):
+            u, p = rng.integers(1, SC.N_USERS, T), rng.integers(1, SC.M_ITEMS, T)
+            n = rng.integers(1, SC.M_ITEMS, (T, c["R"]) if c["kind"] in ("multi", "inbatch_mix") else T)
             for a in (p, n):                                 # as tests/storage_cases.make_batches: no slot names these two rows
                 a[(a == SC.BIG_ITEM) | (a == SC.ISOLATED_ITEM)] = 20
             if c.get("saturate"):
                 u, p, n = sat
-            if c.get("void"):
+            if c.get("void") and c["kind"] == "inbatch":
+                p[c["void"]] = SC.M_ITEMS
+            elif c.get("void"):
                 n[c["void"], c["R"] - 1] = SC.M_ITEMS
-            if c["kind"] == "multi":                         # R = 1 under --loss bpr included: the batch-row launch, not the three-slot step
+            if c.get("epoch"):
+                losses = list(m.fused_epoch(ids(u), ids(p), ids(n.T), B))
+            elif c.get("then_plain") and step > 0:           # mixing is set on the context: the plain entry point, called directly
+                held.append((ids(u), ids(p), torch.empty(3, dtype=torch.float32, device=dev)))      # (the launches read them after the call returns)
+                du, dp, out = held[-1]
+                pkg._lib.check(pkg._lib.load().lgcn_train_step_inbatch(m._dev['ctx'], pkg._lib.tp(du), pkg._lib.tp(dp), B, pkg._lib.tp(out), pkg._lib.current_stream()),
+                               "lgcn_train_step_inbatch")
+                m.invalidate_cache()
+                losses.append(out)
+            elif c["kind"] == "inbatch_mix":
+                losses.append(m.fused_step(ids(u), ids(p), ids(n.T)))
+            elif c["kind"] == "multi":                         # R = 1 under --loss bpr included: the batch-row launch, not the three-slot step
                 losses.append(m._fused_step_multi(ids(u), ids(p), ids(n.T), None, None))
             else:
                 losses.append(m.fused_step(ids(u), ids(p), ids(n)))
