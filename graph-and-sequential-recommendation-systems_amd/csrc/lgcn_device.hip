@@ -1,5 +1,7 @@
 // lgcn_device.hip -- hand-written gfx950 (CDNA4, wave64) kernels of the LightGCN/BPR
-// training hot path and their C-ABI launchers (include/lgcn_hip.h).
+// training hot path: kernels and their launchers (lgcn_kernels.h).  The host side -- the graph
+// object and its plan, the training context and the step driver -- is lgcn_graph.cpp and
+// lgcn_train.cpp; build.kernel_hash() is the hash of this file.
 //
 // The path is sparse and HBM/cache-bandwidth bound (<= 0.5 flop/byte): no MFMA.
 // What matters here: 16-byte (fp32) / 8-byte (bf16) per-lane row gathers that
@@ -26,15 +28,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include <math.h>
-#include <algorithm>
-#include <array>
-#include <new>
-#include <vector>
 
-#include "lgcn_device_common.h"
+#include "lgcn_device_common.h"      // (through lgcn_internal.h: lgcn_kernels.h, the args structs and the constants the host shares)
 
 typedef __attribute__((ext_vector_type(8))) float f32x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
@@ -56,10 +52,6 @@ struct fp8_t { uint8_t v; };
 __host__ __device__ __forceinline__ int fp8_byte_of_col(int c, int D) { const int L = D / 16, q = c >> 2; return (q % L) * 16 + 4 * (q / L) + (c & 3); }
 __device__ __forceinline__ const float *fp8_scales(const void *tab, int64_t n_rows, int D) { return (const float *)((const char *)tab + n_rows * D); }
 __device__ __forceinline__ float *fp8_scales(void *tab, int64_t n_rows, int D) { return (float *)((char *)tab + n_rows * D); }
-
-#ifndef LGCN_GATHER_U
-#define LGCN_GATHER_U 8      /* max row gathers in flight per lane (8 x 16 B raw = 32 VGPRs) */
-#endif
 
 // C fp32 values per lane (C = 4: 16 B of fp32 / 8 B of bf16; C = 8: 32 B of fp32 / 16 B of bf16)
 template <int C> struct VecF;
@@ -190,9 +182,8 @@ template <int C> __device__ __forceinline__ typename VecF<C>::T loadv_fixed(cons
 // 32-bit multiplies, shifts and xors on the VALU (about two dozen instructions per staged entry, five of them multiplies), no table, no LDS.  The mask is applied
 // where an entry is STAGED (tile_stage's callers, the pack path of k_spmm): its weight becomes val * (1 / keep_prob) or zero;
 // gather loops, epilogues and the chunk hand-off never see it.  tr: the launch computes A_drop^T h (backward), where the
-// entry stored at (row, col) stands for A_drop[col, row] and carries keep(col, row).
+// entry stored at (row, col) stands for A_drop[col, row] and carries keep(col, row).  (DropArgs: lgcn_kernels.h)
 // ---------------------------------------------------------------------------------
-struct DropArgs { uint32_t k0, k1, thr; float inv; int32_t tr; int32_t on; };
 __host__ __device__ __forceinline__ uint32_t drop_fmix32(uint32_t h) {
     h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
     return h;
@@ -414,91 +405,8 @@ row_gather(const ES &es, int64_t start, int64_t end, const GatherSrc &src, int l
     return reduce_groups<G::LPR>(acc);
 }
 
-// ---------------------------------------------------------------------------------
-// Work plan of one graph (built on the host at lgcn_graph_create).
-//
-// The processing order of the rows is cut into 8 slices, one per XCD (hardware deals
-// workgroups round-robin over the 8 XCDs -- speed-only observation -- so block b works on
-// slice b & 7).  A slice's rows mostly gather rows of the same part of the graph
-// (reorder.py), so the part of the table an XCD touches is a fraction of the whole and
-// lives in that XCD's 4 MiB L2.  Inside a slice:
-//   * rows with more than LONG_T (= one 64-entry tile) non-zeros run as independent waves at
-//     the FRONT of the slice (they start first: their serial tile walk overlaps everything
-//     else).  Rows up to LONG_CH non-zeros are finished by one wave; longer rows are cut into
-//     chunks of LONG_CH (a single wave walking Gowalla's 1415-nnz row = 23 serial tiles was
-//     the critical path = the entire 57 us of an un-split launch): each chunk writes a partial
-//     row and takes a ticket, and the LAST arriver sums the partials in chunk order (fixed
-//     order: bitwise reproducible whoever is last) and runs the epilogue.  The hand-off is not
-//     free (write-through stores, a drain, an atomic round trip, an L1 invalidate), which is
-//     why the chunk is 512 and not one tile.  Long rows stay in the slice of their part of the
-//     graph: they are 29 % of Gowalla's non-zeros, and dealt round-robin over the XCDs (round 1)
-//     they alone produced half of the L2 misses.
-//   * the other rows go NPW at a time per wave, ONE ROW PER LANE GROUP (NPW = 64 / lanes per row:
-//     4 fp32 rows or 8 bf16 rows at d = 64), 4 waves per workgroup, in order.  The plan sorts every
-//     window of SHORT_WIN consecutive short rows by length, so the rows of a pack are about equally
-//     long (the window is far smaller than what an XCD has in flight: locality is unaffected).
-// ---------------------------------------------------------------------------------
-#define LONG_T 64             /* rows with more non-zeros than one tile leave the short path */
-#define SLICE_PAD 64          /* short rows of a slice are padded to a multiple of this (>= rows per workgroup of every variant) */
-#ifndef SHORT_WIN
-#define SHORT_WIN 2048        /* window of the length sort (measured 128 / 512 / 1024 / 2048 / 4096 / 8192: 6082 / 6330 / 6403 / 6400 / 6378 / 6329 steps/s) */
-#endif
-#ifndef LONG_CH
-#define LONG_CH 512           /* measured on Gowalla: 64 -> 58 us, 128 -> 40, 256 -> 34, 512 -> 32.5, 768 -> 39, none -> 57 */
-#endif
-#define XCDS 8
-// The (col,val) pairs of the planned rows are kept a second time as ONE packed stream of 8-byte entries in
-// plan order (chunks of a slice, then its short rows): the rows of a pack are contiguous there, so a wave
-// loads a whole pack's index tiles with one or two 512-byte instructions instead of two 4-byte loads per
-// row.  What bounds these kernels is the number of vector-memory instructions a CU retires (a 13-lane index
-// load holds its address/return path as long as a 64-lane 1-KiB row gather, 26-30 cycles per instruction
-// measured on both the fp32 and the bf16 table), so every instruction saved is time saved.
-struct LongPlan {
-    const int4 *chunks;           // [n_chunk_slots] (index o into long_row | -1 = padding, first entry, end entry in the stream, ordinal in row)
-    const int32_t *long_row;      // [n_long] row ids with nnz > LONG_T
-    const int32_t *long_nch;      // [n_long] chunks of that row
-    float *partials;              // [n_chunk_slots, D]  (slot = position in `chunks`)
-    int32_t *counters;            // [n_long] arrival tickets (zero between launches)
-    int32_t n_long, n_chunk_slots;
-};
-struct SlicePlan {                // per XCD slice x: chunk blocks [cblk[x], cblk[x+1]) then short rows [rows[x], rows[x+1]) of rowinfo
-    int32_t cblk[XCDS + 1];
-    int32_t rows[XCDS + 1];       // multiples of SLICE_PAD
-};
-
-struct SpmmArgs {
-    const int2 *pk;               // packed (col, val bits) stream in plan order
-    const int4 *rowinfo;          // short rows of the slices, padded per slice: (row | -1, first entry in the stream, count, 0)
-    LongPlan lp; SlicePlan sp;
-    const void *X; void *Y;
-    int64_t n_rows;               // rows of X (picks 32- or 64-bit gather offsets)
-    long long *G64; uint32_t *bitmap; float div;   // sparse gradient rows (fixed point), K+1
-    const float *G32;             // their fp32 copy Gs = G64 / 2^50 / (K+1), valid on the flagged rows (k_g32)
-    float *P; float *M; float *V;
-    bf16_t *Pb;                   // optional bf16 shadow of P written by the Adam epilogue
-    void *Pq;                     // optional fp8 shadow of P (rows + scales), same
-    // last kernel of a step (K >= 2): its epilogue zeroes the G64 rows / bitmap bits it consumes and one
-    // wave reduces the per-triplet loss terms, so no separate clean-up launch is needed
-    int clear;
-    const float *terms; const float *gathered; float *loss_out; int32_t B, shard; float decay;
-    float ent_coeff;              // popularity gate: coefficient of the gates' entropy term in the loss (0: no gate)
-    int64_t blk;                  // data parallel: floats per rank in `gathered` (0: the default layout 3*shard*D + 2*shard)
-    float step_size, bc2_sqrt, w1, beta2, omb2, eps;
-    int remap;
-    const float *selfX;           // M_ADDSELF: Y[row] = selfX[row] + (A X)[row]  (item-item smoothing, model.py:228-229)
-    int32_t *cnt; float lam;      // reg_ego: slots of the batch naming each row (zeroed as consumed), decay / B: grad += lam * cnt[row] * P[row]
-    DropArgs dr;                  // edge dropout of the step (dr.on: the DROP instantiation is launched); behind the older fields, so that every one of them keeps its offset
-    float w_in, w_add;            // M_WTS launches only (layer weights): Y = w_add * G[row] + w_in * (A X)[row]
-};
-
-enum { M_SPARSE = 1, M_ADDG = 2, M_ADAM = 4, M_ADDSELF = 8, M_WTS = 16 };
-
-//   M_ADDG  : add Gs[row] where flagged (Horner term)
-//   M_ADAM  : apply torch.optim.Adam to P/M/V with grad = result, else store to Y
-//   M_WTS   : layer weights are set (lgcn_ctx_set_layer_weights): G32 holds the UNSCALED gradient rows and the launch carries the
-//             two coefficients of its Horner step, h_{k-1} = w_{k-1} G + A h_k with h_K = w_K G.  The first backward layer gathers
-//             G itself, so its product takes w_in = w_K and its Horner term w_add = w_{K-1}; every later layer has w_in = 1.
-//             A MODE bit and not a run-time test: the instantiations without it are what they were
+// (The work plan of a graph -- its slices, long-row chunks and packed stream -- with LongPlan, SlicePlan, SpmmArgs and the M_* mode
+//  bits of k_spmm: lgcn_kernels.h, beside the constants the plan builder reads.)
 // Adam's operands of one row piece, fetched under the LAST gather batch of a pack (see pack_batch)
 template <int C> struct AdamPre { typename VecF<C>::T p, m, v; bool have; };
 
@@ -1005,12 +913,6 @@ __global__ void __launch_bounds__(64 * SPMM_WPB, sizeof(TI) == 1 ? 4 : ((MODE & 
 // out = (X_0 + X_1 + ... + X_{K-1} + out) / (K+1), `out` holding X_K on entry -- the stack + mean of
 // computer() (model.py:221-222) as one streaming pass.  The K-th layer itself runs through k_spmm
 // like the others, so evaluation gets the split long rows too.
-struct MeanArgs {
-    const float *X0; const void *Xl[LGCN_MAX_LAYERS + 1]; int K;
-    float *out; int64_t n4;      // number of 4-element pieces
-    int32_t d; int64_t N;        // row width and rows of the tables (fp8 tables: where a piece's row scale lies)
-    float w[LGCN_MAX_LAYERS + 1];   // WTS instantiations only (lgcn_propagate_weighted): out = sum_k w[k] X_k
-};
 // piece i (4 consecutive elements) of an [N,d] table of TI
 template <typename TI> __device__ __forceinline__ f32x4 tab_load4(const void *tab, int64_t i, int d, int64_t N) { return load4((const TI *)tab + i * 4); }
 template <> __device__ __forceinline__ f32x4 tab_load4<fp8_t>(const void *tab, int64_t i, int d, int64_t N) {
@@ -1038,6 +940,16 @@ __global__ void __launch_bounds__(256) k_layer_mean(MeanArgs a) {
         }
     }
 }
+void lgcn_layer_mean_launch(const MeanArgs &m, int act_dtype, bool wts, hipStream_t st) {
+    const int64_t blocks = (m.n4 + 255) / 256;
+    const unsigned grid = (unsigned)(blocks < 2048 ? blocks : 2048);
+    if (wts) {          // (no fp8 form: lgcn_propagate_weighted refuses it)
+        if (act_dtype == LGCN_F32) hipLaunchKernelGGL((k_layer_mean<float, true>), dim3(grid), dim3(256), 0, st, m);
+        else hipLaunchKernelGGL((k_layer_mean<bf16_t, true>), dim3(grid), dim3(256), 0, st, m);
+    } else if (act_dtype == LGCN_F32) hipLaunchKernelGGL((k_layer_mean<float>), dim3(grid), dim3(256), 0, st, m);
+    else if (act_dtype == LGCN_BF16) hipLaunchKernelGGL((k_layer_mean<bf16_t>), dim3(grid), dim3(256), 0, st, m);
+    else hipLaunchKernelGGL((k_layer_mean<fp8_t>), dim3(grid), dim3(256), 0, st, m);
+}
 
 // bf16 copy of the parameter table: with bf16 activation storage (K >= 2) layer 1 gathers THIS instead of the fp32
 // rows -- every SpMM input is then a 2-byte table.  Made at the start of a training call and kept current by the
@@ -1060,7 +972,7 @@ __global__ void __launch_bounds__(256) k_to_fp8(const float *src, void *dst, int
         else { float amax = 0.f; for (int o = 1; o < LPR; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o)); }   // (keep the group's shuffles matched)
     }
 }
-static int launch_to_fp8(const float *src, void *dst, int64_t n_rows, int d, hipStream_t st) {
+int lgcn_to_fp8_launch(const float *src, void *dst, int64_t n_rows, int d, hipStream_t st) {
     const int64_t blocks = (n_rows * (d / 16) + 255) / 256;
     const unsigned grid = (unsigned)(blocks < 8192 ? (blocks > 0 ? blocks : 1) : 8192);
     switch (d) {
@@ -1071,7 +983,7 @@ static int launch_to_fp8(const float *src, void *dst, int64_t n_rows, int d, hip
     lgcn_set_error("fp8 storage needs an embedding dim of 64, 128 or 256");
     return 3;
 }
-static void launch_to_bf16(const float *src, bf16_t *dst, int64_t n, hipStream_t st) {
+void lgcn_to_bf16_launch(const float *src, bf16_t *dst, int64_t n, hipStream_t st) {
     const int64_t n4 = n / 4, blocks = (n4 + 255) / 256;
     hipLaunchKernelGGL(k_to_bf16, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, src, dst, n4);
 }
@@ -1089,42 +1001,8 @@ static void launch_to_bf16(const float *src, bf16_t *dst, int64_t n, hipStream_t
 //   (Round 1/2 history: one workgroup per SLOT + a loss launch = 24.6K waves of which 18K ended after reading
 //   two indices; the launch skeleton alone -- ids, indptr, nothing else -- measured 7.3 of its 16.7 us, and
 //   the slot rows made a round trip through HBM to the 6.7 us loss launch.)
-// k_triplet_dense: the same when the last layer was propagated densely (cfg.dense_last).
+// k_triplet_dense: the same when the last layer was propagated densely (cfg.dense_last).  (BprArgs: lgcn_kernels.h)
 // ---------------------------------------------------------------------------------
-struct BprArgs {
-    const int32_t *indptr; const int32_t *indices; const float *vals;
-    const float *X0; const void *Xl[LGCN_MAX_LAYERS + 1]; int K;
-    int32_t n_users; int64_t N;
-    const int32_t *users; const int32_t *pos; const int32_t *neg;   // already offset to the local shard
-    int32_t B_local;      // triplets handled by this launch
-    int32_t shard;        // row stride of the contrib block (>= B_local)
-    float inv_B;          // 1 / global batch
-    float lam;            // decay / global batch
-    long long *G64;       // if non-null: atomics
-    uint32_t *bitmap;
-    uint32_t *stale_bitmap; int64_t bitmap_words;   // last step's bitmap: zeroed here (plain stores)
-    uint32_t *item_bitmap;  // item-item smoothing: bit i = item i is named by the batch (or NULL)
-    float *contrib;       // exchange block [3*shard*D | shard | shard] (data parallel)
-    int32_t exchange;     // write the gradient rows and loss terms to `contrib` (instead of / besides the atomics)
-    const float *Xhub; int32_t hub_nnz;     // rows with more than hub_nnz non-zeros: X_K[row] is read from Xhub (0: none)
-    float *terms;         // atomics mode: [2*terms_stride] (loss terms | reg terms), this launch at terms_off
-    int32_t terms_off, terms_stride;
-    int32_t *err;
-    int32_t dense_last;   // X_K exists densely (Xl[K]): the slot rows are read, not gathered
-    int32_t reg_ego;      // L2 term on the tables' own rows X0[row] (upstream LightGCN) instead of the propagated rows (the fork)
-    int32_t *cnt;         // reg_ego: per-row count of the batch slots naming the row (bumped where the row is flagged), or NULL
-    // column-sharded data parallelism: this rank holds D of the table's columns.  cols_phase 1: the batch-row kernel stops after
-    // the slot rows -- it writes them to erows [3][B_local][D] and the PARTIAL dot products / squared norms over its columns to
-    // colsum [3][B_local] (pos score, neg score, reg term); the ranks all-reduce colsum; k_cols_finish does the rest.
-    int32_t cols_phase; float *erows; float *colsum;
-    DropArgs dr;          // edge dropout of the step (dr.on: k_triplet's DROP instantiation gathers the last layer); behind the older fields: their offsets stay
-    float w[LGCN_MAX_LAYERS + 1];   // WTS instantiations only (layer weights): slot row e = sum_k w[k] X_k[row] instead of the mean
-    // The fold of k_g32 into this launch (lgcn_train_epoch's single-GPU steps): mult != NULL.  mult[c * B_local + b]
-    // = slots of THIS batch that name slot (c, b)'s row (k_slot_mult, once per call); the workgroup that completes a row writes
-    // its fp32 copy G32[row] = (float)(G64[row] * 2^-50) / gdiv itself.  arrive: [N] arrival tickets of the shared rows, zero between steps
-    const uint16_t *mult; float *G32; float gdiv; int32_t *arrive;
-};
-
 __device__ __forceinline__ bool triplet_bad(const BprArgs &a, int b) {
     const int u = a.users[b], p = a.pos[b], n = a.neg[b];
     return u < 0 || u >= a.n_users || p < 0 || (int64_t)p + a.n_users >= a.N || n < 0 || (int64_t)n + a.n_users >= a.N;
@@ -1263,13 +1141,6 @@ __device__ __forceinline__ void triplet_finish(const BprArgs &a, int b, int l, c
     if (a.G64 && !tbad && a.mult) fold_close_rows<D>(a, rows, mm, l);
 }
 
-#ifndef TRIPLET_HUB_NNZ
-#define TRIPLET_HUB_NNZ 131072  /* rows longer than this get their last-layer row from the hub plan (whole chip) instead of one workgroup
-                                  (10M x 1M graph, ms per step: off 264, 8192: 242, 32768: 236, 65536: 239, 131072: 228, 262144: 231, 524288: 244) */
-#endif
-#ifndef TRIPLET_HUB_CHUNK
-#define TRIPLET_HUB_CHUNK 2048   /* non-zeros per chunk of the hub plan's rows */
-#endif
 #ifndef TRIPLET_MIN_WAVES
 #define TRIPLET_MIN_WAVES 4    /* bf16 tables: a 64-VGPR cap spills (7290 vs 7610 steps/s); fp32 tables fit 64 without (8 workgroups per CU, +0.4 %) */
 #endif
@@ -1484,6 +1355,44 @@ __global__ void __launch_bounds__(256) k_cols_finish(BprArgs a) {
     triplet_finish<D>(a, b, l, e[0], e[1], e[2], a.colsum[b], a.colsum[a.B_local + b], a.colsum[2 * a.B_local + b]);
 }
 
+// The instantiations of the batch-row launch for one width and table type.  The holes are the launcher's: an fp8 table has no
+// DROP and no WTS form, WTS and DROP never meet (the setters refuse the pair; WTS comes first), the dense form has neither a
+// BIG nor a DROP axis.
+template <int D, typename TI, bool DROP, bool WTS>
+static void launch_triplet_gathered(const BprArgs &a, bool big, hipStream_t st) {
+    const dim3 grid(a.B_local), block(64 * TripletGeo<TI>::NW);
+    if (big) hipLaunchKernelGGL((k_triplet<D, TI, true, DROP, WTS>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_triplet<D, TI, false, DROP, WTS>), grid, block, 0, st, a);
+}
+template <int D, typename TI>
+static void launch_triplet_t(const BprArgs &a, bool wts, bool big, hipStream_t st) {
+    constexpr bool AXES = sizeof(TI) != 1;          // fp8: the plain instantiations only
+    if (a.dense_last) {
+        constexpr int tpb = 256 / (D < 64 ? D : 64);
+        const dim3 grid((unsigned)((a.B_local + tpb - 1) / tpb));
+        if constexpr (AXES) if (wts) { hipLaunchKernelGGL((k_triplet_dense<D, TI, true>), grid, dim3(256), 0, st, a); return; }
+        hipLaunchKernelGGL((k_triplet_dense<D, TI>), grid, dim3(256), 0, st, a);
+        return;
+    }
+    if constexpr (AXES) {
+        if (wts) return launch_triplet_gathered<D, TI, false, true>(a, big, st);
+        if (a.dr.on) return launch_triplet_gathered<D, TI, true, false>(a, big, st);      // edge dropout: the last layer's gathers take the step's mask
+    }
+    launch_triplet_gathered<D, TI, false, false>(a, big, st);
+}
+int lgcn_triplet_launch(const BprArgs &a, int d, int act_dtype, bool wts, bool big, hipStream_t st) {
+    DISPATCH_D(d, {
+        if (a.cols_phase == 2) {      // column shard, after the all-reduce: loss terms + gradient scatter from the stored slot rows
+            const int tpb = 256 / (D < 64 ? D : 64);
+            hipLaunchKernelGGL((k_cols_finish<D>), dim3((unsigned)((a.B_local + tpb - 1) / tpb)), dim3(256), 0, st, a);
+        } else if (act_dtype == LGCN_FP8) {
+            if constexpr (D >= 64) launch_triplet_t<D, fp8_t>(a, wts, big, st);
+        } else if (act_dtype == LGCN_F32) launch_triplet_t<D, float>(a, wts, big, st);
+        else launch_triplet_t<D, bf16_t>(a, wts, big, st);
+    });
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------
 // The fork's optional branches in the fused step.
 //
@@ -1501,28 +1410,7 @@ __global__ void __launch_bounds__(256) k_cols_finish(BprArgs a) {
 // gradients summed in two deterministic stages: per workgroup over its slots (phase 2 below, fixed slot order),
 // then over the workgroups in index order inside k_gate_adam, which also applies torch.optim.Adam to the MLP parameters.
 // ---------------------------------------------------------------------------------
-#define GATE_TPB 8            /* triplets per workgroup (two per wave) */
 #define GATE_S (2 * GATE_TPB) /* item slots per workgroup */
-#define GATE_HMAX 64          /* pop_hidden, gate_hidden <= 64 (lane = hidden unit) */
-struct GateArgs {
-    const float *E;               // [N,d] final propagated table (layer mean, item-item smoothing applied)
-    const float *item_pop;        // [m_items]
-    const float *params;          // flat: W1[Hp] b1[Hp] W2[d*Hp] b2[d] V1[Hg*2d] c1[Hg] V2[Hg] c2[1]  (torch.nn.Linear layouts)
-    long long *partials;          // [grid, P] per-workgroup parameter-gradient sums, FIXED POINT (2^50): every slot's contribution is
-                                  // converted before it is added, so the total is independent of how slots fall into workgroups and
-                                  // ranks (integer sums are associative) -- the data-parallel step equals the single-GPU step bit for bit
-    int32_t Hp, Hg, P;
-    float inv_temp, ent_scale;    // 1 / pop_gate_temp ; gate_entropy_coeff / (2 B)
-    int32_t n_users; int64_t N;
-    const int32_t *users; const int32_t *pos; const int32_t *neg;
-    int32_t B; float inv_B, lam;
-    long long *G64; uint32_t *bitmap; uint32_t *item_bitmap;      // item_bitmap: bit i = item i named by the batch (or NULL)
-    uint32_t *stale_bitmap; int64_t bitmap_words;
-    float *terms; int32_t terms_stride;
-    int32_t *err;
-    float *contrib; int32_t shard; int32_t exchange;   // data parallel: gradient rows and loss terms of this rank's shard go to the exchange
-                                                        // block [3*shard*D | shard | shard | shard] (besides / instead of the atomics)
-};
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -1716,15 +1604,24 @@ static size_t gate_lds_bytes(int D) {
                     + (size_t)GATE_S * 2 * D + 2 * GATE_S * GATE_HMAX + (size_t)GATE_S * D + 2 * GATE_S * GATE_HMAX + 2 * GATE_S;
     return fl * sizeof(float);
 }
+int lgcn_gate_launch(const GateArgs &g, int d, hipStream_t st) {
+    const unsigned grid = (unsigned)((g.B + GATE_TPB - 1) / GATE_TPB);
+    const size_t lds = gate_lds_bytes(d);
+    switch (d) {
+    case 32: HIP_OK(hipFuncSetAttribute((const void *)k_triplet_gate<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+             hipLaunchKernelGGL((k_triplet_gate<32>), dim3(grid), dim3(256), lds, st, g); break;
+    case 64: HIP_OK(hipFuncSetAttribute((const void *)k_triplet_gate<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+             hipLaunchKernelGGL((k_triplet_gate<64>), dim3(grid), dim3(256), lds, st, g); break;
+    case 128: HIP_OK(hipFuncSetAttribute((const void *)k_triplet_gate<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+             hipLaunchKernelGGL((k_triplet_gate<128>), dim3(grid), dim3(256), lds, st, g); break;
+    default: lgcn_set_error("popularity gate: embedding dim must be 32, 64 or 128"); return 3;
+    }
+    return 0;
+}
 
 // sum of the fixed-point partial sums (of the workgroups on one GPU; of the ranks' totals in the exchange blocks under data
 // parallelism -- integer sums: any grouping gives the same bits) + torch.optim.Adam on the MLP parameters (same arithmetic as
 // spmm_epilogue's); grad_out keeps the reduced gradient (tests, inspection)
-struct GateAdamArgs {
-    const long long *src; int32_t n_src; int64_t stride; int32_t P;      // n_src vectors of P sums, `stride` int64 apart
-    float *params, *m, *v, *grad_out;
-    float step_size, bc2_sqrt, w1, beta2, omb2, eps;
-};
 __global__ void __launch_bounds__(256) k_gate_adam(GateAdamArgs a) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.P) return;
@@ -1753,13 +1650,15 @@ __global__ void __launch_bounds__(256) k_gate_rank_total(const long long *partia
     for (int w = 0; w < n_part; w++) q += partials[(int64_t)w * P + i];
     out[i] = q;
 }
+void lgcn_gate_adam_launch(const GateAdamArgs &a, hipStream_t st) {
+    hipLaunchKernelGGL(k_gate_adam, dim3((unsigned)((a.P + 255) / 256)), dim3(256), 0, st, a);
+}
+void lgcn_gate_rank_total_launch(const long long *partials, int32_t n_part, int32_t P, long long *out, hipStream_t st) {
+    hipLaunchKernelGGL(k_gate_rank_total, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, partials, n_part, P, out);
+}
 
 // T = mean of the K+1 layers (the stack + mean of computer(), model.py:221-222): user rows to out_u, item rows to out_i
 // (two destinations: with item-item smoothing the item block is an SpMM input and its result lands beside the users)
-struct MeanSplitArgs {
-    const float *X0; const void *Xl[LGCN_MAX_LAYERS + 1]; int K;
-    float *out_u, *out_i; int64_t n4_users, n4;      // 4-element pieces: of the user block, of the whole table
-};
 template <typename TI>
 __global__ void __launch_bounds__(256) k_mean_layers(MeanSplitArgs a) {
     const float div = (float)(a.K + 1);
@@ -1779,6 +1678,16 @@ __global__ void __launch_bounds__(256) k_flag_range(uint32_t *bm, int64_t lo, in
         if (m == 0xffffffffu) bm[wd] = m; else if (m) atomicOr(bm + wd, m);
     }
 }
+void lgcn_mean_layers_launch(const MeanSplitArgs &m, int act_dtype, hipStream_t st) {
+    const int64_t blocks = (m.n4 + 255) / 256;
+    const unsigned grid = (unsigned)(blocks < 2048 ? blocks : 2048);
+    if (act_dtype == LGCN_F32) hipLaunchKernelGGL((k_mean_layers<float>), dim3(grid), dim3(256), 0, st, m);
+    else hipLaunchKernelGGL((k_mean_layers<bf16_t>), dim3(grid), dim3(256), 0, st, m);
+}
+void lgcn_flag_range_launch(uint32_t *bm, int64_t lo, int64_t hi, hipStream_t st) {
+    const int64_t words = (hi + 31) / 32;         // (of the whole bitmap up to hi: 64 workgroups at the most)
+    hipLaunchKernelGGL(k_flag_range, dim3((unsigned)((words + 255) / 256 < 64 ? (words + 255) / 256 : 64)), dim3(256), 0, st, bm, lo, hi);
+}
 
 // slot -> destination row of the global batch (-1: the slot's triplet has a bad id)
 __device__ __forceinline__ int64_t slot_row(int c, int b, const int32_t *users, const int32_t *pos,
@@ -1787,20 +1696,6 @@ __device__ __forceinline__ int64_t slot_row(int c, int b, const int32_t *users, 
     if (u < 0 || u >= n_users || p < 0 || (int64_t)p + n_users >= N || n < 0 || (int64_t)n + n_users >= N) return -1;
     return c == 0 ? (int64_t)u : (int64_t)(c == 1 ? p : n) + n_users;
 }
-
-struct SlotArgs {
-    const int32_t *users; const int32_t *pos; const int32_t *neg;
-    int32_t B; int32_t n_users; int64_t N;
-    long long *G64; uint32_t *bitmap;
-    float *G32; float div;                                 // k_g32: fp32 copy of the flagged rows, K+1
-    const float *gathered; int32_t shard; int32_t world;   // DP scatter
-    int32_t skip_rank;                                     // DP scatter: this rank's own block is in G64 already (-1: none)
-    const float *terms; float *loss_out; float decay;
-    float ent_coeff;
-    int64_t blk;                                           // floats per rank in `gathered` (0: default layout)
-    uint32_t *item_bitmap;                                 // DP scatter with item-item smoothing: items named by the global batch
-    int32_t *cnt;                                          // reg_ego: per-row slot counts (k_scatter / k_flag_rows bump, k_finish clears), or NULL
-};
 
 // DP: order-independent scatter of every rank's gradient rows into G64 (+ row flags)
 template <int D>
@@ -1848,13 +1743,6 @@ __global__ void __launch_bounds__(256) k_g32(SlotArgs a) {
 // slots of a triplet with an out-of-range id (slot_row's rule, which is triplet_bad's).  It depends on the ids alone, so one
 // launch ahead of the loop serves every step.  One workgroup per batch: an open-addressing hash (linear probing) of the
 // batch's row ids in LDS, H slots of key + count with 3 * B <= 3/4 H, so every probe sequence ends within H steps.
-#define SLOT_MULT_HMAX 16384        /* hash slots, 8 bytes each: 128 KiB of a CU's 160 KiB; batches up to B = 4096 */
-#define SLOT_MULT_THREADS 1024
-struct SlotMultArgs {
-    const int32_t *users; const int32_t *pos; const int32_t *neg;
-    int64_t T; int32_t B; int32_t n_users; int64_t N;
-    uint16_t *out; int32_t H;
-};
 __global__ void __launch_bounds__(SLOT_MULT_THREADS) k_slot_mult(SlotMultArgs a) {
     // One thread per triplet (tid, tid + 1024, ...): its three ids are one round trip and its three rows follow from them.  The
     // loops are NOT unrolled: the launch runs once per call with a cold instruction cache, and an unrolled body (four triplets
@@ -1901,22 +1789,8 @@ __global__ void __launch_bounds__(SLOT_MULT_THREADS) k_slot_mult(SlotMultArgs a)
         }
     }
 }
-// hash slots for batches of B triplets: a power of two with 3 B <= 3/4 H, or 0 where that exceeds the LDS budget
-static int32_t slot_mult_hash(int32_t B) {
-    if (B <= 0) return 0;
-    int64_t H = 64;
-    while (3 * H < 12 * (int64_t)B) H <<= 1;
-    return H <= SLOT_MULT_HMAX ? (int32_t)H : 0;
-}
-// steps whose multiplicities one launch computes (and the context's buffer holds): 1024 steps = 3 * B * 1024 uint16 = 12 MiB at
-// B = 2048, 24 MiB at the largest batch that folds.  LGCN_FOLD_SEGMENT: for tests only (a call longer than a small segment)
-static int64_t fold_segment_steps() {
-    const char *e = getenv("LGCN_FOLD_SEGMENT");
-    const long v = e ? atol(e) : 0;
-    return v > 0 ? (int64_t)v : 1024;
-}
-static int launch_slot_mult(const int32_t *users, const int32_t *pos, const int32_t *neg, int64_t T, int32_t B, int32_t n_users,
-                            int64_t N, uint16_t *out, hipStream_t st) {
+int lgcn_slot_mult_launch(const int32_t *users, const int32_t *pos, const int32_t *neg, int64_t T, int32_t B, int32_t n_users,
+                          int64_t N, uint16_t *out, hipStream_t st) {
     SlotMultArgs a{};
     a.users = users; a.pos = pos; a.neg = neg; a.T = T; a.B = B; a.n_users = n_users; a.N = N; a.out = out; a.H = slot_mult_hash(B);
     const size_t lds = sizeof(int32_t) * 2 * (size_t)a.H;
@@ -1931,21 +1805,6 @@ static int launch_slot_mult(const int32_t *users, const int32_t *pos, const int3
     hipLaunchKernelGGL(k_slot_mult, dim3((unsigned)((T + B - 1) / B)), dim3(SLOT_MULT_THREADS), lds, st, a);
     return 0;
 }
-extern "C" int lgcn_slot_multiplicity(const int32_t *users, const int32_t *pos, const int32_t *neg, int64_t T, int32_t B,
-                                      int32_t n_users, int64_t N, uint16_t *mult_out, void *stream) {
-    if (T <= 0) return 0;
-    if (!users || !pos || !neg || !mult_out) { lgcn_set_error("lgcn_slot_multiplicity: null argument"); return 3; }
-    if (B <= 0 || n_users <= 0 || N <= n_users || N > 0x7fffffffLL) { lgcn_set_error("lgcn_slot_multiplicity: bad sizes (0 < B, 0 < n_users < N < 2^31)"); return 3; }
-    if (!slot_mult_hash(B)) { lgcn_set_error("lgcn_slot_multiplicity: the row ids of a batch of B triplets do not fit the LDS hash (B <= 4096)"); return 3; }
-    const int64_t seg = fold_segment_steps() * B;          // triplets per launch
-    for (int64_t t = 0; t < T; t += seg) {
-        int rc = launch_slot_mult(users + t, pos + t, neg + t, (T - t) < seg ? (T - t) : seg, B, n_users, N, mult_out + 3 * t, (hipStream_t)stream);
-        if (rc) return rc;
-    }
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
 // dense data-parallel form: flag the rows of the WHOLE global batch (every rank knows all ids), so the
 // row bitmap needs no collective (RCCL has no bitwise-OR reduction)
 __global__ void __launch_bounds__(256) k_flag_rows(SlotArgs a) {
@@ -1978,6 +1837,30 @@ __global__ void __launch_bounds__(256) k_finish(SlotArgs a) {
     if (blockIdx.x == 0 && threadIdx.x < 64)
         reduce_loss_wave(a.terms, a.gathered, a.B, a.shard, D, a.decay, a.loss_out, (int)threadIdx.x, a.ent_coeff, a.blk);
 }
+// k_scatter: one lane group of min(d, 64) lanes per slot; k_g32, k_finish: d / 4 lanes per slot
+static unsigned scatter_grid(int d, int32_t B) {
+    const int spb = 256 / (d < 64 ? d : 64);
+    return (unsigned)((3 * (int64_t)B + spb - 1) / spb);
+}
+static unsigned slot_grid(int d, int64_t slots_per_sample, int32_t B) {
+    const int spb = 256 / (d / 4);
+    return (unsigned)((slots_per_sample * B + spb - 1) / spb);
+}
+int lgcn_scatter_launch(const SlotArgs &s, int d, hipStream_t st) {
+    DISPATCH_D(d, hipLaunchKernelGGL((k_scatter<D>), dim3(scatter_grid(d, s.B)), dim3(256), 0, st, s));
+    return 0;
+}
+int lgcn_g32_launch(const SlotArgs &s, int d, hipStream_t st) {
+    DISPATCH_D(d, hipLaunchKernelGGL((k_g32<D>), dim3(slot_grid(d, 3, s.B)), dim3(256), 0, st, s));
+    return 0;
+}
+int lgcn_finish_launch(const SlotArgs &s, int d, hipStream_t st) {
+    DISPATCH_D(d, hipLaunchKernelGGL((k_finish<D>), dim3(slot_grid(d, 3, s.B)), dim3(256), 0, st, s));
+    return 0;
+}
+void lgcn_flag_rows_launch(const SlotArgs &s, hipStream_t st) {
+    hipLaunchKernelGGL(k_flag_rows, dim3((3 * s.B + 255) / 256), dim3(256), 0, st, s);
+}
 
 __global__ void __launch_bounds__(256) k_apply_perm(const int32_t *S, int cols, const int64_t *perm, int64_t T,
                                                    int32_t *users, int32_t *pos, int32_t *neg) {
@@ -1986,14 +1869,14 @@ __global__ void __launch_bounds__(256) k_apply_perm(const int32_t *S, int cols, 
     const int64_t j = perm ? perm[t] : t;
     users[t] = S[j * cols]; pos[t] = S[j * cols + 1]; neg[t] = S[j * cols + 2];
 }
+void lgcn_apply_perm_launch(const int32_t *S, int cols, const int64_t *perm, int64_t T, int32_t *users, int32_t *pos, int32_t *neg,
+                            hipStream_t st) {
+    hipLaunchKernelGGL(k_apply_perm, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, S, cols, perm, T, users, pos, neg);
+}
 
 // Several negatives per positive (lgcn_train_step_multi): the slot kernels' siblings over the (2 + R) B slots of a
 // batch of B samples.  Slot s = c * B + b: c = 0 the user, 1 the positive, 2 + r negative r, read from negs + r * neg_stride.
 // The three-slot launches above receive what they always received.
-struct SlotArgsMulti {
-    SlotArgs s;                    // users / pos / B / tables / loss reduction as in the three-slot kernels (s.neg unused)
-    const int32_t *negs; int64_t neg_stride; int32_t R;
-};
 // slot -> destination row (-1: the slot's sample has an out-of-range id among its 2 + R: the whole sample is void)
 __device__ __forceinline__ int64_t slot_row_multi(const SlotArgsMulti &a, int c, int b) {
     const int u = a.s.users[b], p = a.s.pos[b];
@@ -2034,6 +1917,14 @@ __global__ void __launch_bounds__(256) k_finish_multi(SlotArgsMulti a) {
     if (blockIdx.x == 0 && threadIdx.x < 64)
         reduce_loss_wave(a.s.terms, nullptr, a.s.B, a.s.shard, D, a.s.decay, a.s.loss_out, (int)threadIdx.x, 0.f, 0);
 }
+int lgcn_g32_multi_launch(const SlotArgsMulti &s, int d, hipStream_t st) {
+    DISPATCH_D(d, hipLaunchKernelGGL((k_g32_multi<D>), dim3(slot_grid(d, 2 + (int64_t)s.R, s.s.B)), dim3(256), 0, st, s));
+    return 0;
+}
+int lgcn_finish_multi_launch(const SlotArgsMulti &s, int d, hipStream_t st) {
+    DISPATCH_D(d, hipLaunchKernelGGL((k_finish_multi<D>), dim3(slot_grid(d, 2 + (int64_t)s.R, s.s.B)), dim3(256), 0, st, s));
+    return 0;
+}
 __global__ void __launch_bounds__(256) k_apply_perm_multi(const int32_t *S, int cols, const int64_t *perm, int64_t T,
                                                          int32_t *users, int32_t *pos, int32_t *negs, int32_t R) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -2042,13 +1933,62 @@ __global__ void __launch_bounds__(256) k_apply_perm_multi(const int32_t *S, int 
     users[t] = S[j * cols]; pos[t] = S[j * cols + 1];
     for (int r = 0; r < R; r++) negs[(int64_t)r * T + t] = S[j * cols + 2 + r];
 }
+void lgcn_apply_perm_multi_launch(const int32_t *S, int cols, const int64_t *perm, int64_t T, int32_t *users, int32_t *pos,
+                                  int32_t *negs, int32_t R, hipStream_t st) {
+    hipLaunchKernelGGL(k_apply_perm_multi, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, S, cols, perm, T, users, pos, negs, R);
+}
+
+// column indices must address rows of X: flag any index outside [0, n_rows)
+__global__ void __launch_bounds__(256) k_index_range(const int32_t *indices, int64_t nnz, int32_t n_rows, int32_t *bad) {
+    bool b = false;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nnz; i += (int64_t)gridDim.x * 256) {
+        const int32_t c = indices[i];
+        b |= (c < 0 || c >= n_rows);
+    }
+    if (__ballot(b) && (threadIdx.x & 63) == 0) atomicOr(bad, 1);
+}
+void lgcn_index_range_launch(const int32_t *indices, int64_t nnz, int32_t n_rows, int32_t *bad) {
+    const int64_t blocks = (nnz + 255) / 256;
+    hipLaunchKernelGGL(k_index_range, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, 0, indices, nnz, n_rows, bad);
+}
+
+// copy the planned rows' CSR segments into the packed stream: items = (first CSR entry, first stream entry, count, 0)
+__global__ void __launch_bounds__(256) k_pack_stream(const int4 *items, int64_t n_items, const int32_t *indices,
+                                                     const float *vals, int2 *pk) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
+    for (int64_t i = wave; i < n_items; i += nwaves) {
+        const int4 it = items[i];
+        for (int e = lane; e < it.z; e += 64)
+            pk[(int64_t)it.y + e] = make_int2(indices[(int64_t)it.x + e], __float_as_int(vals[(int64_t)it.x + e]));
+    }
+}
+void lgcn_pack_stream_launch(const int4 *items, int64_t n_items, const int32_t *indices, const float *vals, int2 *pk) {
+    const int64_t blocks = (n_items + 3) / 4;
+    hipLaunchKernelGGL(k_pack_stream, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, 0, items, n_items, indices, vals, pk);
+}
+
+// keep_out[p] = keep(row of p, indices[p]): one wave per row, its lanes over the row's entries
+__global__ void __launch_bounds__(256) k_dropout_mask(const int32_t *indptr, const int32_t *indices, int64_t n_rows, int64_t nnz,
+                                                      uint32_t k0, uint32_t k1, uint64_t thr, uint8_t *keep_out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
+    for (int64_t row = wave; row < n_rows; row += nwaves) {
+        const int64_t s = max((int64_t)indptr[row], (int64_t)0), e = min((int64_t)indptr[row + 1], nnz);      // never past the arrays
+        for (int64_t p = s + lane; p < e; p += 64)
+            keep_out[p] = (uint64_t)drop_hash(k0, k1, (uint32_t)row, (uint32_t)indices[p]) < thr ? 1 : 0;
+    }
+}
+void lgcn_dropout_mask_launch(const int32_t *indptr, const int32_t *indices, int64_t n_rows, int64_t nnz, uint32_t k0, uint32_t k1,
+                              uint64_t thr, uint8_t *keep_out, hipStream_t st) {
+    const int64_t blocks = (n_rows + 3) / 4;
+    hipLaunchKernelGGL(k_dropout_mask, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, st,
+                       indptr, indices, n_rows, nnz, k0, k1, thr, keep_out);
+}
 
 // ---------------------------------------------------------------------------------
 // launch helpers
 // ---------------------------------------------------------------------------------
-// gathered tables of 4 GiB or more need 64-bit offsets (priced at the fp32 row size whatever the table type)
-static inline bool big_table(int64_t n_rows, int d) { return n_rows * (int64_t)d * 4 >= (1ll << 32); }
-
 template <int D, typename TI, typename TO, int MODE, bool DROP = false>
 static void launch_spmm_t(const SpmmArgs &a, hipStream_t st) {
     constexpr int RPB = PackGeo<RowGeo<D, TI, (MODE & M_SPARSE) != 0>::RPK>::RPB;
@@ -2080,7 +2020,7 @@ static int launch_spmm_d(const SpmmArgs &a, int x_dtype, int y_dtype, hipStream_
         return 3;
     }
     // every MODE that comes through here (0, ADDG, ADDG|ADAM, SPARSE|ADDG, SPARSE|ADDG|ADAM) is one the dropout step launches;
-    // M_ADDSELF has its own helper below and no DROP instantiation
+    // M_ADDSELF is launched by lgcn_spmm_launch itself and has no DROP instantiation
     static_assert(!(MODE & M_ADDSELF), "item-item smoothing never takes the dropout branch");
     if (a.dr.on) {
         // edge dropout: its own instantiations, and only the type pairs a launch can ask for (a sparse input is fp32, Adam writes fp32)
@@ -2124,1697 +2064,24 @@ static int launch_spmm_dm(const SpmmArgs &a, int x_dtype, int y_dtype, hipStream
 
 template <int MODE>
 static int launch_spmm(const SpmmArgs &a, int d, int x_dtype, int y_dtype, hipStream_t st) {
-    switch (d) {
-    case 32: return launch_spmm_dm<32, MODE>(a, x_dtype, y_dtype, st);
-    case 64: return launch_spmm_dm<64, MODE>(a, x_dtype, y_dtype, st);
-    case 128: return launch_spmm_dm<128, MODE>(a, x_dtype, y_dtype, st);
-    case 256: return launch_spmm_dm<256, MODE>(a, x_dtype, y_dtype, st);
-    }
-    lgcn_set_error("embedding dim must be 32, 64, 128 or 256");
-    return 3;
+    DISPATCH_D(d, return (launch_spmm_dm<D, MODE>(a, x_dtype, y_dtype, st)));
 }
 
-// Y = selfX + A X on fp32 tables (item-item smoothing): only the fp32 instance exists
-static int launch_spmm_addself(const SpmmArgs &a, int d, hipStream_t st) {
-    switch (d) {
-    case 32: launch_spmm_t<32, float, float, M_ADDSELF>(a, st); return 0;
-    case 64: launch_spmm_t<64, float, float, M_ADDSELF>(a, st); return 0;
-    case 128: launch_spmm_t<128, float, float, M_ADDSELF>(a, st); return 0;
-    case 256: launch_spmm_t<256, float, float, M_ADDSELF>(a, st); return 0;
-    }
-    lgcn_set_error("embedding dim must be 32, 64, 128 or 256");
-    return 3;
-}
-
-static int check_dtype(int t) {
-    if (t != LGCN_F32 && t != LGCN_BF16 && t != LGCN_FP8) { lgcn_set_error("dtype must be LGCN_F32, LGCN_BF16 or LGCN_FP8"); return 3; }
-    return 0;
-}
-
-extern "C" int lgcn_device_available(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    return n > 0;
-}
-
-// ---------------------------------------------------------------------------------
-// graph object: device CSR (borrowed) + the long-row plan and its scratch (owned)
-// ---------------------------------------------------------------------------------
-struct lgcn_graph {
-    const int32_t *indptr; const int32_t *indices; const float *vals; const int4 *rowinfo;
-    const int2 *pk;       // the planned rows' (col,val) pairs, packed, in plan order
-    int64_t n_rows, nnz;
-    int32_t d_max;
-    LongPlan lp; SlicePlan sp;
-    void *owned;          // one device allocation holding plan arrays, partials and counters
-    // The long-row scratch (partials, tickets) is shared by every launch on this graph: launches
-    // are ordered.  A launch on another stream than the previous one first waits for it.
-    mutable hipStream_t last_stream; mutable bool used; mutable hipEvent_t order_ev;
-};
-
-// a launch on `st` is about to use the graph's scratch: order it behind the previous user
-static int graph_acquire(const lgcn_graph *g, hipStream_t st) {
-    if (g->used && g->last_stream != st) {
-        HIP_OK(hipEventRecord(g->order_ev, g->last_stream));
-        HIP_OK(hipStreamWaitEvent(st, g->order_ev, 0));
-    }
-    g->used = true; g->last_stream = st;
-    return 0;
-}
-
-// column indices must address rows of X: flag any index outside [0, n_rows)
-__global__ void __launch_bounds__(256) k_index_range(const int32_t *indices, int64_t nnz, int32_t n_rows, int32_t *bad) {
-    bool b = false;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nnz; i += (int64_t)gridDim.x * 256) {
-        const int32_t c = indices[i];
-        b |= (c < 0 || c >= n_rows);
-    }
-    if (__ballot(b) && (threadIdx.x & 63) == 0) atomicOr(bad, 1);
-}
-
-// copy the planned rows' CSR segments into the packed stream: items = (first CSR entry, first stream entry, count, 0)
-__global__ void __launch_bounds__(256) k_pack_stream(const int4 *items, int64_t n_items, const int32_t *indices,
-                                                     const float *vals, int2 *pk) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
-    for (int64_t i = wave; i < n_items; i += nwaves) {
-        const int4 it = items[i];
-        for (int e = lane; e < it.z; e += 64)
-            pk[(int64_t)it.y + e] = make_int2(indices[(int64_t)it.x + e], __float_as_int(vals[(int64_t)it.x + e]));
-    }
-}
-
-static int graph_create_impl(const int32_t *indptr, const int32_t *indices, const float *vals,
-                             int64_t n_rows, int64_t nnz, int32_t d_max, const int32_t *row_order,
-                             int64_t n_order, const int64_t *xcd_start, int32_t long_ch, lgcn_graph **out);
-extern "C" int lgcn_graph_create(const int32_t *indptr, const int32_t *indices, const float *vals,
-                                 int64_t n_rows, int64_t nnz, int32_t d_max, const int32_t *row_order,
-                                 int64_t n_order, const int64_t *xcd_start, lgcn_graph **out) {
-    return graph_create_impl(indptr, indices, vals, n_rows, nnz, d_max, row_order, n_order, xcd_start, LONG_CH, out);
-}
-// long_ch: non-zeros per chunk of a split row (LONG_CH for the propagation plans; the hub plan of k_triplet, whose rows
-// have 10^4 .. 10^6 non-zeros, takes longer chunks so that a row's last arriver has hundreds, not thousands, of partials to add)
-static int graph_create_impl(const int32_t *indptr, const int32_t *indices, const float *vals,
-                             int64_t n_rows, int64_t nnz, int32_t d_max, const int32_t *row_order,
-                             int64_t n_order, const int64_t *xcd_start, int32_t long_ch, lgcn_graph **out) {
-    if (!indptr || !indices || !vals || !out || n_rows <= 0 || nnz < 0 || nnz > 0x7fffffffLL ||
-        n_rows >= 0x7fffffffLL) { lgcn_set_error("lgcn_graph_create: invalid argument"); return 3; }
-    if (d_max != 32 && d_max != 64 && d_max != 128 && d_max != 256) { lgcn_set_error("lgcn_graph_create: d_max must be 32, 64, 128 or 256"); return 3; }
-    std::vector<int32_t> ip((size_t)n_rows + 1);
-    HIP_OK(hipMemcpy(ip.data(), indptr, sizeof(int32_t) * ip.size(), hipMemcpyDeviceToHost));
-    if (ip[0] != 0 || (int64_t)ip[(size_t)n_rows] != nnz) { lgcn_set_error("lgcn_graph_create: indptr does not match nnz"); return 3; }
-    if (nnz > 0) {               // a bad column index would become an out-of-bounds row gather
-        int32_t *bad = nullptr, hbad = 0;
-        HIP_OK(hipMalloc((void **)&bad, sizeof(int32_t)));
-        hipError_t e0 = hipMemset(bad, 0, sizeof(int32_t));
-        if (e0 == hipSuccess) {
-            const int64_t blocks = (nnz + 255) / 256;
-            hipLaunchKernelGGL(k_index_range, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, 0,
-                               indices, nnz, (int32_t)n_rows, bad);
-            e0 = hipMemcpy(&hbad, bad, sizeof(int32_t), hipMemcpyDeviceToHost);
-        }
-        (void)hipFree(bad);
-        if (e0 != hipSuccess) { lgcn_set_error("lgcn_graph_create: index check failed to run"); return 10; }
-        if (hbad) { lgcn_set_error("lgcn_graph_create: column index out of range [0, n_rows)"); return 3; }
-    }
-    std::vector<int32_t> ord;
-    if (!row_order) n_order = n_rows;
-    if (n_order < 0 || n_order > n_rows) { lgcn_set_error("lgcn_graph_create: n_order out of range"); return 3; }
-    if (row_order) {             // a permutation of 0..n_rows-1, or a subset of the rows without repetition
-        ord.resize((size_t)n_order);
-        if (n_order) HIP_OK(hipMemcpy(ord.data(), row_order, sizeof(int32_t) * ord.size(), hipMemcpyDeviceToHost));
-        std::vector<char> seen((size_t)n_rows, 0);
-        for (int64_t i = 0; i < n_order; i++) {
-            const int32_t r = ord[(size_t)i];
-            if (r < 0 || r >= n_rows || seen[(size_t)r]) { lgcn_set_error("lgcn_graph_create: row_order is not a permutation / repeats a row"); return 3; }
-            seen[(size_t)r] = 1;
-        }
-    }
-    for (int64_t r = 0; r < n_rows; r++)
-        if (ip[(size_t)r + 1] < ip[(size_t)r]) { lgcn_set_error("lgcn_graph_create: indptr not monotone"); return 3; }
-    // ---- slices of the processing order, one per XCD
-    int64_t xs[XCDS + 1];
-    if (xcd_start) {
-        for (int x = 0; x <= XCDS; x++) xs[x] = xcd_start[x];
-        bool ok = xs[0] == 0 && xs[XCDS] == n_order;
-        for (int x = 0; x < XCDS; x++) ok = ok && xs[x] <= xs[x + 1];
-        if (!ok) { lgcn_set_error("lgcn_graph_create: xcd_start must be 9 non-decreasing positions from 0 to n_order"); return 3; }
-    } else {                     // balance the work: non-zeros plus a per-row constant (see reorder.py _row_cost)
-        const double ROW_COST = 4.0;           // small per-row term (measured: 0..16 equal on Gowalla, larger is slower)
-        double total = ROW_COST * (double)n_order;
-        for (int64_t p = 0; p < n_order; p++) {
-            const int32_t r = row_order ? ord[(size_t)p] : (int32_t)p;
-            total += (double)(ip[(size_t)r + 1] - ip[(size_t)r]);
-        }
-        double acc = 0.0; int x = 1;
-        xs[0] = 0;
-        for (int64_t p = 0; p < n_order && x < XCDS; p++) {
-            const int32_t r = row_order ? ord[(size_t)p] : (int32_t)p;
-            acc += (double)(ip[(size_t)r + 1] - ip[(size_t)r]) + ROW_COST;
-            while (x < XCDS && acc >= total * x / XCDS) xs[x++] = p + 1;
-        }
-        while (x <= XCDS) xs[x++] = n_order;
-        xs[XCDS] = n_order;
-    }
-    // ---- per slice: chunks of its long rows (padded to whole workgroups), then its short rows; the
-    //      planned rows' entries go into the packed stream in exactly that order
-    std::vector<int32_t> long_row, long_nch, chunks, rowinfo, copyplan;
-    SlicePlan sp{};
-    rowinfo.reserve((size_t)n_order * 4 + 4 * SLICE_PAD * XCDS);
-    copyplan.reserve((size_t)n_order * 4);
-    int64_t n_pk = 0;
-    for (int x = 0; x < XCDS; x++) {
-        sp.cblk[x] = (int32_t)(chunks.size() / 16); sp.rows[x] = (int32_t)(rowinfo.size() / 4);
-        const size_t slice_begin = rowinfo.size();
-        for (int64_t p = xs[x]; p < xs[x + 1]; p++) {
-            const int32_t r = row_order ? ord[(size_t)p] : (int32_t)p;
-            const int32_t s0 = ip[(size_t)r], deg = ip[(size_t)r + 1] - s0;
-            if (deg > LONG_T) {
-                const int nch = (deg + long_ch - 1) / long_ch;
-                const int32_t lb = (int32_t)n_pk;
-                for (int k = 0; k < nch; k++) {
-                    const int32_t c0 = k * long_ch, c1 = c0 + long_ch < deg ? c0 + long_ch : deg;
-                    const int32_t e[4] = {(int32_t)long_row.size(), lb + c0, lb + c1, k};
-                    chunks.insert(chunks.end(), e, e + 4);
-                }
-                const int32_t cp[4] = {s0, lb, deg, 0};
-                copyplan.insert(copyplan.end(), cp, cp + 4);
-                n_pk += deg;
-                long_row.push_back(r); long_nch.push_back(nch);
-            } else {
-                const int32_t e[4] = {r, s0, deg, 0};
-                rowinfo.insert(rowinfo.end(), e, e + 4);
-            }
-        }
-        // rows of a pack run in lock step: sort every window of SHORT_WIN short rows by length (stable)
-        for (size_t w0 = slice_begin; w0 < rowinfo.size(); w0 += 4 * SHORT_WIN) {
-            const size_t w1 = std::min(rowinfo.size(), w0 + 4 * (size_t)SHORT_WIN), n = (w1 - w0) / 4;
-            std::vector<std::array<int32_t, 4>> tmp(n);
-            for (size_t i = 0; i < n; i++) for (int k = 0; k < 4; k++) tmp[i][k] = rowinfo[w0 + 4 * i + k];
-            std::stable_sort(tmp.begin(), tmp.end(), [](const std::array<int32_t, 4> &p, const std::array<int32_t, 4> &q) { return p[2] > q[2]; });
-            for (size_t i = 0; i < n; i++) for (int k = 0; k < 4; k++) rowinfo[w0 + 4 * i + k] = tmp[i][k];
-        }
-        // stream positions of the short rows, in their final order
-        for (size_t i = slice_begin; i < rowinfo.size(); i += 4) {
-            const int32_t cp[4] = {rowinfo[i + 1], (int32_t)n_pk, rowinfo[i + 2], 0};
-            if (cp[2] > 0) copyplan.insert(copyplan.end(), cp, cp + 4);
-            rowinfo[i + 1] = (int32_t)n_pk;
-            n_pk += rowinfo[i + 2];
-        }
-        const int32_t pad[4] = {-1, 0, 0, 0};
-        while ((chunks.size() / 4) % 4) chunks.insert(chunks.end(), pad, pad + 4);
-        while ((rowinfo.size() / 4) % SLICE_PAD) rowinfo.insert(rowinfo.end(), pad, pad + 4);
-    }
-    sp.cblk[XCDS] = (int32_t)(chunks.size() / 16); sp.rows[XCDS] = (int32_t)(rowinfo.size() / 4);
-    lgcn_graph *g = new (std::nothrow) lgcn_graph;
-    if (!g) { lgcn_set_error("out of memory"); return 4; }
-    g->indptr = indptr; g->indices = indices; g->vals = vals; g->rowinfo = nullptr; g->pk = nullptr;
-    g->n_rows = n_rows; g->nnz = nnz; g->d_max = d_max;
-    g->owned = nullptr; g->lp = LongPlan{}; g->sp = sp;
-    g->used = false; g->last_stream = nullptr; g->order_ev = nullptr;
-    if (hipEventCreateWithFlags(&g->order_ev, hipEventDisableTiming) != hipSuccess) { delete g; lgcn_set_error("lgcn_graph_create: hipEventCreate failed"); return 10; }
-    const size_t n_long = long_row.size(), n_slots = chunks.size() / 4, n_info = rowinfo.size() / 4;
-    {
-        auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        const size_t o_info = 0, o_chk = up(o_info + 16 * n_info), o_row = up(o_chk + 16 * n_slots),
-                     o_nch = up(o_row + 4 * n_long), o_cnt = up(o_nch + 4 * n_long),
-                     o_par = up(o_cnt + 4 * n_long), o_pk = up(o_par + n_slots * (size_t)d_max * 4),
-                     total = o_pk + 8 * (size_t)n_pk + 256;
-        char *base = nullptr;
-        if (hipMalloc((void **)&base, total) != hipSuccess) { (void)hipEventDestroy(g->order_ev); delete g; lgcn_set_error("lgcn_graph_create: hipMalloc failed"); return 4; }
-        g->owned = base;
-        hipError_t e1 = hipMemset(base, 0, total);
-        if (e1 == hipSuccess && n_info) e1 = hipMemcpy(base + o_info, rowinfo.data(), 16 * n_info, hipMemcpyHostToDevice);
-        if (e1 == hipSuccess && n_long) {
-            e1 = hipMemcpy(base + o_chk, chunks.data(), 16 * n_slots, hipMemcpyHostToDevice);
-            if (e1 == hipSuccess) e1 = hipMemcpy(base + o_row, long_row.data(), 4 * n_long, hipMemcpyHostToDevice);
-            if (e1 == hipSuccess) e1 = hipMemcpy(base + o_nch, long_nch.data(), 4 * n_long, hipMemcpyHostToDevice);
-        }
-        if (e1 == hipSuccess && !copyplan.empty()) {        // fill the packed stream on the device
-            int4 *items = nullptr;
-            e1 = hipMalloc((void **)&items, copyplan.size() * 4);
-            if (e1 == hipSuccess) e1 = hipMemcpy(items, copyplan.data(), copyplan.size() * 4, hipMemcpyHostToDevice);
-            if (e1 == hipSuccess) {
-                const int64_t n_items = (int64_t)(copyplan.size() / 4), blocks = (n_items + 3) / 4;
-                hipLaunchKernelGGL(k_pack_stream, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, 0,
-                                   items, n_items, indices, vals, (int2 *)(base + o_pk));
-                e1 = hipDeviceSynchronize();
-            }
-            if (items) (void)hipFree(items);
-        }
-        if (e1 != hipSuccess) { (void)hipFree(base); (void)hipEventDestroy(g->order_ev); delete g; lgcn_set_error("lgcn_graph_create: plan upload failed"); return 10; }
-        g->rowinfo = (const int4 *)(base + o_info);
-        g->pk = (const int2 *)(base + o_pk);
-        if (n_long) {
-            g->lp.chunks = (const int4 *)(base + o_chk);
-            g->lp.long_row = (const int32_t *)(base + o_row); g->lp.long_nch = (const int32_t *)(base + o_nch);
-            g->lp.counters = (int32_t *)(base + o_cnt);
-            g->lp.partials = (float *)(base + o_par);
-            g->lp.n_long = (int32_t)n_long; g->lp.n_chunk_slots = (int32_t)n_slots;
-        }
-    }
-    *out = g;
-    return 0;
-}
-
-extern "C" void lgcn_graph_destroy(lgcn_graph *g) {
-    if (!g) return;
-    if (g->owned) (void)hipFree(g->owned);
-    if (g->order_ev) (void)hipEventDestroy(g->order_ev);
-    delete g;
-}
-
-static SpmmArgs graph_spmm(const lgcn_graph *g) {
-    SpmmArgs a{};
-    a.pk = g->pk; a.rowinfo = g->rowinfo; a.lp = g->lp; a.sp = g->sp; a.n_rows = g->n_rows;
-    return a;
-}
-
-extern "C" int lgcn_spmm_csr(const lgcn_graph *g, const void *X, int x_dtype, void *Y, int y_dtype, int d, void *stream) {
-    if (!g || !X || !Y) { lgcn_set_error("lgcn_spmm_csr: null/invalid argument"); return 3; }
-    if (check_dtype(x_dtype) || check_dtype(y_dtype)) return 3;
-    if (d > g->d_max) { lgcn_set_error("lgcn_spmm_csr: d exceeds the graph's d_max"); return 3; }
-    SpmmArgs a = graph_spmm(g);
-    a.X = X; a.Y = Y; a.remap = 1;
-    int rc = graph_acquire(g, (hipStream_t)stream);
-    if (rc) return rc;
-    rc = launch_spmm<0>(a, d, x_dtype, y_dtype, (hipStream_t)stream);
-    if (rc) return rc;
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------
-// edge dropout: the step's keys, the exported mask, the masked SpMM
-// ---------------------------------------------------------------------------------
-static inline uint64_t splitmix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-static inline bool drop_prob_ok(float keep_prob) { return keep_prob > 0.f && keep_prob <= 1.f; }      // (NaN fails both)
-// floor(keep_prob * 2^32): exact in double; 2^32 itself (keep_prob = 1) means "keep everything"
-static inline uint64_t drop_threshold(float keep_prob) { return (uint64_t)floor((double)keep_prob * 4294967296.0); }
-// the mask of one step; keep_prob in (0, 1): at 1 there is nothing to drop and on stays 0 (the launch is the plain one)
-static DropArgs make_drop(float keep_prob, uint64_t seed, int64_t step, int transposed) {
-    DropArgs d{};
-    if (!(keep_prob < 1.f)) return d;
-    const uint64_t k = splitmix64(splitmix64(seed) + (uint64_t)step);
-    d.k0 = (uint32_t)k; d.k1 = (uint32_t)(k >> 32);
-    d.thr = (uint32_t)drop_threshold(keep_prob); d.inv = 1.0f / keep_prob; d.tr = transposed ? 1 : 0; d.on = 1;
-    return d;
-}
-
-// keep_out[p] = keep(row of p, indices[p]): one wave per row, its lanes over the row's entries
-__global__ void __launch_bounds__(256) k_dropout_mask(const int32_t *indptr, const int32_t *indices, int64_t n_rows, int64_t nnz,
-                                                      uint32_t k0, uint32_t k1, uint64_t thr, uint8_t *keep_out) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
-    for (int64_t row = wave; row < n_rows; row += nwaves) {
-        const int64_t s = max((int64_t)indptr[row], (int64_t)0), e = min((int64_t)indptr[row + 1], nnz);      // never past the arrays
-        for (int64_t p = s + lane; p < e; p += 64)
-            keep_out[p] = (uint64_t)drop_hash(k0, k1, (uint32_t)row, (uint32_t)indices[p]) < thr ? 1 : 0;
-    }
-}
-
-extern "C" int lgcn_dropout_mask(const int32_t *indptr, const int32_t *indices, int64_t n_rows, int64_t nnz,
-                                 float keep_prob, uint64_t seed, int64_t step, uint8_t *keep_out, void *stream) {
-    if (!indptr || n_rows <= 0 || nnz < 0 || (nnz > 0 && (!indices || !keep_out))) { lgcn_set_error("lgcn_dropout_mask: invalid argument"); return 3; }
-    if (!drop_prob_ok(keep_prob)) { lgcn_set_error("lgcn_dropout_mask: dropout keep_prob must be in (0, 1]"); return 3; }
-    if (nnz == 0) return 0;
-    const uint64_t k = splitmix64(splitmix64(seed) + (uint64_t)step);
-    const int64_t blocks = (n_rows + 3) / 4;
-    hipLaunchKernelGGL(k_dropout_mask, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, (hipStream_t)stream,
-                       indptr, indices, n_rows, nnz, (uint32_t)k, (uint32_t)(k >> 32), drop_threshold(keep_prob), keep_out);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int lgcn_spmm_csr_drop(const lgcn_graph *g, const void *X, int x_dtype, void *Y, int y_dtype, int d,
-                                  float keep_prob, uint64_t seed, int64_t step, int transposed, void *stream) {
-    if (!g || !X || !Y) { lgcn_set_error("lgcn_spmm_csr_drop: null/invalid argument"); return 3; }
-    if (check_dtype(x_dtype) || check_dtype(y_dtype)) return 3;
-    if (x_dtype == LGCN_FP8 || y_dtype == LGCN_FP8) { lgcn_set_error("lgcn_spmm_csr_drop: edge dropout is not implemented for fp8 tables"); return 3; }
-    if (!drop_prob_ok(keep_prob)) { lgcn_set_error("lgcn_spmm_csr_drop: dropout keep_prob must be in (0, 1]"); return 3; }
-    if (d > g->d_max) { lgcn_set_error("lgcn_spmm_csr_drop: d exceeds the graph's d_max"); return 3; }
-    SpmmArgs a = graph_spmm(g);
-    a.X = X; a.Y = Y; a.remap = 1; a.dr = make_drop(keep_prob, seed, step, transposed);
-    int rc = graph_acquire(g, (hipStream_t)stream);
-    if (rc) return rc;
-    rc = launch_spmm<0>(a, d, x_dtype, y_dtype, (hipStream_t)stream);
-    if (rc) return rc;
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-// bytes of one [N,d] table of a storage type (fp8: rows + fp32 row scales, padded so that the next table stays 256-byte aligned)
-static inline size_t table_bytes(int64_t N, int d, int dtype) {
-    if (dtype == LGCN_FP8) return (((size_t)N * d + (size_t)N * 4) + 255) & ~(size_t)255;
-    return (size_t)N * d * (dtype == LGCN_BF16 ? 2 : 4);
-}
-extern "C" int64_t lgcn_table_bytes(int64_t n_rows, int32_t d, int32_t dtype) { return n_rows > 0 && d > 0 ? (int64_t)table_bytes(n_rows, d, dtype) : 0; }
-extern "C" int lgcn_to_fp8(const float *src, void *dst, int64_t n_rows, int32_t d, void *stream) {
-    if (!src || !dst || n_rows <= 0) { lgcn_set_error("lgcn_to_fp8: invalid argument"); return 3; }
-    int rc = launch_to_fp8(src, dst, n_rows, d, (hipStream_t)stream);
-    if (rc) return rc;
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-// Layer weights w_0..w_K: fp32 values taken as they are.  n values for a model of K layers; finite, not all zero.
-static int check_layer_weights(const char *who, const float *w, int n, int K) {
-    char buf[192];
-    bool ok = w && n == K + 1, any = false;
-    for (int k = 0; ok && k < n; k++) { ok = isfinite(w[k]); any = any || w[k] != 0.f; }
-    if (ok && any) return 0;
-    snprintf(buf, sizeof buf, "%s: layer weights must be K + 1 = %d finite fp32 values that are not all zero (got %d)", who, K + 1, n);
-    lgcn_set_error(buf);
-    return 3;
-}
-
-// w: NULL = the mean (lgcn_propagate_mean), else K + 1 layer weights (lgcn_propagate_weighted)
-static int propagate_impl(const char *who, const lgcn_graph *g, const float *E0, int K, int d, int act_dtype, void *work,
-                          const float *w, float *out, void *stream) {
-    char buf[160];
-    if (!g || !E0 || !out || K < 1 || K > LGCN_MAX_LAYERS) { snprintf(buf, sizeof buf, "%s: invalid argument", who); lgcn_set_error(buf); return 3; }
-    if (K > 1 && !work) { snprintf(buf, sizeof buf, "%s: workspace required for K > 1", who); lgcn_set_error(buf); return 3; }
-    if (check_dtype(act_dtype)) return 3;
-    if (d > g->d_max) { snprintf(buf, sizeof buf, "%s: d exceeds the graph's d_max", who); lgcn_set_error(buf); return 3; }
-    hipStream_t st = (hipStream_t)stream;
-    { int rc0 = graph_acquire(g, st); if (rc0) return rc0; }
-    const int64_t N = g->n_rows;
-    MeanArgs m{};
-    m.X0 = E0; m.K = K; m.out = out; m.n4 = N * d / 4; m.d = d; m.N = N;
-    const size_t stride = table_bytes(N, d, act_dtype);
-    const void *prev = E0; int prev_dtype = LGCN_F32;
-    if (act_dtype == LGCN_BF16 && K >= 2) {
-        // the same rule as the training step: with bf16 activation storage layer 1 reads bf16(E0).  `out` is free until
-        // the last layer writes it (K >= 2): its memory holds the 2-byte copy meanwhile
-        launch_to_bf16(E0, (bf16_t *)out, N * d, st);
-        prev = out; prev_dtype = LGCN_BF16;
-    }
-    if (act_dtype == LGCN_FP8 && K >= 2) {                 // the same with fp8 storage: rows + scales fit the fp32 `out`
-        int rc = launch_to_fp8(E0, out, N, d, st);
-        if (rc) return rc;
-        prev = out; prev_dtype = LGCN_FP8;
-    }
-    for (int k = 1; k <= K; k++) {
-        const bool last = (k == K);
-        void *y = last ? (void *)out : (void *)((char *)work + (size_t)(k - 1) * stride);
-        SpmmArgs a = graph_spmm(g);
-        a.X = prev; a.Y = y; a.remap = 1;
-        int rc = launch_spmm<0>(a, d, prev_dtype, last ? LGCN_F32 : act_dtype, st);
-        if (rc) return rc;
-        if (!last) { m.Xl[k] = y; prev = y; prev_dtype = act_dtype; }
-    }
-    const int64_t blocks = (m.n4 + 255) / 256;
-    const unsigned grid = (unsigned)(blocks < 2048 ? blocks : 2048);
-    if (w) {
-        for (int k = 0; k <= K; k++) m.w[k] = w[k];
-        if (act_dtype == LGCN_F32) hipLaunchKernelGGL((k_layer_mean<float, true>), dim3(grid), dim3(256), 0, st, m);
-        else hipLaunchKernelGGL((k_layer_mean<bf16_t, true>), dim3(grid), dim3(256), 0, st, m);
-    } else if (act_dtype == LGCN_F32) hipLaunchKernelGGL((k_layer_mean<float>), dim3(grid), dim3(256), 0, st, m);
-    else if (act_dtype == LGCN_BF16) hipLaunchKernelGGL((k_layer_mean<bf16_t>), dim3(grid), dim3(256), 0, st, m);
-    else hipLaunchKernelGGL((k_layer_mean<fp8_t>), dim3(grid), dim3(256), 0, st, m);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-extern "C" int lgcn_propagate_mean(const lgcn_graph *g, const float *E0, int K, int d, int act_dtype, void *work,
-                                   float *out, void *stream) {
-    return propagate_impl("lgcn_propagate_mean", g, E0, K, d, act_dtype, work, nullptr, out, stream);
-}
-extern "C" int lgcn_propagate_weighted(const lgcn_graph *g, const float *E0, int K, int d, int act_dtype, void *work,
-                                       const float *w_host, float *out, void *stream) {
-    if (K < 1 || K > LGCN_MAX_LAYERS) { lgcn_set_error("lgcn_propagate_weighted: invalid argument"); return 3; }
-    if (act_dtype == LGCN_FP8) { lgcn_set_error("lgcn_propagate_weighted: layer weights are not implemented for LGCN_FP8 activation storage"); return 3; }
-    if (int rc = check_layer_weights("lgcn_propagate_weighted", w_host, K + 1, K)) return rc;
-    return propagate_impl("lgcn_propagate_weighted", g, E0, K, d, act_dtype, work, w_host, out, stream);
-}
-
-extern "C" int lgcn_apply_perm(const int32_t *S, int s_cols, const int64_t *perm, int64_t T,
-                               int32_t *users, int32_t *pos, int32_t *neg, void *stream) {
-    if (!S || !users || !pos || !neg || s_cols < 3 || T < 0) { lgcn_set_error("lgcn_apply_perm: invalid argument"); return 3; }
-    if (T == 0) return 0;
-    hipLaunchKernelGGL(k_apply_perm, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       S, s_cols, perm, T, users, pos, neg);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int lgcn_apply_perm_multi(const int32_t *S, int s_cols, const int64_t *perm, int64_t T,
-                                     int32_t *users, int32_t *pos, int32_t *negs, int32_t R, void *stream) {
-    if (R < 1 || R > LGCN_MAX_NEG_RATIO) { lgcn_set_error("lgcn_apply_perm_multi: the negative ratio R must be in 1..16"); return 3; }
-    if (!S || !users || !pos || !negs || s_cols < 2 + R || T < 0) { lgcn_set_error("lgcn_apply_perm_multi: invalid argument (s_cols >= 2 + R)"); return 3; }
-    if (T == 0) return 0;
-    hipLaunchKernelGGL(k_apply_perm_multi, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       S, s_cols, perm, T, users, pos, negs, R);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------
-// training context
-// ---------------------------------------------------------------------------------
-struct lgcn_ctx {
-    lgcn_train_config c;
-    int64_t step;
-    int64_t N;
-    int64_t bm_words;             // words per bitmap; cfg.bitmap holds two, used alternately
-    int flip;
-    void *act[LGCN_MAX_LAYERS + 1];   // act[k] = X_k storage for k = 1..K-1 (K with dense_last; also reused for H)
-    int fwd_layers;               // dense forward layers per step: K-1, or K with dense_last
-    float *g32;                   // [N,d] fp32 copy of the step's flagged gradient rows (library-owned; k_g32)
-    bf16_t *e0b;                  // [N,d] bf16 copy of E0 (library-owned; bf16 activation storage with K >= 2 only)
-    void *e0q;                    // fp8 copy of E0, rows + scales (library-owned; fp8 activation storage with K >= 2 only); e0b_fresh covers it too
-    bool e0b_fresh;               // e0b == bf16(E0) right now (set by the Adam epilogue inside a multi-step call)
-    bool in_loop;                 // inside lgcn_train_epoch / lgcn_train_epoch_dp: the Adam epilogue keeps e0b current
-    lgcn_graph *hub_graph;        // plan over the rows with more than hub_nnz non-zeros (or NULL): their last-layer rows are
-    int32_t hub_nnz;              //   computed by k_spmm into g32 before k_triplet instead of by the one workgroup of a triplet
-    int64_t hub_rows;             // rows in that plan
-    bool dp_local;                // data parallel (rows): part 1 also adds this rank's own rows into G64, part 2 scatters the others'
-    int dp_rank;                  // rank of the last part 1
-    // optional branches of the fork (popularity gate / item-item smoothing): the step runs on ONE final table
-    bool variant;                 // either branch is on
-    float *tvar;                  // [N,d] fp32 final propagated table T (library-owned)
-    uint32_t *item_bitmap;        // [ceil(m_items/32)] items named by the batch (item-item backward), library-owned
-    long long *gate_partials;     // [n_wg, P] parameter-gradient partial sums, fixed point (library-owned)
-    long long *gate_total;        // [P] this rank's sum of them, all-reduced by the dense data-parallel form (behind gate_partials)
-    int32_t gate_P, gate_wgs;
-    int32_t *cnt;                 // reg_ego: [N] slots of the running step naming each row (library-owned, zero between steps)
-    float *colsum;                // [3 * max_batch] partial scores / reg terms of a column-sharded step (library-owned)
-    // edge dropout (lgcn_ctx_set_dropout): drop_keep < 1 = on.  dr is the mask of the running step, made by lgcn_train_step from
-    // the step counter as it stands BEFORE the step; forward, batch rows and backward all read it (dr.on = 0: off)
-    float drop_keep; uint64_t drop_seed; DropArgs dr;
-    // layer weights (lgcn_ctx_set_layer_weights): lw_n = K + 1 values in lw, or 0 = the mean
-    int32_t lw_n; float lw[LGCN_MAX_LAYERS + 1];
-    // the fold of k_g32 into k_triplet (lgcn_ctx_set_fold_g32): lgcn_train_epoch computes the slot multiplicities
-    // of its steps (k_slot_mult) into `mult` and points fold_mult at the running step's slice; NULL everywhere else
-    bool fold_g32;                // the setter's switch (default on)
-    uint16_t *mult; int64_t mult_cap;     // library-owned, grown when a call needs more (elements)
-    const uint16_t *fold_mult;    // multiplicities of the running step's slots, or NULL: the step launches k_g32
-    int32_t *arrive;              // [N] arrival tickets of the rows several slots name (library-owned, zero between steps; allocated by the first call that folds)
-    int64_t folded_steps;         // steps run with the fold since the context was created
-    // the (2 + R) B slot form of the running step (SlotScope): on only while a multi-negative step (R >= 1), an
-    // in-batch step (R = 0, no negatives) or a mixed one (R >= 1) runs -- its backward enumerates (2 + R) B slots (negative column
-    // r at negs + r * stride) and, with R > 0, the reg_ego epilogue takes decay / (B R)
-    struct SlotForm { const int32_t *negs; int64_t stride; int32_t R; bool on; } mn;
-    // the loss of the multi-negative step (lgcn_ctx_set_loss): LGCN_LOSS_BPR launches the BPR instantiations of k_multineg,
-    // LGCN_LOSS_SOFTMAX the softmax ones with the temperature loss_temp; the three-slot and rank-splitting entry points refuse
-    int32_t loss_kind; float loss_temp;
-    // the in-batch softmax (LGCN_LOSS_INBATCH): the workspace of its launches, allocated by the first lgcn_ctx_set_loss
-    // that accepts the loss (ib_cap = max_batch rounded up to 32 rows) and freed with the context; ONE allocation, carved up
-    void *ib_ws; int32_t ib_cap;
-    // its score options (lgcn_ctx_set_inbatch_scores): independent of loss_kind, (LGCN_SCORE_DOT, NULL) by default
-    int32_t ib_score; const float *ib_logq;
-    // mixed negatives (lgcn_ctx_set_inbatch_mix): ib_mix = R_max (0: off).  While it is on, ib_ws is large enough for
-    // both carvings: the plain step's (the one above, unchanged) and the mixed step's with (1 + R_max) ib_cap item rows
-    int32_t ib_mix;
-};
-// a multi-step call: nobody but this library touches E0 between its steps
-struct LoopScope {
-    lgcn_ctx *x;
-    explicit LoopScope(lgcn_ctx *x_) : x(x_) { x->in_loop = true; x->e0b_fresh = false; }
-    ~LoopScope() { x->in_loop = false; x->e0b_fresh = false; }
-};
-// a slot-form step: the loss launch, the backward's slot kernels and the reg_ego epilogue read x->mn; cleared on every way out
-struct SlotScope {
-    lgcn_ctx *x;
-    SlotScope(lgcn_ctx *x_, const int32_t *negs, int64_t stride, int32_t R) : x(x_) { x->mn = {negs, stride, R, true}; }
-    ~SlotScope() { x->mn = {}; }
-};
-
-extern "C" int lgcn_ctx_create(const lgcn_train_config *cfg, lgcn_ctx **out) {
-    if (!cfg || !out) { lgcn_set_error("lgcn_ctx_create: null argument"); return 3; }
-    const lgcn_train_config &c = *cfg;
-    if (!c.graph || !c.E0 || !c.adam_m || !c.adam_v || !c.G64 ||
-        !c.bitmap || !c.terms || !c.err) { lgcn_set_error("lgcn_ctx_create: null buffer"); return 3; }
-    if (c.K < 1 || c.K > LGCN_MAX_LAYERS) { lgcn_set_error("lgcn_ctx_create: K out of range"); return 3; }
-    if ((c.K > 1 || c.dense_last) && !c.act) { lgcn_set_error("lgcn_ctx_create: activation workspace missing"); return 3; }
-    if (c.d != 32 && c.d != 64 && c.d != 128 && c.d != 256) { lgcn_set_error("embedding dim must be 32, 64, 128 or 256"); return 3; }
-    if (check_dtype(c.act_dtype)) return 3;
-    if (c.act_dtype == LGCN_FP8 && c.d < 64) { lgcn_set_error("lgcn_ctx_create: fp8 activation storage needs an embedding dim of 64, 128 or 256"); return 3; }
-    if (c.act_dtype == LGCN_FP8 && (c.item_pop || c.i2i)) { lgcn_set_error("lgcn_ctx_create: fp8 activation storage is implemented for the default model, not with the optional branches"); return 3; }
-    if (c.n_users <= 0 || c.n_users >= c.graph->n_rows || c.max_batch <= 0) { lgcn_set_error("lgcn_ctx_create: bad sizes"); return 3; }
-    if (c.d > c.graph->d_max) { lgcn_set_error("lgcn_ctx_create: d exceeds the graph's d_max"); return 3; }
-    const bool gate = c.item_pop != nullptr, smooth = c.i2i != nullptr;
-    if (gate || smooth) {
-        if (!c.dense_last) { lgcn_set_error("lgcn_ctx_create: the optional branches need dense_last = 1 (every layer propagated densely)"); return 3; }
-        const int64_t m_items = c.graph->n_rows - c.n_users;
-        if (smooth && (!c.i2i_t || c.i2i->n_rows != m_items || c.i2i_t->n_rows != m_items || c.i2i->d_max < c.d || c.i2i_t->d_max < c.d)) {
-            lgcn_set_error("lgcn_ctx_create: i2i / i2i_t must be [m_items, m_items] graphs with d_max >= d"); return 3; }
-        if (gate && (!c.gate_params || !c.gate_adam_m || !c.gate_adam_v || !c.gate_grad || c.pop_hidden < 1 || c.pop_hidden > GATE_HMAX ||
-                     c.gate_hidden < 1 || c.gate_hidden > GATE_HMAX || c.d > 128 || !(c.pop_gate_temp > 0.f))) {
-            lgcn_set_error("lgcn_ctx_create: popularity gate needs its parameter / Adam buffers, hidden sizes in 1..64, d <= 128, temperature > 0"); return 3; }
-    }
-    if (c.reg_ego && (gate || smooth)) { lgcn_set_error("lgcn_ctx_create: reg_ego (upstream's L2 term) is defined for the default model only, not with the optional branches"); return 3; }
-    lgcn_ctx *x = new (std::nothrow) lgcn_ctx;
-    if (!x) { lgcn_set_error("out of memory"); return 4; }
-    x->c = c; x->step = 0; x->N = c.graph->n_rows; x->cnt = nullptr; x->colsum = nullptr;
-    x->drop_keep = 1.f; x->drop_seed = 0; x->dr = DropArgs{};
-    x->lw_n = 0; for (int k = 0; k <= LGCN_MAX_LAYERS; k++) x->lw[k] = 0.f;
-    x->fold_g32 = true; x->mult = nullptr; x->mult_cap = 0; x->fold_mult = nullptr; x->arrive = nullptr; x->folded_steps = 0;
-    x->mn = {};
-    x->loss_kind = LGCN_LOSS_BPR; x->loss_temp = 1.f; x->ib_ws = nullptr; x->ib_cap = 0;
-    x->ib_score = LGCN_SCORE_DOT; x->ib_logq = nullptr; x->ib_mix = 0;
-    x->bm_words = (x->N + 31) / 32; x->flip = 0;
-    const size_t stride = table_bytes(x->N, c.d, c.act_dtype);
-    for (int k = 0; k <= LGCN_MAX_LAYERS; k++) x->act[k] = nullptr;
-    x->fwd_layers = c.dense_last ? c.K : c.K - 1;
-    for (int k = 1; k <= x->fwd_layers; k++) x->act[k] = (char *)c.act + (size_t)(k - 1) * stride;
-    // rows that are never flagged are never read; zero-filled so that the zero-weight padding reads of row 0 stay finite
-    x->g32 = nullptr; x->e0b = nullptr; x->e0q = nullptr; x->e0b_fresh = false; x->in_loop = false; x->dp_local = false; x->dp_rank = -1;
-    x->hub_graph = nullptr; x->hub_nnz = 0; x->hub_rows = 0;
-    x->variant = gate || smooth; x->tvar = nullptr; x->item_bitmap = nullptr; x->gate_partials = nullptr; x->gate_total = nullptr; x->gate_P = 0; x->gate_wgs = 0;
-    const size_t gbytes = (size_t)x->N * c.d * sizeof(float);
-    bool ok = hipMalloc((void **)&x->g32, gbytes) == hipSuccess && hipMemset(x->g32, 0, gbytes) == hipSuccess;
-    if (ok) ok = hipMalloc((void **)&x->colsum, sizeof(float) * 3 * (size_t)c.max_batch) == hipSuccess;
-    if (ok && c.reg_ego) ok = hipMalloc((void **)&x->cnt, sizeof(int32_t) * (size_t)x->N) == hipSuccess && hipMemset(x->cnt, 0, sizeof(int32_t) * (size_t)x->N) == hipSuccess;
-    if (ok && x->variant) ok = hipMalloc((void **)&x->tvar, gbytes) == hipSuccess;
-    if (ok && smooth) {
-        const size_t wb = sizeof(uint32_t) * (size_t)((x->N - c.n_users + 31) / 32);
-        ok = hipMalloc((void **)&x->item_bitmap, wb) == hipSuccess && hipMemset(x->item_bitmap, 0, wb) == hipSuccess;
-    }
-    if (ok && gate) {
-        x->gate_P = 2 * c.pop_hidden + c.d * c.pop_hidden + c.d + 2 * c.d * c.gate_hidden + 2 * c.gate_hidden + 1;
-        x->gate_wgs = (c.max_batch + GATE_TPB - 1) / GATE_TPB;
-        ok = hipMalloc((void **)&x->gate_partials, sizeof(long long) * ((size_t)x->gate_wgs + 1) * x->gate_P) == hipSuccess;
-        if (ok) x->gate_total = x->gate_partials + (size_t)x->gate_wgs * x->gate_P;
-    }
-    if (ok && c.act_dtype == LGCN_BF16 && c.K >= 2) ok = hipMalloc((void **)&x->e0b, gbytes / 2) == hipSuccess;
-    if (ok && c.act_dtype == LGCN_FP8 && c.K >= 2) ok = hipMalloc(&x->e0q, table_bytes(x->N, c.d, LGCN_FP8)) == hipSuccess;
-    if (ok && !c.dense_last) {
-        // Rows too long for one workgroup (a 800 000-neighbour item of the 10M x 1M graph kept ONE k_triplet workgroup busy
-        // for 37 ms, several times per batch): a plan over just those rows; k_spmm computes their last-layer rows for
-        // the whole chip to share, once per step, before k_triplet.
-        const int32_t thr = c.hub_nnz == 0 ? TRIPLET_HUB_NNZ : c.hub_nnz;
-        if (thr > 0) {
-            std::vector<int32_t> ip((size_t)x->N + 1), hubs;
-            ok = hipMemcpy(ip.data(), c.graph->indptr, sizeof(int32_t) * ip.size(), hipMemcpyDeviceToHost) == hipSuccess;
-            for (int64_t r = 0; ok && r < x->N; r++) if (ip[(size_t)r + 1] - ip[(size_t)r] > thr) hubs.push_back((int32_t)r);
-            if (ok && !hubs.empty()) {
-                int32_t *dh = nullptr;
-                ok = hipMalloc((void **)&dh, sizeof(int32_t) * hubs.size()) == hipSuccess &&
-                     hipMemcpy(dh, hubs.data(), sizeof(int32_t) * hubs.size(), hipMemcpyHostToDevice) == hipSuccess;
-                const int32_t hub_chunk = c.hub_chunk > 0 ? c.hub_chunk : TRIPLET_HUB_CHUNK;
-                if (ok) ok = graph_create_impl(c.graph->indptr, c.graph->indices, c.graph->vals, x->N, c.graph->nnz, c.d, dh,
-                                               (int64_t)hubs.size(), nullptr, hub_chunk, &x->hub_graph) == 0;
-                if (dh) (void)hipFree(dh);
-                x->hub_nnz = thr; x->hub_rows = (int64_t)hubs.size();
-            }
-        }
-    }
-    if (!ok) {
-        if (x->g32) (void)hipFree(x->g32);
-        if (x->colsum) (void)hipFree(x->colsum);
-        if (x->cnt) (void)hipFree(x->cnt);
-        if (x->arrive) (void)hipFree(x->arrive);
-        if (x->tvar) (void)hipFree(x->tvar);
-        if (x->item_bitmap) (void)hipFree(x->item_bitmap);
-        if (x->gate_partials) (void)hipFree(x->gate_partials);
-        if (x->e0b) (void)hipFree(x->e0b);
-        if (x->e0q) (void)hipFree(x->e0q);
-        if (x->hub_graph) lgcn_graph_destroy(x->hub_graph);
-        delete x;
-        lgcn_set_error("lgcn_ctx_create: cannot allocate the library-owned tables (N*d*4 bytes fp32 gradient rows, N*d*2 bf16 parameters)");
-        return 4;
-    }
-    *out = x;
-    return 0;
-}
-extern "C" void lgcn_ctx_destroy(lgcn_ctx *ctx) {
-    if (!ctx) return;
-    if (ctx->g32) (void)hipFree(ctx->g32);
-    if (ctx->colsum) (void)hipFree(ctx->colsum);
-    if (ctx->cnt) (void)hipFree(ctx->cnt);
-    if (ctx->arrive) (void)hipFree(ctx->arrive);
-    if (ctx->mult) (void)hipFree(ctx->mult);
-    if (ctx->ib_ws) (void)hipFree(ctx->ib_ws);
-    if (ctx->tvar) (void)hipFree(ctx->tvar);
-    if (ctx->item_bitmap) (void)hipFree(ctx->item_bitmap);
-    if (ctx->gate_partials) (void)hipFree(ctx->gate_partials);
-    if (ctx->e0b) (void)hipFree(ctx->e0b);
-    if (ctx->e0q) (void)hipFree(ctx->e0q);
-    if (ctx->hub_graph) lgcn_graph_destroy(ctx->hub_graph);
-    delete ctx;
-}
-extern "C" int lgcn_ctx_set_dp_local(lgcn_ctx *ctx, int on) {
-    if (!ctx) { lgcn_set_error("lgcn_ctx_set_dp_local: null context"); return 3; }
-    ctx->dp_local = on != 0; ctx->dp_rank = -1;
-    return 0;
-}
-extern "C" int lgcn_ctx_set_fold_g32(lgcn_ctx *ctx, int on) {
-    if (!ctx) { lgcn_set_error("lgcn_ctx_set_fold_g32: null context"); return 3; }
-    ctx->fold_g32 = on != 0;
-    return 0;
-}
-extern "C" int64_t lgcn_ctx_folded_steps(const lgcn_ctx *ctx) { return ctx ? ctx->folded_steps : -1; }
-extern "C" int lgcn_ctx_copy_arrivals(const lgcn_ctx *ctx, int32_t *dst_host, int64_t n) {
-    if (!ctx || !dst_host) { lgcn_set_error("lgcn_ctx_copy_arrivals: null argument"); return 3; }
-    if (ctx->variant || n < 0 || n > ctx->N) { lgcn_set_error("lgcn_ctx_copy_arrivals: the context has no arrival array of that size"); return 3; }
-    if (!ctx->arrive) { memset(dst_host, 0, sizeof(int32_t) * (size_t)n); return 0; }       // no call has folded yet: nothing was ever counted
-    HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(dst_host, ctx->arrive, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
-    return 0;
-}
-extern "C" int64_t lgcn_ctx_get_step(const lgcn_ctx *ctx) { return ctx ? ctx->step : -1; }
-extern "C" int64_t lgcn_ctx_hub_rows(const lgcn_ctx *ctx) { return (ctx && ctx->hub_graph) ? ctx->hub_rows : 0; }
-extern "C" void lgcn_ctx_set_step(lgcn_ctx *ctx, int64_t s) { if (ctx) ctx->step = s; }
-extern "C" void lgcn_ctx_set_lr(lgcn_ctx *ctx, double lr) { if (ctx) ctx->c.lr = lr; }
-extern "C" int lgcn_ctx_set_dropout(lgcn_ctx *ctx, float keep_prob, uint64_t seed) {
-    if (!ctx) { lgcn_set_error("lgcn_ctx_set_dropout: null context"); return 3; }
-    if (!drop_prob_ok(keep_prob)) { lgcn_set_error("lgcn_ctx_set_dropout: dropout keep_prob must be in (0, 1]"); return 3; }
-    if (ctx->c.act_dtype == LGCN_FP8) { lgcn_set_error("lgcn_ctx_set_dropout: edge dropout is not implemented for LGCN_FP8 activation storage"); return 3; }
-    if (ctx->variant) { lgcn_set_error("lgcn_ctx_set_dropout: edge dropout is not implemented with the optional branches (item-item smoothing / popularity gate)"); return 3; }
-    if (ctx->lw_n && keep_prob < 1.f) { lgcn_set_error("lgcn_ctx_set_dropout: edge dropout is not implemented together with layer weights (lgcn_ctx_set_layer_weights)"); return 3; }
-    ctx->drop_keep = keep_prob; ctx->drop_seed = seed; ctx->dr = DropArgs{};
-    return 0;
-}
-// the entry points that split a step over ranks have no dropout form: say so instead of training undropped
-static int refuse_dropout(const lgcn_ctx *x, const char *who) {
-    if (!x || !(x->drop_keep < 1.f)) return 0;
-    char buf[192];
-    snprintf(buf, sizeof buf, "%s: edge dropout (lgcn_ctx_set_dropout) is implemented for the single-GPU step only", who);
-    lgcn_set_error(buf);
-    return 3;
-}
-
-extern "C" int lgcn_ctx_set_layer_weights(lgcn_ctx *ctx, const float *w_host, int32_t n) {
-    if (!ctx) { lgcn_set_error("lgcn_ctx_set_layer_weights: null context"); return 3; }
-    if (!w_host || n == 0) { ctx->lw_n = 0; return 0; }            // back to the mean: the step launches what it always launched
-    if (n < 0 || n > LGCN_MAX_LAYERS + 1) n = -1;                    // (reported as a wrong count)
-    if (int rc = check_layer_weights("lgcn_ctx_set_layer_weights", w_host, n, ctx->c.K)) return rc;
-    if (ctx->c.act_dtype == LGCN_FP8) { lgcn_set_error("lgcn_ctx_set_layer_weights: layer weights are not implemented for LGCN_FP8 activation storage"); return 3; }
-    if (ctx->variant) { lgcn_set_error("lgcn_ctx_set_layer_weights: layer weights are not implemented with the optional branches (item-item smoothing / popularity gate)"); return 3; }
-    if (ctx->drop_keep < 1.f) { lgcn_set_error("lgcn_ctx_set_layer_weights: layer weights are not implemented together with edge dropout (lgcn_ctx_set_dropout)"); return 3; }
-    for (int k = 0; k < n; k++) ctx->lw[k] = w_host[k];
-    ctx->lw_n = n;
-    return 0;
-}
-extern "C" int32_t lgcn_ctx_get_layer_weights(const lgcn_ctx *ctx, float *w_out) {
-    if (!ctx || !ctx->lw_n) return 0;
-    if (w_out) for (int k = 0; k < ctx->lw_n; k++) w_out[k] = ctx->lw[k];
-    return ctx->lw_n;
-}
-// ... nor a weighted form: say so instead of training the mean
-static int refuse_layer_weights(const lgcn_ctx *x, const char *who) {
-    if (!x || !x->lw_n) return 0;
-    char buf[192];
-    snprintf(buf, sizeof buf, "%s: layer weights (lgcn_ctx_set_layer_weights) are implemented for the single-GPU step only", who);
-    lgcn_set_error(buf);
-    return 3;
-}
-
-// THE carving of the in-batch workspace for `cap` rows of dim d, in floats from its start:
-//   U | P | sbb | uid | pid | mrg | part | invu | invp | lq      with icap = (1 + R_max) cap item rows in P, pid, invp and lq
-// R_max = 0 is the plain step's carving, R_max >= 1 the mixed step's; both live in ONE allocation of `words` floats, which is
-// never smaller than the plain carving's.  The plain kernels do not take the three score vectors as arguments: ib_invu() in
-// lgcn_inbatch.hip finds them at part + 2 cap lgcn_inbatch_parts(cap), which is where `invu` lands here -- `part` holds exactly
-// that many floats under R_max = 0 and invu, invp, lq ([cap] each) are the next blocks
-struct InBatchWs {
-    size_t U, P, sbb, uid, pid, mrg, part, invu, invp, lq, words, icap;
-    InBatchWs(int32_t cap_, int d, int32_t R_max) {
-        const size_t cap = (size_t)cap_;
-        const size_t parts = (size_t)(R_max ? lgcn_inbatch_mix_parts(cap_, R_max) : lgcn_inbatch_parts(cap_));
-        size_t at = 0;
-        auto take = [&at](size_t n) { const size_t o = at; at += n; return o; };
-        icap = (size_t)(1 + R_max) * cap;
-        U = take(cap * d); P = take(icap * d); sbb = take(cap); uid = take(cap); pid = take(icap); mrg = take(2 * cap);
-        part = take(2 * cap * parts); invu = take(cap); invp = take(icap); lq = take(icap);
-        words = at;
-        if (R_max) words = std::max(words, InBatchWs(cap_, d, 0).words);
-    }
-};
-
-// the conditions of the two softmax losses (`what`: the loss as the messages name it, `slots`: its slot form)
-static int refuse_loss_config(const lgcn_ctx *ctx, float temperature, const char *what, const char *slots) {
-    char buf[256];
-    const char *fmt = nullptr;
-    if (!(temperature > 0.f) || !isfinite(temperature)) fmt = "lgcn_ctx_set_loss: %s needs a finite temperature > 0";
-    else if (ctx->c.act_dtype == LGCN_FP8) fmt = "lgcn_ctx_set_loss: %s is not implemented for LGCN_FP8 activation storage";
-    else if (ctx->variant) fmt = "lgcn_ctx_set_loss: %s is not implemented with the optional branches (item-item smoothing / popularity gate)";
-    else if (!ctx->c.dense_last) fmt = "lgcn_ctx_set_loss: %s needs a context with dense_last = 1 (the gathered last layer has no %s slot form)";
-    if (!fmt) return 0;
-    snprintf(buf, sizeof buf, fmt, what, slots);
-    lgcn_set_error(buf);
-    return 3;
-}
-
-extern "C" int lgcn_ctx_set_loss(lgcn_ctx *ctx, int32_t kind, float temperature) {
-    if (!ctx) { lgcn_set_error("lgcn_ctx_set_loss: null context"); return 3; }
-    if (kind == LGCN_LOSS_BPR) { ctx->loss_kind = LGCN_LOSS_BPR; ctx->loss_temp = 1.f; return 0; }      // the step launches what it always launched
-    if (kind != LGCN_LOSS_SOFTMAX && kind != LGCN_LOSS_INBATCH) { lgcn_set_error("lgcn_ctx_set_loss: unknown loss kind (LGCN_LOSS_BPR, LGCN_LOSS_SOFTMAX or LGCN_LOSS_INBATCH)"); return 3; }
-    const bool inbatch = kind == LGCN_LOSS_INBATCH;
-    if (int rc = refuse_loss_config(ctx, temperature, inbatch ? "the in-batch softmax loss (inbatch)" : "the sampled-softmax loss", inbatch ? "2 B" : "2 + R")) return rc;
-    if (inbatch && !ctx->ib_ws) {       // the workspace is allocated once, before anything is changed
-        const int32_t cap = lgcn_inbatch_rows(ctx->c.max_batch);
-        void *ws = nullptr;
-        if (hipMalloc(&ws, sizeof(float) * InBatchWs(cap, ctx->c.d, 0).words) != hipSuccess) {
-            (void)hipGetLastError();
-            lgcn_set_error("lgcn_ctx_set_loss: cannot allocate the workspace of the in-batch softmax loss (inbatch): 2 * max_batch * d * 4 bytes and a few vectors");
-            return 4;
-        }
-        ctx->ib_ws = ws; ctx->ib_cap = cap;
-    }
-    ctx->loss_kind = kind; ctx->loss_temp = temperature;
-    return 0;
-}
-extern "C" int lgcn_ctx_set_inbatch_scores(lgcn_ctx *ctx, int score, const float *item_logq) {
-    if (!ctx) { lgcn_set_error("lgcn_ctx_set_inbatch_scores: null context"); return 3; }
-    if (score != LGCN_SCORE_DOT && score != LGCN_SCORE_COSINE) {
-        lgcn_set_error("lgcn_ctx_set_inbatch_scores: unknown score kind (LGCN_SCORE_DOT or LGCN_SCORE_COSINE)"); return 3; }
-    ctx->ib_score = score; ctx->ib_logq = item_logq;
-    return 0;
-}
-extern "C" int lgcn_ctx_get_inbatch_scores(const lgcn_ctx *ctx, const float **item_logq) {
-    if (!ctx) return -1;
-    if (item_logq) *item_logq = ctx->ib_logq;
-    return ctx->ib_score;
-}
-extern "C" int lgcn_ctx_set_inbatch_mix(lgcn_ctx *ctx, int32_t R_max) {
-    if (!ctx) { lgcn_set_error("lgcn_ctx_set_inbatch_mix: null context"); return 3; }
-    if (R_max == 0) { ctx->ib_mix = 0; return 0; }      // off: the workspace stays (the plain step carves the same allocation)
-    if (R_max < 1 || R_max > LGCN_MAX_NEG_RATIO) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "lgcn_ctx_set_inbatch_mix: R_max = %d is out of range (0 = off, or 1..%d)", (int)R_max, LGCN_MAX_NEG_RATIO);
-        lgcn_set_error(buf); return 3;
-    }
-    if (ctx->loss_kind != LGCN_LOSS_INBATCH || !ctx->ib_ws) {
-        lgcn_set_error("lgcn_ctx_set_inbatch_mix: mixed negatives need the in-batch softmax loss (inbatch) set on the context first (lgcn_ctx_set_loss with LGCN_LOSS_INBATCH)");
-        return 3;
-    }
-    if (R_max > ctx->ib_mix) {      // grow only: the new block first, so a failure changes nothing
-        HIP_OK(hipDeviceSynchronize());     // steps in flight still read the old block
-        void *ws = nullptr;
-        if (hipMalloc(&ws, sizeof(float) * InBatchWs(ctx->ib_cap, ctx->c.d, R_max).words) != hipSuccess) {
-            (void)hipGetLastError();
-            lgcn_set_error("lgcn_ctx_set_inbatch_mix: cannot allocate the workspace of the mixed in-batch step: (2 + R_max) * max_batch * d * 4 bytes and a few vectors");
-            return 4;
-        }
-        (void)hipFree(ctx->ib_ws);
-        ctx->ib_ws = ws;
-    }
-    ctx->ib_mix = R_max;
-    return 0;
-}
-extern "C" int32_t lgcn_ctx_get_inbatch_mix(const lgcn_ctx *ctx) { return ctx ? ctx->ib_mix : -1; }
-extern "C" int32_t lgcn_ctx_get_loss(const lgcn_ctx *ctx, float *temperature_out) {
-    if (!ctx) return -1;
-    if (temperature_out) *temperature_out = ctx->loss_temp;
-    return ctx->loss_kind;
-}
-// today's three-slot kernels, and every form that splits a step over ranks, compute BPR: say so instead of training another
-// loss.  The in-batch loss trains through its own two entry points only, so lgcn_train_step_multi / _epoch_multi refuse it too.
-// (Declared in lgcn_internal.h: lgcn_train_step_i64 in lgcn_ids.hip refuses in the same words.)
-int lgcn_refuse_loss(const lgcn_ctx *x, const char *who) {
-    if (!x || x->loss_kind == LGCN_LOSS_BPR) return 0;
-    char buf[256];
-    if (x->loss_kind == LGCN_LOSS_INBATCH)
-        snprintf(buf, sizeof buf, "%s: the in-batch softmax loss (inbatch; lgcn_ctx_set_loss) is implemented for lgcn_train_step_inbatch / lgcn_train_epoch_inbatch only", who);
-    else
-        snprintf(buf, sizeof buf, "%s: the sampled-softmax loss (lgcn_ctx_set_loss) is implemented for lgcn_train_step_multi / lgcn_train_epoch_multi only", who);
-    lgcn_set_error(buf);
-    return 3;
-}
-
-static SpmmArgs base_spmm(const lgcn_ctx *x) {
-    SpmmArgs a = graph_spmm(x->c.graph);
-    a.G64 = (long long *)x->c.G64; a.G32 = x->g32; a.bitmap = x->c.bitmap + x->flip * x->bm_words;
-    a.div = (float)(x->c.K + 1); a.remap = x->c.xcd_remap;
-    return a;
-}
-
-// forward layers X_1..X_{K-1}
-static int run_forward(lgcn_ctx *x, hipStream_t st) {
-    const lgcn_train_config &c = x->c;
-    { int rc0 = graph_acquire(c.graph, st); if (rc0) return rc0; }
-    const void *prev = c.E0; int prev_dt = LGCN_F32;
-    if (x->e0b && x->fwd_layers >= 1) {                 // bf16 activation storage: layer 1 gathers bf16(E0)
-        if (!x->in_loop) x->e0b_fresh = false;          // a single-step call: E0 may have been written by anybody since
-        if (!x->e0b_fresh) launch_to_bf16(c.E0, x->e0b, x->N * c.d, st);
-        x->e0b_fresh = true;
-        prev = x->e0b; prev_dt = LGCN_BF16;
-    }
-    if (x->e0q && x->fwd_layers >= 1) {                 // fp8 activation storage: layer 1 gathers fp8(E0)
-        if (!x->in_loop) x->e0b_fresh = false;
-        if (!x->e0b_fresh) { int rc = launch_to_fp8(c.E0, x->e0q, x->N, c.d, st); if (rc) return rc; }
-        x->e0b_fresh = true;
-        prev = x->e0q; prev_dt = LGCN_FP8;
-    }
-    for (int k = 1; k <= x->fwd_layers; k++) {
-        SpmmArgs a = base_spmm(x);
-        a.X = prev; a.Y = x->act[k]; a.dr = x->dr;
-        int rc = launch_spmm<0>(a, c.d, prev_dt, c.act_dtype, st);
-        if (rc) return rc;
-        prev = x->act[k]; prev_dt = c.act_dtype;
-    }
-    return 0;
-}
-
-static int run_bpr(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *neg,
-                   int32_t B_global, int32_t b_off, int32_t B_local, int32_t shard, bool atomics, bool exchange, hipStream_t st,
-                   bool count_slots = true, int cols_phase = 0) {
-    const lgcn_train_config &c = x->c;
-    BprArgs a{};
-    a.reg_ego = c.reg_ego; a.cnt = (atomics && count_slots) ? x->cnt : nullptr;
-    a.dr = x->dr;
-    const bool wts = x->lw_n != 0;
-    for (int k = 0; k < x->lw_n; k++) a.w[k] = x->lw[k];
-    a.cols_phase = cols_phase; a.erows = c.contrib; a.colsum = x->colsum;
-    a.indptr = c.graph->indptr; a.indices = c.graph->indices; a.vals = c.graph->vals; a.X0 = c.E0; a.K = c.K;
-    for (int k = 1; k <= x->fwd_layers; k++) a.Xl[k] = x->act[k];
-    a.dense_last = c.dense_last;
-    a.n_users = c.n_users; a.N = x->N;
-    a.users = users + b_off; a.pos = pos + b_off; a.neg = neg + b_off;
-    a.B_local = B_local; a.shard = shard;
-    a.inv_B = 1.0f / (float)B_global; a.lam = c.decay / (float)B_global;
-    a.G64 = atomics ? (long long *)c.G64 : nullptr; a.bitmap = c.bitmap + x->flip * x->bm_words;
-    a.stale_bitmap = c.bitmap + (x->flip ^ 1) * x->bm_words; a.bitmap_words = x->bm_words;
-    a.contrib = c.contrib; a.terms = c.terms; a.err = c.err; a.exchange = exchange ? 1 : 0;
-    a.terms_off = exchange ? 0 : b_off; a.terms_stride = B_global;
-    if (x->fold_mult && atomics && !exchange && cols_phase == 0 && b_off == 0 && B_local == B_global) {
-        // a step of lgcn_train_epoch with the fold: the launch below also writes the fp32 copies of its gradient rows
-        a.mult = x->fold_mult; a.G32 = x->g32; a.gdiv = x->lw_n ? 1.f : (float)(c.K + 1); a.arrive = x->arrive;
-    }
-    if (cols_phase == 2) {      // column shard, after the all-reduce: loss terms + gradient scatter from the stored slot rows
-        if (B_local <= 0) return 0;
-        DISPATCH_D(c.d, {
-            const int tpb = 256 / (D < 64 ? D : 64);
-            hipLaunchKernelGGL((k_cols_finish<D>), dim3((unsigned)((B_local + tpb - 1) / tpb)), dim3(256), 0, st, a);
-        });
+int lgcn_spmm_launch(const SpmmArgs &a, int mode, int d, int x_dtype, int y_dtype, hipStream_t st) {
+    switch (mode) {
+    case 0: return launch_spmm<0>(a, d, x_dtype, y_dtype, st);
+    case M_ADDSELF:       // Y = selfX + A X on fp32 tables (item-item smoothing): only the fp32 instance exists
+        DISPATCH_D(d, launch_spmm_t<D, float, float, M_ADDSELF>(a, st));
         return 0;
+    case M_ADDG: return launch_spmm<M_ADDG>(a, d, x_dtype, y_dtype, st);
+    case M_ADDG | M_ADAM: return launch_spmm<M_ADDG | M_ADAM>(a, d, x_dtype, y_dtype, st);
+    case M_SPARSE | M_ADDG: return launch_spmm<M_SPARSE | M_ADDG>(a, d, x_dtype, y_dtype, st);
+    case M_SPARSE | M_ADDG | M_ADAM: return launch_spmm<M_SPARSE | M_ADDG | M_ADAM>(a, d, x_dtype, y_dtype, st);
+    case M_ADDG | M_WTS: return launch_spmm<M_ADDG | M_WTS>(a, d, x_dtype, y_dtype, st);
+    case M_ADDG | M_ADAM | M_WTS: return launch_spmm<M_ADDG | M_ADAM | M_WTS>(a, d, x_dtype, y_dtype, st);
+    case M_SPARSE | M_ADDG | M_WTS: return launch_spmm<M_SPARSE | M_ADDG | M_WTS>(a, d, x_dtype, y_dtype, st);
+    case M_SPARSE | M_ADDG | M_ADAM | M_WTS: return launch_spmm<M_SPARSE | M_ADDG | M_ADAM | M_WTS>(a, d, x_dtype, y_dtype, st);
     }
-    if (x->hub_graph && !c.dense_last && B_local > 0) {
-        // last layer of the hub rows, X_K[hub] = (A_hat X_{K-1})[hub] in fp32, into the library's [N,d] table (free until k_g32)
-        { int rc0 = graph_acquire(x->hub_graph, st); if (rc0) return rc0; }
-        SpmmArgs h = graph_spmm(x->hub_graph);
-        h.X = c.K == 1 ? (const void *)c.E0 : x->act[c.K - 1]; h.Y = x->g32; h.remap = c.xcd_remap; h.dr = x->dr;
-        int rc = launch_spmm<0>(h, c.d, c.K == 1 ? LGCN_F32 : c.act_dtype, LGCN_F32, st);
-        if (rc) return rc;
-        a.Xhub = x->g32; a.hub_nnz = x->hub_nnz;
-    }
-    if (B_local <= 0) {
-        // a rank whose shard of a short last batch is empty launches nothing, but the row bitmap of
-        // two steps ago still has to be cleared (k_triplet / k_triplet_dense does it on the other ranks)
-        HIP_OK(hipMemsetAsync(a.stale_bitmap, 0, sizeof(uint32_t) * (size_t)x->bm_words, st));
-        return 0;
-    }
-    DISPATCH_D(c.d, {
-        if (c.act_dtype == LGCN_FP8) {
-            if constexpr (D >= 64) {
-                if (c.dense_last) {
-                    const int tpb = 256 / 64;
-                    hipLaunchKernelGGL((k_triplet_dense<D, fp8_t>), dim3((unsigned)((B_local + tpb - 1) / tpb)), dim3(256), 0, st, a);
-                } else if (big_table(x->N, D)) hipLaunchKernelGGL((k_triplet<D, fp8_t, true>), dim3(B_local), dim3(64 * TripletGeo<fp8_t>::NW), 0, st, a);
-                else hipLaunchKernelGGL((k_triplet<D, fp8_t, false>), dim3(B_local), dim3(64 * TripletGeo<fp8_t>::NW), 0, st, a);
-            }
-        } else if (c.dense_last) {
-            const int tpb = 256 / (D < 64 ? D : 64);
-            const unsigned gd = (unsigned)((B_local + tpb - 1) / tpb);
-            if (wts) {
-                if (c.act_dtype == LGCN_F32) hipLaunchKernelGGL((k_triplet_dense<D, float, true>), dim3(gd), dim3(256), 0, st, a);
-                else hipLaunchKernelGGL((k_triplet_dense<D, bf16_t, true>), dim3(gd), dim3(256), 0, st, a);
-            } else if (c.act_dtype == LGCN_F32) hipLaunchKernelGGL((k_triplet_dense<D, float>), dim3(gd), dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((k_triplet_dense<D, bf16_t>), dim3(gd), dim3(256), 0, st, a);
-        } else if (wts) {          // layer weights: the weighted slot rows (never with dropout: the setters refuse the pair)
-            if (big_table(x->N, D)) {
-                if (c.act_dtype == LGCN_F32) hipLaunchKernelGGL((k_triplet<D, float, true, false, true>), dim3(B_local), dim3(64 * TripletGeo<float>::NW), 0, st, a);
-                else hipLaunchKernelGGL((k_triplet<D, bf16_t, true, false, true>), dim3(B_local), dim3(64 * TripletGeo<bf16_t>::NW), 0, st, a);
-            } else if (c.act_dtype == LGCN_F32) hipLaunchKernelGGL((k_triplet<D, float, false, false, true>), dim3(B_local), dim3(64 * TripletGeo<float>::NW), 0, st, a);
-            else hipLaunchKernelGGL((k_triplet<D, bf16_t, false, false, true>), dim3(B_local), dim3(64 * TripletGeo<bf16_t>::NW), 0, st, a);
-        } else if (a.dr.on) {      // edge dropout: the last layer's gathers take the step's mask
-            if (big_table(x->N, D)) {
-                if (c.act_dtype == LGCN_F32) hipLaunchKernelGGL((k_triplet<D, float, true, true>), dim3(B_local), dim3(64 * TripletGeo<float>::NW), 0, st, a);
-                else hipLaunchKernelGGL((k_triplet<D, bf16_t, true, true>), dim3(B_local), dim3(64 * TripletGeo<bf16_t>::NW), 0, st, a);
-            } else if (c.act_dtype == LGCN_F32) hipLaunchKernelGGL((k_triplet<D, float, false, true>), dim3(B_local), dim3(64 * TripletGeo<float>::NW), 0, st, a);
-            else hipLaunchKernelGGL((k_triplet<D, bf16_t, false, true>), dim3(B_local), dim3(64 * TripletGeo<bf16_t>::NW), 0, st, a);
-        } else if (big_table(x->N, D)) {
-            if (c.act_dtype == LGCN_F32) hipLaunchKernelGGL((k_triplet<D, float, true>), dim3(B_local), dim3(64 * TripletGeo<float>::NW), 0, st, a);
-            else hipLaunchKernelGGL((k_triplet<D, bf16_t, true>), dim3(B_local), dim3(64 * TripletGeo<bf16_t>::NW), 0, st, a);
-        } else if (c.act_dtype == LGCN_F32) hipLaunchKernelGGL((k_triplet<D, float, false>), dim3(B_local), dim3(64 * TripletGeo<float>::NW), 0, st, a);
-        else hipLaunchKernelGGL((k_triplet<D, bf16_t, false>), dim3(B_local), dim3(64 * TripletGeo<bf16_t>::NW), 0, st, a);
-    });
-    return 0;
-}
-
-// floats per rank of the data-parallel exchange block for a shard of S triplets: [3*S*d gradient rows | S loss | S reg terms], with
-// the popularity gate also [S entropy terms | pad to an even count | 2*P floats = P int64: the rank's fixed-point MLP gradient sums]
-static int64_t dp_block_floats(const lgcn_ctx *x, int64_t S) {
-    int64_t n = 3 * S * x->c.d + 2 * S;
-    if (x->variant && x->c.item_pop) { n += S; n += n & 1; n += 2 * (int64_t)x->gate_P; }
-    return n;
-}
-static int64_t dp_block_tail(const lgcn_ctx *x, int64_t S) {          // float offset of the int64 tail inside a block
-    int64_t n = 3 * S * x->c.d + 3 * S;
-    return n + (n & 1);
-}
-extern "C" int64_t lgcn_dp_block_floats(const lgcn_ctx *x, int32_t B_global, int32_t world) {
-    if (!x || B_global <= 0 || world < 1) return 0;
-    return dp_block_floats(x, (B_global + world - 1) / world);
-}
-
-// The optional branches' forward tail and loss: T = mean of the K+1 dense layers, item-item smoothing, then the loss on the
-// ONE final table (popularity gate inside k_triplet_gate).  The batch slice [b_off, b_off + B_local) of a global batch of
-// B_global triplets (single GPU: the whole batch); atomics: into G64 / the row flags; exchange: into the exchange block.
-static int run_variant_loss(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *neg, int32_t B_global,
-                            int32_t b_off, int32_t B_local, int32_t shard, bool atomics, bool exchange, hipStream_t st) {
-    const lgcn_train_config &c = x->c;
-    const int64_t m_items = x->N - c.n_users;
-    float *items_mean = c.i2i ? x->g32 : x->tvar;           // with smoothing the item block of T is an SpMM input first
-    MeanSplitArgs m{};
-    m.X0 = c.E0; m.K = c.K; m.out_u = x->tvar; m.out_i = items_mean;
-    for (int k = 1; k <= c.K; k++) m.Xl[k] = x->act[k];
-    m.n4_users = (int64_t)c.n_users * c.d / 4; m.n4 = x->N * c.d / 4;
-    {
-        const int64_t blocks = (m.n4 + 255) / 256;
-        const unsigned grid = (unsigned)(blocks < 2048 ? blocks : 2048);
-        if (c.act_dtype == LGCN_F32) hipLaunchKernelGGL((k_mean_layers<float>), dim3(grid), dim3(256), 0, st, m);
-        else hipLaunchKernelGGL((k_mean_layers<bf16_t>), dim3(grid), dim3(256), 0, st, m);
-    }
-    if (c.i2i) {            // items = T_items + (alpha I2I) T_items   (model.py:228-229)
-        { int rc0 = graph_acquire(c.i2i, st); if (rc0) return rc0; }
-        SpmmArgs h = graph_spmm(c.i2i);
-        h.X = x->g32 + (int64_t)c.n_users * c.d; h.selfX = (const float *)h.X; h.Y = x->tvar + (int64_t)c.n_users * c.d; h.remap = c.xcd_remap;
-        int rc = launch_spmm_addself(h, c.d, st);
-        if (rc) return rc;
-        HIP_OK(hipMemsetAsync(x->item_bitmap, 0, sizeof(uint32_t) * (size_t)((m_items + 31) / 32), st));
-    }
-    uint32_t *bm = c.bitmap + x->flip * x->bm_words, *stale = c.bitmap + (x->flip ^ 1) * x->bm_words;
-    const int64_t tail = dp_block_tail(x, shard);
-    if (B_local <= 0) {     // an empty shard: nothing to launch, but the stale bitmap must go and the block's MLP sums must read zero
-        HIP_OK(hipMemsetAsync(stale, 0, sizeof(uint32_t) * (size_t)x->bm_words, st));
-        if (exchange && c.item_pop) HIP_OK(hipMemsetAsync(c.contrib + tail, 0, sizeof(long long) * (size_t)x->gate_P, st));
-        return 0;
-    }
-    if (c.item_pop) {
-        GateArgs g{};
-        g.E = x->tvar; g.item_pop = c.item_pop; g.params = c.gate_params; g.partials = x->gate_partials;
-        g.Hp = c.pop_hidden; g.Hg = c.gate_hidden; g.P = x->gate_P;
-        g.inv_temp = 1.0f / c.pop_gate_temp; g.ent_scale = c.gate_entropy_coeff / (float)(2 * B_global);
-        g.n_users = c.n_users; g.N = x->N; g.users = users + b_off; g.pos = pos + b_off; g.neg = neg + b_off; g.B = B_local;
-        g.inv_B = 1.0f / (float)B_global; g.lam = c.decay / (float)B_global;
-        g.G64 = atomics ? (long long *)c.G64 : nullptr; g.bitmap = bm; g.item_bitmap = c.i2i ? x->item_bitmap : nullptr;
-        g.stale_bitmap = stale; g.bitmap_words = x->bm_words; g.terms = c.terms + (exchange ? 0 : b_off); g.terms_stride = B_global; g.err = c.err;
-        g.contrib = c.contrib; g.shard = shard; g.exchange = exchange ? 1 : 0;
-        const unsigned grid = (unsigned)((B_local + GATE_TPB - 1) / GATE_TPB);
-        const size_t lds = gate_lds_bytes(c.d);
-        switch (c.d) {
-        case 32: HIP_OK(hipFuncSetAttribute((const void *)k_triplet_gate<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                 hipLaunchKernelGGL((k_triplet_gate<32>), dim3(grid), dim3(256), lds, st, g); break;
-        case 64: HIP_OK(hipFuncSetAttribute((const void *)k_triplet_gate<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                 hipLaunchKernelGGL((k_triplet_gate<64>), dim3(grid), dim3(256), lds, st, g); break;
-        case 128: HIP_OK(hipFuncSetAttribute((const void *)k_triplet_gate<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                 hipLaunchKernelGGL((k_triplet_gate<128>), dim3(grid), dim3(256), lds, st, g); break;
-        default: lgcn_set_error("popularity gate: embedding dim must be 32, 64 or 128"); return 3;
-        }
-        if (exchange)       // this rank's MLP gradient sums into the tail of its exchange block
-            hipLaunchKernelGGL(k_gate_rank_total, dim3((unsigned)((x->gate_P + 255) / 256)), dim3(256), 0, st,
-                               (const long long *)x->gate_partials, (int32_t)grid, x->gate_P, (long long *)(c.contrib + tail));
-    } else {
-        BprArgs a{};
-        a.X0 = x->tvar; a.K = 0; a.dense_last = 1;            // e = the row of the final table
-        a.n_users = c.n_users; a.N = x->N; a.users = users + b_off; a.pos = pos + b_off; a.neg = neg + b_off; a.B_local = B_local; a.shard = shard;
-        a.inv_B = 1.0f / (float)B_global; a.lam = c.decay / (float)B_global;
-        a.G64 = atomics ? (long long *)c.G64 : nullptr; a.bitmap = bm; a.stale_bitmap = stale; a.bitmap_words = x->bm_words;
-        a.item_bitmap = x->item_bitmap; a.terms = c.terms; a.err = c.err; a.terms_off = exchange ? 0 : b_off; a.terms_stride = B_global;
-        a.contrib = c.contrib; a.exchange = exchange ? 1 : 0;
-        DISPATCH_D(c.d, {
-            const int tpb = 256 / (D < 64 ? D : 64);
-            hipLaunchKernelGGL((k_triplet_dense<D, float>), dim3((unsigned)((B_local + tpb - 1) / tpb)), dim3(256), 0, st, a);
-        });
-    }
-    return 0;
-}
-
-static SlotArgs slot_args(const lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *neg, int32_t B,
-                          const float *gathered, int32_t shard, int32_t world, float *loss_out) {
-    const lgcn_train_config &c = x->c;
-    SlotArgs s{};
-    s.users = users; s.pos = pos; s.neg = neg; s.B = B; s.n_users = c.n_users; s.N = x->N;
-    s.G64 = (long long *)c.G64; s.G32 = x->g32; s.div = x->lw_n ? 1.f : (float)(c.K + 1);      // layer weights: G32 = G, the launches scale it
-    s.bitmap = c.bitmap + x->flip * x->bm_words; s.gathered = gathered; s.shard = shard; s.world = world;
-    s.terms = c.terms; s.loss_out = loss_out; s.decay = c.decay; s.skip_rank = -1;
-    s.ent_coeff = c.item_pop ? c.gate_entropy_coeff : 0.f;
-    s.blk = gathered ? dp_block_floats(x, shard) : 0;
-    s.item_bitmap = (x->variant && c.i2i) ? x->item_bitmap : nullptr;
-    s.cnt = x->cnt;
-    return s;
-}
-static unsigned scatter_grid(const lgcn_ctx *x, int32_t B) {      // k_scatter: one lane group of min(d, 64) lanes per slot
-    const int spb = 256 / (x->c.d < 64 ? x->c.d : 64);
-    return (unsigned)((3 * (int64_t)B + spb - 1) / spb);
-}
-static unsigned slot_grid(const lgcn_ctx *x, int32_t B) {
-    const int spb = 256 / (x->c.d / 4);
-    return (unsigned)((3 * (int64_t)B + spb - 1) / spb);
-}
-
-static SlotArgsMulti slot_args_multi(const lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B, float *loss_out) {
-    SlotArgsMulti m{};
-    m.s = slot_args(x, users, pos, nullptr, B, nullptr, B, 1, loss_out);
-    m.negs = x->mn.negs; m.neg_stride = x->mn.stride; m.R = x->mn.R;
-    return m;
-}
-static unsigned slot_grid_multi(const lgcn_ctx *x, int32_t B) {
-    const int spb = 256 / (x->c.d / 4);
-    return (unsigned)(((2 + (int64_t)x->mn.R) * B + spb - 1) / spb);
-}
-
-// buffer the backward layer k writes (k > 1): ping-pong inside the activation workspace (forward
-// activations are dead by then)
-static void *bwd_buffer(const lgcn_ctx *x, int k) {
-    return (x->c.K == 2) ? x->act[1] : x->act[1 + ((x->c.K - k) & 1)];
-}
-
-// One layer of the Horner chain h_{k-1} = Gs + A h_k (k = K: sparse input Gs; k = 1: feeds Adam).
-// fused_finish: the Adam launch also zeroes the G64 rows it consumes and reduces the loss (single-GPU
-// and batch-sharded steps, where every rank runs every row); the row-sharded step finishes separately.
-static int backward_layer(lgcn_ctx *x, int k, const int32_t *users, const int32_t *pos, const int32_t *neg, int32_t B,
-                          const float *gathered, int32_t shard, float *loss_out, bool fused_finish, hipStream_t st) {
-    const lgcn_train_config &c = x->c;
-    const bool first = (k == c.K), last = (k == 1);
-    if (first) {        // every contribution is in G64 by now: convert the batch rows once (the fold: k_triplet has done it)
-        if (x->mn.on) {     // several negatives per positive, or the in-batch loss (R = 0): (2 + R) B slots, never folded
-            SlotArgsMulti s = slot_args_multi(x, users, pos, B, loss_out);
-            DISPATCH_D(c.d, hipLaunchKernelGGL((k_g32_multi<D>), dim3(slot_grid_multi(x, B)), dim3(256), 0, st, s));
-        } else if (!x->fold_mult) {
-            SlotArgs s = slot_args(x, users, pos, neg, B, gathered, shard, 1, loss_out);
-            DISPATCH_D(c.d, hipLaunchKernelGGL((k_g32<D>), dim3(slot_grid(x, B)), dim3(256), 0, st, s));
-        }
-        if (x->variant && c.i2i) {
-            // backward of the smoothing: Gs_items <- Gs_items + (alpha I2I)^T Gs_items, a sparse-input SpMM on the item block; the
-            // result is dense, so every item row of Gs counts as non-zero from here on
-            { int rc0 = graph_acquire(c.i2i_t, st); if (rc0) return rc0; }
-            const int64_t ioff = (int64_t)c.n_users * c.d, m_items = x->N - c.n_users;
-            SpmmArgs h = graph_spmm(c.i2i_t);
-            h.G32 = x->g32 + ioff; h.bitmap = x->item_bitmap; h.Y = x->tvar + ioff; h.div = (float)(c.K + 1); h.remap = c.xcd_remap;
-            int rc = launch_spmm<M_SPARSE | M_ADDG>(h, c.d, LGCN_F32, LGCN_F32, st);
-            if (rc) return rc;
-            HIP_OK(hipMemcpyAsync(x->g32 + ioff, x->tvar + ioff, sizeof(float) * (size_t)m_items * c.d, hipMemcpyDeviceToDevice, st));
-            const int64_t words = (x->N + 31) / 32;
-            hipLaunchKernelGGL(k_flag_range, dim3((unsigned)((words + 255) / 256 < 64 ? (words + 255) / 256 : 64)), dim3(256), 0, st,
-                               c.bitmap + x->flip * x->bm_words, (int64_t)c.n_users, x->N);
-        }
-    }
-    SpmmArgs a = base_spmm(x);
-    a.dr = x->dr; a.dr.tr = 1;           // the chain multiplies by A_drop^T: the entry stored at (i, j) carries keep(j, i)
-    a.X = first ? nullptr : bwd_buffer(x, k + 1);
-    if (!last) a.Y = bwd_buffer(x, k);
-    else {
-        const double bc1 = 1.0 - pow(c.beta1, (double)x->step);
-        const double bc2 = 1.0 - pow(c.beta2, (double)x->step);
-        a.P = c.E0; a.M = c.adam_m; a.V = c.adam_v;
-        a.cnt = x->cnt; a.lam = c.decay / (float)B;
-        if (x->mn.R > 0) a.lam = c.decay / (float)((int64_t)B * x->mn.R);      // the counts are R per user / positive slot, 1 per negative slot
-        // inside a multi-step call on replicated tables the epilogue keeps the bf16 copy of E0 current (row-sharded steps
-        // update only the owned rows and convert again after the exchange)
-        a.Pb = (x->e0b && x->in_loop && fused_finish) ? x->e0b : nullptr;
-        a.Pq = (x->e0q && x->in_loop && fused_finish) ? x->e0q : nullptr;
-        x->e0b_fresh = a.Pb != nullptr || a.Pq != nullptr;
-        a.step_size = (float)(c.lr / bc1); a.bc2_sqrt = (float)sqrt(bc2);
-        a.w1 = (float)(1.0 - c.beta1); a.beta2 = (float)c.beta2; a.omb2 = (float)(1.0 - c.beta2); a.eps = (float)c.eps;
-        if (!first && fused_finish) {       // K >= 2: this launch also cleans the workspace and reduces the loss
-            a.clear = 1; a.terms = c.terms; a.gathered = gathered; a.loss_out = loss_out;
-            a.B = B; a.shard = shard; a.decay = c.decay; a.ent_coeff = c.item_pop ? c.gate_entropy_coeff : 0.f;
-            a.blk = gathered ? dp_block_floats(x, shard) : 0;
-        }
-    }
-    const int prev_dt = first ? LGCN_F32 : c.act_dtype;
-    if (x->lw_n) {      // layer weights: h_{k-1} = w_{k-1} G + A h_k, h_K = w_K G (G32 is G unscaled; the first layer gathers it)
-        a.w_in = first ? x->lw[c.K] : 1.f; a.w_add = x->lw[k - 1];
-        if (first && last) return launch_spmm<M_SPARSE | M_ADDG | M_ADAM | M_WTS>(a, c.d, prev_dt, LGCN_F32, st);
-        if (first) return launch_spmm<M_SPARSE | M_ADDG | M_WTS>(a, c.d, prev_dt, c.act_dtype, st);
-        if (last) return launch_spmm<M_ADDG | M_ADAM | M_WTS>(a, c.d, prev_dt, LGCN_F32, st);
-        return launch_spmm<M_ADDG | M_WTS>(a, c.d, prev_dt, c.act_dtype, st);
-    }
-    if (first && last) return launch_spmm<M_SPARSE | M_ADDG | M_ADAM>(a, c.d, prev_dt, LGCN_F32, st);
-    if (first) return launch_spmm<M_SPARSE | M_ADDG>(a, c.d, prev_dt, c.act_dtype, st);
-    if (last) return launch_spmm<M_ADDG | M_ADAM>(a, c.d, prev_dt, LGCN_F32, st);
-    return launch_spmm<M_ADDG>(a, c.d, prev_dt, c.act_dtype, st);
-}
-
-// [DP scatter] + backward chain + Adam + finish
-// gate_reduced: the MLP gradient of the global batch is the all-reduced gate_total (dense data-parallel form)
-static int run_backward(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *neg, int32_t B,
-                        const float *gathered, int32_t shard, int32_t world, float *loss_out, hipStream_t st, bool gate_reduced = false) {
-    const lgcn_train_config &c = x->c;
-    { int rc0 = graph_acquire(c.graph, st); if (rc0) return rc0; }
-    SlotArgs s = slot_args(x, users, pos, neg, B, gathered, shard, world, loss_out);
-    const unsigned sgrid = slot_grid(x, B);
-    if (gathered) {
-        s.skip_rank = x->dp_local ? x->dp_rank : -1;       // part 1 already added this rank's own rows
-        DISPATCH_D(c.d, hipLaunchKernelGGL((k_scatter<D>), dim3(scatter_grid(x, B)), dim3(256), 0, st, s));
-    }
-    x->step += 1;
-    // Horner: h_{K-1} = Gs + A Gs (sparse input); h_{k-1} = Gs + A h_k; last one feeds Adam
-    for (int k = c.K; k >= 1; k--) {
-        int rc = backward_layer(x, k, users, pos, neg, B, gathered, shard, loss_out, true, st);
-        if (rc) return rc;
-    }
-    if (x->variant && c.item_pop) {          // torch.optim.Adam on the gate's MLP parameters, same step count as the tables
-        GateAdamArgs ga{};
-        if (gathered) {      // data parallel: the ranks' totals sit in the tails of their exchange blocks
-            ga.src = (const long long *)(gathered + dp_block_tail(x, shard)); ga.n_src = world; ga.stride = dp_block_floats(x, shard) / 2;
-        } else if (gate_reduced) {             // dense form: the all-reduced total
-            ga.src = x->gate_total; ga.n_src = 1; ga.stride = x->gate_P;
-        } else { ga.src = x->gate_partials; ga.n_src = (B + GATE_TPB - 1) / GATE_TPB; ga.stride = x->gate_P; }
-        ga.P = x->gate_P;
-        ga.params = c.gate_params; ga.m = c.gate_adam_m; ga.v = c.gate_adam_v; ga.grad_out = c.gate_grad;
-        const double bc1 = 1.0 - pow(c.beta1, (double)x->step), bc2 = 1.0 - pow(c.beta2, (double)x->step);
-        ga.step_size = (float)(c.lr / bc1); ga.bc2_sqrt = (float)sqrt(bc2);
-        ga.w1 = (float)(1.0 - c.beta1); ga.beta2 = (float)c.beta2; ga.omb2 = (float)(1.0 - c.beta2); ga.eps = (float)c.eps;
-        hipLaunchKernelGGL(k_gate_adam, dim3((unsigned)((x->gate_P + 255) / 256)), dim3(256), 0, st, ga);
-    }
-    if (c.K >= 2) { x->flip ^= 1; return 0; }       // next step flags rows in the other bitmap
-    if (x->mn.on) {
-        SlotArgsMulti sm = slot_args_multi(x, users, pos, B, loss_out);
-        DISPATCH_D(c.d, hipLaunchKernelGGL((k_finish_multi<D>), dim3(slot_grid_multi(x, B)), dim3(256), 0, st, sm));
-        return 0;
-    }
-    DISPATCH_D(c.d, hipLaunchKernelGGL((k_finish<D>), dim3(sgrid), dim3(256), 0, st, s));
-    if (x->variant && c.i2i) {
-        // K = 1 keeps ONE bitmap (k_finish clears the batch rows' words); the smoothing's backward flagged EVERY item row in it
-        // and zeroed nothing of G64 beyond the batch rows, which k_finish has just done: clear the whole bitmap
-        HIP_OK(hipMemsetAsync(c.bitmap + x->flip * x->bm_words, 0, sizeof(uint32_t) * (size_t)x->bm_words, st));
-    }
-    return 0;
-}
-
-// What the batch-row launch of every slot-form step takes (lgcn_multineg.hip, lgcn_inbatch.hip), from the context and the slot
-// form of the running step (x->mn).  Without negatives (the plain in-batch step) inv_BR, inv_R and lam_n stay 0; under
-// LGCN_LOSS_BPR tau and inv_tauB do
-static MultiNegArgs multineg_args(const lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B) {
-    const lgcn_train_config &c = x->c;
-    MultiNegArgs a{};
-    a.X0 = c.E0; a.K = c.K;
-    for (int k = 1; k <= x->fwd_layers; k++) a.Xl[k] = x->act[k];
-    a.n_users = c.n_users; a.N = x->N;
-    a.users = users; a.pos = pos; a.negs = x->mn.negs; a.neg_stride = x->mn.stride; a.R = x->mn.R; a.B = B;
-    a.lam = c.decay / (float)B;
-    if (x->mn.R > 0) {
-        const float BR = (float)((int64_t)B * x->mn.R);
-        a.inv_BR = 1.0f / BR; a.inv_R = 1.0f / (float)x->mn.R; a.lam_n = c.decay / BR;
-    }
-    a.G64 = (long long *)c.G64; a.bitmap = c.bitmap + x->flip * x->bm_words;
-    a.stale_bitmap = c.bitmap + (x->flip ^ 1) * x->bm_words; a.bitmap_words = x->bm_words;
-    a.terms = c.terms; a.terms_stride = B; a.err = c.err;
-    a.reg_ego = c.reg_ego; a.cnt = x->cnt;
-    for (int k = 0; k < x->lw_n; k++) a.w[k] = x->lw[k];
-    a.loss = x->loss_kind;
-    if (x->loss_kind != LGCN_LOSS_BPR) {       // the same rows, flags and terms; another coefficient per negative
-        a.tau = x->loss_temp; a.inv_tauB = (float)(1.0 / ((double)x->loss_temp * (double)B));
-    }
-    return a;
-}
-
-// The four launches of lgcn_inbatch.hip: the plain step on the plain carving of the workspace, a step with
-// negatives on the mixed carving for the context's R_max, with the pool's (1 + R_max) cap item rows
-static int run_inbatch(lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B, hipStream_t st) {
-    const lgcn_train_config &c = x->c;
-    const bool mix = x->mn.R > 0;
-    const InBatchWs ws(x->ib_cap, c.d, mix ? x->ib_mix : 0);
-    float *w = (float *)x->ib_ws;
-    InBatchArgs ia{};
-    ia.m = multineg_args(x, users, pos, B);
-    ia.cap = x->ib_cap;
-    ia.U = w + ws.U; ia.P = w + ws.P; ia.sbb = w + ws.sbb;
-    ia.uid = (int32_t *)(w + ws.uid); ia.pid = (int32_t *)(w + ws.pid);
-    ia.mrg = w + ws.mrg; ia.part = w + ws.part;
-    if (mix) { ia.mix = 1; ia.icap = (int32_t)ws.icap; ia.xinvu = w + ws.invu; ia.xinvp = w + ws.invp; ia.xlq = w + ws.lq; }
-    ia.score = x->ib_score; ia.item_logq = x->ib_logq;
-    return lgcn_inbatch_launch(ia, c.d, c.act_dtype, x->lw_n != 0, st);
-}
-
-// One training step on one GPU: the drop mask, the forward layers, the loss launch of the step's form -- three slots (BPR or
-// the optional branches) unless a SlotScope is open, else the batch-row launch of the context's loss -- and the backward
-static int run_step(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *neg, int32_t B, float *loss_out, hipStream_t st) {
-    const lgcn_train_config &c = x->c;
-    int rc;
-    x->dr = make_drop(x->drop_keep, x->drop_seed, x->step, 0);        // ONE mask per step, from the counter before the step
-    if ((rc = run_forward(x, st))) return rc;
-    if (!x->mn.on) rc = x->variant ? run_variant_loss(x, users, pos, neg, B, 0, B, B, true, false, st) : run_bpr(x, users, pos, neg, B, 0, B, B, true, false, st);
-    else if (x->loss_kind == LGCN_LOSS_INBATCH) rc = run_inbatch(x, users, pos, B, st);
-    else rc = lgcn_multineg_launch(multineg_args(x, users, pos, B), c.d, c.act_dtype, x->lw_n != 0, st);
-    if (rc) return rc;
-    if ((rc = run_backward(x, users, pos, neg, B, nullptr, B, 1, loss_out, st))) return rc;
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-static int check_batch(const lgcn_ctx *x, const void *u, const void *p, const void *n, int32_t B) {
-    if (!x || !u || !p || !n) { lgcn_set_error("train step: null argument"); return 3; }
-    if (B <= 0 || B > x->c.max_batch) { lgcn_set_error("train step: batch size out of range (0 < B <= max_batch)"); return 3; }
-    return 0;
-}
-
-extern "C" int lgcn_train_step(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *neg,
-                               int32_t B, float *loss_out, void *stream) {
-    int rc = check_batch(x, users, pos, neg, B);
-    if (rc) return rc;
-    if ((rc = lgcn_refuse_loss(x, "lgcn_train_step"))) return rc;
-    if (!loss_out) { lgcn_set_error("train step: loss_out is null"); return 3; }
-    return run_step(x, users, pos, neg, B, loss_out, (hipStream_t)stream);
-}
-
-extern "C" int lgcn_train_epoch(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *neg,
-                                int64_t T, int32_t B, float *loss_out, void *stream) {
-    if (T <= 0) return 0;
-    if (!x) { lgcn_set_error("train epoch: null context"); return 3; }
-    if (int rc = lgcn_refuse_loss(x, "lgcn_train_epoch")) return rc;
-    LoopScope scope(x);
-    // The fold of k_g32: the call's triplets are all here, so how many slots of each batch name a row is known
-    // before the first step -- one k_slot_mult launch per segment of steps, into the context's buffer -- and k_triplet writes
-    // the fp32 copies of the gradient rows itself.  Not with the optional branches (they run another loss kernel), not with a
-    // hub plan (its rows live in the same table until k_g32), not where a batch's row ids do not fit the LDS hash
-    const bool fold = x->fold_g32 && !x->variant && !x->hub_graph && users && pos && neg &&
-                      B > 0 && B <= x->c.max_batch && x->N <= 0x7fffffffLL && slot_mult_hash(B) != 0;
-    const int64_t seg = fold_segment_steps();
-    if (fold) {
-        if (!x->arrive) {         // the first call that folds: every other path leaves the context's footprint as it was
-            HIP_OK(hipMalloc((void **)&x->arrive, sizeof(int32_t) * (size_t)x->N));
-            HIP_OK(hipMemsetAsync(x->arrive, 0, sizeof(int32_t) * (size_t)x->N, (hipStream_t)stream));
-        }
-        // room for a whole segment of the context's largest batch that folds, whatever this call's length: a longer call
-        // later (an epoch after a few warm-up steps) finds the buffer in place, and only a larger segment grows it
-        const int64_t bmax = x->c.max_batch < 4096 ? x->c.max_batch : 4096;
-        const int64_t need = 3 * (B > bmax ? (int64_t)B : bmax) * seg;
-        if (x->mult_cap < need) {
-            if (x->mult) (void)hipFree(x->mult);
-            x->mult = nullptr; x->mult_cap = 0;
-            HIP_OK(hipMalloc((void **)&x->mult, sizeof(uint16_t) * (size_t)need));
-            x->mult_cap = need;
-        }
-    }
-    int64_t i = 0, seg_t0 = 0;
-    for (int64_t t = 0; t < T; t += B, i++) {
-        const int32_t b = (int32_t)((T - t) < B ? (T - t) : B);
-        if (fold) {
-            if (i % seg == 0) {       // the next segment's multiplicities (the steps that read the last one's are ahead on the stream)
-                seg_t0 = t;
-                const int64_t Ts = (T - t) < seg * B ? (T - t) : seg * B;
-                int rc = launch_slot_mult(users + t, pos + t, neg + t, Ts, B, x->c.n_users, x->N, x->mult, (hipStream_t)stream);
-                if (rc) return rc;
-            }
-            x->fold_mult = x->mult + 3 * (t - seg_t0);
-        }
-        int rc = lgcn_train_step(x, users + t, pos + t, neg + t, b, loss_out + 3 * i, stream);
-        x->fold_mult = nullptr;
-        if (rc) return rc;
-        if (fold) x->folded_steps += 1;
-    }
-    return 0;
-}
-
-// The slot-form steps: several negatives per positive under BPR or the sampled softmax (SLOT_MULTI), the
-// in-batch softmax over (users, pos) alone (SLOT_INBATCH; 4.19, 4.20: R = 0, no negatives) and the in-batch softmax with the
-// batch's sampled negatives as a shared pool (SLOT_MIX; 4.21).  Everything is checked before anything is launched or counted: a
-// refusal leaves the outputs, the step counter and the workspace as they were.
-enum SlotKind { SLOT_MULTI, SLOT_INBATCH, SLOT_MIX };
-static int check_slot_step(const lgcn_ctx *x, SlotKind kind, const void *u, const void *p, const void *n, const void *loss_out,
-                           int32_t R, int32_t B, int64_t neg_stride, const char *who) {
-    char buf[256];
-    auto refuse = [&](const char *fmt, int v0 = 0, int v1 = 0) { snprintf(buf, sizeof buf, fmt, who, v0, v1); lgcn_set_error(buf); return 3; };
-    const bool negs = kind != SLOT_INBATCH;
-    if (!x || !u || !p || (negs && !n) || !loss_out) return refuse("%s: null argument");
-    if (kind == SLOT_MULTI) {
-        if (x->loss_kind == LGCN_LOSS_INBATCH) return lgcn_refuse_loss(x, who);
-        if (R < 1 || R > LGCN_MAX_NEG_RATIO) return refuse("%s: the negative ratio R = %d is out of range (1..%d)", R, LGCN_MAX_NEG_RATIO);
-        if (!x->c.dense_last) return refuse("%s: a negative ratio above the three-slot step's needs a context with dense_last = 1 (the gathered last layer has no 2 + R slot form)");
-        if (x->c.act_dtype == LGCN_FP8) return refuse("%s: the negative ratio (several negatives per positive) is not implemented for LGCN_FP8 activation storage");
-        if (x->variant) return refuse("%s: the negative ratio (several negatives per positive) is not implemented with the optional branches (item-item smoothing / popularity gate)");
-    } else {
-        if (x->loss_kind != LGCN_LOSS_INBATCH || !x->ib_ws) return refuse("%s: the in-batch softmax loss (inbatch) is not set on this context (lgcn_ctx_set_loss with LGCN_LOSS_INBATCH)");
-        if (kind == SLOT_MIX && x->ib_mix < 1) return refuse("%s: mixed negatives are not set on this context (lgcn_ctx_set_inbatch_mix)");
-        if (kind == SLOT_MIX && (R < 1 || R > x->ib_mix)) return refuse("%s: the negative ratio R = %d is out of range (1..%d, the R_max of lgcn_ctx_set_inbatch_mix)", R, x->ib_mix);
-    }
-    if (B <= 0 || B > x->c.max_batch) return refuse("%s: batch size out of range (0 < B <= max_batch)");
-    if (negs && neg_stride < B) return refuse("%s: neg_stride must be at least B (negative ratio columns would overlap)");
-    return 0;
-}
-
-static int slot_step(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int64_t neg_stride, int32_t R,
-                     int32_t B, float *loss_out, void *stream) {
-    SlotScope scope(x, negs, neg_stride, R);
-    return run_step(x, users, pos, negs, B, loss_out, (hipStream_t)stream);
-}
-// T samples in batches of B (a short last one), negative column r at negs + r * T (or no negatives); stops at the first failure
-static int slot_epoch(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int32_t R, int64_t T, int32_t B,
-                      float *loss_out, void *stream) {
-    LoopScope scope(x);
-    int64_t i = 0;
-    for (int64_t t = 0; t < T; t += B, i++) {
-        const int32_t b = (int32_t)((T - t) < B ? (T - t) : B);
-        if (int rc = slot_step(x, users + t, pos + t, negs ? negs + t : nullptr, negs ? T : 0, R, b, loss_out + 3 * i, stream)) return rc;
-    }
-    return 0;
-}
-
-extern "C" int lgcn_train_step_multi(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int64_t neg_stride,
-                                     int32_t R, int32_t B, float *loss_out, void *stream) {
-    if (int rc = check_slot_step(x, SLOT_MULTI, users, pos, negs, loss_out, R, B, neg_stride, "lgcn_train_step_multi")) return rc;
-    return slot_step(x, users, pos, negs, neg_stride, R, B, loss_out, stream);
-}
-extern "C" int lgcn_train_epoch_multi(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int32_t R,
-                                      int64_t T, int32_t B, float *loss_out, void *stream) {
-    if (T <= 0) return 0;
-    if (int rc = check_slot_step(x, SLOT_MULTI, users, pos, negs, loss_out, R, B, T < B ? (int64_t)B : T, "lgcn_train_epoch_multi")) return rc;
-    return slot_epoch(x, users, pos, negs, R, T, B, loss_out, stream);
-}
-
-extern "C" int lgcn_train_step_inbatch(lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B, float *loss_out, void *stream) {
-    if (int rc = check_slot_step(x, SLOT_INBATCH, users, pos, nullptr, loss_out, 0, B, 0, "lgcn_train_step_inbatch")) return rc;
-    return slot_step(x, users, pos, nullptr, 0, 0, B, loss_out, stream);
-}
-extern "C" int lgcn_train_epoch_inbatch(lgcn_ctx *x, const int32_t *users, const int32_t *pos, int64_t T, int32_t B, float *loss_out,
-                                        void *stream) {
-    if (T <= 0) return 0;
-    if (int rc = check_slot_step(x, SLOT_INBATCH, users, pos, nullptr, loss_out, 0, B, 0, "lgcn_train_epoch_inbatch")) return rc;
-    return slot_epoch(x, users, pos, nullptr, 0, T, B, loss_out, stream);
-}
-
-extern "C" int lgcn_train_step_inbatch_mix(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int64_t neg_stride,
-                                           int32_t R, int32_t B, float *loss_out, void *stream) {
-    if (int rc = check_slot_step(x, SLOT_MIX, users, pos, negs, loss_out, R, B, neg_stride, "lgcn_train_step_inbatch_mix")) return rc;
-    return slot_step(x, users, pos, negs, neg_stride, R, B, loss_out, stream);
-}
-extern "C" int lgcn_train_epoch_inbatch_mix(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *negs, int32_t R,
-                                            int64_t T, int32_t B, float *loss_out, void *stream) {
-    if (T <= 0) return 0;
-    if (int rc = check_slot_step(x, SLOT_MIX, users, pos, negs, loss_out, R, B, T < B ? (int64_t)B : T, "lgcn_train_epoch_inbatch_mix")) return rc;
-    return slot_epoch(x, users, pos, negs, R, T, B, loss_out, stream);
-}
-
-extern "C" int lgcn_train_step_dp_part1(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *neg,
-                                        int32_t B_global, int32_t world, int32_t rank, void *stream) {
-    int rc = check_batch(x, users, pos, neg, B_global);
-    if (rc) return rc;
-    if ((rc = refuse_dropout(x, "lgcn_train_step_dp_part1"))) return rc;
-    if ((rc = refuse_layer_weights(x, "lgcn_train_step_dp_part1"))) return rc;
-    if ((rc = lgcn_refuse_loss(x, "lgcn_train_step_dp_part1"))) return rc;
-    if (!x->c.contrib) { lgcn_set_error("dp step: cfg.contrib exchange buffer missing"); return 3; }
-    if (world < 1 || rank < 0 || rank >= world) { lgcn_set_error("dp step: bad world/rank"); return 3; }
-    const int32_t shard = (B_global + world - 1) / world;
-    const int32_t b_off = rank * shard;
-    int32_t B_local = B_global - b_off;
-    if (B_local > shard) B_local = shard;
-    if (B_local < 0) B_local = 0;
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = run_forward(x, st))) return rc;
-    // with dp_local the rank's own rows go into G64 here (atomics) AND into the exchange block; part 2 scatters the others'
-    if (x->variant) rc = run_variant_loss(x, users, pos, neg, B_global, b_off, B_local, shard, x->dp_local, true, st);
-    else rc = run_bpr(x, users, pos, neg, B_global, b_off, B_local, shard, x->dp_local, true, st);
-    if (rc) return rc;
-    x->dp_rank = rank;
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int lgcn_train_step_dp_dense_part1(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *neg,
-                                              int32_t B_global, int32_t world, int32_t rank, void *stream) {
-    int rc = check_batch(x, users, pos, neg, B_global);
-    if (rc) return rc;
-    if ((rc = refuse_dropout(x, "lgcn_train_step_dp_dense_part1"))) return rc;
-    if ((rc = refuse_layer_weights(x, "lgcn_train_step_dp_dense_part1"))) return rc;
-    if ((rc = lgcn_refuse_loss(x, "lgcn_train_step_dp_dense_part1"))) return rc;
-    if (world < 1 || rank < 0 || rank >= world) { lgcn_set_error("dp step: bad world/rank"); return 3; }
-    const int32_t shard = (B_global + world - 1) / world;
-    const int32_t b_off = rank * shard;
-    int32_t B_local = B_global - b_off;
-    if (B_local > shard) B_local = shard;
-    if (B_local < 0) B_local = 0;
-    hipStream_t st = (hipStream_t)stream;
-    const bool gate = x->variant && x->c.item_pop;
-    // this rank owns positions [b_off, b_off+B_local) of the global loss-term arrays (loss | reg | with the gate: entropy);
-    // the rest must be zero
-    HIP_OK(hipMemsetAsync(x->c.terms, 0, sizeof(float) * (gate ? 3 : 2) * (size_t)B_global, st));
-    if ((rc = run_forward(x, st))) return rc;
-    if (x->variant) {
-        // optional branches: the shard's rows go into this rank's G64 by atomics like the default model's; the MLP
-        // parameter gradients of the shard are summed (fixed point: any order) into gate_total, one more all-reduce
-        if ((rc = run_variant_loss(x, users, pos, neg, B_global, b_off, B_local, shard, true, false, st))) return rc;
-        if (gate) {
-            if (B_local > 0)
-                hipLaunchKernelGGL(k_gate_rank_total, dim3((unsigned)((x->gate_P + 255) / 256)), dim3(256), 0, st,
-                                   (const long long *)x->gate_partials, (int32_t)((B_local + GATE_TPB - 1) / GATE_TPB), x->gate_P, x->gate_total);
-            else HIP_OK(hipMemsetAsync(x->gate_total, 0, sizeof(long long) * (size_t)x->gate_P, st));
-        }
-    } else if ((rc = run_bpr(x, users, pos, neg, B_global, b_off, B_local, shard, true, false, st, false))) return rc;
-    SlotArgs s{};
-    s.users = users; s.pos = pos; s.neg = neg; s.B = B_global; s.n_users = x->c.n_users; s.N = x->N;
-    s.bitmap = x->c.bitmap + x->flip * x->bm_words; s.cnt = x->cnt;
-    s.item_bitmap = (x->variant && x->c.i2i) ? x->item_bitmap : nullptr;      // the smoothing's backward reads the items of the GLOBAL batch
-    hipLaunchKernelGGL(k_flag_rows, dim3((3 * B_global + 255) / 256), dim3(256), 0, st, s);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int lgcn_ctx_gate_total(const lgcn_ctx *x, void **buf, int32_t *count) {
-    if (!x || !buf || !count) { lgcn_set_error("lgcn_ctx_gate_total: null argument"); return 3; }
-    *buf = x->gate_total; *count = x->gate_total ? x->gate_P : 0;
-    return 0;
-}
-
-extern "C" int lgcn_train_step_dp_part2(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *neg,
-                                        int32_t B_global, int32_t world, const float *gathered, float *loss_out,
-                                        void *stream) {
-    int rc = check_batch(x, users, pos, neg, B_global);
-    if (rc) return rc;
-    if ((rc = refuse_dropout(x, "lgcn_train_step_dp_part2"))) return rc;
-    if ((rc = refuse_layer_weights(x, "lgcn_train_step_dp_part2"))) return rc;
-    if ((rc = lgcn_refuse_loss(x, "lgcn_train_step_dp_part2"))) return rc;
-    if (!loss_out || world < 1) { lgcn_set_error("dp step part 2: invalid argument"); return 3; }
-    const int32_t shard = (B_global + world - 1) / world;
-    // gathered == NULL is the dense form: G64, the terms and (popularity gate) gate_total hold the reduced sums of the global batch
-    if ((rc = run_backward(x, users, pos, neg, B_global, gathered, shard, world, loss_out, (hipStream_t)stream, gathered == nullptr))) return rc;
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------
-// Column-sharded data parallelism: rank r holds columns [r d/W, (r+1) d/W) of E0, of the Adam state and of every activation --
-// its context is an ordinary context of width d / W over the same graph.  Propagation, the gradient scatter, the backward
-// chain and Adam are independent per column; the one thing that is not is the score of a triplet, a dot product over ALL
-// columns.  So the step is: part 1 (forward + slot rows + PARTIAL scores / reg terms of this rank's columns), ONE all-reduce
-// of 3 B floats, part 2 (loss terms, gradient rows of this rank's columns, backward, Adam).  Per-rank SpMM work falls with
-// the world size (rows of d / W elements), which batch sharding cannot offer.  Not bitwise equal to the single-GPU step: the
-// dot products are summed in another order (W partial sums); everything else is.
-// ---------------------------------------------------------------------------------
-extern "C" int lgcn_train_step_cols_part1(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *neg,
-                                          int32_t B, float **partials, void *stream) {
-    int rc = check_batch(x, users, pos, neg, B);
-    if (rc) return rc;
-    if ((rc = refuse_dropout(x, "lgcn_train_step_cols_part1"))) return rc;
-    if ((rc = refuse_layer_weights(x, "lgcn_train_step_cols_part1"))) return rc;
-    if ((rc = lgcn_refuse_loss(x, "lgcn_train_step_cols_part1"))) return rc;
-    if (x->variant) { lgcn_set_error("column-sharded step: the popularity gate / item-item smoothing mix columns (MLPs over the row): not supported"); return 3; }
-    if (!x->c.contrib) { lgcn_set_error("column-sharded step: cfg.contrib (3*max_batch*d floats: the batch's slot rows) missing"); return 3; }
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = run_forward(x, st))) return rc;
-    if ((rc = run_bpr(x, users, pos, neg, B, 0, B, B, false, false, st, false, 1))) return rc;
-    if (partials) *partials = x->colsum;
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-extern "C" int lgcn_train_step_cols_part2(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *neg,
-                                          int32_t B, float *loss_out, void *stream) {
-    int rc = check_batch(x, users, pos, neg, B);
-    if (rc) return rc;
-    if ((rc = refuse_dropout(x, "lgcn_train_step_cols_part2"))) return rc;
-    if ((rc = refuse_layer_weights(x, "lgcn_train_step_cols_part2"))) return rc;
-    if ((rc = lgcn_refuse_loss(x, "lgcn_train_step_cols_part2"))) return rc;
-    if (!loss_out) { lgcn_set_error("column-sharded step part 2: loss_out is null"); return 3; }
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = run_bpr(x, users, pos, neg, B, 0, B, B, true, false, st, true, 2))) return rc;
-    if ((rc = run_backward(x, users, pos, neg, B, nullptr, B, 1, loss_out, st))) return rc;
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------
-// Row-sharded propagation (SURVEY 8e "beyond the contract"; the analogue of the reference's A_split
-// row folds, dataloader.py:192-201): the context's graph plan holds only the rows this rank owns; a
-// phase computes those rows of one layer, and the owners' rows are exchanged before the next phase.
-// ---------------------------------------------------------------------------------
-extern "C" int lgcn_rs_phase(lgcn_ctx *x, int32_t phase, int32_t k, const int32_t *users, const int32_t *pos, const int32_t *neg,
-                             int32_t B_global, int32_t world, int32_t rank, const float *gathered, float *loss_out, void *stream) {
-    int rc = check_batch(x, users, pos, neg, B_global);
-    if (rc) return rc;
-    if ((rc = refuse_dropout(x, "lgcn_rs_phase"))) return rc;
-    if ((rc = refuse_layer_weights(x, "lgcn_rs_phase"))) return rc;
-    if ((rc = lgcn_refuse_loss(x, "lgcn_rs_phase"))) return rc;
-    if (x->variant) { lgcn_set_error("lgcn_rs_phase: the popularity gate / item-item smoothing run on one GPU only"); return 3; }
-    const lgcn_train_config &c = x->c;
-    hipStream_t st = (hipStream_t)stream;
-    if (world < 1 || rank < 0 || rank >= world) { lgcn_set_error("lgcn_rs_phase: bad world/rank"); return 3; }
-    const int32_t shard = (B_global + world - 1) / world;
-    if ((rc = graph_acquire(c.graph, st))) return rc;
-    switch (phase) {
-    case LGCN_RS_FWD: {                               // X_k[owned] = (A X_{k-1})[owned], k = 1..K-1
-        if (k < 1 || k > x->fwd_layers) { lgcn_set_error("lgcn_rs_phase: forward layer out of range"); return 3; }
-        SpmmArgs a = base_spmm(x);
-        // bf16 / fp8 activation storage: layer 1 gathers bf16(E0) / fp8(E0), converted after every exchange of the owners' Adam rows
-        const bool shadow = k == 1 && (x->e0b != nullptr || x->e0q != nullptr);
-        if (shadow) {
-            if (x->e0b) launch_to_bf16(c.E0, x->e0b, x->N * c.d, st);
-            else if ((rc = launch_to_fp8(c.E0, x->e0q, x->N, c.d, st))) return rc;
-            x->e0b_fresh = false;
-        }
-        a.X = k == 1 ? (shadow ? (x->e0b ? (const void *)x->e0b : (const void *)x->e0q) : (const void *)c.E0) : x->act[k - 1]; a.Y = x->act[k];
-        rc = launch_spmm<0>(a, c.d, k == 1 && !shadow ? LGCN_F32 : c.act_dtype, c.act_dtype, st);
-        break;
-    }
-    case LGCN_RS_BPR: {                               // this rank's batch shard -> cfg.contrib
-        if (!c.contrib) { lgcn_set_error("lgcn_rs_phase: cfg.contrib exchange buffer missing"); return 3; }
-        const int32_t b_off = rank * shard;
-        int32_t B_local = B_global - b_off;
-        if (B_local > shard) B_local = shard;
-        if (B_local < 0) B_local = 0;
-        rc = run_bpr(x, users, pos, neg, B_global, b_off, B_local, shard, false, true, st);
-        break;
-    }
-    case LGCN_RS_SCATTER: {                           // all ranks' gradient rows -> G64 + row flags
-        if (!gathered) { lgcn_set_error("lgcn_rs_phase: gathered blocks missing"); return 3; }
-        SlotArgs s = slot_args(x, users, pos, neg, B_global, gathered, shard, world, loss_out);
-        DISPATCH_D(c.d, hipLaunchKernelGGL((k_scatter<D>), dim3(scatter_grid(x, B_global)), dim3(256), 0, st, s));
-        break;
-    }
-    case LGCN_RS_BWD:                                 // h_{k-1}[owned] = Gs + (A h_k)[owned], k = K..1; k = 1: Adam on the owned rows
-        if (k < 1 || k > c.K) { lgcn_set_error("lgcn_rs_phase: backward layer out of range"); return 3; }
-        if (k == c.K) x->step += 1;
-        rc = backward_layer(x, k, users, pos, neg, B_global, gathered, shard, loss_out, false, st);
-        break;
-    case LGCN_RS_FINISH: {                            // zero the batch rows of G64 + their flags, reduce the loss
-        if (!loss_out) { lgcn_set_error("lgcn_rs_phase: loss_out is null"); return 3; }
-        SlotArgs s = slot_args(x, users, pos, neg, B_global, gathered, shard, world, loss_out);
-        DISPATCH_D(c.d, hipLaunchKernelGGL((k_finish<D>), dim3(slot_grid(x, B_global)), dim3(256), 0, st, s));
-        break;
-    }
-    default: lgcn_set_error("lgcn_rs_phase: unknown phase"); return 3;
-    }
-    if (rc) return rc;
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-// what a phase wrote and the owners must exchange: buffer + element type
-extern "C" int lgcn_rs_buffer(const lgcn_ctx *x, int32_t phase, int32_t k, void **buf, int32_t *dtype) {
-    if (!x || !buf || !dtype) { lgcn_set_error("lgcn_rs_buffer: null argument"); return 3; }
-    const lgcn_train_config &c = x->c;
-    if (phase == LGCN_RS_FWD && k >= 1 && k <= x->fwd_layers) { *buf = x->act[k]; *dtype = c.act_dtype; return 0; }
-    if (phase == LGCN_RS_BWD && k > 1 && k <= c.K) { *buf = bwd_buffer(x, k); *dtype = c.act_dtype; return 0; }
-    if (phase == LGCN_RS_BWD && k == 1) { *buf = c.E0; *dtype = LGCN_F32; return 0; }
-    lgcn_set_error("lgcn_rs_buffer: this phase exchanges nothing");
+    lgcn_set_error("spmm: no such launch");
     return 3;
-}
-
-// every owner broadcasts its two row ranges (users, items) of `buf` in place; one RCCL group
-// (an fp8 table: the rows are d bytes each and the owners' row scales, fp32 behind the rows, travel with them)
-static int rs_exchange(const RcclApi *api, lgcn_dp *dp, void *buf, int dtype, int d, int64_t n_rows, const int64_t *ranges, hipStream_t st) {
-    const size_t es = dtype == LGCN_BF16 ? 2 : dtype == LGCN_FP8 ? 1 : 4;
-    const ncclDataType_t nt = dtype == LGCN_BF16 ? ncclBfloat16 : dtype == LGCN_FP8 ? ncclUint8 : ncclFloat32;
-    float *scales = dtype == LGCN_FP8 ? (float *)((char *)buf + (size_t)n_rows * d) : nullptr;
-    ncclResult_t r = api->GroupStart();
-    for (int q = 0; q < dp->world && r == ncclSuccess; q++)
-        for (int part = 0; part < 2 && r == ncclSuccess; part++) {
-            const int64_t lo = ranges[4 * q + 2 * part], hi = ranges[4 * q + 2 * part + 1];
-            if (hi <= lo) continue;
-            char *p = (char *)buf + (size_t)lo * d * es;
-            r = api->Broadcast(p, p, (size_t)(hi - lo) * d, nt, q, dp->comm, st);
-            if (scales && r == ncclSuccess) r = api->Broadcast(scales + lo, scales + lo, (size_t)(hi - lo), ncclFloat32, q, dp->comm, st);
-        }
-    if (r == ncclSuccess) r = api->GroupEnd(); else (void)api->GroupEnd();
-    if (r != ncclSuccess) { lgcn_set_error("RCCL broadcast of owned rows failed"); return 11; }
-    return 0;
-}
-
-// A whole data-parallel epoch from ONE host call: per global batch, part 1 -> RCCL collective on the
-// SAME stream (no host synchronisation, no Python between the kernels and the collective) -> part 2.
-static int train_epoch_dp_impl(lgcn_ctx *x, lgcn_dp *dp, const int32_t *users, const int32_t *pos, const int32_t *neg,
-                               int64_t T, int32_t B_global, int32_t reduce, const int64_t *row_ranges, float *gathered,
-                               float *loss_out, void *stream) {
-    if (!x || !dp || !users || !pos || !neg || !loss_out) { lgcn_set_error("lgcn_train_epoch_dp: null argument"); return 3; }
-    if (reduce != LGCN_DP_ROWS && reduce != LGCN_DP_DENSE && reduce != LGCN_DP_ROW_SHARDED && reduce != LGCN_DP_COLS) { lgcn_set_error("lgcn_train_epoch_dp: unknown reduce mode"); return 3; }
-    if (reduce == LGCN_DP_ROW_SHARDED && !row_ranges) { lgcn_set_error("lgcn_train_epoch_dp: row_ranges missing"); return 3; }
-    if (reduce != LGCN_DP_DENSE && reduce != LGCN_DP_COLS && !gathered) { lgcn_set_error("lgcn_train_epoch_dp: gathered workspace missing"); return 3; }
-    if (B_global <= 0 || B_global > x->c.max_batch) { lgcn_set_error("lgcn_train_epoch_dp: batch size out of range"); return 3; }
-    const RcclApi *api = dp->api;             // RCCL, or the in-process loopback of the tests
-    if (!api) { lgcn_set_error("lgcn_train_epoch_dp: communicator without collectives"); return 12; }
-    hipStream_t st = (hipStream_t)stream;
-    const int world = dp->world, rank = dp->rank;
-    LoopScope scope(x);
-    struct LocalScope {         // batch-sharded rows mode: every rank adds its own rows itself, k_scatter the other ranks'
-        lgcn_ctx *x; bool was;
-        LocalScope(lgcn_ctx *x_, bool on) : x(x_), was(x_->dp_local) { x->dp_local = on; x->dp_rank = -1; }
-        ~LocalScope() { x->dp_local = was; x->dp_rank = -1; }
-    } local_scope(x, reduce == LGCN_DP_ROWS);
-    int64_t i = 0;
-    for (int64_t t = 0; t < T; t += B_global, i++) {
-        const int32_t b = (int32_t)((T - t) < B_global ? (T - t) : B_global);
-        int rc;
-        ncclResult_t r;
-        if (reduce == LGCN_DP_COLS) {
-            if ((rc = lgcn_train_step_cols_part1(x, users + t, pos + t, neg + t, b, nullptr, stream))) return rc;
-            r = api->AllReduce(x->colsum, x->colsum, (size_t)3 * b, ncclFloat32, ncclSum, dp->comm, st);
-            if (r != ncclSuccess) { lgcn_set_error("ncclAllReduce failed"); return 11; }
-            if ((rc = lgcn_train_step_cols_part2(x, users + t, pos + t, neg + t, b, loss_out + 3 * i, stream))) return rc;
-        } else if (reduce == LGCN_DP_ROW_SHARDED) {
-            const int32_t K = x->c.K, d = x->c.d;
-            const int32_t *u = users + t, *p = pos + t, *n = neg + t;
-            void *buf; int32_t dt;
-            for (int k = 1; k <= x->fwd_layers; k++) {
-                if ((rc = lgcn_rs_phase(x, LGCN_RS_FWD, k, u, p, n, b, world, rank, nullptr, nullptr, stream))) return rc;
-                if ((rc = lgcn_rs_buffer(x, LGCN_RS_FWD, k, &buf, &dt))) return rc;
-                if ((rc = rs_exchange(api, dp, buf, dt, d, x->N, row_ranges, st))) return rc;
-            }
-            if ((rc = lgcn_rs_phase(x, LGCN_RS_BPR, 0, u, p, n, b, world, rank, nullptr, nullptr, stream))) return rc;
-            const int64_t S = (b + world - 1) / world, blk = 3 * S * d + 2 * S;
-            r = api->AllGather(x->c.contrib, gathered, (size_t)blk, ncclFloat32, dp->comm, st);
-            if (r != ncclSuccess) { lgcn_set_error("ncclAllGather failed"); return 11; }
-            if ((rc = lgcn_rs_phase(x, LGCN_RS_SCATTER, 0, u, p, n, b, world, rank, gathered, nullptr, stream))) return rc;
-            for (int k = K; k >= 1; k--) {
-                if ((rc = lgcn_rs_phase(x, LGCN_RS_BWD, k, u, p, n, b, world, rank, gathered, nullptr, stream))) return rc;
-                if ((rc = lgcn_rs_buffer(x, LGCN_RS_BWD, k, &buf, &dt))) return rc;
-                if ((rc = rs_exchange(api, dp, buf, dt, d, x->N, row_ranges, st))) return rc;
-            }
-            if ((rc = lgcn_rs_phase(x, LGCN_RS_FINISH, 0, u, p, n, b, world, rank, gathered, loss_out + 3 * i, stream))) return rc;
-        } else if (reduce == LGCN_DP_ROWS) {
-            if ((rc = lgcn_train_step_dp_part1(x, users + t, pos + t, neg + t, b, world, rank, stream))) return rc;
-            const int64_t S = (b + world - 1) / world, blk = dp_block_floats(x, S);
-            r = api->AllGather(x->c.contrib, gathered, (size_t)blk, ncclFloat32, dp->comm, st);
-            if (r != ncclSuccess) { lgcn_set_error("ncclAllGather failed"); return 11; }
-            if ((rc = lgcn_train_step_dp_part2(x, users + t, pos + t, neg + t, b, world, gathered, loss_out + 3 * i, stream))) return rc;
-        } else {
-            if ((rc = lgcn_train_step_dp_dense_part1(x, users + t, pos + t, neg + t, b, world, rank, stream))) return rc;
-            r = api->AllReduce(x->c.G64, x->c.G64, (size_t)x->N * x->c.d, ncclInt64, ncclSum, dp->comm, st);
-            const bool gate = x->variant && x->c.item_pop;
-            if (r == ncclSuccess) r = api->AllReduce(x->c.terms, x->c.terms, (size_t)(gate ? 3 : 2) * b, ncclFloat32, ncclSum, dp->comm, st);
-            if (r == ncclSuccess && gate) r = api->AllReduce(x->gate_total, x->gate_total, (size_t)x->gate_P, ncclInt64, ncclSum, dp->comm, st);
-            if (r != ncclSuccess) { lgcn_set_error("ncclAllReduce failed"); return 11; }
-            if ((rc = lgcn_train_step_dp_part2(x, users + t, pos + t, neg + t, b, world, nullptr, loss_out + 3 * i, stream))) return rc;
-        }
-    }
-    return 0;
-}
-
-extern "C" int lgcn_train_epoch_dp(lgcn_ctx *x, lgcn_dp *dp, const int32_t *users, const int32_t *pos, const int32_t *neg,
-                                   int64_t T, int32_t B_global, int32_t reduce, const int64_t *row_ranges, float *gathered,
-                                   float *loss_out, void *stream) {
-    if (refuse_dropout(x, "lgcn_train_epoch_dp") || refuse_layer_weights(x, "lgcn_train_epoch_dp") || lgcn_refuse_loss(x, "lgcn_train_epoch_dp")) return 3;         // (every rank's context says the same: nobody waits in a collective)
-    const int rc = train_epoch_dp_impl(x, dp, users, pos, neg, T, B_global, reduce, row_ranges, gathered, loss_out, stream);
-    // a rank that leaves the loop early never reaches its next collective: release the loopback ranks waiting for it
-    // (RCCL has its own abort / timeout machinery)
-    if (rc && dp && dp->loopback) lgcn_dp_loopback_abort(dp);
-    return rc;
-}
-
-extern "C" int lgcn_ctx_check(lgcn_ctx *x, void *stream) {
-    if (!x) { lgcn_set_error("null context"); return 3; }
-    int32_t flag = 0;
-    HIP_OK(hipMemcpyAsync(&flag, x->c.err, sizeof flag, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
-    if (flag) {
-        HIP_OK(hipMemsetAsync(x->c.err, 0, sizeof flag, (hipStream_t)stream));
-        lgcn_set_error("device flagged an out-of-range user/item id in a batch");
-    }
-    return flag;
 }

@@ -1,7 +1,7 @@
-// lgcn_device_common.h -- what the device translation units of liblgcn_hip.so share (not installed): the error macro of the
-// launchers, the 2^50 fixed point of G64, the vector typedefs, the switch over the embedding dim, and the few device functions
-// that more than one file needs.  ONE definition of each lives here; build.kernel_hash() covers lgcn_device.hip alone, so code
-// that another file needs too belongs in this header, not in a copy.
+// lgcn_device_common.h -- what the device translation units of liblgcn_hip.so share (not installed): the 2^50 fixed point of
+// G64, the vector typedefs, the switch over the embedding dim, and the few device functions that more than one file needs.  ONE
+// definition of each lives here; build.kernel_hash() covers lgcn_device.hip alone, so code that another file needs too belongs
+// in this header, not in a copy.
 #ifndef LGCN_DEVICE_COMMON_H
 #define LGCN_DEVICE_COMMON_H
 #include <hip/hip_runtime.h>
@@ -10,26 +10,14 @@
 #include <stdio.h>
 
 #include "lgcn_hip.h"
-#include "lgcn_internal.h"
-
-#define HIP_OK(expr)                                                            \
-    do {                                                                        \
-        hipError_t e_ = (expr);                                                 \
-        if (e_ != hipSuccess) {                                                 \
-            char buf_[256];                                                     \
-            snprintf(buf_, sizeof buf_, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-            lgcn_set_error(buf_);                                               \
-            return 10;                                                          \
-        }                                                                       \
-    } while (0)
+#include "lgcn_internal.h"      // HIP_OK, the launchers' error macro, comes from there (the host files use it too)
 
 // G64 holds gradient rows as 64-bit fixed point: integer addition is associative, so a row's sum is order-free
 #define FIXED_SCALE 1125899906842624.0   /* 2^50 */
 #define FIXED_INV   8.8817841970012523e-16 /* 2^-50 */
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) long long i64x2;
-typedef __bf16 bf16_t;
+typedef __attribute__((ext_vector_type(2))) long long i64x2;      // (bf16_t: lgcn_kernels.h, whose args structs name it)
 
 // runs the statement with D a compile-time constant; any other d is the caller's error 3
 #define DISPATCH_D(d, ...)                                                       \

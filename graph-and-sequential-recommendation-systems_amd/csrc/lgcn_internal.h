@@ -3,12 +3,94 @@
 #define LGCN_INTERNAL_H
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>       // types only: RCCL is resolved with dlopen at run time, never linked
+#include <math.h>
+#include <stdio.h>
 #include "lgcn_hip.h"
+#include "lgcn_kernels.h"      // (every unit gets its macros -- XCDS, LONG_T, GATE_TPB, ... -- with it: keep such names out of the other files)
 
 extern "C" void lgcn_set_error(const char *msg);   // lgcn_host.cpp
-// 0 under LGCN_LOSS_BPR; else rc 3 and the message "<who>: the ... loss ... is implemented for ... only" (lgcn_device.hip): ONE wording
+// 0 under LGCN_LOSS_BPR; else rc 3 and the message "<who>: the ... loss ... is implemented for ... only" (lgcn_train.cpp): ONE wording
 // for every entry point that does not train the loss set on the context
 int lgcn_refuse_loss(const lgcn_ctx *x, const char *who);
+
+#define HIP_OK(expr)                                                            \
+    do {                                                                        \
+        hipError_t e_ = (expr);                                                 \
+        if (e_ != hipSuccess) {                                                 \
+            char buf_[256];                                                     \
+            snprintf(buf_, sizeof buf_, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+            lgcn_set_error(buf_);                                               \
+            return 10;                                                          \
+        }                                                                       \
+    } while (0)
+
+// ---------------------------------------------------------------------------------
+// What lgcn_graph.cpp (graph object, propagation) and lgcn_train.cpp (training context, step driver) share
+// ---------------------------------------------------------------------------------
+// graph object: device CSR (borrowed) + the long-row plan and its scratch (owned)
+struct lgcn_graph {
+    const int32_t *indptr; const int32_t *indices; const float *vals; const int4 *rowinfo;
+    const int2 *pk;       // the planned rows' (col,val) pairs, packed, in plan order
+    int64_t n_rows, nnz;
+    int32_t d_max;
+    LongPlan lp; SlicePlan sp;
+    void *owned;          // one device allocation holding plan arrays, partials and counters
+    // The long-row scratch (partials, tickets) is shared by every launch on this graph: launches
+    // are ordered.  A launch on another stream than the previous one first waits for it.
+    mutable hipStream_t last_stream; mutable bool used; mutable hipEvent_t order_ev;
+};
+// long_ch: non-zeros per chunk of a split row (LONG_CH for the propagation plans; the hub plan of k_triplet, whose rows
+// have 10^4 .. 10^6 non-zeros, takes longer chunks so that a row's last arriver has hundreds, not thousands, of partials to add)
+int lgcn_graph_create_impl(const int32_t *indptr, const int32_t *indices, const float *vals,
+                           int64_t n_rows, int64_t nnz, int32_t d_max, const int32_t *row_order,
+                           int64_t n_order, const int64_t *xcd_start, int32_t long_ch, lgcn_graph **out);
+int lgcn_check_layer_weights(const char *who, const float *w, int n, int K);
+int64_t lgcn_fold_segment_steps();      // lgcn_train.cpp
+
+// a launch on `st` is about to use the graph's scratch: order it behind the previous user
+static inline int graph_acquire(const lgcn_graph *g, hipStream_t st) {
+    if (g->used && g->last_stream != st) {
+        HIP_OK(hipEventRecord(g->order_ev, g->last_stream));
+        HIP_OK(hipStreamWaitEvent(st, g->order_ev, 0));
+    }
+    g->used = true; g->last_stream = st;
+    return 0;
+}
+static inline SpmmArgs graph_spmm(const lgcn_graph *g) {
+    SpmmArgs a{};
+    a.pk = g->pk; a.rowinfo = g->rowinfo; a.lp = g->lp; a.sp = g->sp; a.n_rows = g->n_rows;
+    return a;
+}
+// gathered tables of 4 GiB or more need 64-bit offsets (priced at the fp32 row size whatever the table type)
+static inline bool big_table(int64_t n_rows, int d) { return n_rows * (int64_t)d * 4 >= (1ll << 32); }
+// bytes of one [N,d] table of a storage type (fp8: rows + fp32 row scales, padded so that the next table stays 256-byte aligned)
+static inline size_t table_bytes(int64_t N, int d, int dtype) {
+    if (dtype == LGCN_FP8) return (((size_t)N * d + (size_t)N * 4) + 255) & ~(size_t)255;
+    return (size_t)N * d * (dtype == LGCN_BF16 ? 2 : 4);
+}
+static inline int check_dtype(int t) {
+    if (t != LGCN_F32 && t != LGCN_BF16 && t != LGCN_FP8) { lgcn_set_error("dtype must be LGCN_F32, LGCN_BF16 or LGCN_FP8"); return 3; }
+    return 0;
+}
+// edge dropout: the step's keys (the hash itself: lgcn_device.hip)
+static inline uint64_t splitmix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+static inline bool drop_prob_ok(float keep_prob) { return keep_prob > 0.f && keep_prob <= 1.f; }      // (NaN fails both)
+// floor(keep_prob * 2^32): exact in double; 2^32 itself (keep_prob = 1) means "keep everything"
+static inline uint64_t drop_threshold(float keep_prob) { return (uint64_t)floor((double)keep_prob * 4294967296.0); }
+// the mask of one step; keep_prob in (0, 1): at 1 there is nothing to drop and on stays 0 (the launch is the plain one)
+static inline DropArgs make_drop(float keep_prob, uint64_t seed, int64_t step, int transposed) {
+    DropArgs d{};
+    if (!(keep_prob < 1.f)) return d;
+    const uint64_t k = splitmix64(splitmix64(seed) + (uint64_t)step);
+    d.k0 = (uint32_t)k; d.k1 = (uint32_t)(k >> 32);
+    d.thr = (uint32_t)drop_threshold(keep_prob); d.inv = 1.0f / keep_prob; d.tr = transposed ? 1 : 0; d.on = 1;
+    return d;
+}
 
 // The RCCL entry points the data-parallel path uses.  Resolved once, preferring the librccl that is
 // already mapped into the process (PyTorch-ROCm ships its own copy; two RCCL instances in one process

@@ -73,6 +73,27 @@ def test_source_hash_reads_every_file_the_library_includes(pkg):
     assert digest(b"") == b.source_hash() != digest(b" ")
 
 
+def test_training_kernels_live_in_one_file(pkg):
+    """build.kernel_hash() is the hash of csrc/lgcn_device.hip and stands for "the training kernels": the host side of the graph
+    object and of the training step (lgcn_graph.*, lgcn_train.*) is built from files of its own that hold no kernel and no
+    launch, and every launcher the boundary header lgcn_kernels.h declares is defined in lgcn_device.hip, beside its kernel."""
+    b = pkg.build
+    csrc = os.path.dirname(b.SOURCES[0])
+    by_stem = {os.path.splitext(os.path.basename(f))[0]: f for f in b.SOURCES}
+    for stem in ("lgcn_graph", "lgcn_train"):
+        assert stem in by_stem and os.path.exists(by_stem[stem]), stem
+        text = open(by_stem[stem]).read()
+        for word in ("__global__", "__device__", "hipLaunchKernelGGL", "<<<"):
+            assert word not in text, f"{os.path.basename(by_stem[stem])} contains {word}"
+    header = open(os.path.join(csrc, "lgcn_kernels.h")).read()
+    assert "__global__" not in header and "__device__" not in header
+    declared = set(re.findall(r"\b(lgcn_\w+_launch)\s*\(", header))
+    assert len(declared) >= 20 and {"lgcn_spmm_launch", "lgcn_triplet_launch", "lgcn_gate_launch"} <= declared
+    device = open(os.path.join(csrc, "lgcn_device.hip")).read()
+    for fn in sorted(declared):                             # a definition: the name at the start of a line's declarator, a body behind it
+        assert re.search(r"^(?:int|void) " + fn + r"\([^;{]*\)\s*\{", device, flags=re.M), f"{fn} is not defined in lgcn_device.hip"
+
+
 def test_glibc_stream_and_randint(pkg):
     s = pkg.sampling
     s.seed(2020)

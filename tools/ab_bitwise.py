@@ -23,8 +23,13 @@ Cases (cases()):
             the one allocation); one batch with an out-of-range negative, one lgcn_train_epoch_inbatch_mix over T = 2 B + 3, and
             one mixed step followed by plain lgcn_train_step_inbatch steps on the same context.
   mf        lgcn_mf_train_step: d 32/64/128/256, B 1/7/67.
-  step      the three-slot lgcn_train_step at d = 64: gathered and dense_last forms, fp32 / bf16 / fp8 tables, and one case each
-            with edge dropout, layer weights, the popularity gate and item-item smoothing."""
+  step      the three-slot lgcn_train_step, every instantiation the batch-row launcher (lgcn_triplet_launch) chooses and every
+            mode of the SpMM launcher's switch (lgcn_spmm_launch) at every d it exists for: d 32/64/128/256 with fp32 / bf16
+            tables and d 64/128/256 with fp8 tables, each with K 1/2/3 (K = 1: the sparse input feeds Adam and a finish launch
+            follows; K = 2: one backward buffer; K = 3: a middle layer) in the gathered and the dense_last form; per d and for
+            fp32 and bf16 each, one step with edge dropout (gathered: the batch rows take the mask) and layer weights in both
+            forms, at K = 1 and K = 3 between them (the four weighted modes); the popularity gate and item-item smoothing at d
+            32/64/128; B 1/7/67 in rotation.  (The big-table instantiations need 2^32 bytes per table: tests/test_gpu_large.py.)"""
 import argparse
 import importlib
 import itertools
@@ -42,6 +47,7 @@ DS, MODES, WTS, KS, RS, BS, REGS = (32, 64, 128, 256), ("fp32", "bf16"), (False,
 LOSSES = (("bpr", 1.0), ("softmax", 0.2), ("softmax", 1.0))
 SCORES, LOGQS, MIX_RS, MIX_RMAX, IB_TAU = ("dot", "cosine"), (False, True), (1, 2, 16), 16, 0.2
 IB_KINDS = ("inbatch", "inbatch_mix")
+STEP_KS, STEP_DLS, GATE_DS = (1, 2, 3), (0, 1), (32, 64, 128)
 
 
 def cases():
@@ -71,12 +77,24 @@ def cases():
         out.append(dict(base, mode="bf16", epoch=True))     # the epoch entry point over T = 2 B + 3
     out.append(dict(base, B=67, then_plain=True))           # a mixed step, then plain steps on the same context
     out += [dict(kind="mf", d=d, B=B) for d in DS for B in BS]
-    for dl in (0, 1):
-        out += [dict(kind="step", d=64, mode=mode, K=3, dl=dl, B=67, cfg={}) for mode in ("fp32", "bf16", "fp8")]
-    out.append(dict(kind="step", d=64, mode="fp32", K=3, dl=0, B=67, cfg={'dropout': 1, 'keep_prob': 0.8}))
-    out.append(dict(kind="step", d=64, mode="bf16", K=3, dl=1, B=67, cfg={'layer_weights': 'exp'}))
-    out.append(dict(kind="step", d=64, mode="fp32", K=2, dl=0, B=67, cfg={'use_pop_gate': True}))
-    out.append(dict(kind="step", d=64, mode="fp32", K=2, dl=0, B=67, cfg={'use_item_item': True, 'i2i_build': 'cooc', 'i2i_alpha': 0.5}))
+    n = 0                                                   # step cases so far: B rotates with it, one further per six cases (every block
+                                                            # below is a multiple of three long: n % 3 alone would tie B to (K, dl))
+
+    def step(d, mode, K, dl, **cfg):
+        nonlocal n
+        out.append(dict(kind="step", d=d, mode=mode, K=K, dl=dl, B=BS[(n + n // 6) % 3], cfg=cfg))
+        n += 1
+    for d in DS:
+        for mode in MODES + (("fp8",) if d >= 64 else ()):
+            for K, dl in itertools.product(STEP_KS, STEP_DLS):
+                step(d, mode, K, dl)
+        for j, mode in enumerate(MODES):
+            step(d, mode, 3 - j, 0, dropout=1, keep_prob=0.8)
+            step(d, mode, 1 + 2 * j, 0, layer_weights='exp')        # the gathered and the dense weighted rows, K = 1 and K = 3 each
+            step(d, mode, 3 - 2 * j, 1, layer_weights='exp')
+    for j, d in enumerate(GATE_DS):
+        step(d, MODES[j % 2], 2, 0, use_pop_gate=True)
+        step(d, MODES[(j + 1) % 2], 2, 0, use_item_item=True, i2i_build='cooc', i2i_alpha=0.5)
     return out
 
 
@@ -96,6 +114,21 @@ def check_coverage(cs):
                 assert {c[key] for c in at} == set(values), (kind, d, key)
         for tag, n in (("void", 1), ("epoch", 1), ("then_plain", int(kind == "inbatch_mix"))):
             assert sum(1 for c in cs if c["kind"] == kind and c.get(tag)) == n, (kind, tag)
+    steps = [c for c in cs if c["kind"] == "step"]
+    for K, dl in itertools.product(STEP_KS, STEP_DLS):          # every form of the finish and Adam launches at every batch size
+        assert {c["B"] for c in steps if not c["cfg"] and (c["K"], c["dl"]) == (K, dl)} == set(BS), (K, dl)
+    for d in DS:
+        at = [c for c in steps if c["d"] == d]
+        plain = {(c["mode"], c["K"], c["dl"]) for c in at if not c["cfg"]}
+        assert plain == set(itertools.product(MODES + (("fp8",) if d >= 64 else ()), STEP_KS, STEP_DLS)), d
+        assert {c["B"] for c in at} == set(BS), d
+        for mode in MODES:
+            assert any(c["cfg"].get("dropout") and c["mode"] == mode and c["dl"] == 0 for c in at), (d, mode, "dropout")
+            for dl in STEP_DLS:
+                assert any(c["cfg"].get("layer_weights") and c["mode"] == mode and c["dl"] == dl for c in at), (d, mode, dl, "layer_weights")
+        assert {c["K"] for c in at if c["cfg"].get("layer_weights")} >= {1, 3}, d
+        for key in ("use_pop_gate", "use_item_item"):
+            assert any(c["cfg"].get(key) for c in at) == (d in GATE_DS), (d, key)
 
 
 def name(c):
@@ -109,7 +142,7 @@ def name(c):
                 + (f"-R{c['R']}of{MIX_RMAX}" if c["kind"] == "inbatch_mix" else "") + tag)
     if c["kind"] == "mf":
         return f"mf-d{c['d']}-B{c['B']}"
-    return f"step-d{c['d']}-{c['mode']}-K{c['K']}-dl{c['dl']}" + "".join(f"-{k}" for k in c["cfg"] if k in ("dropout", "layer_weights", "use_pop_gate", "use_item_item"))
+    return f"step-d{c['d']}-{c['mode']}-K{c['K']}-dl{c['dl']}-B{c['B']}" + "".join(f"-{k}" for k in c["cfg"] if k in ("dropout", "layer_weights", "use_pop_gate", "use_item_item"))
 
 
 def child(out_path):
@@ -240,6 +273,8 @@ def driver(a):
                     n = int((x.view(np.uint32) != y.view(np.uint32)).sum()) if x.shape == y.shape else -1
                     print(f"DIFFERS {k}: {n} of {x.size} elements")
     n = len(cases())
+    kinds = [c["kind"] for c in cases()]
+    print("cases per kind: " + ", ".join(f"{k} {kinds.count(k)}" for k in dict.fromkeys(kinds)))
     if differing:
         print(f"first differing case: {differing[0]}")
     print(f"{n} cases x {STEPS} steps, {len(differing)} differing")
@@ -251,7 +286,7 @@ if __name__ == "__main__":
     ap.add_argument("--lib-a")
     ap.add_argument("--lib-b")
     ap.add_argument("--child", default="", metavar="NPZ", help="child: run the cases on the library LGCN_LIB_PATH names and write this file")
-    ap.add_argument("--child-timeout", type=int, default=240, help="seconds each child may take")
+    ap.add_argument("--child-timeout", type=int, default=480, help="seconds each child may take")
     a = ap.parse_args()
     if a.child:
         child(a.child)
