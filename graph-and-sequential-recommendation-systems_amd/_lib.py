@@ -173,7 +173,13 @@ SIGNATURES = {
     "lgcn_ctx_folded_steps": (C.c_int64, [_vp]),
     "lgcn_ctx_copy_arrivals": (C.c_int, [_vp, _vp, C.c_int64]),
     "lgcn_slot_multiplicity": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int64, _vp, _vp]),
+    # write-through stores for outputs nobody gathers
+    "lgcn_ctx_set_store_policy": (C.c_int, [_vp, C.c_int]),
+    "lgcn_ctx_get_store_policy": (C.c_int, [_vp, _c_i32p]),
 }
+
+STORE_ADAM, STORE_XLAST = 1, 2                       # LGCN_STORE_*: lgcn_ctx_set_store_policy
+STORE_ARG_MV, STORE_ARG_P, STORE_ARG_Y = 1, 2, 4     # LGCN_STORE_ARG_*: what a launch carried (lgcn_ctx_get_store_policy)
 
 _LIB = None
 

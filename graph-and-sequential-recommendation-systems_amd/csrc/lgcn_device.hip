@@ -81,6 +81,25 @@ __device__ __forceinline__ f32x4 load4(const float *p) { return loadv<4>(p); }
 __device__ __forceinline__ f32x4 load4(const bf16_t *p) { return loadv<4>(p); }
 __device__ __forceinline__ void store4(float *p, f32x4 v) { storev<4>(p, v); }
 __device__ __forceinline__ void store4(bf16_t *p, f32x4 v) { storev<4>(p, v); }
+// A lane's 16-byte piece at p + OFF bytes, stored WRITE-THROUGH (the vector store with sc1): the bytes go on to memory and the
+// line is dropped from this XCD's L2 instead of staying there dirty.  For rows that nobody gathers and the next reader takes row
+// by row; SpmmArgs::wt says which stores of a launch take this form.  A 16-byte sc1 store costs what the plain one
+// costs (narrower ones do not), so this is the one form.  p: a global address, 16-byte aligned with OFF.  The trailing s_nop 1:
+// a store of more than 8 bytes reads its data registers late, and nothing outside the string is padded for it.
+template <int OFF> __device__ __forceinline__ void store16_wt(void *p, f32x4 v) {
+    static_assert(OFF >= 0 && OFF < 4096 && OFF % 16 == 0, "immediate offset of a global store");
+    asm volatile("global_store_dwordx4 %0, %1, off offset:%2 sc1\n\ts_nop 1" : : "v"(p), "v"(v), "n"(OFF) : "memory");
+}
+// C consecutive fp32 values (C / 4 pieces) / 8 bf16 values (one piece) of a lane, write-through
+template <int C> __device__ __forceinline__ void storev_wt(float *p, typename VecF<C>::T v) {
+    store16_wt<0>(p, f32x4{v[0], v[1], v[2], v[3]});
+    if constexpr (C >= 8) store16_wt<16>(p, f32x4{v[4], v[5], v[6], v[7]});
+    if constexpr (C == 16) { store16_wt<32>(p, f32x4{v[8], v[9], v[10], v[11]}); store16_wt<48>(p, f32x4{v[12], v[13], v[14], v[15]}); }
+}
+__device__ __forceinline__ void storev_wt(bf16_t *p, f32x8 v) {
+    union { bf16x8 b; f32x4 f; } u; u.b = __builtin_convertvector(v, bf16x8);
+    store16_wt<0>(p, u.f);
+}
 // one fp8 element of a table, decoded (k_triplet's lower-layer rows: lane = column): the fp8 form of the header's tab_elem
 __device__ __forceinline__ float fp8_decode(uint8_t b) { return __builtin_amdgcn_cvt_pk_f32_fp8((int)b, false)[0]; }
 template <> __device__ __forceinline__ float tab_elem<fp8_t>(const void *tab, int64_t n_rows, int D, int64_t row, int col) {
@@ -140,23 +159,35 @@ template <int D, int C, bool IL> __device__ __forceinline__ typename VecF<C>::T 
         return r;
     }
 }
-template <int D, int C, bool IL> __device__ __forceinline__ void row_store(float *base, int64_t row, int l, typename VecF<C>::T v) {
-    if constexpr (!IL) storev<C>(base + row * D + l * C, v);
-    else {
+// wt (wave-uniform): the pieces go write-through (store16_wt)
+template <int D, int C, bool IL> __device__ __forceinline__ void row_store(float *base, int64_t row, int l, typename VecF<C>::T v, bool wt = false) {
+    if constexpr (!IL) {
+        if (wt) storev_wt<C>(base + row * D + l * C, v);
+        else storev<C>(base + row * D + l * C, v);
+    } else if (wt) {      // the four chunks lie D / 16 pieces = D bytes apart
+        float *p = base + row * D + l * 4;
+        store16_wt<0>(p, f32x4{v[0], v[1], v[2], v[3]}); store16_wt<D>(p, f32x4{v[4], v[5], v[6], v[7]});
+        store16_wt<2 * D>(p, f32x4{v[8], v[9], v[10], v[11]}); store16_wt<3 * D>(p, f32x4{v[12], v[13], v[14], v[15]});
+    } else {
 #pragma unroll
         for (int j = 0; j < 4; j++) store4(base + row * D + (j * (D / 16) + l) * 4, f32x4{v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]});
     }
 }
+// (wt: honoured for fp32 and bf16 outputs whose piece per lane is 16 bytes or a multiple -- what a forward launch on fp32 / bf16
+//  tables writes; the 8-byte bf16 pieces of a launch that gathered fp32 rows stay plain.  A launch that gathered an fp8 table
+//  ignores it: its instantiations are budgeted at 4-5 waves per SIMD, and the second store form took the forward ones from
+//  88-94 to 126-128 VGPRs -- lgcn_train.cpp does not ask for it there)
 template <int D, int C, typename TO, bool IL> struct RowStore {
-    static __device__ __forceinline__ void put(void *Y, int64_t, int64_t row, int l, typename VecF<C>::T v) {
+    static __device__ __forceinline__ void put(void *Y, int64_t, int64_t row, int l, typename VecF<C>::T v, bool wt = false) {
         static_assert(!IL, "an fp8 gather writes fp32 or fp8");
+        if constexpr (C == 8) { if (wt) { storev_wt((TO *)Y + row * D + l * C, v); return; } }
         storev<C>((TO *)Y + row * D + l * C, v); }
 };
 template <int D, int C, bool IL> struct RowStore<D, C, float, IL> {
-    static __device__ __forceinline__ void put(void *Y, int64_t, int64_t row, int l, typename VecF<C>::T v) { row_store<D, C, IL>((float *)Y, row, l, v); }
+    static __device__ __forceinline__ void put(void *Y, int64_t, int64_t row, int l, typename VecF<C>::T v, bool wt = false) { row_store<D, C, IL>((float *)Y, row, l, v, IL ? false : wt); }
 };
 template <int D, int C, bool IL> struct RowStore<D, C, fp8_t, IL> {
-    static __device__ __forceinline__ void put(void *Y, int64_t n_rows, int64_t row, int l, typename VecF<C>::T v) { store_row_fp8<D, C, IL>(Y, n_rows, row, l, v); }
+    static __device__ __forceinline__ void put(void *Y, int64_t n_rows, int64_t row, int l, typename VecF<C>::T v, bool = false) { store_row_fp8<D, C, IL>(Y, n_rows, row, l, v); }
 };
 __device__ __forceinline__ bool bit_set(const uint32_t *bm, int i) { return (bm[i >> 5] >> (i & 31)) & 1u; }
 
@@ -456,11 +487,18 @@ __device__ __forceinline__ void spmm_epilogue(const SpmmArgs &a, int64_t row, in
 #pragma unroll
         for (int i = 0; i < C; i++) denom[i] = sqrtf(v[i]) / a.bc2_sqrt + a.eps;
         p = p - a.step_size * (m / denom);              // addcdiv_(exp_avg, denom, -step_size)
-        row_store<D, C, IL>(a.P, row, l, p); row_store<D, C, IL>(a.M, row, l, m); row_store<D, C, IL>(a.V, row, l, v);
-        if (a.Pb) storev<C>(a.Pb + off, p);          // (bf16 shadow: only with bf16 tables, never IL)
-        if (a.Pq) store_row_fp8<D, C, IL>(a.Pq, a.n_rows, row, l, p);
+        // M and V are read next by this epilogue of the next step, P (where a shadow is gathered in its place) by that and by the
+        // batch rows: under a.wt they go write-through.  The shadows are gathered with slice affinity and stay plain
+        row_store<D, C, IL>(a.P, row, l, p, (a.wt & LGCN_STORE_ARG_P) != 0);
+        row_store<D, C, IL>(a.M, row, l, m, (a.wt & LGCN_STORE_ARG_MV) != 0); row_store<D, C, IL>(a.V, row, l, v, (a.wt & LGCN_STORE_ARG_MV) != 0);
+        // (a sparse-input launch that feeds Adam is the whole backward of K = 1: no forward layer, so no shadow -- lgcn_spmm_launch
+        //  refuses one; the four pointer registers pay for the store field in the instantiations that sit at a register boundary)
+        if constexpr (!(MODE & M_SPARSE)) {
+            if (a.Pb) storev<C>(a.Pb + off, p);          // (bf16 shadow: only with bf16 tables, never IL)
+            if (a.Pq) store_row_fp8<D, C, IL>(a.Pq, a.n_rows, row, l, p);
+        }
     } else {
-        RowStore<D, C, TO, IL>::put(a.Y, a.n_rows, row, l, acc);
+        RowStore<D, C, TO, IL>::put(a.Y, a.n_rows, row, l, acc, (a.wt & LGCN_STORE_ARG_Y) != 0);
     }
 }
 
@@ -2068,6 +2106,7 @@ static int launch_spmm(const SpmmArgs &a, int d, int x_dtype, int y_dtype, hipSt
 }
 
 int lgcn_spmm_launch(const SpmmArgs &a, int mode, int d, int x_dtype, int y_dtype, hipStream_t st) {
+    if ((mode & M_SPARSE) && (mode & M_ADAM) && (a.Pb || a.Pq)) { lgcn_set_error("spmm: a sparse-input launch keeps no shadow of P"); return 3; }
     switch (mode) {
     case 0: return launch_spmm<0>(a, d, x_dtype, y_dtype, st);
     case M_ADDSELF:       // Y = selfX + A X on fp32 tables (item-item smoothing): only the fp32 instance exists

@@ -93,6 +93,8 @@ struct SpmmArgs {
     int32_t *cnt; float lam;      // reg_ego: slots of the batch naming each row (zeroed as consumed), decay / B: grad += lam * cnt[row] * P[row]
     DropArgs dr;                  // edge dropout of the step (dr.on: the DROP instantiation is launched); behind the older fields, so that every one of them keeps its offset
     float w_in, w_add;            // M_WTS launches only (layer weights): Y = w_add * G[row] + w_in * (A X)[row]
+    int32_t wt;                   // LGCN_STORE_ARG_* bits: which of the launch's row stores go write-through (0: all plain).
+                                  //   A run-time, wave-uniform field and no template axis: the instantiations stay what they were
 };
 
 enum { M_SPARSE = 1, M_ADDG = 2, M_ADAM = 4, M_ADDSELF = 8, M_WTS = 16 };

@@ -70,7 +70,21 @@ struct lgcn_ctx {
     // mixed negatives (lgcn_ctx_set_inbatch_mix): ib_mix = R_max (0: off).  While it is on, ib_ws is large enough for
     // both carvings: the plain step's (the one above, unchanged) and the mixed step's with (1 + R_max) ib_cap item rows
     int32_t ib_mix;
+    // the store policy (lgcn_ctx_set_store_policy): LGCN_STORE_* bits, and the SpmmArgs::wt the last +Adam launch and
+    // the last forward launch of the deepest layer carried (the getter reports them)
+    int32_t store_policy, wt_adam, wt_fwd;
 };
+// The policy of a new context: LGCN_STORE_POLICY (0..3) or the default below; -1: the variable is set and is neither.
+// Default: what the alternating runs of profiles/store_policy/README.md adopted.
+#ifndef LGCN_STORE_POLICY_DEFAULT
+#define LGCN_STORE_POLICY_DEFAULT LGCN_STORE_ADAM
+#endif
+static int store_policy_initial() {
+    const char *e = getenv("LGCN_STORE_POLICY");
+    if (!e) return LGCN_STORE_POLICY_DEFAULT;
+    if (e[0] < '0' || e[0] > '0' + (LGCN_STORE_ADAM | LGCN_STORE_XLAST) || e[1] != '\0') return -1;
+    return e[0] - '0';
+}
 // steps whose multiplicities one launch computes (and the context's buffer holds): 1024 steps = 3 * B * 1024 uint16 = 12 MiB at
 // B = 2048, 24 MiB at the largest batch that folds.  LGCN_FOLD_SEGMENT: for tests only (a call longer than a small segment)
 int64_t lgcn_fold_segment_steps() {
@@ -115,8 +129,11 @@ extern "C" int lgcn_ctx_create(const lgcn_train_config *cfg, lgcn_ctx **out) {
             lgcn_set_error("lgcn_ctx_create: popularity gate needs its parameter / Adam buffers, hidden sizes in 1..64, d <= 128, temperature > 0"); return 3; }
     }
     if (c.reg_ego && (gate || smooth)) { lgcn_set_error("lgcn_ctx_create: reg_ego (upstream's L2 term) is defined for the default model only, not with the optional branches"); return 3; }
+    const int policy = store_policy_initial();
+    if (policy < 0) { lgcn_set_error("lgcn_ctx_create: LGCN_STORE_POLICY must be one of 0, 1, 2, 3 (LGCN_STORE_* bits)"); return 3; }
     lgcn_ctx *x = new (std::nothrow) lgcn_ctx;
     if (!x) { lgcn_set_error("out of memory"); return 4; }
+    x->store_policy = policy; x->wt_adam = 0; x->wt_fwd = 0;
     x->c = c; x->step = 0; x->N = c.graph->n_rows; x->cnt = nullptr; x->colsum = nullptr;
     x->drop_keep = 1.f; x->drop_seed = 0; x->dr = DropArgs{};
     x->lw_n = 0; for (int k = 0; k <= LGCN_MAX_LAYERS; k++) x->lw[k] = 0.f;
@@ -216,6 +233,16 @@ extern "C" int lgcn_ctx_set_fold_g32(lgcn_ctx *ctx, int on) {
     return 0;
 }
 extern "C" int64_t lgcn_ctx_folded_steps(const lgcn_ctx *ctx) { return ctx ? ctx->folded_steps : -1; }
+extern "C" int lgcn_ctx_set_store_policy(lgcn_ctx *ctx, int bits) {
+    if (bits & ~(LGCN_STORE_ADAM | LGCN_STORE_XLAST)) { lgcn_set_error("lgcn_ctx_set_store_policy: unknown store policy bits (LGCN_STORE_ADAM | LGCN_STORE_XLAST)"); return 3; }
+    if (!ctx) { lgcn_set_error("lgcn_ctx_set_store_policy: null context"); return 3; }
+    ctx->store_policy = bits;
+    return 0;
+}
+extern "C" int lgcn_ctx_get_store_policy(const lgcn_ctx *ctx, int32_t *launch_out) {
+    if (launch_out) { launch_out[0] = ctx ? ctx->wt_adam : 0; launch_out[1] = ctx ? ctx->wt_fwd : 0; }
+    return ctx ? ctx->store_policy : store_policy_initial();
+}
 extern "C" int lgcn_ctx_copy_arrivals(const lgcn_ctx *ctx, int32_t *dst_host, int64_t n) {
     if (!ctx || !dst_host) { lgcn_set_error("lgcn_ctx_copy_arrivals: null argument"); return 3; }
     if (ctx->variant || n < 0 || n > ctx->N) { lgcn_set_error("lgcn_ctx_copy_arrivals: the context has no arrival array of that size"); return 3; }
@@ -411,6 +438,13 @@ static int run_forward(lgcn_ctx *x, hipStream_t st) {
     for (int k = 1; k <= x->fwd_layers; k++) {
         SpmmArgs a = base_spmm(x);
         a.X = prev; a.Y = x->act[k]; a.dr = x->dr;
+        if (k == x->fwd_layers) {
+            // X_{K-1} of the gathered last layer: only the batch-row launch gathers it, and its workgroups have no slice affinity
+            // (a dense last layer is read by slot, and the lower layers are gathered by the next one: plain.  fp8 tables: plain too,
+            //  the forward instantiations there have no registers to spare for the second store form -- RowStore, lgcn_device.hip)
+            if ((x->store_policy & LGCN_STORE_XLAST) && !c.dense_last && c.act_dtype != LGCN_FP8) a.wt = LGCN_STORE_ARG_Y;
+            x->wt_fwd = a.wt;
+        }
         int rc = lgcn_spmm_launch(a, 0, c.d, prev_dt, c.act_dtype, st);
         if (rc) return rc;
         prev = x->act[k]; prev_dt = c.act_dtype;
@@ -603,6 +637,9 @@ static int backward_layer(lgcn_ctx *x, int k, const int32_t *users, const int32_
         a.Pb = (x->e0b && x->in_loop && fused_finish) ? x->e0b : nullptr;
         a.Pq = (x->e0q && x->in_loop && fused_finish) ? x->e0q : nullptr;
         x->e0b_fresh = a.Pb != nullptr || a.Pq != nullptr;
+        // nothing gathers M or V; P is gathered (layer 1, with slice affinity) unless this launch keeps a shadow for that
+        if (x->store_policy & LGCN_STORE_ADAM) a.wt = LGCN_STORE_ARG_MV | ((a.Pb || a.Pq) ? LGCN_STORE_ARG_P : 0);
+        x->wt_adam = a.wt;
         a.step_size = (float)(c.lr / bc1); a.bc2_sqrt = (float)sqrt(bc2);
         a.w1 = (float)(1.0 - c.beta1); a.beta2 = (float)c.beta2; a.omb2 = (float)(1.0 - c.beta2); a.eps = (float)c.eps;
         if (!first && fused_finish) {       // K >= 2: this launch also cleans the workspace and reduces the loss

@@ -632,6 +632,12 @@ class LightGCN(nn.Module):
                 msg = lib.lgcn_last_error()
                 lib.lgcn_ctx_destroy(h)
                 raise _lib.LgcnError(f"lgcn_ctx_set_fold_g32 failed (rc={rc}): {msg.decode() if msg else ''}")
+        if self.config.get('store_policy') is not None:      # config['store_policy'] = LGCN_STORE_* bits (A/B, tests); unset: LGCN_STORE_POLICY or the library's default
+            rc = lib.lgcn_ctx_set_store_policy(h, int(self.config['store_policy']))
+            if rc:
+                msg = lib.lgcn_last_error()
+                lib.lgcn_ctx_destroy(h)
+                raise _lib.LgcnError(f"lgcn_ctx_set_store_policy failed (rc={rc}): {msg.decode() if msg else ''}")
         st['ctx'], st['max_batch'], st['dp_world'], st['table_ptr'] = h, max_batch, dp_world, self._table.data_ptr()
         st['ctx_rows'] = rows
 

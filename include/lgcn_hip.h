@@ -437,6 +437,27 @@ int64_t lgcn_ctx_folded_steps(const lgcn_ctx *ctx);
  * are zero between steps (the array is allocated by the first lgcn_train_epoch call that folds; before that, zeros are
  * written).  rc 3: no such array (optional branches) or n > N.                                                              */
 int lgcn_ctx_copy_arrivals(const lgcn_ctx *ctx, int32_t *dst_host, int64_t n);
+
+/* The store policy of outputs that are read once, row by row, and never gathered.  A plain store keeps its
+ * line dirty in the writing XCD's L2; a write-through store (16 bytes per lane, sc1) sends it on and drops the line, so the
+ * launch ends with that much less to write back and the write-once lines do not compete with the table the launch gathers.
+ *   LGCN_STORE_ADAM  (bit 0): the Adam epilogue writes the rows of M and V write-through, and those of P where a bf16 / fp8
+ *                             shadow of P is maintained by the same epilogue (fp32 tables gather P itself: plain).
+ *   LGCN_STORE_XLAST (bit 1): the forward launch whose output only the batch-row kernel gathers (X_{K-1} of a context with the
+ *                             gathered last layer) writes it write-through.  fp32 and bf16 tables; fp8 tables keep plain stores.
+ * Arithmetic, and every result, is bit for bit the same under every policy.  Any other bit: rc 3.  A new context takes
+ * LGCN_STORE_POLICY from the environment (0..3, read at lgcn_ctx_create; anything else makes the create fail with rc 3) or,
+ * without it, the library's default.                                                                                          */
+#define LGCN_STORE_ADAM 1
+#define LGCN_STORE_XLAST 2
+int lgcn_ctx_set_store_policy(lgcn_ctx *ctx, int bits);
+/* -> the context's policy bits.  launch_out (or NULL): [2] the store field the last +Adam launch and the last forward launch of
+ * the deepest layer carried (LGCN_STORE_ARG_* bits; 0 before the first step).  ctx == NULL: what a context created now would
+ * start with (-1: LGCN_STORE_POLICY is set and is not one of 0..3).                                                            */
+#define LGCN_STORE_ARG_MV 1     /* M and V rows write-through */
+#define LGCN_STORE_ARG_P 2      /* P rows write-through */
+#define LGCN_STORE_ARG_Y 4      /* the launch's output table write-through */
+int lgcn_ctx_get_store_policy(const lgcn_ctx *ctx, int32_t *launch_out);
 /* Slot multiplicities of a multi-step call: the triplets [0, T) (device int32 ids) are cut into consecutive batches of B, the
  * last one shorter; for batch i of b_i triplets and slot s = c * b_i + b (c = 0 user, 1 positive, 2 negative),
  * mult_out[3 * i * B + s] = the number of slots of batch i whose destination row is slot s's (user u -> row u, item j -> row
