@@ -82,6 +82,9 @@ SIGNATURES = {
     "lgcn_sample_negative_device_multi_workspace": (C.c_int64, [C.c_int, C.c_int64, C.c_int]),
     "lgcn_sample_negative_device_multi": (C.c_int, [C.c_int, C.c_int, C.c_int64, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int64, _vp]),
     "lgcn_np_seed": (None, [C.c_uint32]),
+    "lgcn_np_get_state": (None, [_vp, C.POINTER(C.c_uint32)]),
+    "lgcn_np_set_state": (None, [_vp, C.c_uint32]),
+    "lgcn_fy_resolve_device": (C.c_int, [_vp, C.c_int64, _vp, _vp, C.c_int64, _vp]),     # test hook
     "lgcn_sample_python": (C.c_int64, [C.c_int, C.c_int, C.c_int64, _vp, _vp, _vp]),
     "lgcn_np_shuffle_perm": (C.c_int, [C.c_int64, _vp]),
     "lgcn_build_user_item_csr": (C.c_int, [C.c_int, C.c_int, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -23,18 +23,18 @@
 //      next step that targets i, pointer doubling finds the chains' roots (tools/fy_parallel_prototype.py checks this form
 //      against np.random.shuffle on the CPU).
 // tests/test_gpu_parity.py compares the device permutation and the generator position afterwards with the host restatement
-// (lgcn_np_shuffle_perm), which tests/test_oracle.py pins to numpy itself.
+// (lgcn_np_shuffle_perm), which tests/test_oracle.py pins to numpy itself.  tests/test_gpu_shuffle.py starts k_fy_stream on
+// chosen (key, read position, n) -- tests/shuffle_cases.py models its path choice and tests/test_shuffle_host.py asserts that the
+// cases meet every hand-over between its paths -- and feeds stage 3 chosen J through the test hook lgcn_fy_resolve_device.
 #include <hip/hip_runtime.h>
 #include <cstring>
+#include <string>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <stdint.h>
 #include <math.h>
 
 #include "lgcn_hip.h"
 #include "lgcn_internal.h"
-
-extern "C" void lgcn_np_get_state(uint32_t *key624, uint32_t *pos);          // lgcn_host.cpp
-extern "C" void lgcn_np_set_state(const uint32_t *key624, uint32_t pos);
 
 #define MT_N 624
 #define MT_M 397
@@ -251,6 +251,28 @@ extern "C" int64_t lgcn_np_shuffle_perm_device_workspace(int64_t n) {
     return (int64_t)layout(n).total;
 }
 
+// Stage 3 on the J the workspace holds (n >= 2): keys, sort, parents, pointer doubling, output -- launches only, no
+// synchronisation.  The shuffle and the test hook lgcn_fy_resolve_device both end in it.
+static int fy_resolve_launch(const Layout &L, char *ws, int64_t n, int64_t *d_perm, hipStream_t st, const char *who) {
+    uint32_t *J = (uint32_t *)(ws + L.o_J), *g0 = (uint32_t *)(ws + L.o_g0), *g1 = (uint32_t *)(ws + L.o_g1);
+    unsigned long long *ka = (unsigned long long *)(ws + L.o_ka), *kb = (unsigned long long *)(ws + L.o_kb);
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(k_fy_keys, dim3(blocks), dim3(256), 0, st, (const uint32_t *)J, n, ka);
+    int bits = 1;
+    while (bits < 64 && ((unsigned long long)(n + 1) * (unsigned long long)(n + 1)) >> bits) bits++;
+    size_t tb = L.tmp_bytes;
+    if (rocprim::radix_sort_keys(ws + L.o_tmp, tb, (const unsigned long long *)ka, kb, (size_t)(n - 1), 0, bits, st) != hipSuccess) {
+        lgcn_set_error((std::string(who) + ": radix sort failed").c_str()); return 10; }
+    hipLaunchKernelGGL(k_fy_parent, dim3(blocks), dim3(256), 0, st, (const unsigned long long *)kb, n, g0);
+    uint32_t *cur = g0, *nxt = g1;
+    for (int64_t span = 1; span < n; span <<= 1) {                 // pointer doubling: after r rounds a node points 2^r hops up its chain
+        hipLaunchKernelGGL(k_fy_double, dim3(blocks), dim3(256), 0, st, (const uint32_t *)cur, nxt, n);
+        uint32_t *t = cur; cur = nxt; nxt = t;
+    }
+    hipLaunchKernelGGL(k_fy_out, dim3(blocks), dim3(256), 0, st, (const unsigned long long *)kb, (const uint32_t *)J, (const uint32_t *)cur, n, d_perm);
+    return 0;
+}
+
 extern "C" int lgcn_np_shuffle_perm_device(int64_t n, int64_t *d_perm, void *workspace, int64_t workspace_bytes, void *stream) {
     if (n < 0 || (n > 0 && !d_perm)) { lgcn_set_error("np_shuffle_perm_device: invalid argument"); return 3; }
     hipStream_t st = (hipStream_t)stream;
@@ -261,33 +283,40 @@ extern "C" int lgcn_np_shuffle_perm_device(int64_t n, int64_t *d_perm, void *wor
     if (!workspace || workspace_bytes < (int64_t)L.total) { lgcn_set_error("np_shuffle_perm_device: workspace too small"); return 3; }
     char *ws = (char *)workspace;
     uint32_t *key0 = (uint32_t *)(ws + L.o_key0), *keyf = (uint32_t *)(ws + L.o_keyf);
-    uint32_t *J = (uint32_t *)(ws + L.o_J), *g0 = (uint32_t *)(ws + L.o_g0), *g1 = (uint32_t *)(ws + L.o_g1);
-    unsigned long long *ka = (unsigned long long *)(ws + L.o_ka), *kb = (unsigned long long *)(ws + L.o_kb);
+    uint32_t *J = (uint32_t *)(ws + L.o_J);
     long long *res = (long long *)(ws + L.o_res);
     uint32_t hkey[MT_N], hpos = 0;
     lgcn_np_get_state(hkey, &hpos);
     if (hipMemcpyAsync(key0, hkey, sizeof hkey, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess) { lgcn_set_error("np_shuffle_perm_device: state upload failed"); return 10; }
     hipLaunchKernelGGL(k_fy_stream, dim3(1), dim3(64), 0, st, (const uint32_t *)key0, hpos, n, J, keyf, res);
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(k_fy_keys, dim3(blocks), dim3(256), 0, st, (const uint32_t *)J, n, ka);
-    int bits = 1;
-    while (bits < 64 && ((unsigned long long)(n + 1) * (unsigned long long)(n + 1)) >> bits) bits++;
-    size_t tb = L.tmp_bytes;
-    if (rocprim::radix_sort_keys(ws + L.o_tmp, tb, (const unsigned long long *)ka, kb, (size_t)(n - 1), 0, bits, st) != hipSuccess) {
-        lgcn_set_error("np_shuffle_perm_device: radix sort failed"); return 10; }
-    hipLaunchKernelGGL(k_fy_parent, dim3(blocks), dim3(256), 0, st, (const unsigned long long *)kb, n, g0);
-    uint32_t *cur = g0, *nxt = g1;
-    for (int64_t span = 1; span < n; span <<= 1) {                 // pointer doubling: after r rounds a node points 2^r hops up its chain
-        hipLaunchKernelGGL(k_fy_double, dim3(blocks), dim3(256), 0, st, (const uint32_t *)cur, nxt, n);
-        uint32_t *t = cur; cur = nxt; nxt = t;
-    }
-    hipLaunchKernelGGL(k_fy_out, dim3(blocks), dim3(256), 0, st, (const unsigned long long *)kb, (const uint32_t *)J, (const uint32_t *)cur, n, d_perm);
+    if (const int rc = fy_resolve_launch(L, ws, n, d_perm, st, "np_shuffle_perm_device")) return rc;
     long long hres[2] = {0, 0};
     if (hipMemcpyAsync(hkey, keyf, sizeof hkey, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipMemcpyAsync(hres, res, sizeof hres, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) { lgcn_set_error("np_shuffle_perm_device: kernels failed"); return 10; }
     const uint32_t idx = (uint32_t)hres[0];
     lgcn_np_set_state(hkey, idx);          // the host generator continues where the device stopped
+    return 0;
+}
+
+// TEST HOOK (include/lgcn_hip.h): stage 3 alone on a J the caller supplies.  Real draws give chains about log n deep; a
+// test reaches deep chains, long runs of equal targets and the sort's bit-count steps only by choosing J.
+extern "C" int lgcn_fy_resolve_device(const uint32_t *J_host, int64_t n, int64_t *d_perm, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (n < 0 || (n > 0 && (!d_perm || !J_host))) { lgcn_set_error("fy_resolve_device: invalid argument"); return 3; }
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) return 0;
+    if (n > 0x7ffffff0LL) { lgcn_set_error("fy_resolve_device: n too large for the device form"); return 3; }
+    if (J_host[0] != 0u) { lgcn_set_error("fy_resolve_device: J[0] must be 0"); return 3; }
+    for (int64_t i = 1; i < n; i++)
+        if ((int64_t)J_host[i] > i) { lgcn_set_error("fy_resolve_device: J[i] must be <= i"); return 3; }
+    if (n == 1) { if (hipMemsetAsync(d_perm, 0, sizeof(int64_t), st) != hipSuccess) { lgcn_set_error("fy_resolve_device: memset failed"); return 10; } return 0; }
+    const Layout L = layout(n);
+    if (!workspace || workspace_bytes < (int64_t)L.total) { lgcn_set_error("fy_resolve_device: workspace too small"); return 3; }
+    char *ws = (char *)workspace;
+    if (hipMemcpyAsync(ws + L.o_J, J_host, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) { lgcn_set_error("fy_resolve_device: J upload failed"); return 10; }
+    if (const int rc = fy_resolve_launch(L, ws, n, d_perm, st, "fy_resolve_device")) return rc;
+    if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) { lgcn_set_error("fy_resolve_device: kernels failed"); return 10; }
     return 0;
 }

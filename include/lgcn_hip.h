@@ -97,7 +97,11 @@ int lgcn_sample_negative_device_multi(int user_num, int item_num, int64_t train_
  * the fallback sampler and the epoch shuffle.                                 */
 /* utils.set_seed -> np.random.seed(seed)                    utils.py:114-120 */
 void lgcn_np_seed(uint32_t seed);
-/* utils.UniformSample_original_python                       utils.py:84-110
+/* The generator's whole state, as numpy's RandomState.get_state() / set_state() name it: key[624] (the untempered MT19937
+ * words) and the read position pos in 0..624 (624: the next draw twists first; larger values are taken as 624).          */
+void lgcn_np_get_state(uint32_t key[624], uint32_t *pos);
+void lgcn_np_set_state(const uint32_t key[624], uint32_t pos);
+/* utils.UniformSample_original_python                      utils.py:84-110
  * S_out: int64 [train_num,3]; returns the number of rows written (users with no
  * positives are skipped), or -1 on error.                                      */
 int64_t lgcn_sample_python(int n_users, int m_items, int64_t train_num,
@@ -186,6 +190,13 @@ int lgcn_propagate_weighted(const lgcn_graph *g, const float *E0, int K, int d, 
  * uses lgcn_np_shuffle_perm).  Synchronises `stream`. */
 int64_t lgcn_np_shuffle_perm_device_workspace(int64_t n);
 int lgcn_np_shuffle_perm_device(int64_t n, int64_t *d_perm, void *workspace, int64_t workspace_bytes, void *stream);
+/* TEST HOOK: the swap resolution of lgcn_np_shuffle_perm_device alone (keys, sort, parents, pointer doubling, output -- the same
+ * launches, the same workspace layout and size) on targets the caller chooses: d_perm (device int64[n]) = the result of
+ * x = arange(n); for i = n-1 .. 1: swap(x[i], x[J[i]]).  J_host: HOST uint32[n] with J[0] == 0 and J[i] <= i, checked before
+ * anything is launched (rc 3 otherwise, as for a short workspace or n >= 2^31 - 16).  Draws from MT19937 give chains about
+ * log n deep; a test reaches deep chains and long runs of equal targets only through here.  The host generator is neither
+ * read nor written.  Synchronises `stream`. */
+int lgcn_fy_resolve_device(const uint32_t *J_host, int64_t n, int64_t *d_perm, void *workspace, int64_t workspace_bytes, void *stream);
 /* users/pos/neg[T] = S[perm[t], 0..2] -- the device side of utils.shuffle
  * (utils.py:150) applied to the sampler output (main.py:217-220).            */
 int lgcn_apply_perm(const int32_t *S, int s_cols, const int64_t *perm, int64_t T,

@@ -1590,11 +1590,16 @@ def test_gpu_sampler_segments_heavy_tail_bit_exact(pkg):
 
 def test_device_shuffle_bit_exact(pkg):
     """lgcn_np_shuffle_perm_device: np.random.shuffle(arange(n)) (utils.py:148-149, numpy's legacy MT19937 + masked-rejection
-    Fisher-Yates) computed on the GPU -- MT19937 twisted in LDS, the draw-to-step alignment 256 draws at a time, the swaps as
-    sorted chains + pointer doubling -- against the host restatement lgcn_np_shuffle_perm (which test_oracle / test_host pin to
-    numpy itself): identical permutations for sizes around every special case (one and two steps, the serial tail at 1024, chunk
-    and mask boundaries, powers of two +- 1, Gowalla's epoch), starting in the middle of a generator block, and the generator
-    left exactly where the host loop leaves it (host and device calls interleaved draw the same stream)."""
+    Fisher-Yates) computed on the GPU -- ONE wave twists MT19937 in LDS and aligns the draws to the steps as it generates them,
+    64 draws per pass or a whole block of 624 on the fast path, with no stream buffer in memory; the swaps as sorted chains +
+    pointer doubling -- against the host restatement lgcn_np_shuffle_perm (which test_oracle / test_host pin to numpy itself):
+    identical permutations for one and two steps, sizes around the serial tail at 1024 and around powers of two, Gowalla's epoch
+    and sizes in the millions, every call starting wherever the last one left the generator block, and the generator left exactly
+    where the host loop leaves it (host and device calls interleaved draw the same stream).  The sizes here descend through every
+    mask boundary at whatever block offset the stream gives them (1279..1281 and 65536 +- 255..257 date from a first form that
+    aligned 256 draws at a time and mark nothing in this kernel); the hand-overs between the kernel's paths (the fast guard
+    i - 624 >= max(1024, low), the pass guard i - 64 >= low, the serial stretches) are started deliberately, from chosen read
+    positions, in tests/test_gpu_shuffle.py, and its swap resolution is fed deep chains there."""
     U = pkg.utils
     sizes = [1, 2, 3, 7, 64, 255, 256, 257, 1000, 1023, 1024, 1025, 1279, 1280, 1281, 1535, 1536, 2047, 2048, 2049, 4095, 4097, 5000,
              65535, 65536, 65537, 65536 + 255, 65536 + 256, 65536 + 257, 70000, 131071, 131072 + 300, 806166, 810128,
