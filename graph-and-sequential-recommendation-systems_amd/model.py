@@ -226,7 +226,16 @@ class _I2ISmooth(torch.autograd.Function):
         return ctx.model._i2i_apply(grad, transpose=True), None
 
 
-class LightGCN(nn.Module):
+class _TableModel(nn.Module):
+    """What LightGCN and PureMF share: the two embedding tables as views of ONE contiguous [N, d] fp32 table (rows [0, n_users)
+    the users), the device state `_dev` with its training context, and the host side of a fused step or epoch around its C call.
+
+    The two context types differ in the names of their entry points, `_CTX`; a subclass adds what is its own: how a context is
+    built (`_make_ctx`, from the pieces below), when one is stale (`_ctx_stale`), what else its device state holds
+    (`_open_state`, `_ctx_rows`, `_close_state`), which entry point a batch goes to (`_dispatch`) and what it memoises
+    (`invalidate_cache`)."""
+    _CTX = None     # {'destroy', 'get_step', 'set_step', 'set_lr', 'check', 'step', 'epoch'} -> entry point of the context type
+
     def __init__(self, config, dataset):
         super().__init__()
         self.config = config
@@ -235,6 +244,228 @@ class LightGCN(nn.Module):
         self.n_users = dataset.n_users
         self.m_items = dataset.m_items
         self.latent_dim = config['latent_dim_rec']
+
+    # -- config keys that are read when they are needed, not at construction (tests and BPRLoss assign them later) --
+    def _act(self):
+        return str(self.config.get('act_dtype', 'fp32'))
+
+    def _reg_ego(self):
+        return str(self.config.get('reg_rows', 'propagated')) == 'ego'
+
+    def _batch(self, default):
+        return int(self.config.get('bpr_batch_size', default))
+
+    # -- parameters live in one table ------------------------------------------------
+    def _bind_table(self):
+        """The two freshly initialised nn.Embedding weights move into ONE contiguous [N, d] storage (the cat of model.py:209
+        becomes a no-op)."""
+        with torch.no_grad():
+            table = torch.cat([self.embedding_user.weight, self.embedding_item.weight], dim=0).contiguous()
+        self._table = table
+        self._rebind()
+        self._dev = None            # device-side state (graph, workspace, context)
+
+    def _rebind(self):
+        self.embedding_user.weight.data = self._table[:self.n_users]
+        self.embedding_item.weight.data = self._table[self.n_users:]
+
+    def _apply(self, fn, recurse=True):
+        # keep the single-storage invariant through .to()/.cuda()/.float()
+        new = fn(self._table)
+        if new is not self._table:
+            self._table = new
+            self._drop_device_state()
+        self._rebind()
+        for p in (self.embedding_user.weight, self.embedding_item.weight):
+            if p.grad is not None:
+                p.grad = fn(p.grad)
+        return self
+
+    def _check_table(self):
+        """state_dict loads and optimisers write through the parameter views; make sure
+        nobody replaced them by independent tensors."""
+        u, i = self.embedding_user.weight, self.embedding_item.weight
+        if (u.data_ptr() != self._table.data_ptr()
+                or i.data_ptr() != self._table.data_ptr() + self.n_users * self.latent_dim * 4):
+            with torch.no_grad():
+                self._table[:self.n_users].copy_(u.data)
+                self._table[self.n_users:].copy_(i.data)
+            self._rebind()
+
+    # -- device state -----------------------------------------------------------------
+    def invalidate_cache(self):
+        """Hook probed by main.py:190-191 before each Test; here nothing is cached."""
+
+    def _open_state(self):
+        return {'ctx': None, 'max_batch': 0}
+
+    def _ctx_rows(self, st, row_subset):
+        return 'all'
+
+    def _close_state(self, st):
+        pass
+
+    def _retire_ctx(self, st):
+        """Destroys the context of st, if any -> its Adam step counter (0 without one), which the next context takes over."""
+        if not st.get('ctx'):
+            return 0
+        lib = _lib.load()
+        step = getattr(lib, self._CTX['get_step'])(st['ctx'])
+        getattr(lib, self._CTX['destroy'])(st['ctx'])
+        st['ctx'] = None
+        return step
+
+    def _drop_device_state(self):
+        st = self._dev
+        if st is not None:
+            self._retire_ctx(st)
+            self._close_state(st)
+        self._dev = None
+        self.invalidate_cache()
+
+    def __del__(self):
+        try:
+            self._drop_device_state()
+        except Exception:
+            pass
+
+    def _state(self, max_batch=None, need_ctx=False, dp_world=1, row_subset=None):
+        _lib.require_gpu()
+        if not self._table.is_cuda:
+            raise _lib.LgcnError("model parameters are not on the GPU: call .to(world.device) first")
+        self._check_table()
+        if self._dev is None:
+            self._dev = self._open_state()
+        st = self._dev
+        rows = 'all' if row_subset is None else self._ctx_rows(st, row_subset)
+        if need_ctx:
+            max_batch = int(max_batch or self._batch(2048))
+            if st['ctx'] is None or st['max_batch'] < max_batch or self._ctx_stale(st, dp_world, rows):
+                self._make_ctx(max_batch, dp_world, rows)
+        return st
+
+    # -- the pieces of _make_ctx both context types use ---------------------------------------
+    def _step_workspace(self, st, n_terms):
+        """Adam's moments (kept over a rebuild) and what one step accumulates in: G64, the row bitmaps, n_terms loss / reg terms,
+        the error flag (a step leaves G64 all zero and one bitmap flagged; a new context starts on fresh ones)."""
+        N, d, dev = self.n_users + self.m_items, self.latent_dim, self._table.device
+        if 'adam_m' not in st:
+            st['adam_m'] = torch.zeros(N, d, dtype=torch.float32, device=dev)
+            st['adam_v'] = torch.zeros(N, d, dtype=torch.float32, device=dev)
+        st['G64'] = torch.zeros(N, d, dtype=torch.int64, device=dev)
+        st['bitmap'] = torch.zeros(2 * ((N + 31) // 32), dtype=torch.int32, device=dev)
+        st['terms'] = torch.zeros(n_terms, dtype=torch.float32, device=dev)
+        st['err'] = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def _fill_step_config(self, cfg, st, max_batch):
+        """The fields lgcn_train_config and lgcn_mf_config share: sizes, the table, _step_workspace's buffers, Adam's constants."""
+        cfg.n_users, cfg.d = self.n_users, self.latent_dim
+        cfg.E0, cfg.adam_m, cfg.adam_v = self._table.data_ptr(), st['adam_m'].data_ptr(), st['adam_v'].data_ptr()
+        cfg.G64, cfg.bitmap, cfg.terms = st['G64'].data_ptr(), st['bitmap'].data_ptr(), st['terms'].data_ptr()
+        cfg.err, cfg.max_batch = st['err'].data_ptr(), max_batch
+        cfg.decay = float(self.config.get('decay', 1e-4))
+        cfg.lr = float(self.config.get('lr', 1e-3))
+        cfg.beta1, cfg.beta2, cfg.eps = 0.9, 0.999, 1e-8
+        return cfg
+
+    def _create_ctx(self, create, cfg, setters):
+        """`create`(cfg) -> the context handle, after every (entry, args) of `setters` was applied to it in order.  A setter that
+        fails destroys the new context (it holds device allocations) and its error goes on."""
+        lib = _lib.load()
+        h = C.c_void_p()
+        _lib.check(getattr(lib, create)(C.byref(cfg), C.byref(h)), create)
+        try:
+            for entry, args in setters:
+                _lib.check(getattr(lib, entry)(h, *args) or 0, entry)      # (set_step returns nothing: it cannot fail)
+        except Exception:
+            getattr(lib, self._CTX['destroy'])(h)
+            raise
+        return h
+
+    # -- fused path (what BPRLoss.stageOne calls) ------------------------------------------
+    @staticmethod
+    def _ids(t, dev):
+        if not torch.is_tensor(t):
+            t = torch.as_tensor(np.asarray(t))
+        return t.to(device=dev, dtype=torch.int32).contiguous()
+
+    def _dispatch(self, users, pos, neg, batch_size=None):
+        """A step's batch (batch_size None) or an epoch's id arrays -> (entry point, its arguments between the context and the
+        output, number of samples, the converted id tensors: the caller holds them until the call has been made).  Here: the
+        three-slot form, one negative per positive."""
+        dev = self._table.device
+        held = users, pos, neg = self._ids(users, dev), self._ids(pos, dev), self._ids(neg, dev)
+        T = int(users.numel())
+        if batch_size is None:
+            return self._CTX['step'], (_lib.tp(users), _lib.tp(pos), _lib.tp(neg), T), T, held
+        return self._CTX['epoch'], (_lib.tp(users), _lib.tp(pos), _lib.tp(neg), T, int(batch_size)), T, held
+
+    def _dp_begin(self, users, pos, neg, lr, dp_world, global_batch=None, row_subset=None):
+        """parallel.DataParallelBPR's preamble of a step on the given samples, or of an epoch over them in global batches:
+        int32 ids, the state for max(B, --bpr_batch) (B the step's or the global batch) and this world size, the learning
+        rate, the output -> (users, pos, neg, state, loss_out [3] or [steps, 3])."""
+        dev = self._table.device
+        users, pos, neg = self._ids(users, dev), self._ids(pos, dev), self._ids(neg, dev)
+        T = int(users.numel())
+        B = global_batch or T
+        st = self._state(max_batch=max(B, self._batch(B)), need_ctx=True, dp_world=dp_world, row_subset=row_subset)
+        getattr(_lib.load(), self._CTX['set_lr'])(st['ctx'], float(lr))
+        loss = torch.empty(((T + B - 1) // B, 3) if global_batch else 3, dtype=torch.float32, device=dev)
+        return users, pos, neg, st, loss
+
+    def _fused_call(self, entry, args, T, batch_size=None, loss_out=None, lr=None):
+        """What every fused step and epoch does around its C call: the state for max_batch (an epoch's batch_size; a step's T, or
+        --bpr_batch if that is larger), the learning rate, the output -- loss_out [3] of a step, [steps, 3] of an epoch --,
+        `entry`(ctx, *args, output, stream), its check, the cache.  args: the entry point's arguments between the context and
+        the output, or a function of the state that returns them.  Returns the output."""
+        dev = self._table.device
+        epoch = batch_size is not None
+        st = self._state(max_batch=batch_size if epoch else max(T, self._batch(T)), need_ctx=True,
+                         dp_world=(self._dev or {}).get('dp_world', 1))
+        lib = _lib.load()
+        if lr is not None:
+            getattr(lib, self._CTX['set_lr'])(st['ctx'], float(lr))
+        if epoch:
+            loss_out = torch.empty((T + batch_size - 1) // batch_size, 3, dtype=torch.float32, device=dev)
+        elif loss_out is None:
+            loss_out = torch.empty(3, dtype=torch.float32, device=dev)
+        if callable(args):
+            args = args(st)
+        _lib.check(getattr(lib, entry)(st['ctx'], *args, _lib.tp(loss_out), _lib.current_stream()), entry.replace("_i64", ""))
+        self.invalidate_cache()
+        return loss_out
+
+    def fused_step(self, users, pos, neg, loss_out=None, lr=None):
+        """One BPRLoss.stageOne (utils.py:53-64) in the HIP kernels.  Returns a device
+        tensor [3] = (bpr + decay*reg, bpr, reg); no host synchronisation."""
+        entry, args, B, held = self._dispatch(users, pos, neg)
+        return self._fused_call(entry, args, B, None, loss_out, lr)
+
+    def fused_epoch(self, users, pos, neg, batch_size, lr=None):
+        """The loop of main.py:223-225 over already-shuffled device id arrays, one C call.
+        Returns a device tensor [steps,3] of per-step (loss, bpr, reg)."""
+        entry, args, T, held = self._dispatch(users, pos, neg, int(batch_size))
+        return self._fused_call(entry, args, T, int(batch_size), None, lr)
+
+    def check_device_errors(self):
+        if self._dev and self._dev.get('ctx'):
+            _lib.check(getattr(_lib.load(), self._CTX['check'])(self._dev['ctx'], _lib.current_stream()), "device id check")
+
+    @property
+    def adam_step(self):
+        return getattr(_lib.load(), self._CTX['get_step'])(self._dev['ctx']) if self._dev and self._dev.get('ctx') else 0
+
+    def set_adam_step(self, step):
+        """torch Adam's state['step'] of a loaded optimizer state -> the training context (made if need be)."""
+        getattr(_lib.load(), self._CTX['set_step'])(self._state(need_ctx=True)['ctx'], int(step))
+
+
+class LightGCN(_TableModel):
+    _CTX = {'destroy': 'lgcn_ctx_destroy', 'get_step': 'lgcn_ctx_get_step', 'set_step': 'lgcn_ctx_set_step', 'set_lr': 'lgcn_ctx_set_lr',
+            'check': 'lgcn_ctx_check', 'step': 'lgcn_train_step', 'epoch': 'lgcn_train_epoch'}
+
+    def __init__(self, config, dataset):
+        super().__init__(config, dataset)
         self.n_layers = config['lightGCN_n_layers']
         # edge dropout (upstream LightGCN's __dropout_x; --dropout 1 --keepprob p): the fused training step draws one mask per
         # optimiser step (lgcn_ctx_set_dropout); evaluation never drops
@@ -242,8 +473,6 @@ class LightGCN(nn.Module):
         self.keep_prob = float(config.get('keep_prob', 0.6))
         if self.dropout and not (0.0 < self.keep_prob <= 1.0):
             raise ValueError(f"--keepprob must be in (0, 1] with --dropout 1, got {self.keep_prob}")
-        if self.dropout and str(config.get('act_dtype', 'fp32')) == 'fp8':
-            raise _lib.LgcnError("--dropout 1 is not implemented together with --act_dtype fp8 (fp32 and bf16 storage only)")
         if self.latent_dim not in (32, 64, 128, 256):
             raise ValueError("latent_dim_rec must be 32, 64, 128 or 256 for the HIP kernels")
         if not (1 <= self.n_layers <= _lib.MAX_LAYERS):
@@ -251,16 +480,12 @@ class LightGCN(nn.Module):
 
         # Same RNG consumption as model.py:57-60 (two nn.Embedding ctors, then two normal_),
         # then both tables are moved into ONE contiguous [N,d] storage: rows [0,n_users) are
-        # embedding_user.weight, rows [n_users,N) embedding_item.weight (the cat of model.py:209
-        # becomes a no-op).
+        # embedding_user.weight, rows [n_users,N) embedding_item.weight.
         self.embedding_user = nn.Embedding(self.n_users, self.latent_dim)
         self.embedding_item = nn.Embedding(self.m_items, self.latent_dim)
         nn.init.normal_(self.embedding_user.weight, std=0.1)
         nn.init.normal_(self.embedding_item.weight, std=0.1)
-        with torch.no_grad():
-            table = torch.cat([self.embedding_user.weight, self.embedding_item.weight], dim=0).contiguous()
-        self._table = table
-        self._rebind()
+        self._bind_table()
 
         # popularity gate (model.py:66-96): same modules, built in the same order -> same initial weights
         self.use_pop_gate = bool(config.get('use_pop_gate', False))
@@ -317,96 +542,85 @@ class LightGCN(nn.Module):
             raise ValueError("adjacency shape does not match n_users + m_items")
         if len(self._adj.indices) and (self._adj.indices.min() < 0 or self._adj.indices.max() >= N):
             raise ValueError("adjacency column index out of range")
-        if self.dropout and self.has_variants:
-            raise _lib.LgcnError("--dropout 1 is not implemented together with --use_pop_gate / --use_item_item "
-                                 "(the popularity gate and the item-item smoothing train without edge dropout only)")
         # weights of the layer combination (--layer_weights, --use_ppr_weights): fp32 [K+1], or None = the reference's mean.
         # The fused step (lgcn_ctx_set_layer_weights), the autograd path and evaluation (lgcn_propagate_weighted) all use them
         self.layer_weights = resolve_layer_weights(config, self.n_layers, np.diff(self._adj.indptr))
+        # several negatives per positive (--neg_ratio R; lgcn_train_step_multi, DESIGN 4.17): the default model, fp32 / bf16 storage
+        self.neg_ratio = int(config.get('neg_ratio', 1))
+        if not 1 <= self.neg_ratio <= _lib.MAX_NEG_RATIO:
+            raise ValueError(f"--neg_ratio must be in 1..{_lib.MAX_NEG_RATIO}, got {self.neg_ratio}")
+        # the loss of the fused step (--loss bpr | softmax, --softmax_temp; lgcn_ctx_set_loss, DESIGN 4.18): softmax = the positive
+        # against all R negatives of its sample in one log-sum-exp; every negative shape then goes to the _multi entry points.
+        # inbatch (DESIGN 4.19) = every user of the batch against every positive of the batch; the sampled negatives are not used
+        self.loss_kind, self.softmax_temp = resolve_loss(config)
+        # mixed negatives (--inbatch_mix 1; lgcn_train_step_inbatch_mix, DESIGN 4.21): the sampled negatives of the batch as shared
+        # extra columns of the in-batch score matrix; --neg_ratio 1..16 is then legal.  Resolved among the refusals, where its own lie
+        self.inbatch_mix = self._refuse_combinations()
+        self._neg_ratio_said = self._loss_said = False      # (_ctx_dense_last says each of its two lines once)
+        # the two options of the in-batch step (--score dot | cosine, --inbatch_logq 0 | 1; lgcn_ctx_set_inbatch_scores, DESIGN 4.20)
+        self.score_kind, self.inbatch_logq = resolve_inbatch_scores(config, self.loss_kind)
+        self._item_logq = None      # fp32 [m_items] log(items_D), rounded once from float64 (None: --inbatch_logq 0)
+        if self.inbatch_logq and self.inbatch_mix:      # the log of the mixture's expected count (DESIGN 4.21)
+            self._item_logq = torch.from_numpy(item_logq_mix(dataset.items_D, self._batch(2048), self.neg_ratio))
+        elif self.inbatch_logq:
+            self._item_logq = torch.from_numpy(item_logq(dataset.items_D))
+        self._gate_flat = None      # the eight MLP tensors of the gate in ONE buffer (what the fused step reads / updates)
+        self._Graph = None
+        self._cache = None          # propagated embeddings memoised between invalidate_cache() calls
+        self._rating_cache = None
+        self._cosine_cache = None   # --score cosine: the row-normalised propagated table evaluation ranks with, memoised likewise
+        self.f = nn.Sigmoid()
+
+    def _refuse_combinations(self):
+        """The pairs of options no launch exists for, first match first: storage, optional branches, dropout, layer weights,
+        --neg_ratio, --loss, --inbatch_mix -> the resolved --inbatch_mix, whose own refusals (resolve_inbatch_mix) stand between
+        those of the loss and the last one.  (A value that is invalid on its own was refused where it was read, before all these.)"""
+        config = self.config
+        fp8 = self._act() == 'fp8'
+        if self.dropout and fp8:
+            raise _lib.LgcnError("--dropout 1 is not implemented together with --act_dtype fp8 (fp32 and bf16 storage only)")
+        if self.dropout and self.has_variants:
+            raise _lib.LgcnError("--dropout 1 is not implemented together with --use_pop_gate / --use_item_item "
+                                 "(the popularity gate and the item-item smoothing train without edge dropout only)")
         if self.layer_weights is not None:
             flag = "--use_ppr_weights" if config.get('use_ppr_weights', False) else "--layer_weights"
-            if str(config.get('act_dtype', 'fp32')) == 'fp8':
+            if fp8:
                 raise _lib.LgcnError(f"{flag} is not implemented together with --act_dtype fp8 (fp32 and bf16 storage only)")
             if self.has_variants:
                 raise _lib.LgcnError(f"{flag} is not implemented together with --use_pop_gate / --use_item_item "
                                      "(the optional branches train with the layer mean only)")
             if self.dropout:
                 raise _lib.LgcnError(f"{flag} is not implemented together with --dropout 1 (edge dropout trains with the layer mean only)")
-        # several negatives per positive (--neg_ratio R; lgcn_train_step_multi, DESIGN 4.17): the default model, fp32 / bf16 storage
-        self.neg_ratio = int(config.get('neg_ratio', 1))
-        if not 1 <= self.neg_ratio <= _lib.MAX_NEG_RATIO:
-            raise ValueError(f"--neg_ratio must be in 1..{_lib.MAX_NEG_RATIO}, got {self.neg_ratio}")
         if self.neg_ratio > 1:
-            if str(config.get('act_dtype', 'fp32')) == 'fp8':
+            if fp8:
                 raise _lib.LgcnError(f"--neg_ratio {self.neg_ratio} is not implemented together with --act_dtype fp8 (fp32 and bf16 storage only)")
             if self.use_pop_gate or self.use_item_item:
                 raise _lib.LgcnError(f"--neg_ratio {self.neg_ratio} is not implemented together with --use_pop_gate / --use_item_item "
                                      "(the optional branches train on one negative per positive)")
-        self._neg_ratio_said = False
-        # the loss of the fused step (--loss bpr | softmax, --softmax_temp; lgcn_ctx_set_loss, DESIGN 4.18): softmax = the positive
-        # against all R negatives of its sample in one log-sum-exp; every negative shape then goes to the _multi entry points
-        self.loss_kind, self.softmax_temp = resolve_loss(config)
-        # inbatch (DESIGN 4.19) = every user of the batch against every positive of the batch; the sampled negatives are not used
         if self.loss_kind != 'bpr':
-            if str(config.get('act_dtype', 'fp32')) == 'fp8':
+            if fp8:
                 raise _lib.LgcnError(f"--loss {self.loss_kind} is not implemented together with --act_dtype fp8 (fp32 and bf16 storage only)")
             if self.use_pop_gate or self.use_item_item:
                 raise _lib.LgcnError(f"--loss {self.loss_kind} is not implemented together with --use_pop_gate / --use_item_item "
                                      "(the optional branches train with the BPR loss only)")
-        # mixed negatives (--inbatch_mix 1; lgcn_train_step_inbatch_mix, DESIGN 4.21): the sampled negatives of the batch as shared
-        # extra columns of the in-batch score matrix; --neg_ratio 1..16 is then legal
-        self.inbatch_mix = resolve_inbatch_mix(config, self.loss_kind)
-        if self.loss_kind == 'inbatch' and self.neg_ratio > 1 and not self.inbatch_mix:
+        mix = resolve_inbatch_mix(config, self.loss_kind)
+        if self.loss_kind == 'inbatch' and self.neg_ratio > 1 and not mix:
             raise _lib.LgcnError(f"--loss inbatch is not implemented together with --neg_ratio {self.neg_ratio}: the in-batch loss has no "
                                  "sampled negatives (the other samples' positives are the negatives); use --neg_ratio 1")
-        self._loss_said = False
-        # the two options of the in-batch step (--score dot | cosine, --inbatch_logq 0 | 1; lgcn_ctx_set_inbatch_scores, DESIGN 4.20)
-        self.score_kind, self.inbatch_logq = resolve_inbatch_scores(config, self.loss_kind)
-        self._item_logq = None      # fp32 [m_items] log(items_D), rounded once from float64 (None: --inbatch_logq 0)
-        if self.inbatch_logq and self.inbatch_mix:      # the log of the mixture's expected count (DESIGN 4.21)
-            self._item_logq = torch.from_numpy(item_logq_mix(dataset.items_D, int(config.get('bpr_batch_size', 2048)), self.neg_ratio))
-        elif self.inbatch_logq:
-            self._item_logq = torch.from_numpy(item_logq(dataset.items_D))
-        self._gate_flat = None      # the eight MLP tensors of the gate in ONE buffer (what the fused step reads / updates)
-        self._Graph = None
-        self._dev = None            # device-side state (graph, workspace, context)
-        self._cache = None          # propagated embeddings memoised between invalidate_cache() calls
-        self._rating_cache = None
-        self._cosine_cache = None   # --score cosine: the row-normalised propagated table evaluation ranks with, memoised likewise
-        self.f = nn.Sigmoid()
+        return mix
 
-    # -- parameters live in one table ------------------------------------------------
-    def _rebind(self):
-        self.embedding_user.weight.data = self._table[:self.n_users]
-        self.embedding_item.weight.data = self._table[self.n_users:]
-
+    # -- parameters live in one table: the gate's tensors follow it ----------------------
     def _apply(self, fn, recurse=True):
-        # keep the single-storage invariant through .to()/.cuda()/.float()
-        new = fn(self._table)
-        if new is not self._table:
-            self._table = new
-            self._drop_device_state()
-        self._rebind()
+        super()._apply(fn)
         for mod in (self.pop_mlp, self.gate_mlp):
             if mod is not None:
                 mod._apply(fn)
         if self.item_pop_scalar is not None:
             self.item_pop_scalar = fn(self.item_pop_scalar)
-        for p in (self.embedding_user.weight, self.embedding_item.weight):
-            if p.grad is not None:
-                p.grad = fn(p.grad)
         return self
 
     def _check_table(self):
-        """state_dict loads and optimisers write through the parameter views; make sure
-        nobody replaced them by independent tensors."""
-        u, i = self.embedding_user.weight, self.embedding_item.weight
-        if (u.data_ptr() != self._table.data_ptr()
-                or i.data_ptr() != self._table.data_ptr() + self.n_users * self.latent_dim * 4):
-            with torch.no_grad():
-                self._table[:self.n_users].copy_(u.data)
-                self._table[self.n_users:].copy_(i.data)
-            self._rebind()
+        super()._check_table()
         if self.use_pop_gate:
             self._pack_gate()
 
@@ -455,78 +669,56 @@ class LightGCN(nn.Module):
         return self._Graph
 
     # -- device state -----------------------------------------------------------------
-    def _drop_device_state(self):
-        if self._dev is not None and self._dev.get('ctx'):
-            _lib.load().lgcn_ctx_destroy(self._dev['ctx'])
-        if self._dev is not None and self._dev.get('graph_rs') is not None:
-            self._dev['graph_rs'].close()
-        if self._dev is not None and self._dev.get('graph') is not None:
-            self._dev['graph'].close()
-        for key in ('i2i', 'i2i_t', 'i2i_s', 'i2i_ts'):
-            if self._dev is not None and self._dev.get(key) is not None:
-                self._dev[key].close()
-        self._dev = None
-        self._cache = None
-        self._rating_cache = None
-        self._cosine_cache = None
+    def _close_state(self, st):
+        for key in ('graph_rs', 'graph', 'i2i', 'i2i_t', 'i2i_s', 'i2i_ts'):
+            if st.get(key) is not None:
+                st[key].close()
 
-    def __del__(self):
-        try:
-            self._drop_device_state()
-        except Exception:
-            pass
+    def _open_state(self):
+        a, dev = self._adj, self._table.device
+        from . import reorder
+        order, xcd_start = reorder.row_order(self.config.get('row_order', 'natural'), self.dataset, a,
+                                             cache_dir=getattr(self.dataset, 'path', None))
+        return {
+            'graph': _lib.Graph(torch.from_numpy(np.ascontiguousarray(a.indptr, np.int32)).to(dev),
+                                torch.from_numpy(np.ascontiguousarray(a.indices, np.int32)).to(dev),
+                                torch.from_numpy(np.ascontiguousarray(a.data, np.float32)).to(dev),
+                                d_max=self.latent_dim, row_order=order, xcd_start=xcd_start),
+            'ctx': None, 'max_batch': 0,
+        }
 
-    def _state(self, max_batch=None, need_ctx=False, dp_world=1, row_subset=None):
-        _lib.require_gpu()
-        if not self._table.is_cuda:
-            raise _lib.LgcnError("model parameters are not on the GPU: call .to(world.device) first")
-        self._check_table()
-        dev = self._table.device
-        if self._dev is None:
-            a = self._adj
-            from . import reorder
-            order, xcd_start = reorder.row_order(self.config.get('row_order', 'natural'), self.dataset, a,
-                                                 cache_dir=getattr(self.dataset, 'path', None))
-            self._dev = {
-                'graph': _lib.Graph(torch.from_numpy(np.ascontiguousarray(a.indptr, np.int32)).to(dev),
-                                    torch.from_numpy(np.ascontiguousarray(a.indices, np.int32)).to(dev),
-                                    torch.from_numpy(np.ascontiguousarray(a.data, np.float32)).to(dev),
-                                    d_max=self.latent_dim, row_order=order, xcd_start=xcd_start),
-                'ctx': None, 'max_batch': 0,
-            }
-        st = self._dev
-        if row_subset is not None and st.get('graph_rs') is None:
+    def _ctx_rows(self, st, row_subset):
+        """A context is bound to ONE plan: the owned rows (row-sharded epochs, which exchange the other rows: a row_subset is
+        given, and this is called) or all rows (every other caller: fused_step / fused_epoch / stageOne / batch-sharded data
+        parallel).  Makes the plan of the owned rows -> 'owned'."""
+        if st.get('graph_rs') is None:
             # row-sharded propagation: the training context works on a plan of the owned rows only
             # (same device CSR arrays); evaluation keeps the full plan
             g = st['graph']
             st['graph_rs'] = _lib.Graph(g.indptr, g.indices, g.vals, d_max=self.latent_dim,
                                         row_order=np.ascontiguousarray(row_subset, np.int32))
-        if need_ctx:
-            max_batch = int(max_batch or self.config.get('bpr_batch_size', 2048))
-            # a context is bound to ONE plan: the owned rows (row-sharded epochs, which exchange the other rows) or all
-            # rows (every other caller: fused_step / fused_epoch / stageOne / batch-sharded data parallel).  A context
-            # made for one must not serve the other -- it would propagate over the owned rows only, with no exchange.
-            rows = 'owned' if row_subset is not None else 'all'
-            if (st['ctx'] is None or st['max_batch'] < max_batch or st.get('dp_world', 1) != dp_world
-                    or st.get('ctx_rows', 'all') != rows):
-                self._make_ctx(max_batch, dp_world, rows)
-        return st
+        return 'owned'
+
+    def _ctx_stale(self, st, dp_world, rows):
+        # a context made for one plan must not serve the other -- it would propagate over the owned rows only, with no exchange
+        return st.get('dp_world', 1) != dp_world or st.get('ctx_rows', 'all') != rows
 
     def _make_ctx(self, max_batch, dp_world, rows=None):
-        st, dev = self._dev, self._table.device
-        lib = _lib.load()
-        old_step = 0
-        if st['ctx'] is not None:
-            old_step = lib.lgcn_ctx_get_step(st['ctx'])
-            lib.lgcn_ctx_destroy(st['ctx'])
-            st['ctx'] = None
-        N, d, K = self.n_users + self.m_items, self.latent_dim, self.n_layers
-        act_dtype = _act_code(self.config.get('act_dtype', 'fp32'))
-        if 'adam_m' not in st:
-            st['adam_m'] = torch.zeros(N, d, dtype=torch.float32, device=dev)
-            st['adam_v'] = torch.zeros(N, d, dtype=torch.float32, device=dev)
-        dense_last = self._dense_last(int(self.config.get('bpr_batch_size', max_batch)))     # the configured batch, not this context's capacity
-        variants = self.fused_variants
+        st = self._dev
+        old_step = self._retire_ctx(st)
+        rows = rows or st.get('ctx_rows', 'all')
+        variants, act_dtype = self.fused_variants, _act_code(self._act())
+        dense_last = self._ctx_dense_last(max_batch, variants)
+        self._ctx_workspace(st, max_batch, dp_world, dense_last, variants, act_dtype)
+        cfg = self._ctx_config(st, max_batch, rows, dense_last, variants, act_dtype)
+        st['ctx'] = self._create_ctx('lgcn_ctx_create', cfg, self._ctx_setters(st, old_step))
+        st['max_batch'], st['dp_world'], st['table_ptr'], st['ctx_rows'] = max_batch, dp_world, self._table.data_ptr(), rows
+        st['dense_last'] = dense_last
+
+    def _ctx_dense_last(self, max_batch, variants):
+        """Is the last forward layer propagated densely?  _dense_last on the configured batch (not this context's capacity), and
+        always where the step has no gathered form: the optional branches, --neg_ratio > 1, a loss other than BPR."""
+        dense_last = self._dense_last(self._batch(max_batch))
         if variants:
             dense_last = True       # the optional branches score on the layer mean of EVERY row (model.py:221-229)
         if self.neg_ratio > 1 and not dense_last:
@@ -539,35 +731,19 @@ class LightGCN(nn.Module):
             if not self._loss_said:
                 world.cprint(f"[loss] --loss {self.loss_kind}: the last layer is propagated densely (dense_last = 1)")
                 self._loss_said = True
+        return dense_last
+
+    def _ctx_workspace(self, st, max_batch, dp_world, dense_last, variants, act_dtype):
+        """Every device buffer and graph a context for max_batch reads or writes, into st."""
+        N, d, K, dev = self.n_users + self.m_items, self.latent_dim, self.n_layers, self._table.device
+        self._step_workspace(st, 3 * max_batch)
         st['act'] = _act_tables(max(1, K if dense_last else K - 1), N, d, act_dtype, dev)
-        st['G64'] = torch.zeros(N, d, dtype=torch.int64, device=dev)
-        st['bitmap'] = torch.zeros(2 * ((N + 31) // 32), dtype=torch.int32, device=dev)
-        st['terms'] = torch.zeros(3 * max_batch, dtype=torch.float32, device=dev)
         shard = (max_batch + dp_world - 1) // dp_world
         gate_p = sum(prm.numel() for prm in self.gate_parameters()) if (variants and self.use_pop_gate) else 0
         # exchange block of a rank (lgcn_dp_block_floats): gradient rows, loss / reg (/ entropy) terms, the gate's fixed-point MLP sums
         st['contrib'] = torch.zeros(3 * shard * d + 3 * shard + 2 + 2 * gate_p, dtype=torch.float32, device=dev)
-        st['err'] = torch.zeros(1, dtype=torch.int32, device=dev)
-        cfg = _lib.TrainConfig()
-        rows = rows or st.get('ctx_rows', 'all')
-        cfg.graph = (st['graph_rs'] if rows == 'owned' else st['graph']).handle
-        cfg.n_users, cfg.d, cfg.K = self.n_users, d, K
-        cfg.act_dtype = act_dtype
-        cfg.E0, cfg.adam_m, cfg.adam_v = self._table.data_ptr(), st['adam_m'].data_ptr(), st['adam_v'].data_ptr()
-        cfg.act, cfg.G64 = st['act'].data_ptr(), st['G64'].data_ptr()
-        cfg.bitmap, cfg.terms, cfg.contrib = st['bitmap'].data_ptr(), st['terms'].data_ptr(), st['contrib'].data_ptr()
-        cfg.err, cfg.max_batch = st['err'].data_ptr(), max_batch
-        cfg.decay = float(self.config.get('decay', 1e-4))
-        cfg.lr = float(self.config.get('lr', 1e-3))
-        cfg.beta1, cfg.beta2, cfg.eps = 0.9, 0.999, 1e-8
-        cfg.reg_ego = 1 if str(self.config.get('reg_rows', 'propagated')) == 'ego' else 0
-        if cfg.reg_ego and variants:
-            raise _lib.LgcnError("--reg_rows ego (upstream LightGCN's L2 term) is defined for the default model, not with "
-                                 "--use_pop_gate / --use_item_item")
-        cfg.xcd_remap = int(self.config.get('xcd_remap', 1))
-        cfg.dense_last = int(dense_last)
-        cfg.hub_nnz = int(self.config.get('hub_nnz', 0))          # 0: library default; < 0: off
-        cfg.hub_chunk = int(self.config.get('hub_chunk', 0))
+        if self.inbatch_logq and (st.get('item_logq') is None or st['item_logq'].device != dev):
+            st['item_logq'] = self._item_logq.to(device=dev, dtype=torch.float32).contiguous()      # uploaded once
         if variants and self.i2i_active:
             # the fused step's graphs hold alpha * I2I and its transpose (model.py:228-229 scales after the product)
             for key, mat in (('i2i_s', self._i2i), ('i2i_ts', self._i2i.T.tocsr())):
@@ -576,7 +752,6 @@ class LightGCN(nn.Module):
                     mat.sort_indices()
                     st[key] = _lib.Graph(torch.from_numpy(mat.indptr.astype(np.int32)).to(dev), torch.from_numpy(mat.indices.astype(np.int32)).to(dev),
                                          torch.from_numpy((np.float32(self.i2i_alpha) * mat.data).astype(np.float32)).to(dev), d_max=d)
-            cfg.i2i, cfg.i2i_t = st['i2i_s'].handle, st['i2i_ts'].handle
         if variants and self.use_pop_gate:
             self._pack_gate()
             P = self._gate_flat.numel()
@@ -584,62 +759,51 @@ class LightGCN(nn.Module):
                 if key not in st or st[key].numel() != P:
                     st[key] = torch.zeros(P, dtype=torch.float32, device=dev)
             st['item_pop'] = self.item_pop_scalar.to(device=dev, dtype=torch.float32).contiguous()
+
+    def _ctx_config(self, st, max_batch, rows, dense_last, variants, act_dtype):
+        """-> lgcn_train_config over the buffers of _ctx_workspace."""
+        cfg = self._fill_step_config(_lib.TrainConfig(), st, max_batch)
+        cfg.graph = (st['graph_rs'] if rows == 'owned' else st['graph']).handle
+        cfg.K, cfg.act_dtype = self.n_layers, act_dtype
+        cfg.act, cfg.contrib = st['act'].data_ptr(), st['contrib'].data_ptr()
+        cfg.reg_ego = int(self._reg_ego())
+        if cfg.reg_ego and variants:
+            raise _lib.LgcnError("--reg_rows ego (upstream LightGCN's L2 term) is defined for the default model, not with "
+                                 "--use_pop_gate / --use_item_item")
+        cfg.xcd_remap = int(self.config.get('xcd_remap', 1))
+        cfg.dense_last = int(dense_last)
+        cfg.hub_nnz = int(self.config.get('hub_nnz', 0))          # 0: library default; < 0: off
+        cfg.hub_chunk = int(self.config.get('hub_chunk', 0))
+        if variants and self.i2i_active:
+            cfg.i2i, cfg.i2i_t = st['i2i_s'].handle, st['i2i_ts'].handle
+        if variants and self.use_pop_gate:
             cfg.item_pop, cfg.gate_params = st['item_pop'].data_ptr(), self._gate_flat.data_ptr()
             cfg.gate_adam_m, cfg.gate_adam_v, cfg.gate_grad = st['gate_m'].data_ptr(), st['gate_v'].data_ptr(), st['gate_grad'].data_ptr()
             cfg.pop_hidden, cfg.gate_hidden = self.pop_hidden, self.gate_hidden
             cfg.gate_entropy_coeff, cfg.pop_gate_temp = self.gate_entropy_coeff, self.pop_gate_temp
-        st['dense_last'] = dense_last
-        h = C.c_void_p()
-        _lib.check(lib.lgcn_ctx_create(C.byref(cfg), C.byref(h)), "lgcn_ctx_create")
-        lib.lgcn_ctx_set_step(h, old_step)
+        return cfg
+
+    def _ctx_setters(self, st, old_step):
+        """-> [(entry point, its arguments after the context)] in the order they are applied.  Each option is set only when it is
+        on: a context that is never told keeps the workspace and runs the launches it always had."""
+        out = [('lgcn_ctx_set_step', (old_step,))]
         if self.dropout:
-            rc = lib.lgcn_ctx_set_dropout(h, self.keep_prob, int(self.config.get('seed', 2020)) & (2 ** 64 - 1))
-            if rc:
-                msg = lib.lgcn_last_error()
-                lib.lgcn_ctx_destroy(h)
-                raise _lib.LgcnError(f"lgcn_ctx_set_dropout failed (rc={rc}): {msg.decode() if msg else ''}")
+            out.append(('lgcn_ctx_set_dropout', (self.keep_prob, int(self.config.get('seed', 2020)) & (2 ** 64 - 1))))
         if self.layer_weights is not None:
-            w = np.ascontiguousarray(self.layer_weights, dtype=np.float32)
-            rc = lib.lgcn_ctx_set_layer_weights(h, w.ctypes.data_as(C.c_void_p), int(w.size))
-            if rc:
-                msg = lib.lgcn_last_error()
-                lib.lgcn_ctx_destroy(h)
-                raise _lib.LgcnError(f"lgcn_ctx_set_layer_weights failed (rc={rc}): {msg.decode() if msg else ''}")
+            w = np.ascontiguousarray(self.layer_weights, dtype=np.float32)      # (the pointer object keeps it alive until it is applied)
+            out.append(('lgcn_ctx_set_layer_weights', (_lib.npp(w), int(w.size))))
         if self.loss_kind != 'bpr':
-            rc = lib.lgcn_ctx_set_loss(h, _lib.LOSS_INBATCH if self.loss_kind == 'inbatch' else _lib.LOSS_SOFTMAX, float(self.softmax_temp))
-            if rc:
-                msg = lib.lgcn_last_error()
-                lib.lgcn_ctx_destroy(h)
-                raise _lib.LgcnError(f"lgcn_ctx_set_loss failed (rc={rc}): {msg.decode() if msg else ''}")
-        if self.score_kind != 'dot' or self.inbatch_logq:      # (a context that is never told runs the launches it always ran)
-            if self.inbatch_logq and (st.get('item_logq') is None or st['item_logq'].device != dev):
-                st['item_logq'] = self._item_logq.to(device=dev, dtype=torch.float32).contiguous()      # uploaded once
-            rc = lib.lgcn_ctx_set_inbatch_scores(h, _lib.SCORE_COSINE if self.score_kind == 'cosine' else _lib.SCORE_DOT,
-                                                 _lib.tp(st['item_logq']) if self.inbatch_logq else None)
-            if rc:
-                msg = lib.lgcn_last_error()
-                lib.lgcn_ctx_destroy(h)
-                raise _lib.LgcnError(f"lgcn_ctx_set_inbatch_scores failed (rc={rc}): {msg.decode() if msg else ''}")
-        if self.inbatch_mix:                     # (a context that is never told keeps the workspace and the launches it always had)
-            rc = lib.lgcn_ctx_set_inbatch_mix(h, int(self.neg_ratio))
-            if rc:
-                msg = lib.lgcn_last_error()
-                lib.lgcn_ctx_destroy(h)
-                raise _lib.LgcnError(f"lgcn_ctx_set_inbatch_mix failed (rc={rc}): {msg.decode() if msg else ''}")
+            out.append(('lgcn_ctx_set_loss', (_lib.LOSS_INBATCH if self.loss_kind == 'inbatch' else _lib.LOSS_SOFTMAX, float(self.softmax_temp))))
+        if self.score_kind != 'dot' or self.inbatch_logq:
+            out.append(('lgcn_ctx_set_inbatch_scores', (_lib.SCORE_COSINE if self.score_kind == 'cosine' else _lib.SCORE_DOT,
+                                                        _lib.tp(st['item_logq']) if self.inbatch_logq else None)))
+        if self.inbatch_mix:
+            out.append(('lgcn_ctx_set_inbatch_mix', (int(self.neg_ratio),)))
         if str(self.config.get('fold_g32', 1)).strip().lower() in ('0', 'false', 'off'):      # config['fold_g32'] = 0: fused_epoch launches k_g32 every step again (A/B, tests)
-            rc = lib.lgcn_ctx_set_fold_g32(h, 0)
-            if rc:
-                msg = lib.lgcn_last_error()
-                lib.lgcn_ctx_destroy(h)
-                raise _lib.LgcnError(f"lgcn_ctx_set_fold_g32 failed (rc={rc}): {msg.decode() if msg else ''}")
+            out.append(('lgcn_ctx_set_fold_g32', (0,)))
         if self.config.get('store_policy') is not None:      # config['store_policy'] = LGCN_STORE_* bits (A/B, tests); unset: LGCN_STORE_POLICY or the library's default
-            rc = lib.lgcn_ctx_set_store_policy(h, int(self.config['store_policy']))
-            if rc:
-                msg = lib.lgcn_last_error()
-                lib.lgcn_ctx_destroy(h)
-                raise _lib.LgcnError(f"lgcn_ctx_set_store_policy failed (rc={rc}): {msg.decode() if msg else ''}")
-        st['ctx'], st['max_batch'], st['dp_world'], st['table_ptr'] = h, max_batch, dp_world, self._table.data_ptr()
-        st['ctx_rows'] = rows
+            out.append(('lgcn_ctx_set_store_policy', (int(self.config['store_policy']),)))
+        return out
 
     def _dense_last(self, batch):
         """Last forward layer: on the 3B batch rows only (default) or densely?  The batch rows hold an
@@ -695,7 +859,7 @@ class LightGCN(nn.Module):
     def _propagate_dense(self):
         st = self._state()
         N, d, K = self.n_users + self.m_items, self.latent_dim, self.n_layers
-        act_dtype = _act_code(self.config.get('act_dtype', 'fp32'))
+        act_dtype = _act_code(self._act())
         work = st.get('eval_work')
         if K > 1 and (work is None or st.get('eval_work_dtype') != act_dtype):
             work = st['eval_work'] = _act_tables(K - 1, N, d, act_dtype, self._table.device)
@@ -809,7 +973,7 @@ class LightGCN(nn.Module):
             bpr = torch.logsumexp(torch.cat([torch.zeros_like(z[:, :1]), z], dim=1), dim=1).sum() / float(B)
         else:
             bpr = -torch.mean(F.logsigmoid(x))
-        if str(self.config.get('reg_rows', 'propagated')) == 'ego':
+        if self._reg_ego():
             u, pos_e, neg_e = self.embedding_user.weight[users.long()], self.embedding_item.weight[pos.long()], self.embedding_item.weight[neg.long()]
         reg_loss = (0.5 * (u.norm(2).pow(2) + pos_e.norm(2).pow(2) + neg_e.norm(2).pow(2) / float(R))) / float(B)
         return bpr, reg_loss
@@ -831,7 +995,7 @@ class LightGCN(nn.Module):
         keep = (pl[None, :] != pl[:, None]) & (ul[None, :] != ul[:, None])          # (u_c != u_b leaves c = b out too)
         z = torch.where(keep, z, torch.full_like(z, float('-inf')))
         sm = torch.logsumexp(torch.cat([torch.zeros_like(z[:, :1]), z], dim=1), dim=1).sum() / float(B)
-        if str(self.config.get('reg_rows', 'propagated')) == 'ego':
+        if self._reg_ego():
             u, p = self.embedding_user.weight[ul], self.embedding_item.weight[pl]
         return sm, (0.5 * (u.norm(2).pow(2) + p.norm(2).pow(2))) / float(B)
 
@@ -859,27 +1023,9 @@ class LightGCN(nn.Module):
         keep = torch.cat([(pl[None, :] != pl[:, None]) & (ul[None, :] != ul[:, None]), nl[None, :] != pl[:, None]], dim=1)
         z = torch.where(keep, z, torch.full_like(z, float('-inf')))
         sm = torch.logsumexp(torch.cat([torch.zeros_like(z[:, :1]), z], dim=1), dim=1).sum() / float(B)
-        if str(self.config.get('reg_rows', 'propagated')) == 'ego':
+        if self._reg_ego():
             u, p, n = self.embedding_user.weight[ul], self.embedding_item.weight[pl], self.embedding_item.weight[nl]
         return sm, (0.5 * (u.norm(2).pow(2) + p.norm(2).pow(2) + n.norm(2).pow(2) / float(R))) / float(B)
-
-    def _fused_inbatch(self, users, pos, neg, batch_size, loss_out, lr):
-        """fused_step (batch_size None) / fused_epoch under --loss inbatch: lgcn_train_step_inbatch / lgcn_train_epoch_inbatch on
-        (users, pos), neg accepted and ignored; under --inbatch_mix 1 lgcn_train_step_inbatch_mix / lgcn_train_epoch_inbatch_mix
-        on (users, pos, neg), neg 1-D (R = 1), [n, R] or [R, n]."""
-        dev = self._table.device
-        users, pos = self._ids(users, dev).reshape(-1), self._ids(pos, dev).reshape(-1)
-        T = int(users.numel())
-        u, p = _lib.tp(users), _lib.tp(pos)
-        if not self.inbatch_mix:
-            if batch_size is None:
-                return self._fused_call("lgcn_train_step_inbatch", (u, p, T), T, None, loss_out, lr)
-            return self._fused_call("lgcn_train_epoch_inbatch", (u, p, T, batch_size), T, batch_size, None, lr)
-        negs = self._negs_rn(neg, T, dev, mixed=True)
-        R = int(negs.shape[0])
-        if batch_size is None:
-            return self._fused_call("lgcn_train_step_inbatch_mix", (u, p, _lib.tp(negs), T, R, T), T, None, loss_out, lr)
-        return self._fused_call("lgcn_train_epoch_inbatch_mix", (u, p, _lib.tp(negs), R, T, batch_size), T, batch_size, None, lr)
 
     def bpr_loss(self, users, pos, neg):
         """model.py:162-183 (unfused, autograd-capable): (bpr [- entropy term of the gate], reg_loss)."""
@@ -895,7 +1041,7 @@ class LightGCN(nn.Module):
         pos_scores = torch.sum(u * pos_e, dim=1)
         neg_scores = torch.sum(u * neg_e, dim=1)
         bpr = -torch.mean(F.logsigmoid(pos_scores - neg_scores))
-        if str(self.config.get('reg_rows', 'propagated')) == 'ego':      # upstream LightGCN: userEmb0 / posEmb0 / negEmb0
+        if self._reg_ego():      # upstream LightGCN: userEmb0 / posEmb0 / negEmb0
             u0, p0, n0 = self.embedding_user.weight[users.long()], self.embedding_item.weight[pos.long()], self.embedding_item.weight[neg.long()]
             reg_loss = (0.5 * (u0.norm(2).pow(2) + p0.norm(2).pow(2) + n0.norm(2).pow(2))) / float(u.shape[0])
         else:
@@ -913,13 +1059,7 @@ class LightGCN(nn.Module):
         i_emb = self._fuse_item_embeddings(all_items) if self.use_pop_gate else all_items
         return (all_users[users] * i_emb[items]).sum(dim=1)
 
-    # -- fused path (what BPRLoss.stageOne calls) ------------------------------------------
-    @staticmethod
-    def _ids(t, dev):
-        if not torch.is_tensor(t):
-            t = torch.as_tensor(np.asarray(t))
-        return t.to(device=dev, dtype=torch.int32).contiguous()
-
+    # -- fused path: which entry point a batch goes to ------------------------------------------
     @staticmethod
     def _neg_dim(neg):
         return neg.dim() if torch.is_tensor(neg) else np.asarray(neg).ndim
@@ -947,102 +1087,50 @@ class LightGCN(nn.Module):
             raise ValueError(f"the negative ratio (neg_ratio) must be in 1..{_lib.MAX_NEG_RATIO}, got {R} negatives per positive")
         return neg.contiguous()
 
-    def _fused_call(self, entry, args, T, batch_size=None, loss_out=None, lr=None):
-        """What every fused step and epoch does around its C call: the state for max_batch (an epoch's batch_size; a step's T, or
-        --bpr_batch if that is larger), the learning rate, the output -- loss_out [3] of a step, [steps, 3] of an epoch --,
-        `entry`(ctx, *args, output, stream), its check, the cache.  args: the entry point's arguments between the context and
-        the output, or a function of the state that returns them.  Returns the output."""
-        dev = self._table.device
-        epoch = batch_size is not None
-        st = self._state(max_batch=batch_size if epoch else max(T, int(self.config.get('bpr_batch_size', T))), need_ctx=True,
-                         dp_world=(self._dev or {}).get('dp_world', 1))
-        lib = _lib.load()
-        if lr is not None:
-            lib.lgcn_ctx_set_lr(st['ctx'], float(lr))
-        if epoch:
-            loss_out = torch.empty((T + batch_size - 1) // batch_size, 3, dtype=torch.float32, device=dev)
-        elif loss_out is None:
-            loss_out = torch.empty(3, dtype=torch.float32, device=dev)
-        if callable(args):
-            args = args(st)
-        _lib.check(getattr(lib, entry)(st['ctx'], *args, _lib.tp(loss_out), _lib.current_stream()), entry.replace("_i64", ""))
-        self.invalidate_cache()
-        return loss_out
-
-    def _fused_step_multi(self, users, pos, negs, loss_out, lr):
-        """fused_step for R > 1 negatives per positive (negs int32 [R, B]): lgcn_train_step_multi."""
-        B = int(users.numel())
-        return self._fused_call("lgcn_train_step_multi", (_lib.tp(users), _lib.tp(pos), _lib.tp(negs), B, int(negs.shape[0]), B), B, None, loss_out, lr)
-
-    def fused_step(self, users, pos, neg, loss_out=None, lr=None):
-        """One BPRLoss.stageOne (utils.py:53-64) in the HIP kernels.  Returns a device
-        tensor [3] = (bpr + decay*reg, bpr, reg); no host synchronisation."""
+    def _dispatch(self, users, pos, neg, batch_size=None):
+        """_TableModel._dispatch by the loss and the shape of neg: in-batch (neg accepted and ignored), mixed in-batch (neg the
+        pool: 1-D, [n, R] or [R, n]), multi-negative ([n, R] or [R, n]; under --loss softmax 1-D too, as R = 1) or three-slot
+        (1-D, or one column).  The arguments are each entry point's own (include/lgcn_hip.h)."""
+        step = batch_size is None
         if self.has_variants and not self.fused_variants:
             raise RuntimeError("this configuration of the popularity gate / item-item smoothing is outside the fused step "
-                               "(--fused_variants 0, or gate hidden sizes > 64 / d > 128): use BPRLoss.stageOne (autograd path)")
+                               "(--fused_variants 0, or gate hidden sizes > 64 / d > 128): use BPRLoss.stageOne (autograd path)" if step else
+                               "this configuration of the optional branches is outside the fused step: loop BPRLoss.stageOne")
         dev = self._table.device
-        if self.loss_kind == 'inbatch':        # --loss inbatch: (users, pos) only, neg is accepted and ignored; the pool under --inbatch_mix 1
-            return self._fused_inbatch(users, pos, neg, None, loss_out, lr)
+        if self.loss_kind == 'inbatch':
+            held = users, pos = self._ids(users, dev).reshape(-1), self._ids(pos, dev).reshape(-1)
+            T = int(users.numel())
+            u, p = _lib.tp(users), _lib.tp(pos)
+            if not self.inbatch_mix:
+                return ("lgcn_train_step_inbatch", (u, p, T), T, held) if step else ("lgcn_train_epoch_inbatch", (u, p, T, batch_size), T, held)
+            negs = self._negs_rn(neg, T, dev, mixed=True)
+            n, R, held = _lib.tp(negs), int(negs.shape[0]), (users, pos, negs)
+            return ("lgcn_train_step_inbatch_mix", (u, p, n, T, R, T), T, held) if step else ("lgcn_train_epoch_inbatch_mix", (u, p, n, R, T, batch_size), T, held)
         if self.loss_kind == 'softmax' and self._neg_dim(neg) == 1:      # --loss softmax: every shape is a multi step, R = 1 included
             neg = self._ids(neg, dev).reshape(1, -1)
-        if self._neg_dim(neg) == 2:            # several negatives per positive: neg [B, R] (the sampler's S[:, 2:]) or [R, B]
+        if self._neg_dim(neg) == 2:            # several negatives per positive: neg [n, R] (the sampler's S[:, 2:]) or [R, n]
             users, pos = self._ids(users, dev), self._ids(pos, dev)
-            negs = self._negs_rn(neg, int(users.numel()), dev)
-            if negs is not None:
-                return self._fused_step_multi(users, pos, negs, loss_out, lr)
-            neg = self._ids(neg, dev).reshape(-1)     # R == 1: the three-slot step, unchanged
+            T = int(users.numel())
+            negs = self._negs_rn(neg, T, dev)
+            if negs is not None:               # (negative column r at negs + r * T)
+                u, p, n, R, held = _lib.tp(users), _lib.tp(pos), _lib.tp(negs), int(negs.shape[0]), (users, pos, negs)
+                return ("lgcn_train_step_multi", (u, p, n, T, R, T), T, held) if step else ("lgcn_train_epoch_multi", (u, p, n, R, T, batch_size), T, held)
+            neg = self._ids(neg, dev).reshape(-1)     # R == 1: the three-slot form, unchanged
         # the reference's call shape: three torch.long device tensors (main.py:217-225) -- narrowed inside the step's own launch
         # sequence (lgcn_train_step_i64) instead of three conversion kernels and allocations here
-        as_i64 = all(torch.is_tensor(t) and t.dtype == torch.int64 and t.device == dev and t.is_contiguous() for t in (users, pos, neg))
-        if not as_i64:
-            users, pos, neg = self._ids(users, dev), self._ids(pos, dev), self._ids(neg, dev)
+        if not (step and all(torch.is_tensor(t) and t.dtype == torch.int64 and t.device == dev and t.is_contiguous() for t in (users, pos, neg))):
+            return _TableModel._dispatch(self, users, pos, neg, batch_size)
         B = int(users.numel())
         ids = (_lib.tp(users), _lib.tp(pos), _lib.tp(neg), B)
-        if not as_i64:
-            return self._fused_call("lgcn_train_step", ids, B, None, loss_out, lr)
 
         def with_scratch(st):
             if st.get('ids32') is None or st['ids32'].numel() < 3 * B:
                 st['ids32'] = torch.empty(3 * max(B, st['max_batch']), dtype=torch.int32, device=dev)
             return (*ids, _lib.tp(st['ids32']))
-        return self._fused_call("lgcn_train_step_i64", with_scratch, B, None, loss_out, lr)
-
-    def fused_epoch(self, users, pos, neg, batch_size, lr=None):
-        """The loop of main.py:223-225 over already-shuffled device id arrays, one C call.
-        Returns a device tensor [steps,3] of per-step (loss, bpr, reg)."""
-        if self.has_variants and not self.fused_variants:
-            raise RuntimeError("this configuration of the optional branches is outside the fused step: loop BPRLoss.stageOne")
-        dev = self._table.device
-        if self.loss_kind == 'inbatch':        # --loss inbatch: (users, pos) only, neg is accepted and ignored; the pool under --inbatch_mix 1
-            return self._fused_inbatch(users, pos, neg, int(batch_size), None, lr)
-        users, pos = self._ids(users, dev), self._ids(pos, dev)
-        T = int(users.numel())
-        negs = None
-        if self.loss_kind == 'softmax' and self._neg_dim(neg) == 1:      # --loss softmax: the multi epoch at R = 1
-            neg = self._ids(neg, dev).reshape(1, -1)
-        if self._neg_dim(neg) == 2:            # several negatives per positive: neg [T, R] or [R, T]
-            negs = self._negs_rn(neg, T, dev)
-        if negs is not None:                   # R > 1: the multi-negative epoch (negative column r at negs + r * T)
-            return self._fused_call("lgcn_train_epoch_multi", (_lib.tp(users), _lib.tp(pos), _lib.tp(negs), int(negs.shape[0]), T, int(batch_size)),
-                                    T, batch_size, None, lr)
-        neg = self._ids(neg, dev).reshape(-1)  # R == 1 (1-D, or one column): the three-slot epoch, unchanged
-        return self._fused_call("lgcn_train_epoch", (_lib.tp(users), _lib.tp(pos), _lib.tp(neg), T, int(batch_size)), T, batch_size, None, lr)
+        return "lgcn_train_step_i64", with_scratch, B, (users, pos, neg)
 
 
-    def check_device_errors(self):
-        if self._dev and self._dev.get('ctx'):
-            _lib.check(_lib.load().lgcn_ctx_check(self._dev['ctx'], _lib.current_stream()), "device id check")
-
-    @property
-    def adam_step(self):
-        return _lib.load().lgcn_ctx_get_step(self._dev['ctx']) if self._dev and self._dev.get('ctx') else 0
-
-    def set_adam_step(self, step):
-        """torch Adam's state['step'] of a loaded optimizer state -> the training context (made if need be)."""
-        _lib.load().lgcn_ctx_set_step(self._state(need_ctx=True)['ctx'], int(step))
-
-
-class PureMF(nn.Module):
+class PureMF(_TableModel):
     """Matrix factorisation trained with BPR: upstream LightGCN's second model (`--model mf`, the class the reference's
     register.py:43-44 registers when it exists) and the baseline every LightGCN number is read against.
 
@@ -1058,15 +1146,11 @@ class PureMF(nn.Module):
     use_pop_gate = False
     dropout = False
     layer_weights = None
+    _CTX = {'destroy': 'lgcn_mf_destroy', 'get_step': 'lgcn_mf_get_step', 'set_step': 'lgcn_mf_set_step', 'set_lr': 'lgcn_mf_set_lr',
+            'check': 'lgcn_mf_check', 'step': 'lgcn_mf_train_step', 'epoch': 'lgcn_mf_train_epoch'}
 
     def __init__(self, config, dataset):
-        super().__init__()
-        self.config = config
-        self.dataset = dataset
-        self.device = world.device
-        self.n_users = dataset.n_users
-        self.m_items = dataset.m_items
-        self.latent_dim = config['latent_dim_rec']
+        super().__init__(config, dataset)
         no = "is not implemented for --model mf"
         if config.get('use_pop_gate', False):
             raise _lib.LgcnError(f"--use_pop_gate {no} (the popularity gate belongs to LightGCN)")
@@ -1079,7 +1163,7 @@ class PureMF(nn.Module):
             raise _lib.LgcnError(f"--layer_weights {lw} {no} (there are no layers to combine)")
         if config.get('use_ppr_weights', False):
             raise _lib.LgcnError(f"--use_ppr_weights {no} (there are no layers to combine)")
-        if str(config.get('act_dtype', 'fp32')) != 'fp32':
+        if self._act() != 'fp32':
             raise _lib.LgcnError(f"--act_dtype {config.get('act_dtype')} {no} (fp32 tables only)")
         if int(config.get('neg_ratio', 1)) != 1:
             raise _lib.LgcnError(f"--neg_ratio {config.get('neg_ratio')} {no} (the matrix-factorisation step trains on triplets, "
@@ -1099,98 +1183,23 @@ class PureMF(nn.Module):
         # RNG consumption of upstream PureMF: the two nn.Embedding constructors in this order, their own N(0, 1) init kept
         self.embedding_user = nn.Embedding(self.n_users, self.latent_dim)
         self.embedding_item = nn.Embedding(self.m_items, self.latent_dim)
-        with torch.no_grad():
-            table = torch.cat([self.embedding_user.weight, self.embedding_item.weight], dim=0).contiguous()
-        self._table = table
-        self._rebind()
-        self._dev = None            # device-side state (Adam moments, workspace, context)
+        self._bind_table()
         self.f = nn.Sigmoid()
 
-    # -- parameters live in one table (as in LightGCN) ---------------------------------
-    def _rebind(self):
-        self.embedding_user.weight.data = self._table[:self.n_users]
-        self.embedding_item.weight.data = self._table[self.n_users:]
+    # -- device state: the context of csrc/lgcn_mf.hip over the table, Adam's moments and a step's workspace ----
+    def _ctx_stale(self, st, dp_world, rows):
+        return st.get('table_ptr') != self._table.data_ptr()
 
-    def _apply(self, fn, recurse=True):
-        new = fn(self._table)
-        if new is not self._table:
-            self._table = new
-            self._drop_device_state()
-        self._rebind()
-        for p in (self.embedding_user.weight, self.embedding_item.weight):
-            if p.grad is not None:
-                p.grad = fn(p.grad)
-        return self
-
-    def _check_table(self):
-        u, i = self.embedding_user.weight, self.embedding_item.weight
-        if (u.data_ptr() != self._table.data_ptr()
-                or i.data_ptr() != self._table.data_ptr() + self.n_users * self.latent_dim * 4):
-            with torch.no_grad():
-                self._table[:self.n_users].copy_(u.data)
-                self._table[self.n_users:].copy_(i.data)
-            self._rebind()
-
-    # -- device state -----------------------------------------------------------------
-    def _drop_device_state(self):
-        if self._dev is not None and self._dev.get('ctx'):
-            _lib.load().lgcn_mf_destroy(self._dev['ctx'])
-        self._dev = None
-
-    def __del__(self):
-        try:
-            self._drop_device_state()
-        except Exception:
-            pass
-
-    def _state(self, max_batch=None, need_ctx=False, **_):
-        _lib.require_gpu()
-        if not self._table.is_cuda:
-            raise _lib.LgcnError("model parameters are not on the GPU: call .to(world.device) first")
-        self._check_table()
-        if self._dev is None:
-            self._dev = {'ctx': None, 'max_batch': 0}
+    def _make_ctx(self, max_batch, dp_world=1, rows=None):
         st = self._dev
-        if need_ctx:
-            max_batch = int(max_batch or self.config.get('bpr_batch_size', 2048))
-            if st['ctx'] is None or st['max_batch'] < max_batch or st.get('table_ptr') != self._table.data_ptr():
-                self._make_ctx(max_batch)
-        return st
-
-    def _make_ctx(self, max_batch):
-        st, dev = self._dev, self._table.device
-        lib = _lib.load()
-        old_step = 0
-        if st['ctx'] is not None:
-            old_step = lib.lgcn_mf_get_step(st['ctx'])
-            lib.lgcn_mf_destroy(st['ctx'])
-            st['ctx'] = None
-        N, d = self.n_users + self.m_items, self.latent_dim
-        if 'adam_m' not in st:
-            st['adam_m'] = torch.zeros(N, d, dtype=torch.float32, device=dev)
-            st['adam_v'] = torch.zeros(N, d, dtype=torch.float32, device=dev)
-        # (a step leaves G64 all zero and one bitmap flagged; a new context starts on fresh ones)
-        st['G64'] = torch.zeros(N, d, dtype=torch.int64, device=dev)
-        st['bitmap'] = torch.zeros(2 * ((N + 31) // 32), dtype=torch.int32, device=dev)
-        st['terms'] = torch.zeros(2 * max_batch, dtype=torch.float32, device=dev)
-        st['err'] = torch.zeros(1, dtype=torch.int32, device=dev)
-        cfg = _lib.MfConfig()
-        cfg.n_users, cfg.m_items, cfg.d = self.n_users, self.m_items, d
-        cfg.E0, cfg.adam_m, cfg.adam_v = self._table.data_ptr(), st['adam_m'].data_ptr(), st['adam_v'].data_ptr()
-        cfg.G64, cfg.bitmap, cfg.terms = st['G64'].data_ptr(), st['bitmap'].data_ptr(), st['terms'].data_ptr()
-        cfg.err, cfg.max_batch = st['err'].data_ptr(), max_batch
-        cfg.decay = float(self.config.get('decay', 1e-4))
-        cfg.lr = float(self.config.get('lr', 1e-3))
-        cfg.beta1, cfg.beta2, cfg.eps = 0.9, 0.999, 1e-8
-        h = C.c_void_p()
-        _lib.check(lib.lgcn_mf_create(C.byref(cfg), C.byref(h)), "lgcn_mf_create")
-        lib.lgcn_mf_set_step(h, old_step)
-        st['ctx'], st['max_batch'], st['table_ptr'] = h, max_batch, self._table.data_ptr()
+        old_step = self._retire_ctx(st)
+        self._step_workspace(st, 2 * max_batch)
+        cfg = self._fill_step_config(_lib.MfConfig(), st, max_batch)
+        cfg.m_items = self.m_items
+        st['ctx'] = self._create_ctx('lgcn_mf_create', cfg, [('lgcn_mf_set_step', (old_step,))])
+        st['max_batch'], st['table_ptr'] = max_batch, self._table.data_ptr()
 
     # -- reference API --------------------------------------------------------------------
-    def invalidate_cache(self):
-        """Nothing is cached: the scores are taken on the table itself."""
-
     def propagated_table(self):
         """The [N, d] fp32 table computer() splits into users / items: the parameters themselves."""
         return self._table
@@ -1225,50 +1234,3 @@ class PureMF(nn.Module):
     def forward(self, users, items):
         all_users, all_items = self.computer()
         return self.f(torch.sum(all_users[users.long()] * all_items[items.long()], dim=1))
-
-    # -- fused path (what BPRLoss.stageOne calls) ------------------------------------------
-    _ids = staticmethod(LightGCN._ids)
-
-    def fused_step(self, users, pos, neg, loss_out=None, lr=None):
-        """One BPRLoss.stageOne in the HIP kernels (lgcn_mf_train_step).  Returns a device tensor [3] =
-        (bpr + decay*reg, bpr, reg); no host synchronisation."""
-        dev = self._table.device
-        users, pos, neg = self._ids(users, dev), self._ids(pos, dev), self._ids(neg, dev)
-        B = int(users.numel())
-        st = self._state(max_batch=max(B, int(self.config.get('bpr_batch_size', B))), need_ctx=True)
-        lib = _lib.load()
-        if lr is not None:
-            lib.lgcn_mf_set_lr(st['ctx'], float(lr))
-        if loss_out is None:
-            loss_out = torch.empty(3, dtype=torch.float32, device=dev)
-        _lib.check(lib.lgcn_mf_train_step(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(neg), B, _lib.tp(loss_out),
-                                          _lib.current_stream()), "lgcn_mf_train_step")
-        return loss_out
-
-    def fused_epoch(self, users, pos, neg, batch_size, lr=None):
-        """The loop of main.py:223-225 over already-shuffled device id arrays, one C call (lgcn_mf_train_epoch).
-        Returns a device tensor [steps,3] of per-step (loss, bpr, reg)."""
-        dev = self._table.device
-        users, pos, neg = self._ids(users, dev), self._ids(pos, dev), self._ids(neg, dev)
-        T = int(users.numel())
-        steps = (T + batch_size - 1) // batch_size
-        st = self._state(max_batch=batch_size, need_ctx=True)
-        lib = _lib.load()
-        if lr is not None:
-            lib.lgcn_mf_set_lr(st['ctx'], float(lr))
-        losses = torch.empty(steps, 3, dtype=torch.float32, device=dev)
-        _lib.check(lib.lgcn_mf_train_epoch(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(neg), T, int(batch_size),
-                                           _lib.tp(losses), _lib.current_stream()), "lgcn_mf_train_epoch")
-        return losses
-
-    def check_device_errors(self):
-        if self._dev and self._dev.get('ctx'):
-            _lib.check(_lib.load().lgcn_mf_check(self._dev['ctx'], _lib.current_stream()), "device id check")
-
-    @property
-    def adam_step(self):
-        return _lib.load().lgcn_mf_get_step(self._dev['ctx']) if self._dev and self._dev.get('ctx') else 0
-
-    def set_adam_step(self, step):
-        """torch Adam's state['step'] of a loaded optimizer state -> the training context (made if need be)."""
-        _lib.load().lgcn_mf_set_step(self._state(need_ctx=True)['ctx'], int(step))

@@ -265,6 +265,10 @@ class DataParallelBPR:
         except Exception:
             pass
 
+    def _begin(self, users, pos, neg, dp_world, **epoch):
+        """the model's preamble of a step, or of an epoch (global_batch=, row_subset=), at the optimiser's learning rate"""
+        return self.model._dp_begin(users, pos, neg, float(self.opt.param_groups[0]['lr']), dp_world, **epoch)
+
     def stageOne(self, users, pos, neg):
         loss = self._step(users, pos, neg)
         return loss[0] if self.lazy else loss[0].cpu().item()
@@ -276,15 +280,10 @@ class DataParallelBPR:
         dev = m._table.device
         T = int(users.numel())
         if self.shard == 'cols' and dev.type == 'cuda' and os.environ.get("LGCN_DP_PYTHON_LOOP") != "1" and self._own_communicator_ok():
-            users, pos, neg = m._ids(users, dev), m._ids(pos, dev), m._ids(neg, dev)
-            st = m._state(max_batch=max(int(global_batch), int(m.config.get('bpr_batch_size', global_batch))), need_ctx=True, dp_world=1)
-            lib = _lib.load()
-            lib.lgcn_ctx_set_lr(st['ctx'], float(self.opt.param_groups[0]['lr']))
-            steps = (T + global_batch - 1) // global_batch
-            losses = torch.empty(steps, 3, dtype=torch.float32, device=dev)
-            _lib.check(lib.lgcn_train_epoch_dp(st['ctx'], self._communicator(), _lib.tp(users), _lib.tp(pos), _lib.tp(neg), T,
+            users, pos, neg, st, losses = self._begin(users, pos, neg, 1, global_batch=int(global_batch))
+            _lib.check(_lib.load().lgcn_train_epoch_dp(st['ctx'], self._communicator(), _lib.tp(users), _lib.tp(pos), _lib.tp(neg), T,
                                                int(global_batch), 3, None, None, _lib.tp(losses), _lib.current_stream()), "lgcn_train_epoch_dp")
-            m._cache = None
+            m.invalidate_cache()
             return losses
         if dev.type != 'cuda' or os.environ.get("LGCN_DP_PYTHON_LOOP") == "1" or not self._own_communicator_ok():
             if self.shard == 'rows':        # (no per-step form exists: _step would come straight back here)
@@ -294,14 +293,9 @@ class DataParallelBPR:
                    for t in range(0, T, global_batch)]
             return torch.stack(out)
         # one host call per epoch: the C loop issues kernels and RCCL collectives on one stream
-        users, pos, neg = m._ids(users, dev), m._ids(pos, dev), m._ids(neg, dev)
-        st = m._state(max_batch=max(int(global_batch), int(m.config.get('bpr_batch_size', global_batch))), need_ctx=True,
-                      dp_world=self.world,
-                      row_subset=owned_rows(self.ranges, self.rank) if self.shard == 'rows' else None)
+        users, pos, neg, st, losses = self._begin(users, pos, neg, self.world, global_batch=int(global_batch),
+                                                  row_subset=owned_rows(self.ranges, self.rank) if self.shard == 'rows' else None)
         lib = _lib.load()
-        lib.lgcn_ctx_set_lr(st['ctx'], float(self.opt.param_groups[0]['lr']))
-        steps = (T + global_batch - 1) // global_batch
-        losses = torch.empty(steps, 3, dtype=torch.float32, device=dev)
         n = self.world * int(lib.lgcn_dp_block_floats(st['ctx'], int(global_batch), self.world))
         if self.reduce == 'rows' and (self._gathered is None or self._gathered.numel() < n):
             self._gathered = torch.empty(n, dtype=torch.float32, device=dev)
@@ -311,7 +305,7 @@ class DataParallelBPR:
                                            int(global_batch), mode, _lib.npp(rr) if rr is not None else None,
                                            _lib.tp(self._gathered) if self.reduce == 'rows' else None,
                                            _lib.tp(losses), _lib.current_stream()), "lgcn_train_epoch_dp")
-        m._cache = None
+        m.invalidate_cache()
         return losses
 
     def gather_table(self):
@@ -325,21 +319,18 @@ class DataParallelBPR:
         """one column-sharded step with the all-reduce through torch.distributed (the fallback of the C loop)"""
         m = self.model
         dev = m._table.device
-        users, pos, neg = m._ids(users, dev), m._ids(pos, dev), m._ids(neg, dev)
+        users, pos, neg, st, loss = self._begin(users, pos, neg, 1)
         B = int(users.numel())
-        st = m._state(max_batch=max(B, int(m.config.get('bpr_batch_size', B))), need_ctx=True, dp_world=1)
         lib = _lib.load()
-        lib.lgcn_ctx_set_lr(st['ctx'], float(self.opt.param_groups[0]['lr']))
         stream = _lib.current_stream()
         ptr = C.c_void_p()
         _lib.check(lib.lgcn_train_step_cols_part1(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(neg), B, C.byref(ptr), stream),
                    "lgcn_train_step_cols_part1")
         partial = torch.as_tensor(_DevArray(ptr.value, 3 * B), device=dev)
         dist.all_reduce(partial, op=dist.ReduceOp.SUM, group=self.group)
-        loss = torch.empty(3, dtype=torch.float32, device=dev)
         _lib.check(lib.lgcn_train_step_cols_part2(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(neg), B, _lib.tp(loss), stream),
                    "lgcn_train_step_cols_part2")
-        m._cache = None
+        m.invalidate_cache()
         return loss
 
     def _step(self, users, pos, neg):
@@ -349,14 +340,10 @@ class DataParallelBPR:
             return self._step_cols(users, pos, neg)
         m = self.model
         dev = m._table.device
-        users, pos, neg = m._ids(users, dev), m._ids(pos, dev), m._ids(neg, dev)
+        users, pos, neg, st, loss = self._begin(users, pos, neg, self.world)
         B = int(users.numel())
-        st = m._state(max_batch=max(B, int(m.config.get('bpr_batch_size', B))), need_ctx=True,
-                      dp_world=self.world)
         lib = _lib.load()
-        lib.lgcn_ctx_set_lr(st['ctx'], float(self.opt.param_groups[0]['lr']))
         stream = _lib.current_stream()
-        loss = torch.empty(3, dtype=torch.float32, device=dev)
         if self.reduce == 'rows':
             _lib.check(lib.lgcn_train_step_dp_part1(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(neg), B,
                                                     self.world, self.rank, stream), "lgcn_train_step_dp_part1")
@@ -377,5 +364,5 @@ class DataParallelBPR:
         _lib.check(lib.lgcn_train_step_dp_part2(st['ctx'], _lib.tp(users), _lib.tp(pos), _lib.tp(neg), B,
                                                 self.world, gptr, _lib.tp(loss), stream),
                    "lgcn_train_step_dp_part2")
-        m._cache = None
+        m.invalidate_cache()
         return loss

@@ -16,6 +16,8 @@ import numpy as np
 import pytest
 import torch
 
+from storage_cases import storage_graph          # noqa: E402,F401  (fixture: the 300 x 600 graph, written once per session)
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 N_USERS, M_ITEMS = 1150, 350
@@ -246,5 +248,40 @@ def test_launch_arguments_follow_the_tables(pkg, graph_dir):
             _run(pkg, m, m._table.detach().clone(), _triplets(B, 5), B, bits, epoch)
             assert _get_policy(pkg, m) == (bits, want_adam, want_fwd), (act, dense_last, bits, epoch)
         assert L.load().lgcn_ctx_set_store_policy(m._dev['ctx'], 4) == 3 and _get_policy(pkg, m)[0] == 0
+    finally:
+        pkg.world.configure([])
+
+
+def test_failed_setter_leaves_no_context(pkg, storage_graph):
+    """config['store_policy'] = 8, an unknown bit: the library refuses the last setter of the context builder with rc 3.  The
+    error is _lib.check's, the half-made context is destroyed, and the same model then trains under a known policy.  PureMF's
+    builder has no setter that can fail: the same construction there, a plain step."""
+    import storage_cases as SC
+    d, K, B = 32, 2, 7
+    rng = np.random.Generator(np.random.PCG64(8))
+    ids = tuple(torch.from_numpy(rng.integers(1, hi, B)).to(torch.int32).to(DEV) for hi in (SC.N_USERS, SC.M_ITEMS - 2, SC.M_ITEMS - 2))
+    try:
+        w = SC.configure(pkg, ("fp32", d, K, 0, -1, "propagated"), storage_graph, B)
+        ds = pkg.dataloader.Loader(w.config, path=storage_graph)
+        pkg.utils.set_seed(SC.MODEL_SEED)
+        m = pkg.model.LightGCN(w.config, ds).to(DEV)
+        m.train()
+        m.config['store_policy'] = 8
+        with pytest.raises(pkg._lib.LgcnError, match=r"^lgcn_ctx_set_store_policy failed \(rc=3\)"):
+            m.fused_step(*ids)
+        assert m._dev is not None and m._dev['ctx'] is None and m.adam_step == 0
+        m.config['store_policy'] = 1
+        loss = m.fused_step(*ids)
+        torch.cuda.synchronize()
+        assert m._dev['ctx'] is not None and m.adam_step == 1 and bool(torch.isfinite(loss).all())
+        assert _get_policy(pkg, m)[0] == 1
+        m.check_device_errors()
+        m.config['store_policy'] = 8                       # (PureMF's contexts have no store policy: not looked at)
+        pkg.utils.set_seed(SC.MODEL_SEED)
+        mf = pkg.model.PureMF(w.config, ds).to(DEV)
+        loss = mf.fused_step(*ids)
+        torch.cuda.synchronize()
+        assert mf._dev['ctx'] is not None and mf.adam_step == 1 and bool(torch.isfinite(loss).all())
+        mf.check_device_errors()
     finally:
         pkg.world.configure([])

@@ -110,7 +110,14 @@ def _worker(rank, world, port, work):
     for mode in ("rows", "dense"):
         mv = fresh_v()
         dpv = pkg.parallel.DataParallelBPR(mv, w.config, reduce=mode)
+        with torch.no_grad():                # (training mode: what a caller that looks at the scores between epochs holds)
+            before = mv.rating_table().clone()
         got_loss = dpv.train_epoch(U, P, N, B).cpu().numpy()
+        # a data-parallel step drops every memo invalidate_cache() drops: the gated rating table is the trained one
+        with torch.no_grad():
+            after = mv.rating_table().clone()
+            mv.invalidate_cache()
+            ok = ok and torch.equal(after, mv.rating_table()) and not torch.equal(after, before)
         ok = ok and np.array_equal(got_loss, want_loss_v)
         for k, v in mv.state_dict().items():
             ok = ok and np.array_equal(v.detach().cpu().numpy().view(np.uint32), want_v[k].view(np.uint32))

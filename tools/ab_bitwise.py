@@ -3,8 +3,12 @@
 a refactor of the kernels must reproduce it exactly.
 
     python tools/ab_bitwise.py --lib-a PATH --lib-b PATH
+    LGCN_LIB_PATH=PATH python tools/ab_bitwise.py --tree-a DIR --tree-b DIR
 
-Driver (default): one fresh CHILD PROCESS per library (LGCN_LIB_PATH in the child's environment), each under its own time limit
+The second form holds the library and compares two checkouts of the Python layer that drives it: each side's child is
+DIR/tools/ab_bitwise.py --child, run in DIR.
+
+Driver (default): one fresh CHILD PROCESS per side (LGCN_LIB_PATH in the child's environment), each under its own time limit
 and in a session of its own; stops at the first child that fails.  Each child runs the same fixed list of tiny cases from fixed
 seeds on the graph of tests/storage_cases.py (300 users, 600 items), 3 steps per case, and writes loss_out of every step, the
 table, both Adam moments and the error flag of every case to an .npz.  The driver compares the two files byte for byte and
@@ -213,7 +217,8 @@ def child(out_path):
             elif c["kind"] == "inbatch_mix":
                 losses.append(m.fused_step(ids(u), ids(p), ids(n.T)))
             elif c["kind"] == "multi":                         # R = 1 under --loss bpr included: the batch-row launch, not the three-slot step
-                losses.append(m._fused_step_multi(ids(u), ids(p), ids(n.T), None, None))
+                du, dp, dn = ids(u), ids(p), ids(n.T)
+                losses.append(m._fused_call("lgcn_train_step_multi", (pkg._lib.tp(du), pkg._lib.tp(dp), pkg._lib.tp(dn), B, c["R"], B), B))
             else:
                 losses.append(m.fused_step(ids(u), ids(p), ids(n)))
         try:
@@ -235,32 +240,36 @@ def child(out_path):
     print(f"CHILD OK {len(cases())} cases, library {pkg.build.LIB_PATH}")
 
 
-def run_child(lib, out_path, timeout):
+def run_child(lib, out_path, timeout, tree=REPO):
     env = dict(os.environ, LGCN_LIB_PATH=os.path.abspath(lib))
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", out_path]
-    p = subprocess.Popen(cmd, cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, start_new_session=True)
+    tree = os.path.abspath(tree)
+    cmd = [sys.executable, os.path.join(tree, "tools", "ab_bitwise.py"), "--child", out_path]
+    p = subprocess.Popen(cmd, cwd=tree, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, start_new_session=True)
     try:
         out, _ = p.communicate(timeout=timeout)
     except subprocess.TimeoutExpired:
         os.killpg(p.pid, signal.SIGKILL)
         out, _ = p.communicate()
         sys.stderr.write(out[-4000:])
-        raise SystemExit(f"child timed out after {timeout} s, process group killed: {lib}")
+        raise SystemExit(f"child timed out after {timeout} s, process group killed: {lib} in {tree}")
     if p.returncode != 0 or "CHILD OK" not in out:
         sys.stderr.write(out[-4000:])
-        raise SystemExit(f"child failed (rc {p.returncode}): {lib}")
+        raise SystemExit(f"child failed (rc {p.returncode}): {lib} in {tree}")
     print(out.strip().splitlines()[-1], flush=True)
 
 
 def driver(a):
-    for lib in (a.lib_a, a.lib_b):
+    trees = (a.tree_a or REPO, a.tree_b or REPO)
+    for lib, tree in zip((a.lib_a, a.lib_b), trees):
         if not os.path.exists(lib):
             raise SystemExit(f"no such library: {lib}")
+        if not os.path.exists(os.path.join(tree, "tools", "ab_bitwise.py")):
+            raise SystemExit(f"no tools/ab_bitwise.py in the tree: {tree}")
     check_coverage(cases())
     with tempfile.TemporaryDirectory(prefix="lgcn_ab_") as tmp:
         files = [os.path.join(tmp, f"{tag}.npz") for tag in "ab"]
-        for lib, f in zip((a.lib_a, a.lib_b), files):
-            run_child(lib, f, a.child_timeout)
+        for lib, tree, f in zip((a.lib_a, a.lib_b), trees, files):
+            run_child(lib, f, a.child_timeout, tree)
         za, zb = np.load(files[0]), np.load(files[1])
         assert za.files == zb.files
         differing = []
@@ -285,12 +294,16 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib-a")
     ap.add_argument("--lib-b")
+    ap.add_argument("--tree-a", metavar="DIR", help="a checkout whose Python layer and tools/ab_bitwise.py --child run side a (default: this one)")
+    ap.add_argument("--tree-b", metavar="DIR")
     ap.add_argument("--child", default="", metavar="NPZ", help="child: run the cases on the library LGCN_LIB_PATH names and write this file")
     ap.add_argument("--child-timeout", type=int, default=480, help="seconds each child may take")
     a = ap.parse_args()
     if a.child:
         child(a.child)
     else:
+        if a.tree_a and a.tree_b and not (a.lib_a or a.lib_b):      # two trees on ONE library: the one LGCN_LIB_PATH names
+            a.lib_a = a.lib_b = os.environ.get("LGCN_LIB_PATH")
         if not (a.lib_a and a.lib_b):
-            ap.error("--lib-a and --lib-b are required")
+            ap.error("--lib-a and --lib-b are required (with --tree-a and --tree-b: both, or LGCN_LIB_PATH for both sides)")
         sys.exit(driver(a))
