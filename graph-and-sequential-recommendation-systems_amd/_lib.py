@@ -122,6 +122,10 @@ SIGNATURES = {
     "lgcn_ctx_get_inbatch_mix": (C.c_int32, [_vp]),
     "lgcn_train_step_inbatch_mix": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp, _vp]),
     "lgcn_train_epoch_inbatch_mix": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int64, C.c_int32, _vp, _vp]),
+    # hard negatives for the multi-negative step, DNS(M, N) (--hard_neg)
+    "lgcn_ctx_set_hard_neg": (C.c_int, [_vp, C.c_int32, C.c_uint64, _vp]),
+    "lgcn_ctx_get_hard_neg": (C.c_int32, [_vp]),
+    "lgcn_hard_neg_rank": (C.c_uint32, [C.c_uint64, C.c_int64, C.c_int32, C.c_int32]),
     "lgcn_dp_block_floats": (C.c_int64, [_vp, C.c_int32, C.c_int32]),
     "lgcn_train_step_dp_part1": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
     "lgcn_train_step_dp_dense_part1": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),

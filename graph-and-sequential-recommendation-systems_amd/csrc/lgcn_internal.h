@@ -10,7 +10,8 @@
 
 extern "C" void lgcn_set_error(const char *msg);   // lgcn_host.cpp
 // 0 under LGCN_LOSS_BPR; else rc 3 and the message "<who>: the ... loss ... is implemented for ... only" (lgcn_train.cpp): ONE wording
-// for every entry point that does not train the loss set on the context
+// for every entry point that does not train the loss set on the context.  The same callers cannot train hard negatives
+// (lgcn_ctx_set_hard_neg) either: while those are set it returns 3 and names them, whatever the loss
 int lgcn_refuse_loss(const lgcn_ctx *x, const char *who);
 
 #define HIP_OK(expr)                                                            \
@@ -72,8 +73,9 @@ static inline int check_dtype(int t) {
     if (t != LGCN_F32 && t != LGCN_BF16 && t != LGCN_FP8) { lgcn_set_error("dtype must be LGCN_F32, LGCN_BF16 or LGCN_FP8"); return 3; }
     return 0;
 }
-// edge dropout: the step's keys (the hash itself: lgcn_device.hip)
-static inline uint64_t splitmix64(uint64_t z) {
+// edge dropout: the step's keys (the hash itself: lgcn_device.hip); hard negatives: the step's picks (lgcn_hn_rank below, which
+// the kernel calls too)
+static __host__ __device__ inline uint64_t splitmix64(uint64_t z) {
     z += 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
@@ -137,6 +139,30 @@ struct MultiNegArgs {
     int32_t loss; float tau, inv_tauB;
 };
 int lgcn_multineg_launch(const MultiNegArgs &a, int d, int act_dtype, bool wts, hipStream_t st);
+
+// Hard negatives, DNS(M, N) (lgcn_hardneg.hip; lgcn_ctx_set_hard_neg).  H: which of the M hardest candidates sample b
+// of a step trains on, 0..M-1.  Keyed as the dropout mask of the step is -- splitmix64(splitmix64(seed) + step), `step` the Adam
+// step counter as it stands BEFORE the step (0 for the first step of a fresh context), make_drop's convention -- then moved into
+// a stream of its own by a domain constant and mixed with the sample index: at equal seeds the dropout mask and the picks share
+// no state.  The high word goes into the modulus (M <= 16: the bias of 2^32 mod M is below 4e-9).  ONE definition: the kernel
+// calls it, lgcn_hard_neg_rank exports it, tests/hard_neg_restatement.py restates it.
+#define LGCN_HN_DOMAIN 0x4841524E45473031ull      /* "HARNEG01" */
+static __host__ __device__ inline uint32_t lgcn_hn_rank(uint64_t seed, int64_t step, int32_t b, int32_t M) {
+    const uint64_t k = splitmix64(splitmix64(seed) + (uint64_t)step);
+    const uint64_t v = splitmix64((k ^ LGCN_HN_DOMAIN) + (uint64_t)(uint32_t)b);
+    return M > 1 ? (uint32_t)(v >> 32) % (uint32_t)M : 0u;
+}
+// `m` carries what the batch-row launch of the multi-negative step carries (inv_BR, inv_R, lam_n, loss, tau are unused: every one of
+// the three slots weighs 1 and the divisor is B)
+struct HardNegArgs {
+    MultiNegArgs m;
+    float inv_B;                  // 1 / B
+    int32_t top_m;                // M, 1..R
+    uint64_t seed; int64_t step;  // the arguments of lgcn_hn_rank (step: the counter before the step)
+    int32_t *sel_id;              // [B] the selected ITEM id of each sample (-1: void) -- the negative column of the backward's three-slot kernels
+    int32_t *sel_out;             // [B] the selected index r (-1: void), or NULL
+};
+int lgcn_hardneg_launch(const HardNegArgs &h, int d, int act_dtype, bool wts, hipStream_t st);
 
 // The in-batch sampled softmax (lgcn_inbatch.hip; lgcn_train_step_inbatch fills this in).  Sample b = (users[b],
 // pos[b]); every user of the batch scores against every positive of the batch.  `m` carries what the batch-row launch of the

@@ -73,6 +73,10 @@ struct lgcn_ctx {
     // the store policy (lgcn_ctx_set_store_policy): LGCN_STORE_* bits, and the SpmmArgs::wt the last +Adam launch and
     // the last forward launch of the deepest layer carried (the getter reports them)
     int32_t store_policy, wt_adam, wt_fwd;
+    // hard negatives (lgcn_ctx_set_hard_neg): hn_m = M (0: off).  While it is on, the multi-negative step launches
+    // k_hardneg, which writes the selected item of each sample to hn_sel (library-owned [max_batch], allocated by the first setter
+    // that turns it on) -- the negative column of the backward's three-slot kernels -- and its index to hn_out (the caller's, or NULL)
+    int32_t hn_m; uint64_t hn_seed; int32_t *hn_sel, *hn_out;
 };
 // The policy of a new context: LGCN_STORE_POLICY (0..3) or the default below; -1: the variable is set and is neither.
 // Default: what the alternating runs of profiles/store_policy/README.md adopted.
@@ -141,6 +145,7 @@ extern "C" int lgcn_ctx_create(const lgcn_train_config *cfg, lgcn_ctx **out) {
     x->mn = {};
     x->loss_kind = LGCN_LOSS_BPR; x->loss_temp = 1.f; x->ib_ws = nullptr; x->ib_cap = 0;
     x->ib_score = LGCN_SCORE_DOT; x->ib_logq = nullptr; x->ib_mix = 0;
+    x->hn_m = 0; x->hn_seed = 0; x->hn_sel = nullptr; x->hn_out = nullptr;
     x->bm_words = (x->N + 31) / 32; x->flip = 0;
     const size_t stride = table_bytes(x->N, c.d, c.act_dtype);
     for (int k = 0; k <= LGCN_MAX_LAYERS; k++) x->act[k] = nullptr;
@@ -214,6 +219,7 @@ extern "C" void lgcn_ctx_destroy(lgcn_ctx *ctx) {
     if (ctx->arrive) (void)hipFree(ctx->arrive);
     if (ctx->mult) (void)hipFree(ctx->mult);
     if (ctx->ib_ws) (void)hipFree(ctx->ib_ws);
+    if (ctx->hn_sel) (void)hipFree(ctx->hn_sel);
     if (ctx->tvar) (void)hipFree(ctx->tvar);
     if (ctx->item_bitmap) (void)hipFree(ctx->item_bitmap);
     if (ctx->gate_partials) (void)hipFree(ctx->gate_partials);
@@ -338,6 +344,7 @@ extern "C" int lgcn_ctx_set_loss(lgcn_ctx *ctx, int32_t kind, float temperature)
     if (!ctx) { lgcn_set_error("lgcn_ctx_set_loss: null context"); return 3; }
     if (kind == LGCN_LOSS_BPR) { ctx->loss_kind = LGCN_LOSS_BPR; ctx->loss_temp = 1.f; return 0; }      // the step launches what it always launched
     if (kind != LGCN_LOSS_SOFTMAX && kind != LGCN_LOSS_INBATCH) { lgcn_set_error("lgcn_ctx_set_loss: unknown loss kind (LGCN_LOSS_BPR, LGCN_LOSS_SOFTMAX or LGCN_LOSS_INBATCH)"); return 3; }
+    if (ctx->hn_m) { lgcn_set_error("lgcn_ctx_set_loss: hard negatives (lgcn_ctx_set_hard_neg) are set on this context and train the BPR loss only"); return 3; }
     const bool inbatch = kind == LGCN_LOSS_INBATCH;
     if (int rc = refuse_loss_config(ctx, temperature, inbatch ? "the in-batch softmax loss (inbatch)" : "the sampled-softmax loss", inbatch ? "2 B" : "2 + R")) return rc;
     if (inbatch && !ctx->ib_ws) {       // the workspace is allocated once, before anything is changed
@@ -397,13 +404,40 @@ extern "C" int32_t lgcn_ctx_get_loss(const lgcn_ctx *ctx, float *temperature_out
     if (temperature_out) *temperature_out = ctx->loss_temp;
     return ctx->loss_kind;
 }
+// Hard negatives, DNS(M, N).  Everything is checked before anything changes; top_m = 0 leaves the allocation in
+// place and restores exactly the launches of a context that was never told.
+extern "C" int lgcn_ctx_set_hard_neg(lgcn_ctx *ctx, int32_t top_m, uint64_t seed, int32_t *sel_out) {
+    if (!ctx) { lgcn_set_error("lgcn_ctx_set_hard_neg: null context"); return 3; }
+    if (top_m == 0) { ctx->hn_m = 0; ctx->hn_seed = 0; ctx->hn_out = nullptr; return 0; }
+    char buf[256];
+    const char *fmt = nullptr;
+    if (top_m < 0 || top_m > LGCN_MAX_NEG_RATIO) fmt = "lgcn_ctx_set_hard_neg: hard negatives: top_m = %d is out of range (0 = off, or 1..%d)";
+    else if (ctx->loss_kind != LGCN_LOSS_BPR) fmt = "lgcn_ctx_set_hard_neg: hard negatives train the BPR loss only, and another loss is set on this context (lgcn_ctx_set_loss)";
+    else if (ctx->c.act_dtype == LGCN_FP8) fmt = "lgcn_ctx_set_hard_neg: hard negatives are not implemented for LGCN_FP8 activation storage";
+    else if (ctx->variant) fmt = "lgcn_ctx_set_hard_neg: hard negatives are not implemented with the optional branches (item-item smoothing / popularity gate)";
+    else if (!ctx->c.dense_last) fmt = "lgcn_ctx_set_hard_neg: hard negatives need a context with dense_last = 1 (the gathered last layer has no 2 + R slot form)";
+    if (fmt) { snprintf(buf, sizeof buf, fmt, (int)top_m, LGCN_MAX_NEG_RATIO); lgcn_set_error(buf); return 3; }
+    if (!ctx->hn_sel && hipMalloc((void **)&ctx->hn_sel, sizeof(int32_t) * (size_t)ctx->c.max_batch) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->hn_sel = nullptr;
+        lgcn_set_error("lgcn_ctx_set_hard_neg: cannot allocate the selected ids of hard negatives (max_batch * 4 bytes)");
+        return 4;
+    }
+    ctx->hn_m = top_m; ctx->hn_seed = seed; ctx->hn_out = sel_out;
+    return 0;
+}
+extern "C" int32_t lgcn_ctx_get_hard_neg(const lgcn_ctx *ctx) { return ctx ? ctx->hn_m : -1; }
+extern "C" uint32_t lgcn_hard_neg_rank(uint64_t seed, int64_t step, int32_t b, int32_t M) { return lgcn_hn_rank(seed, step, b, M); }
 // today's three-slot kernels, and every form that splits a step over ranks, compute BPR: say so instead of training another
 // loss.  The in-batch loss trains through its own two entry points only, so lgcn_train_step_multi / _epoch_multi refuse it too.
 // (Declared in lgcn_internal.h: lgcn_train_step_i64 in lgcn_ids.hip refuses in the same words.)
+// Hard negatives (lgcn_ctx_set_hard_neg) train through lgcn_train_step_multi / _epoch_multi only: the same callers refuse them here.
 int lgcn_refuse_loss(const lgcn_ctx *x, const char *who) {
-    if (!x || x->loss_kind == LGCN_LOSS_BPR) return 0;
+    if (!x || (x->loss_kind == LGCN_LOSS_BPR && !x->hn_m)) return 0;
     char buf[256];
-    if (x->loss_kind == LGCN_LOSS_INBATCH)
+    if (x->hn_m)
+        snprintf(buf, sizeof buf, "%s: hard negatives (lgcn_ctx_set_hard_neg) are implemented for lgcn_train_step_multi / lgcn_train_epoch_multi only", who);
+    else if (x->loss_kind == LGCN_LOSS_INBATCH)
         snprintf(buf, sizeof buf, "%s: the in-batch softmax loss (inbatch; lgcn_ctx_set_loss) is implemented for lgcn_train_step_inbatch / lgcn_train_epoch_inbatch only", who);
     else
         snprintf(buf, sizeof buf, "%s: the sampled-softmax loss (lgcn_ctx_set_loss) is implemented for lgcn_train_step_multi / lgcn_train_epoch_multi only", who);
@@ -756,6 +790,18 @@ static int run_step(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const
     if ((rc = run_forward(x, st))) return rc;
     if (!x->mn.on) rc = x->variant ? run_variant_loss(x, users, pos, neg, B, 0, B, B, true, false, st) : run_bpr(x, users, pos, neg, B, 0, B, B, true, false, st);
     else if (x->loss_kind == LGCN_LOSS_INBATCH) rc = run_inbatch(x, users, pos, B, st);
+    else if (x->hn_m) {
+        // hard negatives: the launch picks one candidate per sample and from there on the step IS the three-slot step on (users,
+        // pos, hn_sel) -- its slot kernels, cnt slots of weight 1, decay / B -- so the slot form ends here.  k_g32 is launched,
+        // never folded: which rows the batch touches is not known ahead
+        HardNegArgs h{};
+        h.m = multineg_args(x, users, pos, B);
+        h.inv_B = 1.0f / (float)B; h.top_m = x->hn_m; h.seed = x->hn_seed; h.step = x->step;      // the counter before the step, as the drop mask's
+        h.sel_id = x->hn_sel; h.sel_out = x->hn_out;
+        rc = lgcn_hardneg_launch(h, c.d, c.act_dtype, x->lw_n != 0, st);
+        x->mn = {};
+        neg = x->hn_sel;
+    }
     else rc = lgcn_multineg_launch(multineg_args(x, users, pos, B), c.d, c.act_dtype, x->lw_n != 0, st);
     if (rc) return rc;
     if ((rc = run_backward(x, users, pos, neg, B, nullptr, B, 1, loss_out, st))) return rc;
@@ -844,7 +890,10 @@ static int check_slot_step(const lgcn_ctx *x, SlotKind kind, const void *u, cons
         if (!x->c.dense_last) return refuse("%s: a negative ratio above the three-slot step's needs a context with dense_last = 1 (the gathered last layer has no 2 + R slot form)");
         if (x->c.act_dtype == LGCN_FP8) return refuse("%s: the negative ratio (several negatives per positive) is not implemented for LGCN_FP8 activation storage");
         if (x->variant) return refuse("%s: the negative ratio (several negatives per positive) is not implemented with the optional branches (item-item smoothing / popularity gate)");
+        if (x->hn_m && (R < 2 || x->hn_m > R))
+            return refuse("%s: hard negatives pick among the M = %d hardest of R >= 2 candidates with M <= R: the negative ratio R = %d does not fit (lgcn_ctx_set_hard_neg)", x->hn_m, R);
     } else {
+        if (x->hn_m) return lgcn_refuse_loss(x, who);
         if (x->loss_kind != LGCN_LOSS_INBATCH || !x->ib_ws) return refuse("%s: the in-batch softmax loss (inbatch) is not set on this context (lgcn_ctx_set_loss with LGCN_LOSS_INBATCH)");
         if (kind == SLOT_MIX && x->ib_mix < 1) return refuse("%s: mixed negatives are not set on this context (lgcn_ctx_set_inbatch_mix)");
         if (kind == SLOT_MIX && (R < 1 || R > x->ib_mix)) return refuse("%s: the negative ratio R = %d is out of range (1..%d, the R_max of lgcn_ctx_set_inbatch_mix)", R, x->ib_mix);

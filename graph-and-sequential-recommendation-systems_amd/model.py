@@ -136,6 +136,41 @@ def resolve_inbatch_mix(config, loss_kind):
     return mix
 
 
+_U64 = np.uint64
+
+
+def _splitmix64(z):
+    """splitmix64 of csrc/lgcn_internal.h on NumPy uint64 (arithmetic mod 2^64)."""
+    with np.errstate(over='ignore'):
+        z = (z + _U64(0x9E3779B97F4A7C15)).astype(np.uint64)
+        z = ((z ^ (z >> _U64(30))) * _U64(0xBF58476D1CE4E5B9)).astype(np.uint64)
+        z = ((z ^ (z >> _U64(27))) * _U64(0x94D049BB133111EB)).astype(np.uint64)
+        return z ^ (z >> _U64(31))
+
+
+def hard_neg_rank(seed, step, b, M):
+    """The pick j_b of --hard_neg M: lgcn_hn_rank of csrc/lgcn_internal.h restated on NumPy uint64, vectorised over the
+    sample indices b -> int64 array in 0..M-1.  step: the Adam step counter BEFORE the step, the convention of the dropout mask."""
+    b = np.asarray(b, np.int64)
+    with np.errstate(over='ignore'):
+        k = _splitmix64((_splitmix64(np.asarray(int(seed) & (2 ** 64 - 1), np.uint64)) + _U64(int(step) & (2 ** 64 - 1))).astype(np.uint64))
+        v = _splitmix64(((k ^ _U64(0x4841524E45473031)) + (b & 0xFFFFFFFF).astype(np.uint64)).astype(np.uint64))
+    if int(M) <= 1:
+        return np.zeros(b.shape, np.int64)
+    return ((v >> _U64(32)) % _U64(int(M))).astype(np.int64)
+
+
+def resolve_hard_neg(config):
+    """--hard_neg M -> int in 0..16 (0: off).  ValueError for anything else; what it combines with is LightGCN._refuse_combinations'."""
+    try:
+        M = int(config.get('hard_neg', 0))
+    except (TypeError, ValueError):
+        M = -1
+    if not 0 <= M <= _lib.MAX_NEG_RATIO:
+        raise ValueError(f"--hard_neg must be in 0..{_lib.MAX_NEG_RATIO} (0 = off), got {config.get('hard_neg')!r}")
+    return M
+
+
 def item_logq_mix(items_D, B, R):
     """The logQ vector of --inbatch_logq 1 under --inbatch_mix 1: the log of the expected number of times item i stands among a
     sample's competitors -- (B - 1) in-batch positives drawn in proportion to the train degree and B R pool ids drawn uniformly --
@@ -553,6 +588,11 @@ class LightGCN(_TableModel):
         # against all R negatives of its sample in one log-sum-exp; every negative shape then goes to the _multi entry points.
         # inbatch = every user of the batch against every positive of the batch; the sampled negatives are not used
         self.loss_kind, self.softmax_temp = resolve_loss(config)
+        # hard negatives (--hard_neg M; lgcn_ctx_set_hard_neg): the multi-negative step trains the BPR triplet on one of the
+        # M hardest of its R candidates.  hard_neg_step: the step counter bpr_loss keys its picks with (None: adam_step, the fused
+        # step's own convention -- the counter before the step)
+        self.hard_neg = resolve_hard_neg(config)
+        self.hard_neg_step = None
         # mixed negatives (--inbatch_mix 1; lgcn_train_step_inbatch_mix): the sampled negatives of the batch as shared
         # extra columns of the in-batch score matrix; --neg_ratio 1..16 is then legal.  Resolved among the refusals, where its own lie
         self.inbatch_mix = self._refuse_combinations()
@@ -572,11 +612,28 @@ class LightGCN(_TableModel):
         self.f = nn.Sigmoid()
 
     def _refuse_combinations(self):
-        """The pairs of options no launch exists for, first match first: storage, optional branches, dropout, layer weights,
+        """The pairs of options no launch exists for, first match first: --hard_neg, storage, optional branches, dropout, layer weights,
         --neg_ratio, --loss, --inbatch_mix -> the resolved --inbatch_mix, whose own refusals (resolve_inbatch_mix) stand between
         those of the loss and the last one.  (A value that is invalid on its own was refused where it was read, before all these.)"""
         config = self.config
         fp8 = self._act() == 'fp8'
+        if self.hard_neg:       # first: every one of these names --hard_neg (with it off nothing here is reached)
+            M, R = self.hard_neg, self.neg_ratio
+            if R < 2:
+                raise _lib.LgcnError(f"--hard_neg {M} needs --neg_ratio >= 2 (the candidates it picks among), got --neg_ratio {R}")
+            if M > R:
+                raise _lib.LgcnError(f"--hard_neg {M} exceeds --neg_ratio {R}: the pick is among the M hardest of R candidates, M <= R")
+            if self.loss_kind != 'bpr':
+                raise _lib.LgcnError(f"--hard_neg {M} is implemented for --loss bpr only, not for --loss {self.loss_kind} "
+                                     "(the selected triplet trains the BPR loss)")
+            if fp8:
+                raise _lib.LgcnError(f"--hard_neg {M} is not implemented together with --act_dtype fp8 (fp32 and bf16 storage only)")
+            if self.use_pop_gate:
+                raise _lib.LgcnError(f"--hard_neg {M} is not implemented together with --use_pop_gate (the popularity gate trains on one "
+                                     "sampled negative per positive)")
+            if self.use_item_item:
+                raise _lib.LgcnError(f"--hard_neg {M} is not implemented together with --use_item_item (the item-item smoothing trains on "
+                                     "one sampled negative per positive)")
         if self.dropout and fp8:
             raise _lib.LgcnError("--dropout 1 is not implemented together with --act_dtype fp8 (fp32 and bf16 storage only)")
         if self.dropout and self.has_variants:
@@ -742,6 +799,9 @@ class LightGCN(_TableModel):
         gate_p = sum(prm.numel() for prm in self.gate_parameters()) if (variants and self.use_pop_gate) else 0
         # exchange block of a rank (lgcn_dp_block_floats): gradient rows, loss / reg (/ entropy) terms, the gate's fixed-point MLP sums
         st['contrib'] = torch.zeros(3 * shard * d + 3 * shard + 2 + 2 * gate_p, dtype=torch.float32, device=dev)
+        # config['hard_neg_record'] = 1 (tests): the steps store the selected index of every sample here (last_selection)
+        st['hard_neg_sel'] = (torch.full((max_batch,), -1, dtype=torch.int32, device=dev)
+                              if self.hard_neg and int(self.config.get('hard_neg_record', 0)) else None)
         if self.inbatch_logq and (st.get('item_logq') is None or st['item_logq'].device != dev):
             st['item_logq'] = self._item_logq.to(device=dev, dtype=torch.float32).contiguous()      # uploaded once
         if variants and self.i2i_active:
@@ -799,6 +859,9 @@ class LightGCN(_TableModel):
                                                         _lib.tp(st['item_logq']) if self.inbatch_logq else None)))
         if self.inbatch_mix:
             out.append(('lgcn_ctx_set_inbatch_mix', (int(self.neg_ratio),)))
+        if self.hard_neg:
+            out.append(('lgcn_ctx_set_hard_neg', (int(self.hard_neg), int(self.config.get('seed', 2020)) & (2 ** 64 - 1),
+                                                  _lib.tp(st['hard_neg_sel']) if st.get('hard_neg_sel') is not None else None)))
         if str(self.config.get('fold_g32', 1)).strip().lower() in ('0', 'false', 'off'):      # config['fold_g32'] = 0: fused_epoch launches k_g32 every step again (A/B, tests)
             out.append(('lgcn_ctx_set_fold_g32', (0,)))
         if self.config.get('store_policy') is not None:      # config['store_policy'] = LGCN_STORE_* bits (A/B, tests); unset: LGCN_STORE_POLICY or the library's default
@@ -1027,12 +1090,44 @@ class LightGCN(_TableModel):
             u, p, n = self.embedding_user.weight[ul], self.embedding_item.weight[pl], self.embedding_item.weight[nl]
         return sm, (0.5 * (u.norm(2).pow(2) + p.norm(2).pow(2) + n.norm(2).pow(2) / float(R))) / float(B)
 
+    def hard_neg_select(self, users, neg):
+        """--hard_neg M on neg [B, R]: the index r of the candidate each sample trains on -> int64 [B], without gradient.  The
+        fused step's selection restated: s_r = e_u.e_{n_r} on the output table, ranked descending with ties by r ascending (a stable
+        sort), rank j_b = hard_neg_rank(--seed, step, b, M) picked; step = hard_neg_step, or the Adam step counter as it stands.
+        That counter belongs to the fused context: it is 0 while none exists and only fused steps advance it.  A caller that
+        trains through autograd with an optimiser of its own must therefore set hard_neg_step to its step count before every
+        call (0 before the first) -- otherwise, with M > 1, sample index b draws the same rank j_b in every step."""
+        B, R = int(neg.shape[0]), int(neg.shape[1])
+        if B != int(users.shape[0]) or R < 2 or self.hard_neg > R:
+            raise ValueError(f"--hard_neg {self.hard_neg}: neg must be [B, R] or [R, B] with B = {int(users.shape[0])}, R >= 2 and "
+                             f"R >= {self.hard_neg}, got {tuple(neg.shape)}")
+        step = self.adam_step if self.hard_neg_step is None else int(self.hard_neg_step)
+        j = hard_neg_rank(int(self.config.get('seed', 2020)), step, np.arange(B), self.hard_neg)
+        with torch.no_grad():
+            all_users, all_items = self.computer()
+            s = torch.sum(all_users[users.long()][:, None, :] * all_items[neg.long()], dim=2)
+            order = torch.sort(s, dim=1, descending=True, stable=True).indices
+            return order.gather(1, torch.from_numpy(j).to(order.device)[:, None]).reshape(-1)
+
+    def last_selection(self):
+        """The selected index r of every sample of the last fused step under --hard_neg (-1: a voided sample) -> int32 device
+        tensor [max_batch]; its first B entries are the step's.  Needs config['hard_neg_record'] = 1 when the context is made."""
+        sel = (self._dev or {}).get('hard_neg_sel')
+        if sel is None:
+            raise _lib.LgcnError("last_selection: no selection is recorded (--hard_neg with config['hard_neg_record'] = 1, after a fused step)")
+        return sel
+
     def bpr_loss(self, users, pos, neg):
-        """model.py:162-183 (unfused, autograd-capable): (bpr [- entropy term of the gate], reg_loss)."""
+        """model.py:162-183 (unfused, autograd-capable): (bpr [- entropy term of the gate], reg_loss).  Under --hard_neg with 2-D
+        negatives the picks are keyed with hard_neg_step, which the caller advances (hard_neg_select says why)."""
         if self.loss_kind == 'inbatch' and self.inbatch_mix:      # the sampled negatives are the batch's shared pool
             return self._inbatch_mix_loss(users, pos, neg)
         if self.loss_kind == 'inbatch':          # the sampled negatives are not used
             return self._inbatch_loss(users, pos)
+        if torch.is_tensor(neg) and neg.dim() == 2 and self.hard_neg:      # the BPR loss of the selected triplets (DESIGN 4.25)
+            neg = neg if neg.shape[0] == int(users.shape[0]) else neg.t()
+            sel = self.hard_neg_select(users, neg)
+            return self.bpr_loss(users, pos, neg.gather(1, sel[:, None]).reshape(-1))
         if torch.is_tensor(neg) and neg.dim() == 2:
             return self._bpr_loss_multi(users, pos, neg)
         if self.loss_kind == 'softmax':          # 1-D negatives: R = 1
@@ -1165,6 +1260,8 @@ class PureMF(_TableModel):
             raise _lib.LgcnError(f"--use_ppr_weights {no} (there are no layers to combine)")
         if self._act() != 'fp32':
             raise _lib.LgcnError(f"--act_dtype {config.get('act_dtype')} {no} (fp32 tables only)")
+        if int(config.get('hard_neg', 0)) != 0:      # (before --neg_ratio, which it implies)
+            raise _lib.LgcnError(f"--hard_neg {config.get('hard_neg')} {no} (hard negatives are picked among LightGCN's --neg_ratio candidates)")
         if int(config.get('neg_ratio', 1)) != 1:
             raise _lib.LgcnError(f"--neg_ratio {config.get('neg_ratio')} {no} (the matrix-factorisation step trains on triplets, "
                                  "one negative per positive)")

@@ -144,6 +144,9 @@ class DataParallelBPR:
         if getattr(recmodel, 'inbatch_mix', False) or str(config.get('inbatch_mix', 0)).strip().lower() in ('1', 'true'):
             raise RuntimeError("--inbatch_mix 1 is implemented for single-GPU training only: DataParallelBPR (every reduce / shard "
                                "mode) computes the BPR loss")
+        if int(getattr(recmodel, 'hard_neg', 0)) > 0 or int(config.get('hard_neg', 0)) > 0:      # (before --neg_ratio, which it implies)
+            raise RuntimeError("--hard_neg is implemented for single-GPU training only: DataParallelBPR (every reduce / shard mode) "
+                               "trains on triplets, one sampled negative per positive and no selection among candidates")
         if int(getattr(recmodel, 'neg_ratio', 1)) > 1 or int(config.get('neg_ratio', 1)) > 1:
             raise RuntimeError("--neg_ratio > 1 is implemented for single-GPU training only: DataParallelBPR (every reduce / shard "
                                "mode) trains on triplets, one negative per positive")

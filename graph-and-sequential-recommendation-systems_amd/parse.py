@@ -140,6 +140,12 @@ def build_parser():
                         '(--neg_ratio 1..16 is then legal); with --inbatch_logq 1 the correction is the log of the mixture, '
                         'log((B - 1) deg / sum deg + B R / m_items) with B = --bpr_batch. 0 (default) = in-batch negatives only. '
                         '--loss inbatch only')
+    p.add_argument('--hard_neg', type=int, default=0,
+                   help='NEW: M > 0 = dynamic negative sampling, DNS(M, N): the fused step scores the --neg_ratio R candidates of a sample '
+                        'with the current model and trains the plain BPR triplet (u, p, n) on ONE of them -- a uniform pick among the M '
+                        'hardest, keyed by --seed, the step counter and the sample (M = 1: the hardest; M = R: a uniform candidate). '
+                        'Three gradient rows per sample instead of 2 + R. Needs --neg_ratio >= 2, M <= R and --loss bpr. 0 (default) = off. '
+                        'fp32 / bf16 storage, single GPU, default model, dense last layer')
     p.add_argument('--data_path', type=str, default=None,
                    help='NEW: directory that holds <dataset>/train.txt (default: <root>/data)')
     return p

@@ -119,6 +119,7 @@ def configure(argv=None):
     config['score'] = args.score
     config['inbatch_logq'] = args.inbatch_logq
     config['inbatch_mix'] = args.inbatch_mix
+    config['hard_neg'] = args.hard_neg
     device =torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     return config
 

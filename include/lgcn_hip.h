@@ -434,6 +434,29 @@ int lgcn_train_step_inbatch_mix(lgcn_ctx *ctx, const int32_t *users, const int32
 int lgcn_train_epoch_inbatch_mix(lgcn_ctx *ctx, const int32_t *users, const int32_t *pos, const int32_t *negs, int32_t R,
                                  int64_t T, int32_t B, float *loss_out, void *stream);
 
+/* Hard negatives for the multi-negative step: dynamic negative sampling, DNS(M, N) (--hard_neg M).  A sample is
+ * (u_b, p_b, n_{b,1..R}) in the layouts of lgcn_train_step_multi / lgcn_train_epoch_multi, R >= 2.  The step scores the R
+ * candidates with the current model, s_r = e_u.e_{n_r}, ranks them by s descending (ties: r ascending), picks rank
+ *   j_b = lgcn_hard_neg_rank(seed, step, b, M)        (step: the Adam step counter BEFORE the step, as the dropout mask's)
+ * and is then exactly lgcn_train_step's BPR step on the B triplets (u_b, p_b, n_sel(b)):
+ *   bpr = -1/B sum_b logsigmoid(e_u.e_p - e_u.e_sel),   reg = 0.5/B sum_b (|e_u|^2 + |e_p|^2 + |e_sel|^2)   (reg_ego: own rows)
+ * Gradient rows, row flags and reg_ego slot counts go to u, p and n_sel only, each of weight 1; the divisor is B.  The R - 1
+ * unselected candidates receive nothing.  M = 1 trains the hardest candidate, M = R a uniform one.  Forward, backward chain,
+ * Adam epilogue, edge dropout, layer weights and reg_ego are the multi-negative step's; the gradient-row conversion is never
+ * folded (the touched rows are not known ahead).  A sample with an out-of-range id is void as before.
+ * lgcn_ctx_set_hard_neg(ctx, top_m, seed, sel_out): top_m = 0 (the default) restores exactly the launches of a context that
+ * was never told.  sel_out: caller-owned DEVICE memory [max_batch], alive while it is set, or NULL; every step stores the
+ * selected index r of sample b to sel_out[b] (-1: void sample).  rc 3 with a message naming hard negatives and nothing changed:
+ * top_m outside 0..LGCN_MAX_NEG_RATIO, a loss other than LGCN_LOSS_BPR in force, LGCN_FP8 storage, an optional branch,
+ * dense_last = 0; rc 4 if the [max_batch] ids cannot be allocated.  While it is set: lgcn_ctx_set_loss to another loss returns
+ * 3; lgcn_train_step_multi / lgcn_train_epoch_multi return 3, naming R and M, for R < 2 or M > R (outputs, step counter and
+ * workspace untouched); every three-slot, in-batch and rank-splitting entry point returns 3 and says so.                      */
+int lgcn_ctx_set_hard_neg(lgcn_ctx *ctx, int32_t top_m, uint64_t seed, int32_t *sel_out);
+/* M in force (0: off; -1: null context).                                                                                      */
+int32_t lgcn_ctx_get_hard_neg(const lgcn_ctx *ctx);
+/* The pick j_b in 0..M-1 on the host (no GPU): the function the kernel calls.  M <= 1 gives 0.                                */
+uint32_t lgcn_hard_neg_rank(uint64_t seed, int64_t step, int32_t b, int32_t M);
+
 /* The fold of the gradient-row conversion into the batch-row launch.  lgcn_train_epoch holds all triplets of
  * the call before its first step, so it computes once (per segment of 1024 steps) how many slots of each batch name each
  * destination row; the batch-row kernel then writes the fp32 copy of a gradient row itself -- directly where one slot names
