@@ -14,6 +14,7 @@ MAX_LAYERS = 8
 MAX_NEG_RATIO = 16     # LGCN_MAX_NEG_RATIO: negatives per positive of lgcn_train_step_multi / _epoch_multi
 
 LOSS_BPR, LOSS_SOFTMAX, LOSS_INBATCH = 0, 1, 2     # LGCN_LOSS_*: lgcn_ctx_set_loss
+LOSS_DIRECTAU = 4                                  # LGCN_LOSS_DIRECTAU: lgcn_ctx_set_directau
 SCORE_DOT, SCORE_COSINE = 0, 1                     # LGCN_SCORE_*: lgcn_ctx_set_inbatch_scores
 
 _c_i32p =C.POINTER(C.c_int32)
@@ -122,6 +123,11 @@ SIGNATURES = {
     "lgcn_ctx_get_inbatch_mix": (C.c_int32, [_vp]),
     "lgcn_train_step_inbatch_mix": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp, _vp]),
     "lgcn_train_epoch_inbatch_mix": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int64, C.c_int32, _vp, _vp]),
+    # the alignment-and-uniformity loss (--loss directau, --au_gamma)
+    "lgcn_ctx_set_directau": (C.c_int, [_vp, C.c_float]),
+    "lgcn_ctx_get_directau": (C.c_int, [_vp, _vp]),
+    "lgcn_train_step_directau": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, _vp]),
+    "lgcn_train_epoch_directau": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int32, _vp, _vp]),
     # hard negatives for the multi-negative step, DNS(M, N) (--hard_neg)
     "lgcn_ctx_set_hard_neg": (C.c_int, [_vp, C.c_int32, C.c_uint64, _vp]),
     "lgcn_ctx_get_hard_neg": (C.c_int32, [_vp]),

@@ -66,9 +66,7 @@
 //   k_inbatch_diag  merges the larger number of parts.
 //   k_inbatch_grad  role "users" owns Bp / 32 tiles and sweeps all item tiles, role "items" owns (1 + R) Bp / 32 tiles and sweeps the
 //                   user tiles: both extents differ, so the grid is flat (the users' workgroups first).
-#include "lgcn_device_common.h"
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
+#include "lgcn_inbatch_tile.h"      // f32x16, ib_row, ib_scores, IbRow / ib_load / ib_scores_reg, IB_REG_D
 
 // the three [cap] vectors of the score options, carved behind `part` in the context's workspace
 __device__ __forceinline__ float *ib_invu(const InBatchArgs &ia) { return ia.part + 2 * (int64_t)ia.cap * lgcn_inbatch_parts(ia.cap); }
@@ -79,52 +77,6 @@ __device__ __forceinline__ float *ib_lqb(const InBatchArgs &ia) { return ib_invu
 template <bool MIX> __device__ __forceinline__ float *ibx_invu(const InBatchArgs &ia) { if constexpr (MIX) return ia.xinvu; else return ib_invu(ia); }
 template <bool MIX> __device__ __forceinline__ float *ibx_invp(const InBatchArgs &ia) { if constexpr (MIX) return ia.xinvp; else return ib_invp(ia); }
 template <bool MIX> __device__ __forceinline__ float *ibx_lq(const InBatchArgs &ia) { if constexpr (MIX) return ia.xlq; else return ib_lqb(ia); }
-
-// tile row of accumulator register `reg` on lane half h (C/D layout of the 32x32 MFMAs)
-__device__ __forceinline__ int ib_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
-
-// 32 x 32 scores acc[i][j] = sum_k A[i][k] B[j][k]: arow / brow point at this lane's row (lane & 31) of each operand, at column
-// h D/2.  MFMA number t multiplies columns (t, D/2 + t): the k order every score of this file is summed in.
-template <int D>
-__device__ __forceinline__ f32x16 ib_scores(const float *arow, const float *brow) {
-    f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll 2
-    for (int s = 0; s < D / 2; s += 8) {
-        const f32x4 a0 = *reinterpret_cast<const f32x4 *>(arow + s), a1 = *reinterpret_cast<const f32x4 *>(arow + s + 4);
-        const f32x4 b0 = *reinterpret_cast<const f32x4 *>(brow + s), b1 = *reinterpret_cast<const f32x4 *>(brow + s + 4);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, b0.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, b0.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, b0.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, b0.w, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, b1.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, b1.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, b1.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, b1.w, acc, 0, 0, 0);
-    }
-    return acc;
-}
-
-// The same scores from operands already in registers (D <= 64: D / 2 floats per operand and lane): the owned side is loaded once
-// per workgroup and the swept side's NEXT tile is loaded while this one is multiplied.  Same k order as ib_scores: the same bits.
-template <int D> struct IbRow { f32x4 v[D / 8]; };
-template <int D>
-__device__ __forceinline__ void ib_load(IbRow<D> &r, const float *row) {
-#pragma unroll
-    for (int i = 0; i < D / 8; i++) r.v[i] = *reinterpret_cast<const f32x4 *>(row + 4 * i);
-}
-template <int D>
-__device__ __forceinline__ f32x16 ib_scores_reg(const IbRow<D> &a, const IbRow<D> &b) {
-    f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < D / 8; i++) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[i].x, b.v[i].x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[i].y, b.v[i].y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[i].z, b.v[i].z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[i].w, b.v[i].w, acc, 0, 0, 0);
-    }
-    return acc;
-}
-constexpr int IB_REG_D = 64;      // up to this D the operands of a tile live in registers (and the next tile's are prefetched)
 
 // (m, r) <- (m, r) + (m2, r2), each standing for the sum exp(m) (1 + r) (m = -inf: the empty sum); every exponent is <= 0
 __device__ __forceinline__ void ib_merge(float &m, float &r, float m2, float r2) {

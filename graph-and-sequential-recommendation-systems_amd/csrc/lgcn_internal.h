@@ -196,4 +196,22 @@ static __host__ __device__ inline int32_t lgcn_inbatch_mix_parts(int32_t B, int3
     return ((1 + R) * (lgcn_inbatch_rows(B) / 32) + LGCN_INBATCH_PART_TILES - 1) / LGCN_INBATCH_PART_TILES;
 }
 int lgcn_inbatch_launch(const InBatchArgs &a, int d, int act_dtype, bool wts, hipStream_t st);
+
+// The alignment-and-uniformity loss (lgcn_directau.hip; lgcn_train_step_directau fills this in).  Sample b = (users[b],
+// pos[b]); `m` carries what the batch-row launch of the other losses carries (negs / R / inv_BR / lam_n / tau / inv_tauB are unused,
+// loss = LGCN_LOSS_DIRECTAU).  The workspace is the context's own: `cap` rows (a multiple of 32, >= B rounded up to 32), the rows
+// and the sweep split of the in-batch step (lgcn_inbatch_rows, lgcn_inbatch_parts, LGCN_INBATCH_PART_TILES).
+struct DirectAuArgs {
+    MultiNegArgs m;
+    float *X, *Y;                 // [cap][d] fp32: the users' / positives' output-table rows over their norms; zero rows for void samples and padding
+    float *invx, *invy;           // [cap] 1 / |e_u|, 1 / |e_p| (0 for a row of norm 0, a void sample, padding)
+    float *qx, *qy;               // [cap] the fp32 sum of squares of the stored x_b, y_b (1 up to rounding; 0 for a zero row)
+    float *al;                    // [cap] |x_b - y_b|^2 (0 for a void sample and padding)
+    int32_t *uid, *pid;           // [cap] the sample's ids, -1 / -1 for a void sample or padding (uid >= 0 is the sound flag)
+    float *part;                  // [2][parts][tiles] partial sums of k over (side, part of the sweep, owner tile)
+    float *scal;                  // [2] the coefficients 2 gamma / Z_X, 2 gamma / Z_Y of the step (0: no pair, or gamma = 0)
+    int32_t cap;
+    float gamma;
+};
+int lgcn_directau_launch(const DirectAuArgs &a, int d, int act_dtype, bool wts, hipStream_t st);
 #endif

@@ -77,6 +77,10 @@ struct lgcn_ctx {
     // k_hardneg, which writes the selected item of each sample to hn_sel (library-owned [max_batch], allocated by the first setter
     // that turns it on) -- the negative column of the backward's three-slot kernels -- and its index to hn_out (the caller's, or NULL)
     int32_t hn_m; uint64_t hn_seed; int32_t *hn_sel, *hn_out;
+    // the alignment-and-uniformity loss (LGCN_LOSS_DIRECTAU; lgcn_ctx_set_directau): gamma, and the workspace of its
+    // launches (DirectAuWs over au_cap = max_batch rounded up to 32 rows), allocated by the first setter call that accepts and freed
+    // with the context
+    float au_gamma; void *au_ws; int32_t au_cap;
 };
 // The policy of a new context: LGCN_STORE_POLICY (0..3) or the default below; -1: the variable is set and is neither.
 // Default: what the alternating runs of profiles/store_policy/README.md adopted.
@@ -146,6 +150,7 @@ extern "C" int lgcn_ctx_create(const lgcn_train_config *cfg, lgcn_ctx **out) {
     x->loss_kind = LGCN_LOSS_BPR; x->loss_temp = 1.f; x->ib_ws = nullptr; x->ib_cap = 0;
     x->ib_score = LGCN_SCORE_DOT; x->ib_logq = nullptr; x->ib_mix = 0;
     x->hn_m = 0; x->hn_seed = 0; x->hn_sel = nullptr; x->hn_out = nullptr;
+    x->au_gamma = 0.f; x->au_ws = nullptr; x->au_cap = 0;
     x->bm_words = (x->N + 31) / 32; x->flip = 0;
     const size_t stride = table_bytes(x->N, c.d, c.act_dtype);
     for (int k = 0; k <= LGCN_MAX_LAYERS; k++) x->act[k] = nullptr;
@@ -220,6 +225,7 @@ extern "C" void lgcn_ctx_destroy(lgcn_ctx *ctx) {
     if (ctx->mult) (void)hipFree(ctx->mult);
     if (ctx->ib_ws) (void)hipFree(ctx->ib_ws);
     if (ctx->hn_sel) (void)hipFree(ctx->hn_sel);
+    if (ctx->au_ws) (void)hipFree(ctx->au_ws);
     if (ctx->tvar) (void)hipFree(ctx->tvar);
     if (ctx->item_bitmap) (void)hipFree(ctx->item_bitmap);
     if (ctx->gate_partials) (void)hipFree(ctx->gate_partials);
@@ -343,6 +349,7 @@ static int refuse_loss_config(const lgcn_ctx *ctx, float temperature, const char
 extern "C" int lgcn_ctx_set_loss(lgcn_ctx *ctx, int32_t kind, float temperature) {
     if (!ctx) { lgcn_set_error("lgcn_ctx_set_loss: null context"); return 3; }
     if (kind == LGCN_LOSS_BPR) { ctx->loss_kind = LGCN_LOSS_BPR; ctx->loss_temp = 1.f; return 0; }      // the step launches what it always launched
+    if (kind == LGCN_LOSS_DIRECTAU) { lgcn_set_error("lgcn_ctx_set_loss: the alignment-and-uniformity loss (directau) takes gamma, not a temperature: set it with lgcn_ctx_set_directau"); return 3; }
     if (kind != LGCN_LOSS_SOFTMAX && kind != LGCN_LOSS_INBATCH) { lgcn_set_error("lgcn_ctx_set_loss: unknown loss kind (LGCN_LOSS_BPR, LGCN_LOSS_SOFTMAX or LGCN_LOSS_INBATCH)"); return 3; }
     if (ctx->hn_m) { lgcn_set_error("lgcn_ctx_set_loss: hard negatives (lgcn_ctx_set_hard_neg) are set on this context and train the BPR loss only"); return 3; }
     const bool inbatch = kind == LGCN_LOSS_INBATCH;
@@ -404,6 +411,50 @@ extern "C" int32_t lgcn_ctx_get_loss(const lgcn_ctx *ctx, float *temperature_out
     if (temperature_out) *temperature_out = ctx->loss_temp;
     return ctx->loss_kind;
 }
+// THE carving of the workspace of the alignment-and-uniformity loss for `cap` rows of dim d, in floats from its start
+struct DirectAuWs {
+    size_t X, Y, invx, invy, qx, qy, al, uid, pid, part, scal, words;
+    DirectAuWs(int32_t cap_, int d) {
+        const size_t cap = (size_t)cap_;
+        size_t at = 0;
+        auto take = [&at](size_t n) { const size_t o = at; at += n; return o; };
+        X = take(cap * d); Y = take(cap * d); invx = take(cap); invy = take(cap); qx = take(cap); qy = take(cap); al = take(cap);
+        uid = take(cap); pid = take(cap); part = take(2 * (size_t)lgcn_inbatch_parts(cap_) * (cap / 32)); scal = take(4);
+        words = at;
+    }
+};
+// The alignment-and-uniformity loss: refused where the in-batch loss is, in the same words; the workspace first
+extern "C" int lgcn_ctx_set_directau(lgcn_ctx *ctx, float gamma) {
+    if (!ctx) { lgcn_set_error("lgcn_ctx_set_directau: null context"); return 3; }
+    const char *what = "the alignment-and-uniformity loss (directau)";
+    char buf[256];
+    const char *fmt = nullptr;
+    if (!(gamma >= 0.f) || !isfinite(gamma)) fmt = "lgcn_ctx_set_directau: %s needs a finite gamma >= 0";
+    else if (ctx->hn_m) fmt = "lgcn_ctx_set_directau: hard negatives (lgcn_ctx_set_hard_neg) are set on this context and train the BPR loss only, not %s";
+    else if (ctx->ib_mix) fmt = "lgcn_ctx_set_directau: mixed negatives (lgcn_ctx_set_inbatch_mix) are set on this context and belong to the in-batch softmax loss, not to %s";
+    else if (ctx->c.act_dtype == LGCN_FP8) fmt = "lgcn_ctx_set_directau: %s is not implemented for LGCN_FP8 activation storage";
+    else if (ctx->variant) fmt = "lgcn_ctx_set_directau: %s is not implemented with the optional branches (item-item smoothing / popularity gate)";
+    else if (!ctx->c.dense_last) fmt = "lgcn_ctx_set_directau: %s needs a context with dense_last = 1 (the gathered last layer has no 2 B slot form)";
+    if (fmt) { snprintf(buf, sizeof buf, fmt, what); lgcn_set_error(buf); return 3; }
+    if (!ctx->au_ws) {                  // the workspace is allocated once, before anything is changed
+        const int32_t cap = lgcn_inbatch_rows(ctx->c.max_batch);
+        void *ws = nullptr;
+        if (hipMalloc(&ws, sizeof(float) * DirectAuWs(cap, ctx->c.d).words) != hipSuccess) {
+            (void)hipGetLastError();
+            lgcn_set_error("lgcn_ctx_set_directau: cannot allocate the workspace of the alignment-and-uniformity loss (directau): 2 * max_batch * d * 4 bytes and a few vectors");
+            return 4;
+        }
+        ctx->au_ws = ws; ctx->au_cap = cap;
+    }
+    ctx->loss_kind = LGCN_LOSS_DIRECTAU; ctx->loss_temp = 1.f; ctx->au_gamma = gamma;
+    return 0;
+}
+extern "C" int lgcn_ctx_get_directau(const lgcn_ctx *ctx, float *gamma) {
+    if (!ctx) { lgcn_set_error("lgcn_ctx_get_directau: null context"); return 3; }
+    if (ctx->loss_kind != LGCN_LOSS_DIRECTAU) { lgcn_set_error("lgcn_ctx_get_directau: the alignment-and-uniformity loss (directau) is not set on this context (lgcn_ctx_set_directau)"); return 3; }
+    if (gamma) *gamma = ctx->au_gamma;
+    return 0;
+}
 // Hard negatives, DNS(M, N).  Everything is checked before anything changes; top_m = 0 leaves the allocation in
 // place and restores exactly the launches of a context that was never told.
 extern "C" int lgcn_ctx_set_hard_neg(lgcn_ctx *ctx, int32_t top_m, uint64_t seed, int32_t *sel_out) {
@@ -439,6 +490,8 @@ int lgcn_refuse_loss(const lgcn_ctx *x, const char *who) {
         snprintf(buf, sizeof buf, "%s: hard negatives (lgcn_ctx_set_hard_neg) are implemented for lgcn_train_step_multi / lgcn_train_epoch_multi only", who);
     else if (x->loss_kind == LGCN_LOSS_INBATCH)
         snprintf(buf, sizeof buf, "%s: the in-batch softmax loss (inbatch; lgcn_ctx_set_loss) is implemented for lgcn_train_step_inbatch / lgcn_train_epoch_inbatch only", who);
+    else if (x->loss_kind == LGCN_LOSS_DIRECTAU)
+        snprintf(buf, sizeof buf, "%s: the alignment-and-uniformity loss (directau; lgcn_ctx_set_directau) is implemented for lgcn_train_step_directau / lgcn_train_epoch_directau only", who);
     else
         snprintf(buf, sizeof buf, "%s: the sampled-softmax loss (lgcn_ctx_set_loss) is implemented for lgcn_train_step_multi / lgcn_train_epoch_multi only", who);
     lgcn_set_error(buf);
@@ -781,6 +834,20 @@ static int run_inbatch(lgcn_ctx *x, const int32_t *users, const int32_t *pos, in
     return lgcn_inbatch_launch(ia, c.d, c.act_dtype, x->lw_n != 0, st);
 }
 
+// The four launches of lgcn_directau.hip on the context's own workspace
+static int run_directau(lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B, hipStream_t st) {
+    const lgcn_train_config &c = x->c;
+    const DirectAuWs ws(x->au_cap, c.d);
+    float *w = (float *)x->au_ws;
+    DirectAuArgs da{};
+    da.m = multineg_args(x, users, pos, B);
+    da.m.tau = 0.f; da.m.inv_tauB = 0.f;      // (no temperature in this loss)
+    da.cap = x->au_cap; da.gamma = x->au_gamma;
+    da.X = w + ws.X; da.Y = w + ws.Y; da.invx = w + ws.invx; da.invy = w + ws.invy; da.qx = w + ws.qx; da.qy = w + ws.qy; da.al = w + ws.al;
+    da.uid = (int32_t *)(w + ws.uid); da.pid = (int32_t *)(w + ws.pid); da.part = w + ws.part; da.scal = w + ws.scal;
+    return lgcn_directau_launch(da, c.d, c.act_dtype, x->lw_n != 0, st);
+}
+
 // One training step on one GPU: the drop mask, the forward layers, the loss launch of the step's form -- three slots (BPR or
 // the optional branches) unless a SlotScope is open, else the batch-row launch of the context's loss -- and the backward
 static int run_step(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const int32_t *neg, int32_t B, float *loss_out, hipStream_t st) {
@@ -790,6 +857,7 @@ static int run_step(lgcn_ctx *x, const int32_t *users, const int32_t *pos, const
     if ((rc = run_forward(x, st))) return rc;
     if (!x->mn.on) rc = x->variant ? run_variant_loss(x, users, pos, neg, B, 0, B, B, true, false, st) : run_bpr(x, users, pos, neg, B, 0, B, B, true, false, st);
     else if (x->loss_kind == LGCN_LOSS_INBATCH) rc = run_inbatch(x, users, pos, B, st);
+    else if (x->loss_kind == LGCN_LOSS_DIRECTAU) rc = run_directau(x, users, pos, B, st);
     else if (x->hn_m) {
         // hard negatives: the launch picks one candidate per sample and from there on the step IS the three-slot step on (users,
         // pos, hn_sel) -- its slot kernels, cnt slots of weight 1, decay / B -- so the slot form ends here.  k_g32 is launched,
@@ -877,23 +945,26 @@ extern "C" int lgcn_train_epoch(lgcn_ctx *x, const int32_t *users, const int32_t
 // in-batch softmax over (users, pos) alone (SLOT_INBATCH; 4.19, 4.20: R = 0, no negatives) and the in-batch softmax with the
 // batch's sampled negatives as a shared pool (SLOT_MIX; 4.21).  Everything is checked before anything is launched or counted: a
 // refusal leaves the outputs, the step counter and the workspace as they were.
-enum SlotKind { SLOT_MULTI, SLOT_INBATCH, SLOT_MIX };
+enum SlotKind { SLOT_MULTI, SLOT_INBATCH, SLOT_MIX, SLOT_DIRECTAU };
 static int check_slot_step(const lgcn_ctx *x, SlotKind kind, const void *u, const void *p, const void *n, const void *loss_out,
                            int32_t R, int32_t B, int64_t neg_stride, const char *who) {
     char buf[256];
     auto refuse = [&](const char *fmt, int v0 = 0, int v1 = 0) { snprintf(buf, sizeof buf, fmt, who, v0, v1); lgcn_set_error(buf); return 3; };
-    const bool negs = kind != SLOT_INBATCH;
+    const bool negs = kind != SLOT_INBATCH && kind != SLOT_DIRECTAU;
     if (!x || !u || !p || (negs && !n) || !loss_out) return refuse("%s: null argument");
     if (kind == SLOT_MULTI) {
-        if (x->loss_kind == LGCN_LOSS_INBATCH) return lgcn_refuse_loss(x, who);
+        if (x->loss_kind == LGCN_LOSS_INBATCH || x->loss_kind == LGCN_LOSS_DIRECTAU) return lgcn_refuse_loss(x, who);
         if (R < 1 || R > LGCN_MAX_NEG_RATIO) return refuse("%s: the negative ratio R = %d is out of range (1..%d)", R, LGCN_MAX_NEG_RATIO);
         if (!x->c.dense_last) return refuse("%s: a negative ratio above the three-slot step's needs a context with dense_last = 1 (the gathered last layer has no 2 + R slot form)");
         if (x->c.act_dtype == LGCN_FP8) return refuse("%s: the negative ratio (several negatives per positive) is not implemented for LGCN_FP8 activation storage");
         if (x->variant) return refuse("%s: the negative ratio (several negatives per positive) is not implemented with the optional branches (item-item smoothing / popularity gate)");
         if (x->hn_m && (R < 2 || x->hn_m > R))
             return refuse("%s: hard negatives pick among the M = %d hardest of R >= 2 candidates with M <= R: the negative ratio R = %d does not fit (lgcn_ctx_set_hard_neg)", x->hn_m, R);
-    } else {
+    } else if (kind == SLOT_DIRECTAU) {
         if (x->hn_m) return lgcn_refuse_loss(x, who);
+        if (x->loss_kind != LGCN_LOSS_DIRECTAU || !x->au_ws) return refuse("%s: the alignment-and-uniformity loss (directau) is not set on this context (lgcn_ctx_set_directau)");
+    } else {
+        if (x->hn_m || x->loss_kind == LGCN_LOSS_DIRECTAU) return lgcn_refuse_loss(x, who);
         if (x->loss_kind != LGCN_LOSS_INBATCH || !x->ib_ws) return refuse("%s: the in-batch softmax loss (inbatch) is not set on this context (lgcn_ctx_set_loss with LGCN_LOSS_INBATCH)");
         if (kind == SLOT_MIX && x->ib_mix < 1) return refuse("%s: mixed negatives are not set on this context (lgcn_ctx_set_inbatch_mix)");
         if (kind == SLOT_MIX && (R < 1 || R > x->ib_mix)) return refuse("%s: the negative ratio R = %d is out of range (1..%d, the R_max of lgcn_ctx_set_inbatch_mix)", R, x->ib_mix);
@@ -940,6 +1011,17 @@ extern "C" int lgcn_train_epoch_inbatch(lgcn_ctx *x, const int32_t *users, const
                                         void *stream) {
     if (T <= 0) return 0;
     if (int rc = check_slot_step(x, SLOT_INBATCH, users, pos, nullptr, loss_out, 0, B, 0, "lgcn_train_epoch_inbatch")) return rc;
+    return slot_epoch(x, users, pos, nullptr, 0, T, B, loss_out, stream);
+}
+
+extern "C" int lgcn_train_step_directau(lgcn_ctx *x, const int32_t *users, const int32_t *pos, int32_t B, float *loss_out, void *stream) {
+    if (int rc = check_slot_step(x, SLOT_DIRECTAU, users, pos, nullptr, loss_out, 0, B, 0, "lgcn_train_step_directau")) return rc;
+    return slot_step(x, users, pos, nullptr, 0, 0, B, loss_out, stream);
+}
+extern "C" int lgcn_train_epoch_directau(lgcn_ctx *x, const int32_t *users, const int32_t *pos, int64_t T, int32_t B, float *loss_out,
+                                         void *stream) {
+    if (T <= 0) return 0;
+    if (int rc = check_slot_step(x, SLOT_DIRECTAU, users, pos, nullptr, loss_out, 0, B, 0, "lgcn_train_epoch_directau")) return rc;
     return slot_epoch(x, users, pos, nullptr, 0, T, B, loss_out, stream);
 }
 

@@ -77,15 +77,28 @@ def load_ppr_weights(path, K, degrees=None):
 
 
 def resolve_loss(config):
-    """--loss bpr | softmax | inbatch and --softmax_temp -> ('bpr' | 'softmax' | 'inbatch', temperature).  ValueError: an unknown
-    loss, or a temperature that is not a finite value > 0."""
+    """--loss bpr | softmax | inbatch | directau and --softmax_temp -> ('bpr' | 'softmax' | 'inbatch' | 'directau', temperature).
+    ValueError: an unknown loss, or a temperature that is not a finite value > 0 (--loss directau has none: it is not looked at)."""
     kind = str(config.get('loss', 'bpr')).strip().lower()
-    if kind not in ('bpr', 'softmax', 'inbatch'):
-        raise ValueError(f"--loss must be bpr, softmax or inbatch, got {config.get('loss')!r}")
+    if kind not in ('bpr', 'softmax', 'inbatch', 'directau'):
+        raise ValueError(f"--loss must be bpr, softmax, inbatch or directau, got {config.get('loss')!r}")
     tau = float(config.get('softmax_temp', 1.0))
+    if kind == 'directau':
+        return kind, 1.0
     if kind != 'bpr' and not (np.isfinite(tau) and tau > 0.0):
         raise ValueError(f"--loss {kind}: --softmax_temp must be a finite value > 0, got {tau}")
     return kind, tau
+
+
+def resolve_au_gamma(config, loss_kind):
+    """--au_gamma -> the weight of the uniformity term of --loss directau.  ValueError naming the flag: not a finite
+    value >= 0.  Under any other loss the flag is not looked at."""
+    if loss_kind != 'directau':
+        return 1.0
+    gamma = float(config.get('au_gamma', 1.0))
+    if not (np.isfinite(gamma) and gamma >= 0.0):
+        raise ValueError(f"--loss directau: --au_gamma must be a finite value >= 0, got {gamma}")
+    return gamma
 
 
 def _unit_rows(x):
@@ -587,7 +600,10 @@ class LightGCN(_TableModel):
         # the loss of the fused step (--loss bpr | softmax, --softmax_temp; lgcn_ctx_set_loss): softmax = the positive
         # against all R negatives of its sample in one log-sum-exp; every negative shape then goes to the _multi entry points.
         # inbatch = every user of the batch against every positive of the batch; the sampled negatives are not used
+        # directau = alignment of the samples' two rows and uniformity of the batch's users and of its items, on the
+        # rows over their norms, weight --au_gamma; no negatives at all
         self.loss_kind, self.softmax_temp = resolve_loss(config)
+        self.au_gamma = resolve_au_gamma(config, self.loss_kind)
         # hard negatives (--hard_neg M; lgcn_ctx_set_hard_neg): the multi-negative step trains the BPR triplet on one of the
         # M hardest of its R candidates.  hard_neg_step: the step counter bpr_loss keys its picks with (None: adam_step, the fused
         # step's own convention -- the counter before the step)
@@ -664,6 +680,9 @@ class LightGCN(_TableModel):
         if self.loss_kind == 'inbatch' and self.neg_ratio > 1 and not mix:
             raise _lib.LgcnError(f"--loss inbatch is not implemented together with --neg_ratio {self.neg_ratio}: the in-batch loss has no "
                                  "sampled negatives (the other samples' positives are the negatives); use --neg_ratio 1")
+        if self.loss_kind == 'directau' and self.neg_ratio > 1:
+            raise _lib.LgcnError(f"--loss directau is not implemented together with --neg_ratio {self.neg_ratio}: the alignment-and-"
+                                 "uniformity loss has no negatives at all; use --neg_ratio 1")
         return mix
 
     # -- parameters live in one table: the gate's tensors follow it ----------------------
@@ -784,7 +803,7 @@ class LightGCN(_TableModel):
                 world.cprint(f"[neg_ratio] --neg_ratio {self.neg_ratio}: the last layer is propagated densely (dense_last = 1)")
                 self._neg_ratio_said = True
         if self.loss_kind != 'bpr' and not dense_last:
-            dense_last = True       # the softmax batch-row kernel is the 2 + R slot form too, the in-batch launches its 2 B slot form
+            dense_last = True       # the softmax batch-row kernel is the 2 + R slot form too, the in-batch and directau launches their 2 B slot form
             if not self._loss_said:
                 world.cprint(f"[loss] --loss {self.loss_kind}: the last layer is propagated densely (dense_last = 1)")
                 self._loss_said = True
@@ -852,7 +871,9 @@ class LightGCN(_TableModel):
         if self.layer_weights is not None:
             w = np.ascontiguousarray(self.layer_weights, dtype=np.float32)      # (the pointer object keeps it alive until it is applied)
             out.append(('lgcn_ctx_set_layer_weights', (_lib.npp(w), int(w.size))))
-        if self.loss_kind != 'bpr':
+        if self.loss_kind == 'directau':
+            out.append(('lgcn_ctx_set_directau', (float(self.au_gamma),)))
+        elif self.loss_kind != 'bpr':
             out.append(('lgcn_ctx_set_loss', (_lib.LOSS_INBATCH if self.loss_kind == 'inbatch' else _lib.LOSS_SOFTMAX, float(self.softmax_temp))))
         if self.score_kind != 'dot' or self.inbatch_logq:
             out.append(('lgcn_ctx_set_inbatch_scores', (_lib.SCORE_COSINE if self.score_kind == 'cosine' else _lib.SCORE_DOT,
@@ -1062,6 +1083,23 @@ class LightGCN(_TableModel):
             u, p = self.embedding_user.weight[ul], self.embedding_item.weight[pl]
         return sm, (0.5 * (u.norm(2).pow(2) + p.norm(2).pow(2))) / float(B)
 
+    def _directau_loss(self, users, pos):
+        """bpr_loss under --loss directau: the autograd statement of the loss of lgcn_train_step_directau -- (au, reg),
+        au = mean_b |x_b - y_b|^2 + gamma (unif(X) + unif(Y)) / 2, unif(X) = log mean_{b<c} exp(-2 |x_b - x_c|^2) over the pairs by
+        position (torch.pdist; 0 for a batch of one), x, y the output rows over their norms."""
+        B = int(users.shape[0])
+        all_users, all_items = self.computer()
+        ul, pl = users.long(), pos.long()
+        u, p = all_users[ul], all_items[pl]
+        x, y = F.normalize(u, dim=1, eps=1e-37), F.normalize(p, dim=1, eps=1e-37)
+        au = (x - y).pow(2).sum() / float(B)
+        if B >= 2 and self.au_gamma != 0.0:
+            unif = sum(torch.log(torch.exp(-2.0 * torch.pdist(t, p=2).pow(2)).mean()) for t in (x, y))
+            au = au + float(self.au_gamma) * unif / 2.0
+        if self._reg_ego():
+            u, p = self.embedding_user.weight[ul], self.embedding_item.weight[pl]
+        return au, (0.5 * (u.norm(2).pow(2) + p.norm(2).pow(2))) / float(B)
+
     def _inbatch_mix_loss(self, users, pos, neg):
         """bpr_loss under --loss inbatch --inbatch_mix 1: the autograd statement of the loss of lgcn_train_step_inbatch_mix (DESIGN
         4.21) -- logsumexp over the masked [B, 1 + B + B R] logits: the positive's 0, the in-batch columns of _inbatch_loss and the
@@ -1124,6 +1162,8 @@ class LightGCN(_TableModel):
             return self._inbatch_mix_loss(users, pos, neg)
         if self.loss_kind == 'inbatch':          # the sampled negatives are not used
             return self._inbatch_loss(users, pos)
+        if self.loss_kind == 'directau':         # no negatives at all
+            return self._directau_loss(users, pos)
         if torch.is_tensor(neg) and neg.dim() == 2 and self.hard_neg:      # the BPR loss of the selected triplets
             neg = neg if neg.shape[0] == int(users.shape[0]) else neg.t()
             sel = self.hard_neg_select(users, neg)
@@ -1183,7 +1223,7 @@ class LightGCN(_TableModel):
         return neg.contiguous()
 
     def _dispatch(self, users, pos, neg, batch_size=None):
-        """_TableModel._dispatch by the loss and the shape of neg: in-batch (neg accepted and ignored), mixed in-batch (neg the
+        """_TableModel._dispatch by the loss and the shape of neg: directau and in-batch (neg accepted and ignored), mixed in-batch (neg the
         pool: 1-D, [n, R] or [R, n]), multi-negative ([n, R] or [R, n]; under --loss softmax 1-D too, as R = 1) or three-slot
         (1-D, or one column).  The arguments are each entry point's own (include/lgcn_hip.h)."""
         step = batch_size is None
@@ -1192,6 +1232,11 @@ class LightGCN(_TableModel):
                                "(--fused_variants 0, or gate hidden sizes > 64 / d > 128): use BPRLoss.stageOne (autograd path)" if step else
                                "this configuration of the optional branches is outside the fused step: loop BPRLoss.stageOne")
         dev = self._table.device
+        if self.loss_kind == 'directau':         # neg accepted and ignored
+            held = users, pos = self._ids(users, dev).reshape(-1), self._ids(pos, dev).reshape(-1)
+            T = int(users.numel())
+            u, p = _lib.tp(users), _lib.tp(pos)
+            return ("lgcn_train_step_directau", (u, p, T), T, held) if step else ("lgcn_train_epoch_directau", (u, p, T, batch_size), T, held)
         if self.loss_kind == 'inbatch':
             held = users, pos = self._ids(users, dev).reshape(-1), self._ids(pos, dev).reshape(-1)
             T = int(users.numel())

@@ -117,14 +117,19 @@ def build_parser():
                         'samples (u, p, n_1..n_R) in the fused step -- the loss of the flattened B*R triplets, with the user and '
                         'positive rows read and added once per sample. Native host sampler (--sampler cpp), fp32 / bf16 storage, '
                         'single GPU, default model, dense last layer')
-    p.add_argument('--loss', type=str, default='bpr', choices=['bpr', 'softmax', 'inbatch'],
+    p.add_argument('--loss', type=str, default='bpr', choices=['bpr', 'softmax', 'inbatch', 'directau'],
                    help='NEW: loss of the fused step. bpr (default) = the reference: -mean logsigmoid(x) over the (flattened) triplets. '
                         'softmax = the sampled-softmax loss: the positive competes against all --neg_ratio negatives of its sample in '
                         'one log-sum-exp at --softmax_temp, log(1 + sum_r exp(-x_r / tau)), one term per sample; the "bpr" slot of the '
                         'reported loss then holds it. inbatch = the in-batch sampled softmax: every user of the batch scores against every '
                         'positive of the batch at --softmax_temp and the other samples\' positives are the negatives (the same item, and '
                         'other positives of the same user, are left out); the sampled negatives are not used, so --neg_ratio must be 1. '
-                        'fp32 / bf16 storage, single GPU, default model, dense last layer')
+                        'directau = alignment and uniformity (DirectAU), no negatives at all: mean |x - y|^2 over the samples plus --au_gamma '
+                        'times the mean over users and items of log mean_{b<c} exp(-2 |x_b - x_c|^2), x and y the rows over their norms; '
+                        'the "bpr" slot of the reported loss then holds it, the sampled negatives are not used (--neg_ratio 1) and '
+                        'evaluation still ranks by the inner product. fp32 / bf16 storage, single GPU, default model, dense last layer')
+    p.add_argument('--au_gamma', type=float, default=1.0,
+                   help='NEW: weight gamma >= 0 of the uniformity term of --loss directau (0 = the alignment term alone)')
     p.add_argument('--softmax_temp', type=float, default=1.0,
                    help='NEW: temperature tau > 0 of --loss softmax (at --neg_ratio 1 and tau = 1 the loss is the BPR loss) and of --loss inbatch')
     p.add_argument('--score', type=str, default='dot', choices=['dot', 'cosine'],

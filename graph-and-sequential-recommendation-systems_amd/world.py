@@ -116,6 +116,7 @@ def configure(argv=None):
     config['neg_ratio'] = args.neg_ratio
     config['loss'] = args.loss
     config['softmax_temp'] = args.softmax_temp
+    config['au_gamma'] = args.au_gamma
     config['score'] = args.score
     config['inbatch_logq'] = args.inbatch_logq
     config['inbatch_mix'] = args.inbatch_mix

@@ -434,6 +434,34 @@ int lgcn_train_step_inbatch_mix(lgcn_ctx *ctx, const int32_t *users, const int32
 int lgcn_train_epoch_inbatch_mix(lgcn_ctx *ctx, const int32_t *users, const int32_t *pos, const int32_t *negs, int32_t R,
                                  int64_t T, int32_t B, float *loss_out, void *stream);
 
+/* The alignment-and-uniformity loss (--loss directau): DirectAU (Wang et al., KDD 2022), training with no negatives.
+ * A batch is B samples (u_b, p_b).  With e the output-table rows, e^ = e inv(e) (inv as under LGCN_SCORE_COSINE), x_b = e^_{u_b},
+ * y_b = e^_{p_b}:
+ *   align   = 1/B sum_b |x_b - y_b|^2
+ *   unif(X) = log( 1/npairs sum_{b<c} exp(-2 |x_b - x_c|^2) ),   npairs = B (B - 1) / 2      (pairs BY POSITION: two samples naming
+ *                                                                  the same user are a pair of distance 0; torch.pdist over the batch)
+ *   reg     = 0.5/B sum_b ( |e_u|^2 + |e_p|^2 )      (on the raw rows; reg_ego: the same on the tables' own rows)
+ *   loss_out = {au + decay * reg, au, reg},   au = align + gamma (unif(X) + unif(Y)) / 2
+ * A sample with an out-of-range id is void (err flag, no alignment term, part of no pair, no gradient); the divisors stay B and
+ * B (B - 1) / 2.  With fewer than two sound samples (B = 1 included) both unif terms are 0 and contribute no gradient: no log of 0
+ * is taken.  The gradient goes through the normalisation as under LGCN_SCORE_COSINE; the reg term and lam e stay on the raw rows.
+ * lgcn_ctx_set_directau(ctx, gamma), gamma finite and >= 0, sets the loss (lgcn_ctx_get_loss then returns LGCN_LOSS_DIRECTAU) and
+ * allocates the library-owned workspace (two [max_batch, d] fp32 row tables and a few vectors) once, before anything is changed.
+ * rc 3, with a message naming directau and nothing changed: a null context, a bad gamma, LGCN_FP8 storage, an optional branch,
+ * dense_last = 0, hard negatives set, mixed negatives set; rc 4 if the workspace cannot be allocated.  lgcn_ctx_set_loss(ctx,
+ * LGCN_LOSS_BPR, anything) leaves the loss; lgcn_ctx_set_loss(ctx, LGCN_LOSS_DIRECTAU, anything) returns 3 and names this setter.
+ * While it is set, ONLY the two entry points below train: every other training entry point returns 3 and says so, and these two
+ * return 3 unless it is set.  Forward, backward chain (over the 2 B slots), Adam epilogue, edge dropout, layer weights and reg_ego
+ * are those of lgcn_train_step_inbatch.  Everything is checked before anything is launched or counted.                         */
+#define LGCN_LOSS_DIRECTAU 4
+int lgcn_ctx_set_directau(lgcn_ctx *ctx, float gamma);
+/* 0, and gamma to *gamma (may be NULL), while the loss is set; 3 (and *gamma untouched) for a null context or another loss.    */
+int lgcn_ctx_get_directau(const lgcn_ctx *ctx, float *gamma);
+int lgcn_train_step_directau(lgcn_ctx *ctx, const int32_t *users, const int32_t *pos, int32_t B, float *loss_out, void *stream);
+/* ceil(T/B) consecutive batches of the (already shuffled) arrays; loss_out: [3*ceil(T/B)].                                   */
+int lgcn_train_epoch_directau(lgcn_ctx *ctx, const int32_t *users, const int32_t *pos, int64_t T, int32_t B, float *loss_out,
+                              void *stream);
+
 /* Hard negatives for the multi-negative step: dynamic negative sampling, DNS(M, N) (--hard_neg M).  A sample is
  * (u_b, p_b, n_{b,1..R}) in the layouts of lgcn_train_step_multi / lgcn_train_epoch_multi, R >= 2.  The step scores the R
  * candidates with the current model, s_r = e_u.e_{n_r}, ranks them by s descending (ties: r ascending), picks rank

@@ -33,7 +33,14 @@ Cases (cases()):
             follows; K = 2: one backward buffer; K = 3: a middle layer) in the gathered and the dense_last form; per d and for
             fp32 and bf16 each, one step with edge dropout (gathered: the batch rows take the mask) and layer weights in both
             forms, at K = 1 and K = 3 between them (the four weighted modes); the popularity gate and item-item smoothing at d
-            32/64/128; B 1/7/67 in rotation.  (The big-table instantiations need 2^32 bytes per table: tests/test_gpu_large.py.)"""
+            32/64/128; B 1/7/67 in rotation.  (The big-table instantiations need 2^32 bytes per table: tests/test_gpu_large.py.)
+  directau  lgcn_train_step_directau: d 32/64/128/256, fp32 / bf16 tables, mean / layer weights, K 1/3, B 1/7/67, reg_rows propagated
+            / ego, gamma 0 / 1; every value of every axis at every d (check_coverage); one batch with an out-of-range positive (a void
+            sample) and one lgcn_train_epoch_directau over T = 2 B + 3.  LAST in the list: the cases before it keep their numbers and
+            seeds, so a library or a tree from before this kind is compared on the cases both sides have.
+
+A side whose tree does not know a case of the other side (an older checkout under --tree-a) is compared on the common cases; the
+cases only one side ran are counted in the report and never differ."""
 import argparse
 import importlib
 import itertools
@@ -52,6 +59,7 @@ LOSSES = (("bpr", 1.0), ("softmax", 0.2), ("softmax", 1.0))
 SCORES, LOGQS, MIX_RS, MIX_RMAX, IB_TAU = ("dot", "cosine"), (False, True), (1, 2, 16), 16, 0.2
 IB_KINDS = ("inbatch", "inbatch_mix")
 STEP_KS, STEP_DLS, GATE_DS = (1, 2, 3), (0, 1), (32, 64, 128)
+AU_GAMMAS = (0.0, 1.0)
 
 
 def cases():
@@ -99,6 +107,13 @@ def cases():
     for j, d in enumerate(GATE_DS):
         step(d, MODES[j % 2], 2, 0, use_pop_gate=True)
         step(d, MODES[(j + 1) % 2], 2, 0, use_item_item=True, i2i_build='cooc', i2i_alpha=0.5)
+    for j, d in enumerate(DS):                              # directau (last: see the module docstring): six cases per d, every value of every axis
+        for i in range(6):
+            out.append(dict(kind="directau", d=d, mode=MODES[(i + j) % 2], wts=WTS[(i // 2) % 2], K=KS[(i // 3) % 2], B=BS[i % 3], reg=REGS[((i + 1) // 2) % 2],
+                            gamma=AU_GAMMAS[(i + i // 3 + j) % 2]))
+    base = dict(kind="directau", d=64, mode="fp32", wts=False, K=3, B=7, reg="propagated", gamma=1.0)
+    out.append(dict(base, void=3))                          # an out-of-range positive
+    out.append(dict(base, mode="bf16", epoch=True))         # the epoch entry point over T = 2 B + 3
     return out
 
 
@@ -118,6 +133,14 @@ def check_coverage(cs):
                 assert {c[key] for c in at} == set(values), (kind, d, key)
         for tag, n in (("void", 1), ("epoch", 1), ("then_plain", int(kind == "inbatch_mix"))):
             assert sum(1 for c in cs if c["kind"] == kind and c.get(tag)) == n, (kind, tag)
+    au = [c for c in cs if c["kind"] == "directau" and not (c.get("void") or c.get("epoch"))]
+    for d in DS:
+        at = [c for c in au if c["d"] == d]
+        for key, values in (("mode", MODES), ("wts", WTS), ("K", KS), ("B", BS), ("reg", REGS), ("gamma", AU_GAMMAS)):
+            assert {c[key] for c in at} == set(values), ("directau", d, key)
+    for tag in ("void", "epoch"):
+        assert sum(1 for c in cs if c["kind"] == "directau" and c.get(tag)) == 1, ("directau", tag)
+    assert all(c["kind"] == "directau" for c in cs[-(len(au) + 2):]) and not any(c["kind"] == "directau" for c in cs[:-(len(au) + 2)])
     steps = [c for c in cs if c["kind"] == "step"]
     for K, dl in itertools.product(STEP_KS, STEP_DLS):          # every form of the finish and Adam launches at every batch size
         assert {c["B"] for c in steps if not c["cfg"] and (c["K"], c["dl"]) == (K, dl)} == set(BS), (K, dl)
@@ -146,6 +169,9 @@ def name(c):
                 + (f"-R{c['R']}of{MIX_RMAX}" if c["kind"] == "inbatch_mix" else "") + tag)
     if c["kind"] == "mf":
         return f"mf-d{c['d']}-B{c['B']}"
+    if c["kind"] == "directau":
+        tag = "-void" if c.get("void") else "-epoch" if c.get("epoch") else ""
+        return f"directau-d{c['d']}-{c['mode']}-{'wts' if c['wts'] else 'mean'}-K{c['K']}-B{c['B']}-{c['reg']}-gamma{c['gamma']}" + tag
     return f"step-d{c['d']}-{c['mode']}-K{c['K']}-dl{c['dl']}-B{c['B']}" + "".join(f"-{k}" for k in c["cfg"] if k in ("dropout", "layer_weights", "use_pop_gate", "use_item_item"))
 
 
@@ -173,6 +199,9 @@ def child(out_path):
             w.config.update({'loss': 'inbatch', 'softmax_temp': IB_TAU, 'score': c["score"], 'inbatch_logq': int(c["logq"])}, **({'layer_weights': 'exp'} if c["wts"] else {}))
             if c["kind"] == "inbatch_mix":
                 w.config.update({'inbatch_mix': 1, 'neg_ratio': MIX_RMAX})
+        elif c["kind"] == "directau":
+            w = SC.configure(pkg, (c["mode"], c["d"], c["K"], 1, -1, c["reg"]), path, 64)
+            w.config.update({'loss': 'directau', 'au_gamma': c["gamma"]}, **({'layer_weights': 'exp'} if c["wts"] else {}))
         elif c["kind"] == "multi":
             w = SC.configure(pkg, (c["mode"], c["d"], c["K"], 1, -1, c["reg"]), path, 64)
             w.config.update({'neg_ratio': c["R"], 'loss': c["loss"], 'softmax_temp': c["tau"]}, **({'layer_weights': 'exp'} if c["wts"] else {}))
@@ -201,7 +230,7 @@ def child(out_path):
                 a[(a == SC.BIG_ITEM) | (a == SC.ISOLATED_ITEM)] = 20
             if c.get("saturate"):
                 u, p, n = sat
-            if c.get("void") and c["kind"] == "inbatch":
+            if c.get("void") and c["kind"] in ("inbatch", "directau"):
                 p[c["void"]] = SC.M_ITEMS
             elif c.get("void"):
                 n[c["void"], c["R"] - 1] = SC.M_ITEMS
@@ -271,9 +300,11 @@ def driver(a):
         for lib, tree, f in zip((a.lib_a, a.lib_b), trees, files):
             run_child(lib, f, a.child_timeout, tree)
         za, zb = np.load(files[0]), np.load(files[1])
-        assert za.files == zb.files
+        common = [k for k in za.files if k in zb.files]
+        only = sorted({k.rsplit(" ", 1)[0] for k in set(za.files) ^ set(zb.files)})
+        assert common and (not only or trees[0] != trees[1]), "one tree, two lists of cases"
         differing = []
-        for k in za.files:
+        for k in common:
             x, y = za[k], zb[k]
             if x.shape != y.shape or x.dtype != y.dtype or x.tobytes() != y.tobytes():
                 case = k.rsplit(" ", 1)[0]
@@ -286,6 +317,8 @@ def driver(a):
     print("cases per kind: " + ", ".join(f"{k} {kinds.count(k)}" for k in dict.fromkeys(kinds)))
     if differing:
         print(f"first differing case: {differing[0]}")
+    if only:
+        print(f"{len(only)} cases ran on one side only (not compared): {only[0]} .. {only[-1]}")
     print(f"{n} cases x {STEPS} steps, {len(differing)} differing")
     return 1 if differing else 0
 
