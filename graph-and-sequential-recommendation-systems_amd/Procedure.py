@@ -237,6 +237,17 @@ class _EvalIndex:
                 _lib.check(lib.lgcn_eval_build_masks(_lib.tp(self.users32), len(self.users), _lib.tp(self.train_ptr), _lib.tp(self.train_idx32),
                                                      int(dataset.m_items), _lib.tp(self.masks), _lib.current_stream()), "lgcn_eval_build_masks")
 
+    def item_info(self, dataset):
+        """(packed item words int32 [m_items] on the device, number of groups) of --pop_metrics, built once per dataset and
+        group spec: utils.pack_item_info of the train popularity and utils.popularity_groups."""
+        key = (str(world.config.get('pop_groups', '[0.2]')), str(world.config.get('pop_group_by', 'items')))
+        if getattr(self, '_item_info', None) is None or self._item_info[0] != key:
+            fr = utils.pop_fractions(key[0])
+            pop = utils.item_popularity(dataset)
+            info = utils.pack_item_info(pop, utils.popularity_groups(pop, fr, by=key[1]))
+            self._item_info = (key, torch.from_numpy(info).to(self.test_ptr.device), len(fr) + 1)
+        return self._item_info[1], self._item_info[2]
+
     def rank_lists(self):
         """(users32, test_ptr, test_sorted32) with the slots ordered by test-list length (longest first, stable), built once: what the rank
         kernels are given.  The compare loop of a wave runs to its longest list, and a workgroup sweeps the items once more
@@ -264,9 +275,10 @@ class _EvalIndex:
         return local, torch.repeat_interleave(start, lens) + offs
 
 
-def _test_fused(Recmodel, ev, max_K):
+def _test_fused(Recmodel, ev, max_K, pop_info=None):
     """Procedure.py:162-192 in two launches: lgcn_eval_topk_ex (scores on the matrix cores + train mask +
-    top-K, no score matrix in memory) and lgcn_eval_metrics_ex (hits, precision / recall / NDCG, sums)."""
+    top-K, no score matrix in memory) and lgcn_eval_metrics_ex (hits, precision / recall / NDCG, sums).  With pop_info =
+    (item words, groups) of --pop_metrics 1, lgcn_eval_pop_metrics reads the same lists and its numbers join the results."""
     E = Recmodel.rating_table()
     n = len(ev.users)
     topk = torch.empty(n, max_K, dtype=torch.int32, device=E.device)
@@ -274,8 +286,12 @@ def _test_fused(Recmodel, ev, max_K):
                    masks=ev.masks)
     ks = list(world.topks)
     _, sums = _lib.eval_metrics(topk, ev.test_ptr, ev.test_sorted32, ks)
+    pop = _lib.eval_pop_metrics(topk, ev.test_ptr, ev.test_sorted32, pop_info[0], pop_info[1], ks) if pop_info is not None else None
     m = (sums.cpu().numpy() / max(n, 1)).reshape(3, len(ks))
-    return {'precision': m[0], 'recall': m[1], 'ndcg': m[2]}, topk
+    results = {'precision': m[0], 'recall': m[1], 'ndcg': m[2]}
+    if pop is not None:                                     # one more small copy: the sums, never the lists
+        results.update(utils.pop_results(*_lib.pop_unpack(pop['packed'].cpu().numpy(), len(ks), pop_info[1]), n, int(pop_info[0].numel())))
+    return results, topk
 
 
 RANKS_BY_LENGTH = True      # --rank_metrics: evaluation slots visited in order of test-list length (measured: profiles/eval_ranks)
@@ -303,8 +319,19 @@ def Test(dataset, Recmodel, epoch, w=None, multicore=0):
     and never uses it).  Per-user results do not depend on the user batch size, so
     several `test_u_batch_size` batches are scored per launch (bounded by ~1 GiB of scores)."""
     u_batch_size = world.config['test_u_batch_size']
-    Recmodel = Recmodel.eval()
     max_K = max(world.topks)
+    pop_metrics = int(world.config.get('pop_metrics', 0))
+    if pop_metrics:                                         # refused by name, before anything touches the GPU
+        if int(world.config.get('rank_metrics', 0)):
+            raise ValueError("--pop_metrics 1 cannot be combined with --rank_metrics 1: the rank path produces no lists")
+        if not int(world.config.get('eval_fused', 1)):
+            raise ValueError("--pop_metrics 1 needs --eval_fused 1: it reads the lists of the fused evaluation")
+        if max_K > _lib.eval_kmax():
+            raise ValueError(f"--pop_metrics 1 needs max(--topks) <= lgcn_eval_kmax() = {_lib.eval_kmax()}, got {max_K}")
+        utils.pop_fractions(world.config.get('pop_groups', '[0.2]'))
+        if not hasattr(Recmodel, 'propagated_table') or torch.device(world.device).type != 'cuda':
+            raise RuntimeError("--pop_metrics 1 needs the HIP model on the GPU (there is no torch fall-back for lgcn_eval_pop_metrics)")
+    Recmodel = Recmodel.eval()
     if hasattr(Recmodel, "invalidate_cache"):
         Recmodel.invalidate_cache()
     dev = world.device
@@ -326,7 +353,7 @@ def Test(dataset, Recmodel, epoch, w=None, multicore=0):
     fused = max_K <= _lib.eval_kmax() and int(world.config.get('eval_fused', 1)) and hasattr(Recmodel, 'propagated_table')
     if fused:
         with torch.no_grad():
-            results, _ = _test_fused(Recmodel, ev, max_K)
+            results, _ = _test_fused(Recmodel, ev, max_K, ev.item_info(dataset) if pop_metrics else None)
         return _finish_test(results, epoch, w)
     per_user = {m: [] for m in ('precision', 'recall', 'ndcg')}
     chunk = max(u_batch_size, min(8192, (1 << 28) // max(1, dataset.m_items)) // u_batch_size * u_batch_size)
@@ -368,5 +395,13 @@ def _finish_test(results, epoch, w):
         for m, tag in (('auc', 'AUC'), ('mrr', 'MRR')):       # (--rank_metrics 1 only)
             if m in results:
                 w.add_scalar(f'Test/{tag}', results[m], epoch)
+        for m in ('recall_share', 'recall_by_group', 'list_share'):          # (--pop_metrics 1 only): one chart per group
+            if m in results:
+                for g in range(len(results[m])):
+                    w.add_scalars(f'Test/Pop/{m}/group{g}@{world.topks}',
+                                  {str(world.topks[i]): results[m][g][i] for i in range(len(world.topks))}, epoch)
+        for m in ('arp', 'coverage', 'gini'):
+            if m in results:
+                w.add_scalars(f'Test/Pop/{m}@{world.topks}', {str(world.topks[i]): results[m][i] for i in range(len(world.topks))}, epoch)
     print(results)
     return results

@@ -152,6 +152,8 @@ SIGNATURES = {
                                   C.c_int32, _vp]),
     "lgcn_eval_rank_metrics": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int32,
                                          _vp, _vp, _vp]),
+    "lgcn_eval_pop_metrics": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp, C.c_int32,
+                                        _vp, _vp, _vp, _vp, _vp, _vp]),
     "lgcn_i2i_topk": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "lgcn_i2i_finish": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp, C.POINTER(C.c_int64), _vp]),
     "lgcn_dp_available": (C.c_int, []),
@@ -430,6 +432,63 @@ def eval_rank_metrics(m_items, users32, train_ptr, train_idx32, test_ptr, test_s
                                         n_test, tp(scores), tp(gt), tp(eq), tp(ks_h), len(ks), tp(per_user), tp(sums),
                                         current_stream()), "lgcn_eval_rank_metrics")
     return per_user, sums
+
+
+def eval_pop_metrics(topk, test_ptr, test_sorted32, item_info, n_groups, ks, exposure=None, per_slot=None, want_exposure=False):
+    """lgcn_eval_pop_metrics, checked: topk int32 [n_eval, K] on the device, the test CSR as eval_metrics takes it, item_info
+    int32 [m_items] (utils.pack_item_info: pop * 8 + group), 1 <= n_groups <= 8, ks 1..8 cut-offs in 1..K.  Returns a dict of
+    device tensors: sums float64 [n_ks, 2, n_groups], counts int64 [n_ks, n_groups + 5], group_slots int64 [n_groups] (views of
+    'packed', one int64 buffer: pop_unpack reads its host copy), and
+    exposure int32 [n_ks, m_items] / per_slot float64 [n_eval, n_ks, 2, n_groups] or None (exposure is allocated with
+    want_exposure).  Everything is validated before any pointer leaves Python (ValueError)."""
+    import torch
+    if not torch.is_tensor(topk) or topk.dim() != 2:
+        raise ValueError("topk must be a 2-D tensor")
+    dev = topk.device
+    _want(topk, "topk", torch.int32, None)
+    if dev.type != "cuda":
+        raise ValueError("topk must be a device tensor")
+    n, K = int(topk.shape[0]), int(topk.shape[1])
+    ks = [int(k) for k in ks]
+    G = int(n_groups)
+    if not 1 <= G <= 8:
+        raise ValueError(f"n_groups must be in 1..8, got {n_groups}")
+    if not 1 <= len(ks) <= 8 or any(not 1 <= k <= K for k in ks) or not 1 <= K <= eval_kmax():
+        raise ValueError(f"1..8 cut-offs in 1..K (K={K} <= {eval_kmax()}), got {ks}")
+    _want(test_ptr, "test_ptr", torch.int64, (n + 1,), dev)
+    _want(test_sorted32, "test_sorted32", torch.int32, None, dev)
+    if test_sorted32.dim() != 1:
+        raise ValueError("test_sorted32 must be 1-D")
+    _want(item_info, "item_info", torch.int32, None, dev)
+    if item_info.dim() != 1 or item_info.numel() < 1:
+        raise ValueError("item_info must be 1-D with one word per item")
+    m_items = int(item_info.numel())
+    if n * K * m_items >= 1 << 62:
+        raise ValueError(f"n_eval * K * m_items = {n * K * m_items} reaches 2^62: the Gini numerator could leave int64")
+    nk = len(ks)
+    if exposure is None and want_exposure:
+        exposure = torch.empty(nk, m_items, dtype=torch.int32, device=dev)
+    if exposure is not None:
+        _want(exposure, "exposure", torch.int32, (nk, m_items), dev)
+    if per_slot is not None:
+        _want(per_slot, "per_slot", torch.float64, (n, nk, 2, G), dev)
+    packed = torch.empty(nk * 2 * G + nk * (G + 5) + G, dtype=torch.int64, device=dev)     # one buffer: one copy brings all sums to the host
+    sums, counts, group_slots = pop_unpack(packed, nk, G)
+    ks_h = torch.tensor(ks, dtype=torch.int32)
+    check(load().lgcn_eval_pop_metrics(tp(topk), n, K, tp(test_ptr), tp(test_sorted32), tp(item_info), m_items, G, tp(ks_h), nk,
+                                       tp(sums), tp(counts), tp(group_slots), tp(exposure), tp(per_slot), current_stream()),
+          "lgcn_eval_pop_metrics")
+    return {'sums': sums, 'counts': counts, 'group_slots': group_slots, 'exposure': exposure, 'per_slot': per_slot, 'packed': packed}
+
+
+def pop_unpack(packed, nk, G):
+    """(sums float64 [nk, 2, G], counts int64 [nk, G + 5], group_slots int64 [G]) as views of eval_pop_metrics' one int64 buffer
+    (a torch tensor, or its host copy as a numpy array)."""
+    import numpy as np
+    import torch
+    a, b = nk * 2 * G, nk * 2 * G + nk * (G + 5)
+    sums = packed[:a].view(np.float64 if isinstance(packed, np.ndarray) else torch.float64)
+    return sums.reshape(nk, 2, G), packed[a:b].reshape(nk, G + 5), packed[b:]
 
 
 I2I_WEIGHTS = {"cooc": 0, "jaccard": 1, "pmi": 2}       # LGCN_I2I_COOC / _JACCARD / _PMI

@@ -94,6 +94,18 @@ def build_parser():
                    help='NEW: 1 = Procedure.Test ranks through lgcn_eval_ranks / lgcn_eval_rank_metrics: the position of every test item '
                         'in the full ranking from one item sweep, so any cut-off up to the catalogue size stays on the GPU, and the '
                         "result also holds 'auc' (utils.AUC) and 'mrr'; 0 (default) = Test as before")
+    p.add_argument('--pop_metrics', type=int, default=0, choices=[0, 1],
+                   help='NEW: 1 = Procedure.Test also reports, at every cut-off of --topks and from the lists the fused evaluation ranked '
+                        '(lgcn_eval_pop_metrics, on the GPU): recall split by item-popularity group (recall_share, recall_by_group), the '
+                        'share of every group in the lists (list_share), the average popularity of the recommended items (arp), catalogue '
+                        'coverage and the Gini index of item exposure; 0 (default) = Test as before. Not with --rank_metrics 1 or '
+                        '--eval_fused 0')
+    p.add_argument('--pop_groups', type=str, default="[0.2]",
+                   help='NEW: boundaries of the popularity groups of --pop_metrics: a strictly increasing list of at most 7 values in '
+                        '(0, 1), cumulative shares of the items ranked by train popularity (group 0 = the most popular). [0.2] = the '
+                        '20 %% head and the 80 %% tail')
+    p.add_argument('--pop_group_by', type=str, default='items', choices=['items', 'interactions'],
+                   help="NEW: what the shares of --pop_groups are taken of: 'items' (default) or the train 'interactions'")
     p.add_argument('--reg_rows', type=str, default='propagated', choices=['propagated', 'ego'],
                    help="NEW: rows the L2 term of bpr_loss is taken on. 'propagated' (default) = this reference (model.py:173: the "
                         "propagated rows of the batch); 'ego' = upstream LightGCN (userEmb0 / posEmb0 / negEmb0, the embedding "

@@ -401,6 +401,96 @@ def AUC(all_item_scores, dataset, test_data):
     return float(u / (n * (m - n)))
 
 
+# ==================== Popularity-aware evaluation (--pop_metrics) ====================
+POP_MAX = 1 << 28          # lgcn_eval_pop_metrics' item word holds pop * 8 + group in 32 bits (_lib.eval_pop_metrics)
+
+
+def item_popularity(dataset):
+    """pop_i = the train interactions of item i (int64 [m_items]): a cold item has 0, not the loader's patched items_D."""
+    _, indices = _pos_csr(dataset)
+    return np.bincount(np.asarray(indices, np.int64), minlength=int(dataset.m_items)).astype(np.int64)
+
+
+def pop_fractions(spec):
+    """--pop_groups as a list of floats: a strictly increasing list of at most 7 values in (0, 1).  ValueError otherwise."""
+    if isinstance(spec, str):
+        import ast
+        try:
+            spec = ast.literal_eval(spec)
+        except (ValueError, SyntaxError) as e:
+            raise ValueError(f"pop_groups {spec!r} is not a list of numbers") from e
+    if isinstance(spec, (int, float)) and not isinstance(spec, bool):
+        spec = [spec]
+    if not isinstance(spec, (list, tuple)) or any(isinstance(f, bool) or not isinstance(f, (int, float)) for f in spec):
+        raise ValueError(f"pop_groups {spec!r} must be a list of numbers")
+    fr = [float(f) for f in spec]
+    if len(fr) > 7:
+        raise ValueError(f"pop_groups {fr}: at most 7 boundaries (8 groups)")
+    if any(not 0.0 < f < 1.0 for f in fr):                   # (also refuses NaN)
+        raise ValueError(f"pop_groups {fr}: every boundary must lie in (0, 1)")
+    if any(b <= a for a, b in zip(fr, fr[1:])):
+        raise ValueError(f"pop_groups {fr} must be strictly increasing")
+    return fr
+
+
+def popularity_groups(pop, fractions, by='items'):
+    """Group id of every item (int32 [m_items], group 0 = the most popular, len(fractions) + 1 groups).  The items are ranked by
+    (pop descending, id ascending).  by='items': `fractions` are cumulative shares of the items -- the item of 1-based rank r
+    belongs to the first group g with r <= fractions[g] * m_items, the last group otherwise.  by='interactions': cumulative shares
+    of the train interactions -- with c the interactions of the items up to and including this one, the first group with
+    c <= fractions[g] * sum(pop).  A group may be empty.  ValueError on a malformed spec."""
+    pop = np.asarray(pop)
+    if pop.ndim != 1 or pop.dtype.kind not in 'iu' or (pop.size and int(pop.min()) < 0):
+        raise ValueError("pop must be a 1-D array of non-negative integers")
+    if by not in ('items', 'interactions'):
+        raise ValueError(f"pop_group_by must be 'items' or 'interactions', got {by!r}")
+    fr = np.asarray(pop_fractions(fractions), np.float64)
+    pop = pop.astype(np.int64)
+    m = len(pop)
+    order = np.lexsort((np.arange(m), -pop))                 # pop descending, id ascending
+    if by == 'items':
+        mass, total = np.arange(1, m + 1, dtype=np.float64), float(m)
+    else:
+        mass, total = np.cumsum(pop[order]).astype(np.float64), float(pop.sum())
+    groups = np.empty(m, np.int32)
+    groups[order] = np.searchsorted(fr * total, mass, side='left').astype(np.int32)     # boundaries below the mass = groups passed
+    return groups
+
+
+def pack_item_info(pop, groups):
+    """item_info[i] = pop_i * 8 + g_i as int32 bits (what lgcn_eval_pop_metrics gathers once per list entry).  ValueError for
+    pop >= 2^28 (the word would overflow), a negative pop, or a group outside 0..7."""
+    pop = np.asarray(pop, np.int64)
+    groups = np.asarray(groups, np.int64)
+    if pop.shape != groups.shape or pop.ndim != 1:
+        raise ValueError("pop and groups must be 1-D arrays of one length")
+    if pop.size and (int(pop.min()) < 0 or int(pop.max()) >= POP_MAX):
+        raise ValueError(f"pop must lie in [0, 2^28): got {int(pop.min())}..{int(pop.max())}")
+    if groups.size and (int(groups.min()) < 0 or int(groups.max()) > 7):
+        raise ValueError("groups must lie in 0..7")
+    return (pop * 8 + groups).astype(np.uint32).view(np.int32)
+
+
+def pop_results(sums, counts, group_slots, n_eval, m_items):
+    """The reported numbers from lgcn_eval_pop_metrics' sums (host arrays: float64 [n_ks, 2, G], int64 [n_ks, G + 5], int64 [G]):
+    one division each.  recall_share / recall_by_group / list_share are [G, n_ks]; arp / coverage / gini [n_ks]; group_users [G]."""
+    sums, counts, group_slots = np.asarray(sums, np.float64), np.asarray(counts, np.int64), np.asarray(group_slots, np.int64)
+    G = len(group_slots)
+    valid = counts[:, G].astype(np.float64)
+    sum_e = counts[:, G + 3].astype(np.float64)
+    ng = group_slots.astype(np.float64)
+
+    def div(a, b):
+        return np.divide(a, b, out=np.zeros(np.broadcast(a, b).shape), where=b != 0)
+    return {'recall_share': sums[:, 0, :].T / max(int(n_eval), 1),
+            'recall_by_group': div(sums[:, 1, :].T, ng[:, None]),
+            'list_share': div(counts[:, :G].T.astype(np.float64), valid[None, :]),
+            'arp': div(counts[:, G + 1].astype(np.float64), valid),
+            'coverage': counts[:, G + 2].astype(np.float64) / float(m_items),
+            'gini': div(counts[:, G + 4].astype(np.float64), float(m_items) * sum_e),
+            'group_users': group_slots.copy()}
+
+
 def getLabel(groundTruth, predictTopK):
     """0/1 float32 vector: is the j-th predicted item in the ground truth?"""
     truth = groundTruth if isinstance(groundTruth, (list, set, tuple, np.ndarray)) else [groundTruth]

@@ -121,6 +121,9 @@ def configure(argv=None):
     config['inbatch_logq'] = args.inbatch_logq
     config['inbatch_mix'] = args.inbatch_mix
     config['hard_neg'] = args.hard_neg
+    config['pop_metrics'] = args.pop_metrics
+    config['pop_groups'] = args.pop_groups
+    config['pop_group_by'] = args.pop_group_by
     device =torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     return config
 

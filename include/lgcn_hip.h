@@ -677,6 +677,39 @@ int lgcn_eval_rank_metrics(int32_t n_eval, int32_t m_items, const int32_t *users
                            const int64_t *test_indptr, const int32_t *test_items_sorted, int64_t n_test,
                            const float *test_scores, const int32_t *gt, const int32_t *eq,
                            const int32_t *ks, int32_t n_ks, double *per_user, double *sums, void *stream);
+/* Popularity-aware evaluation from the ranked lists (additive to ABI 13; csrc/lgcn_eval_pop.hip): which items
+ * the lists hold.  Inputs: topk_items [n_eval, K] as lgcn_eval_topk_ex wrote it (the ids of a list DISTINCT; an id outside
+ * [0, m_items), the -1 padding, counts nowhere), the test CSR over the slots as lgcn_eval_metrics_ex takes it (ids ascending,
+ * test_indptr[n_eval] entries; a test id outside [0, m_items) belongs to no group), and one packed word per item,
+ * item_info[i] = pop_i * 8 + g_i: pop_i < 2^28 the item's train interactions, g_i its popularity group (0 = the most popular).
+ * The group is read as `word & 7` and every per-group array in the kernels holds 8 columns, so no content of item_info can
+ * index out of bounds; an item with g_i >= n_groups is counted in `valid`, the popularity sum and the exposures, and in no
+ * reported group column.  ks: HOST pointer, 1..8 cut-offs in 1..K, any order, duplicates allowed.
+ * With L_s the list and T_s the test list of slot s, h[s,g,k] = #{r < k : L_s[r] in T_s, g(L_s[r]) = g}, t[s,g] = #{i in T_s :
+ * g_i = g}, e_k[i] = #{s : i among the first k entries of L_s} (the exposure):
+ *   sums_f64 [n_ks, 2, n_groups]   [q][0][g] = sum_s h[s,g,k] / |T_s|  (a slot with an empty T_s adds 0; over g and / n_eval: Recall@k)
+ *                                  [q][1][g] = sum_{s : t[s,g] > 0} h[s,g,k] / t[s,g]     (recall on the group's test items)
+ *   group_slots [n_groups]         #{s : t[s,g] > 0}
+ *   counts_i64 [n_ks, n_groups+5]  [q][g] = list entries of group g among the first k | [n_groups] valid entries among the first
+ *                                  k | [n_groups+1] sum of pop over them | [n_groups+2] #{i : e_k[i] > 0} | [n_groups+3] sum_i e_k[i]
+ *                                  | [n_groups+4] sum_{i<j} |e_k[i] - e_k[j]|, the Gini numerator (Gini = it / (m_items sum_i e_k[i]))
+ *   exposure [n_ks, m_items] or NULL   e_k[i] (when given it also serves as the kernels' bucket array: no temporary of that size)
+ *   per_slot [n_eval, n_ks, 2, n_groups] or NULL   the two quotients of every slot, each one correctly rounded division
+ * Every count is an integer sum (order-free, exact); the two float64 sums are added in an order that depends on n_eval and K
+ * alone (per-workgroup partials merged in a fixed order): all outputs are bitwise reproducible, with or without per_slot.  A list
+ * entry costs ONE integer atomic add (into the exposure bucket of the smallest cut-off above its position); the Gini numerator is
+ * sum_v v H[v] (2 R_v + H[v] - m_items) over the histogram H of the exposure values, R_v = sum_{w<v} H[w]: no sort, no floats.
+ * The temporaries come from the stream-ordered pool; nothing synchronises.  n_eval == 0: the outputs are zeroed, nothing else runs.
+ *   rc 3  nothing launched, no output written: n_groups or n_ks outside 1..8, K outside 1..lgcn_eval_kmax(), a cut-off outside
+ *         1..K, n_eval < 0, m_items < 1, a NULL array other than exposure / per_slot, n_eval * K * m_items >= 2^62 (the Gini
+ *         numerator could leave int64); the message names the argument
+ *   rc 4  the temporaries cannot be allocated: nothing launched                                                           */
+int lgcn_eval_pop_metrics(const int32_t *topk_items, int32_t n_eval, int32_t K,
+                          const int64_t *test_indptr, const int32_t *test_items_sorted,
+                          const uint32_t *item_info, int32_t m_items, int32_t n_groups,
+                          const int32_t *ks, int32_t n_ks,
+                          double *sums_f64, int64_t *counts_i64, int64_t *group_slots,
+                          int32_t *exposure, double *per_slot, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* Item-item co-occurrence graph (preprocess_instacart_i2i.py:61-170)         */
