@@ -56,7 +56,8 @@ def side(x, gamma, B):
     if nb < 2:
         z = torch.zeros(nb, nb, dtype=F64)
         return z, torch.zeros((), dtype=F64), torch.zeros((), dtype=F64), z
-    d2 = ((x[:, None, :] - x[None, :, :]) ** 2).sum(2)
+    # (in blocks of rows: the same operations on the same operands, element for element, without a [nb, nb, d] array at nb = 2048)
+    d2 = torch.cat([((x[i:i + 64, None, :] - x[None, :, :]) ** 2).sum(2) for i in range(0, nb, 64)], dim=0)
     k = torch.exp(-2.0 * d2) * (1.0 - torch.eye(nb, dtype=F64))
     Z = torch.triu(k, 1).sum()
     return k, Z, torch.log(Z / npairs(B)), (2.0 * float(gamma) / Z) * k
@@ -123,7 +124,8 @@ def make_batch(B, seed=0):
     """One batch (u [B], p [B]) on the graph of tests/storage_cases.py, on rows of ordinary norm only (the hand-set zero, tiny,
     subnormal and outlier rows of the storage table are left out: the loss normalises every row).  From B = 7 on a repeated user,
     a repeated item and a sample that is another's mirror in position (same user AND same item: a pair of distance 0 on both
-    sides); from B = 65 on the same user and item also across tiles."""
+    sides); from B = 65 on the same user and item also across tiles; from B = 513 (three parts of the sweep) on the same user and
+    the same item also across PARTS: rows 0..255 / the last part (row B - 1), rows 0..255 / part 1, and a mirror across parts."""
     rng = np.random.Generator(np.random.PCG64(9100 * seed + B))
     special_u = {SC.ZERO_USER, SC.TINY_USER}
     special_p = {SC.BIG_ITEM, SC.ISOLATED_ITEM, SC.OUTLIER_ITEM, SC.SUBNORMAL_ITEM}
@@ -142,7 +144,31 @@ def make_batch(B, seed=0):
         u[B - 1] = u[2]                                            # across tiles 0 / the last
     if B >= 65:
         u[40] = u[8]; p[50] = p[15]                                # across tiles 0 / 1
+    if B >= IB.MANY_PARTS_B:
+        p[B - 1] = p[9]                                            # across parts 0 / the last (the user: u[B - 1] = u[2] above)
+        u[300] = u[10]; p[400] = p[11]                             # across parts 0 / 1
+        u[500], p[500] = u[14], p[14]                              # a mirror across parts 0 / 1
     return u.astype(np.int64), p.astype(np.int64)
+
+
+# The sizes at which code runs that no smaller batch reaches (csrc/lgcn_directau.hip): k_directau_merge adds n = tiles * parts
+# partials per side, lane-strided over 64 lanes -- a lane adds a SECOND partial only from n > 64, which 22 tiles x 3 parts = 66
+# are the first to reach.  705 is 23 tiles x 3 parts = 69 with one live row in the last tile; 736 is the same count with full
+# tiles; 2048 is the default --bpr_batch (64 x 8 = 512 partials, eight per lane).
+MERGE_B = 705
+LARGE_BATCH_SIZES = (MERGE_B, 736, 2048)
+
+
+def partials(B):
+    """The partials per side that k_directau_merge adds: tiles x parts."""
+    return ((B + 31) // 32) * IB.parts(B)
+
+
+def skipped_parts(B):
+    """The (owner tile, part) workgroups of the symmetric sweep whose whole part lies below the owner tile (ts = max(t0, bx) >= t1)
+    although the part is neither the first nor the last one: a hole in the middle of the sweep."""
+    nT, NP = (B + 31) // 32, IB.parts(B)
+    return [(bx, by) for bx in range(nT) for by in range(1, NP - 1) if max(by * 8, bx) >= min(by * 8 + 8, nT)]
 
 
 def make_batches(B, steps=3, seed=0):

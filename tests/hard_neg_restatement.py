@@ -124,6 +124,14 @@ CASES = [("fp32", 32, 1, 16, 1, "propagated", None), ("bf16", 32, 2, 16, 16, "eg
 # condition involves the float64 table and the bound only, never the code under test (the device of storage_cases.BATCH_SEED)
 BATCH_SEED = {}
 TIGHT_SHARE = 0.05
+# Batches of MN.LARGE_BATCH_SIZES = 65 and 300 samples (the loss reduction's second addition per lane, which no batch of CASES
+# reaches), at R = 2 and R = 16 with M = 1 and M = R; K in {1, 3}, every width, both storages, both reg rows.  The same condition
+# on the seed (tests/test_hard_neg_host.py::test_the_reference_alone_discriminates runs over both lists).
+LARGE_CASES = [("fp32", 32, 1, 2, 1, "propagated", None), ("bf16", 64, 3, 16, 16, "ego", None),
+               ("fp32", 128, 3, 2, 2, "propagated", None), ("bf16", 256, 1, 16, 1, "ego", None)]
+assert not set(LARGE_CASES) & set(CASES) and {c[1] for c in LARGE_CASES} == set(MN.DS) and {c[2] for c in LARGE_CASES} == {1, 3}
+assert {(c[3], c[4]) for c in LARGE_CASES} == {(R, M) for R in MN.LARGE_RS for M in (1, R)}
+assert {c[0] for c in LARGE_CASES} == {"fp32", "bf16"} and {c[5] for c in LARGE_CASES} == {"propagated", "ego"}
 
 
 def case_id(c):
@@ -135,5 +143,8 @@ def case_batches(c, seed=None):
     """The batches of 64, 37 and 1 samples of a case (multineg_restatement.make_batches: a user in several samples, the same item
     twice among one sample's candidates, the hub rows, the isolated item, the last table row, the hand-set rows)."""
     mode, d, K, R, M, reg, feat = c
-    seq = MN.make_batches(d, K, R, BATCH_SEED.get(case_id(c), 0) if seed is None else seed)
+    seed = BATCH_SEED.get(case_id(c), 0) if seed is None else seed
+    if c in LARGE_CASES:                                                   # the batches of 65 and 300 samples
+        return MN.make_batches(d, K, R, seed, sizes=MN.LARGE_BATCH_SIZES)
+    seq = MN.make_batches(d, K, R, seed)
     return [seq[0], seq[2], seq[3]]

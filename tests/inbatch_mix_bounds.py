@@ -62,6 +62,22 @@ CASES = [
 ]
 AXES = (BS, RS, DS, KS, MS, REGS, TS, OS)
 STEPS = 2
+# The batch sizes the loss is trained and timed at (tests/test_gpu_inbatch_mix.py, section 1b).  CASES reaches many parts only
+# through the ITEM tiles; the user side of the step (the pool rows' and the positives' sweep over the users, NPu parts) never has
+# more than two there.  (2048, 1): the default --bpr_batch, 128 item tiles = 16 parts, EIGHT user parts; (545, 16): 18 user tiles
+# = three user parts, the third ragged (two tiles, the last with one live row), 17 x 18 = 306 item tiles = 39 parts, the last
+# ragged.  K in {1, 3}; every width twice; both storages on the register form (d <= 64) and on the streamed one (d >= 128).
+LARGE_BRS = ((2048, 1), (545, 16))
+LARGE_CASES = [
+    (2048, 1, 64, 1, "bf16", "propagated", 0.1, ("cosine", True)),
+    (2048, 1, 128, 3, "fp32", "ego", 0.2, ("dot", False)),
+    (2048, 1, 32, 3, "fp32", "propagated", 0.2, ("dot", False)),
+    (2048, 1, 256, 1, "bf16", "ego", 0.1, ("cosine", True)),
+    (545, 16, 32, 1, "bf16", "ego", 0.1, ("cosine", True)),
+    (545, 16, 256, 3, "fp32", "propagated", 0.2, ("dot", False)),
+    (545, 16, 64, 3, "fp32", "ego", 0.2, ("cosine", True)),
+    (545, 16, 128, 1, "bf16", "propagated", 0.1, ("dot", False)),
+]
 
 
 def case_id(c):
@@ -86,6 +102,24 @@ def parts_users(B):
 
 def _c(n):
     return int(np.ceil(n / 64.0)) + 8
+
+
+def _check_large_cases():
+    """What LARGE_CASES must reach, asserted at import (no device)."""
+    cs = LARGE_CASES
+    assert {(c[0], c[1]) for c in cs} == set(LARGE_BRS)
+    assert {parts_users(c[0]) for c in cs} == {3, 8} and all(parts_items(c[0], c[1]) > parts_users(c[0]) for c in cs)
+    assert all(sum(c[2] == d for c in cs) >= 2 for d in DS) and {c[3] for c in cs} == {1, 3}
+    assert all({c[4] for c in cs if ok(c[2])} == set(MS) for ok in (lambda d: d <= 64, lambda d: d >= 128))
+    assert {c[5] for c in cs} == set(REGS) and {c[7] for c in cs} == set(OS)
+    for c in cs:
+        for u, p, negs in case_batches(c):
+            B = len(u)
+            assert negs.shape == (c[0], c[1]) and IB.kept_share(u, p) > 0.5
+            assert u[B - 1] in u[:IB.PART_ROWS] and p[B - 1] in p[:IB.PART_ROWS] and negs[B - 1, 0] in p[:IB.PART_ROWS]      # across parts
+
+
+_check_large_cases()
 
 
 def bounds(adj, r, batch, B, K, d, mode, ego, tau, cosine, lq, only_term=False):

@@ -179,7 +179,9 @@ def make_batch(B, R, seed=0, plain=False):
     """One batch (u [B], p [B], negs [B, R]) on the graph of tests/storage_cases.py: (u, p) is inbatch_restatement.make_batch's,
     the negatives are uniform; unless `plain`: a duplicate pool id inside one sample (R >= 2) and across samples (B >= 3), the
     hub / hand-set item rows in the pool (B >= 31), and (B R >= 2) negs[1 % B, R - 1] = p_0 -- a pool id that is masked for sample 0
-    and, being another sample's positive, stands twice among the columns of every other sample."""
+    and, being another sample's positive, stands twice among the columns of every other sample; from B = 513 on (three parts of
+    the user sweep; (u, p) then repeat a user and a positive across parts) a positive of rows 0..255 as a negative of the last
+    part, and a pool id twice across parts 0 / 1."""
     u, p = IB.make_batch(B, seed)
     rng = np.random.Generator(np.random.PCG64(9000 * seed + 16 * B + R))
     negs = rng.integers(30, SC.M_ITEMS - 10, (B, R))
@@ -196,6 +198,9 @@ def make_batch(B, R, seed=0, plain=False):
         negs[3, 0] = SC.HUB_ITEM; negs[4, R - 1] = SC.OUTLIER_ITEM; negs[5, 0] = SC.SUBNORMAL_ITEM; negs[6, R - 1] = SC.M_ITEMS - 1
     if B * R >= 2:                                                          # (never the only pool id: the pool would be empty)
         negs[1 % B, R - 1] = p[0]
+    if B >= IB.MANY_PARTS_B:                                                # the pool across the PARTS of the user sweep (a pool row
+        negs[B - 1, 0] = p[21]                                              #   sweeps the users): a positive of part 0 as a negative of
+        negs[300, R - 1] = negs[8, 0]                                       #   the last part; a duplicate across parts 0 / 1
     return u, p, negs
 
 

@@ -110,12 +110,29 @@ def step(A, n_users, K, decay, tau, table, batch, reg_ego=False, w=None, B_norm=
 PART_ROWS = 256
 SPLIT_B = 260
 BATCH_SIZES = (1, 2, 31, 32, 33, 65, 100, SPLIT_B)
+# The sizes at which code runs that no batch of BATCH_SIZES reaches: 513 is 17 tiles = THREE parts, the third one tile with one
+# live row (the merge loop over the parts, the blockIdx.y extent and the per-part addressing beyond two parts); 2048 is the
+# default --bpr_batch: 64 tiles, eight full parts.
+MANY_PARTS_B = 513
+LARGE_BATCH_SIZES = (MANY_PARTS_B, 2048)
+
+
+def parts(B):
+    """The part count of the sweep over a batch of B samples (lgcn_inbatch_parts)."""
+    return (((B + 31) // 32) + 7) // 8
+
+
+def last_part_rows(B):
+    """The rows of the last part of the sweep: from PART_ROWS (parts - 1) to B - 1."""
+    return np.arange(PART_ROWS * (parts(B) - 1), B)
 
 
 def make_batch(B, seed=0):
     """One batch (u [B], p [B]) on the graph of tests/storage_cases.py: unmasked at B <= 2; from B = 31 on a user in several
     samples and a positive drawn twice inside the first tile, the hub rows, the hand-set rows and the last table rows; from
-    B = 65 on the same user and the same positive also ACROSS two tiles.  (300 users: a batch of 100 repeats users by itself.)"""
+    B = 65 on the same user and the same positive also ACROSS two tiles; from B = 513 (three parts of the sweep) on the same user
+    and the same positive also across PARTS: one sample in rows 0..255, one in the last part (row B - 1: at B = 513 the last part
+    is that row alone), and one pair across parts 0 / 1.  (300 users: a batch of 100 repeats users by itself.)"""
     rng = np.random.Generator(np.random.PCG64(7000 * seed + B))
     u = rng.integers(20, SC.N_USERS, B); p = rng.integers(30, SC.M_ITEMS - 10, B)
     p[(p == SC.BIG_ITEM) | (p == SC.ISOLATED_ITEM)] = 40
@@ -129,7 +146,17 @@ def make_batch(B, seed=0):
     if B >= 65:
         u[40] = u[2]; p[50] = p[15]                               # across tiles 0 / 1
         u[64] = u[16]; p[B - 1] = p[17]                           # across tiles 0 / 2 (.. the last)
+    if B >= MANY_PARTS_B:
+        u[B - 1] = u[18]                                          # across parts 0 / the last (the positive: p[B - 1] = p[17] above)
+        u[300] = u[19]; p[400] = p[20]                            # across parts 0 / 1
     return u, p
+
+
+def kept_share(u, p):
+    """The smallest share of its B - 1 possible competitors that a sample of the batch keeps (300 users, 560 items: a large batch
+    masks some pairs by itself)."""
+    B = len(u)
+    return float(competitors(u, p).sum(1).min()) / max(B - 1, 1)
 
 
 def make_batches(B, steps=3, seed=0):

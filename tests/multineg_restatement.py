@@ -125,14 +125,22 @@ def case_batches(d, K, R, reg):
     return make_batches(d, K, R, BATCH_SEED.get((d, K, R, reg), 0))
 
 
-def make_batches(d, K, R, seed=0):
-    """Batches of 64, 64, 37 and 1 samples (u [B], p [B], negs [B, R]) on the graph of tests/storage_cases.py.  Every batch
-    sequence holds: a user in several samples, an item that is one sample's positive and another's negative, the same item twice
-    among one sample's negatives, the isolated item and the last table row as negatives, the hub user and the hub item, the
-    hand-set rows."""
+# reduce_loss_wave adds terms[lane], terms[lane + 64], ..: with B <= 64 the per-sample terms of the multi-negative, softmax and
+# hard-negative steps (scaled by inv_R, read with terms_stride) never take the second addition.  65: one lane takes it; 300: every
+# lane takes four or five.  Both also leave a last 64-sample block that is not full.
+LARGE_BATCH_SIZES = (65, 300)
+LARGE_RS = (2, 16)
+assert all(-(-B // 64) >= 2 for B in LARGE_BATCH_SIZES) and all(-(-B // 64) == 1 for B in BATCH_SIZES)
+
+
+def make_batches(d, K, R, seed=0, sizes=BATCH_SIZES):
+    """Batches of 64, 64, 37 and 1 samples (u [B], p [B], negs [B, R]) on the graph of tests/storage_cases.py (or of `sizes`
+    samples).  Every batch sequence holds: a user in several samples, an item that is one sample's positive and another's
+    negative, the same item twice among one sample's negatives, the isolated item and the last table row as negatives, the hub
+    user and the hub item, the hand-set rows."""
     rng = np.random.Generator(np.random.PCG64(100000 * seed + 1000 * R + d + K))
     out = []
-    for nb in BATCH_SIZES:
+    for nb in sizes:
         u = rng.integers(1, SC.N_USERS, nb); p = rng.integers(1, SC.M_ITEMS, nb); n = rng.integers(1, SC.M_ITEMS, (nb, R))
         for a in (p, n):                                          # the big row propagates, no slot names it (no saturated sigmoid)
             a[(a == SC.BIG_ITEM) | (a == SC.ISOLATED_ITEM)] = 20

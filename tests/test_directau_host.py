@@ -17,7 +17,7 @@ import inbatch_restatement as IB                 # noqa: E402
 import storage_cases as SC                       # noqa: E402
 from storage_cases import storage_graph          # noqa: E402,F401  (fixture: the graph, written once per session)
 from conftest import REPO                        # noqa: E402
-from test_inbatch_host import _inputs, _model_with   # noqa: E402
+from test_inbatch_host import _inputs, _model_with, _pin   # noqa: E402
 
 
 def _batches():
@@ -54,6 +54,31 @@ def test_restatement_is_the_autograd_of_the_written_loss(pkg, storage_graph, d, 
                 # the projected parts are orthogonal to their rows
                 for g, e in ((r["ga_u"] + r["gu_u"], r["e_u"]), (r["ga_p"] + r["gu_p"], r["e_p"])):
                     assert float(((g * e).sum(1)).abs().max()) <= 1e-12 * float(g.abs().max() + 1e-300) * float(e.abs().max()) * d
+
+
+@pytest.mark.parametrize("reg", ["propagated", "ego"])
+def test_restatement_is_the_autograd_of_the_written_loss_across_three_parts(pkg, storage_graph, reg):
+    """The same pin at B = 705 (23 tiles x 3 parts = 69 partials of the normaliser; a user, an item and a mirror repeated across
+    parts), d = 64, K = 3, gamma = 1: the restatement judges the device at B = 705, 736 and 2048 (tests/test_gpu_directau.py,
+    section 1b).  1e-12 relative, as above."""
+    A, table = _inputs(pkg, storage_graph, 64)
+    B, K = DA.MERGE_B, 3
+    batch = DA.make_batch(B)
+    u, p = batch
+    assert DA.partials(B) == 69 and u[B - 1] in u[:256] and p[B - 1] in p[:256] and (u[500], p[500]) == (u[14], p[14])
+    for w in (None, [0.4, 0.1, 0.3, 0.2]):
+        r = DA.step(A, SC.N_USERS, K, SC.DECAY, 1.0, table, batch, reg == "ego", w)
+        assert float(r["inv_u"].min()) > 0.0 and float(r["inv_p"].min()) > 0.0
+        _pin(r, lambda E, E0: DA.loss(E, E0, SC.N_USERS, batch, SC.DECAY, 1.0, reg == "ego"), A, table, K, w, B)
+
+
+def test_the_blocked_distance_matrix_is_the_whole_one(pkg, storage_graph):
+    """directau_restatement.side forms the squared distances in blocks of 64 rows: array-equal to the one-expression form."""
+    A, table = _inputs(pkg, storage_graph, 32)
+    x = DA.unit(torch.from_numpy(table[20:277].astype(np.float64)))[0]
+    k = DA.side(x, 1.0, len(x))[0]
+    d2 = ((x[:, None, :] - x[None, :, :]) ** 2).sum(2)
+    assert torch.equal(k, torch.exp(-2.0 * d2) * (1.0 - torch.eye(len(x), dtype=DA.F64)))
 
 
 # ---- (b) the conventions ------------------------------------------------------------------------------------------------------

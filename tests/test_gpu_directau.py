@@ -17,7 +17,8 @@ tests/test_gpu_inbatch.py and tests/test_gpu_softmax.py) and are not repeated: t
                 delta_k = k (expm1(2 delta_D2) + 2 u exp(2 delta_D2)).     k is in [e^-8, 1]: no shift, no underflow.
   Z             every pair b < c once, all terms > 0.  A term passes at most 16 * 8 = 128 additions in its lane (16 rows a
                 tile, 8 tiles a part), 6 in the wave's xor tree, ceil(tiles * parts / 64) in the merge's lane-strided sum and 6
-                in its tree: nZ = 140 + ceil(tiles * parts / 64) (141 up to B = 2048).
+                in its tree: nZ = 140 + ceil(tiles * parts / 64) (directau_bounds.z_additions: 141 up to B = 672 = 21 tiles x 3
+                parts, 142 from 22 tiles x 3 parts = 66 partials on, 148 at B = 2048 = 64 tiles x 8 parts).
                 delta_Z = nZ u (Z + sum delta_k) + sum_{b<c} delta_k.  A zero row that lost its mask would add exp(-4) per pair.
   unif          logf(Z / fl(npairs)): two roundings in the argument (2 u absolute in the log), logf to 1 ulp:
                 delta_unif = -log1p(-delta_Z / Z) + 2 u + 2 u |unif|;   the constant gamma (unif(X) + unif(Y)) / 2: gamma as fp32,
@@ -179,6 +180,45 @@ def test_steps_equal_the_restatement(pkg, storage_graph, B, d, K, mode, reg, wts
     _run(pkg, storage_graph, mode, d, K, B, 1.0, reg, w=WTS[:K + 1] if wts else None)
 
 
+# ---- 1b. the batch sizes the loss is trained and timed at ----------------------------------------------------------------------
+# DA.LARGE_BATCH_SIZES.  k_directau_merge adds n = tiles x parts partials per side in a lane-strided loop over 64 lanes: up
+# to 21 tiles (B <= 672) n <= 63 and the loop body runs at most once per lane.  B = 705: n = 69 (the last tile holds one live row); B = 736: the
+# same count with full tiles; B = 2048 (the default --bpr_batch): n = 512, eight per lane.  From three parts on the symmetric
+# sweep also has workgroups whose whole part lies below the owner tile in the MIDDLE of the sweep (DA.skipped_parts), and the
+# blockIdx.y extent of k_directau_norm / k_directau_grad and part[(side * NP + by) * nT + bx] run beyond by = 1.  The bounds are
+# those of the module docstring, unchanged: nZ = directau_bounds.z_additions(B) counts the merge's additions, NP and n = min(Bp,
+# 256) are functions of B, c(B) the loss reduction's.  d = 256 stays at B = 736 (the float64 restatement costs B^2 d and decides
+# the time of a case); two steps per case.
+_LARGE_CASES = [
+    (705, 32, 1, 'fp32', 'ego', False),
+    (705, 128, 3, 'bf16', 'propagated', False),
+    (736, 256, 1, 'bf16', 'ego', False),
+    (736, 64, 3, 'fp32', 'propagated', True),
+    (736, 256, 3, 'fp32', 'propagated', False),
+    (2048, 64, 1, 'bf16', 'propagated', False),
+    (2048, 128, 3, 'fp32', 'ego', False),
+    (2048, 32, 3, 'bf16', 'ego', False),
+]
+assert {c[0] for c in _LARGE_CASES} == set(DA.LARGE_BATCH_SIZES)
+assert all(DA.partials(c[0]) > 64 for c in _LARGE_CASES) and DA.partials(672) == 63 and DA.partials(705) == DA.partials(736) == 69
+assert DA.partials(2048) == 512 and max(DA.partials(c[0]) for c in _CASES) == 18
+assert {DB.z_additions(B) for B in DA.LARGE_BATCH_SIZES} == {142, 148} and DB.z_additions(672) == 141 and DB.z_additions(673) == 142
+assert {DB.parts(c[0]) for c in _LARGE_CASES} == {3, 8} and all(DA.skipped_parts(c[0]) for c in _LARGE_CASES) and not DA.skipped_parts(257)
+assert all(sum(c[1] == d_ for c in _LARGE_CASES) >= 2 for d_ in _DS) and {c[2] for c in _LARGE_CASES} == set(_KS)
+assert all({c[3] for c in _LARGE_CASES if ok(c[1])} == set(_MS) for ok in (lambda d_: d_ <= 64, lambda d_: d_ >= 128))
+assert {c[4] for c in _LARGE_CASES} == {"propagated", "ego"} and all(c[0] <= 736 for c in _LARGE_CASES if c[1] == 256)
+for _c_ in _LARGE_CASES:
+    for _u, _p in DA.make_batches(_c_[0], 2, seed=_c_[1] + _c_[2]):
+        assert _u[-1] in _u[:256] and _p[-1] in _p[:256]              # across parts: rows 0..255 / the last part
+
+
+@pytest.mark.parametrize("B,d,K,mode,reg,wts", [pytest.param(*c, id=f"B{c[0]}-d{c[1]}-K{c[2]}-{c[3]}-{c[4]}{'-wts' if c[5] else ''}") for c in _LARGE_CASES])
+def test_steps_equal_the_restatement_at_the_training_batch_sizes(pkg, storage_graph, B, d, K, mode, reg, wts):
+    """Section 1 at B = 705, 736 and 2048: the same links within the same derived bounds, over two consecutive batches that repeat
+    a user and an item across parts.  The Z / unif / coefficient lines are the ones a merge that dropped partials would miss."""
+    _run(pkg, storage_graph, mode, d, K, B, 1.0, reg, w=WTS[:K + 1] if wts else None)
+
+
 def test_gamma_zero_and_another_gamma(pkg, storage_graph):
     """gamma = 0: the alignment loss alone (no coefficient leaves, the gradient launch adds nothing); gamma = 0.3: not the default."""
     _run(pkg, storage_graph, "fp32", 64, 3, 33, 0.0, steps=1)
@@ -202,6 +242,30 @@ def test_void_samples_and_padding_are_masked(pkg, storage_graph, B):
         assert all(v <= 1.0 for v in share.values()), share
         lost = (B - 2) * np.exp(-4.0)
         assert lost > 10 * bd["dZ"][0] and lost > 10 * bd["dZ"][1], (lost, bd["dZ"])
+        with pytest.raises(pkg._lib.LgcnError, match="out-of-range"):
+            m.check_device_errors()
+        assert not bool(m._dev['G64'].any())
+    finally:
+        pkg.world.configure([])
+
+
+def test_void_samples_in_the_last_part(pkg, storage_graph):
+    """test_void_samples_and_padding_are_masked at B = 705 (three parts, 69 partials): a void sample in row 0, one in part 1 (row
+    300) and the only live row of the last tile (704), beside its 31 padding rows.  The bound of Z grows with the pair count, one
+    lost row's exp(-4) per sound row only with B: here it is asserted to exceed TWICE the bound, which is what it takes for a
+    result that is off by it to lie outside the bound whatever the rounding (|error| <= bound)."""
+    try:
+        d, K, B = 64, 1, DA.MERGE_B
+        u, p = DA.make_batch(B, seed=5)
+        u, p = u.copy(), p.copy()
+        void = (0, 300, B - 1)
+        u[0] = SC.N_USERS + 3; p[300] = SC.M_ITEMS; p[B - 1] = -2
+        _, m = _model(pkg, storage_graph, "fp32", d, K, batch=B, **_cfg(1.0))
+        share, r, (_, _, _, _, bd, _) = _judge(pkg, m, (u, p), K, d, "fp32", "propagated", 1.0, 1, f"void B={B}", void=void)
+        assert all(v <= 1.0 for v in share.values()), share
+        lost = (B - 3) * np.exp(-4.0)
+        print(f"[directau] void B={B}: a lost mask adds {lost:.3g} to Z, the bounds of Z are {bd['dZ'][0]:.3g} / {bd['dZ'][1]:.3g}")
+        assert lost > 2 * bd["dZ"][0] and lost > 2 * bd["dZ"][1], (lost, bd["dZ"])
         with pytest.raises(pkg._lib.LgcnError, match="out-of-range"):
             m.check_device_errors()
         assert not bool(m._dev['G64'].any())

@@ -105,10 +105,21 @@ def _tables_read(pkg, m, case):
 # ---- A + B ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", HN.CASES, ids=HN.case_id)
 def test_selection_is_valid_and_the_step_is_the_bpr_step_on_it(pkg, storage_graph, case):
+    _selection_and_step(pkg, storage_graph, case)
+
+
+@pytest.mark.parametrize("case", HN.LARGE_CASES, ids=HN.case_id)
+def test_selection_and_step_beyond_one_wave_of_terms(pkg, storage_graph, case):
+    """A and B on batches of 65 and 300 samples (HN.LARGE_CASES) in contexts of 300: reduce_loss_wave's second addition per lane,
+    which no batch of HN.CASES reaches, on this step's scaled terms; the same assertions."""
+    _selection_and_step(pkg, storage_graph, case, cap=max(MN.LARGE_BATCH_SIZES))
+
+
+def _selection_and_step(pkg, storage_graph, case, cap=64):
     mode, d, K, R, M, reg, feat = case
     try:
-        mN = _model(pkg, storage_graph, case)
-        mO = _model(pkg, storage_graph, case, hard=False)
+        mN = _model(pkg, storage_graph, case, batch=cap)
+        mO = _model(pkg, storage_graph, case, hard=False, batch=cap)
         assert mN._dev['dense_last'] and mO._dev['dense_last'] and mN.hard_neg == M
         assert pkg._lib.load().lgcn_ctx_get_hard_neg(mN._dev['ctx']) == M and pkg._lib.load().lgcn_ctx_get_hard_neg(mO._dev['ctx']) == 0
         w = None if mN.layer_weights is None else [float(v) for v in mN.layer_weights]

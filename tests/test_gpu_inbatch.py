@@ -314,6 +314,52 @@ def test_steps_equal_the_restatement(pkg, storage_graph, B, d, K, mode, reg, tau
     _run(pkg, storage_graph, mode, d, K, B, tau, reg)
 
 
+# ---- 1b. the batch sizes the loss is trained and timed at ----------------------------------------------------------------------
+# IB.LARGE_BATCH_SIZES: 513 = 17 tiles = three parts of the sweep, the third a single tile with one live row; 2048 = the default
+# --bpr_batch, eight full parts.  No batch of section 1 has more than two parts, so the merge loop of k_inbatch_diag over the
+# parts, the blockIdx.y extent of k_inbatch_norm / k_inbatch_grad beyond 2 and the addressing part + (by * Bp + b) * 2 for by >= 2
+# run here first.  The bounds are section 1's, unchanged: every line is a function of B through NP (kZ, the fixed-point line),
+# n = min(Bp, 256) (the chain of one part) and c(B) (the loss reduction: ceil(B / 64) = 32 additions in the lane at 2048).
+# Together with tests/test_gpu_inbatch_scores.py (the other three score options) every width stands twice among the in-batch
+# cases of these sizes; two steps per case: the float64 restatement decides the time.
+LARGE_STEPS = 2
+_LARGE_CASES = [
+    (513, 32, 1, 'fp32', 'ego', 0.2),
+    (513, 128, 3, 'bf16', 'propagated', 1.0),
+    (2048, 64, 3, 'bf16', 'ego', 1.0),
+    (2048, 256, 1, 'fp32', 'propagated', 0.2),
+]
+
+
+def large_batches(B, d, K):
+    return IB.make_batches(B, LARGE_STEPS, seed=d + K)
+
+
+def check_large_cases(cases, batches_of):
+    """What a list of (B, d, K, mode, reg, ..) cases at the large sizes must reach (asserted at import, without a device)."""
+    assert {c[0] for c in cases} == set(IB.LARGE_BATCH_SIZES)
+    assert {_parts(c[0]) for c in cases} >= {3, 8}
+    assert all(any(_parts(c[0]) >= 3 and ok(c[1]) for c in cases) for ok in (lambda d: d <= 64, lambda d: d >= 128))
+    assert {c[2] for c in cases} == {1, 3} and {c[3] for c in cases} == {"fp32", "bf16"}
+    assert {c[4] for c in cases if c[0] >= IB.MANY_PARTS_B} == {"propagated", "ego"}
+    for c in cases:
+        for u, p in (b[:2] for b in batches_of(c)):
+            B, last = len(u), IB.last_part_rows(len(u))
+            assert B == c[0] and IB.kept_share(u, p) > 0.5, (c, IB.kept_share(u, p))
+            assert last[0] >= IB.PART_ROWS and u[B - 1] in u[:IB.PART_ROWS] and p[B - 1] in p[:IB.PART_ROWS]      # across parts
+
+
+check_large_cases(_LARGE_CASES, lambda c: large_batches(c[0], c[1], c[2]))
+
+
+@pytest.mark.parametrize("B,d,K,mode,reg,tau", [pytest.param(*c, id=f"B{c[0]}-d{c[1]}-K{c[2]}-{c[3]}-{c[4]}-tau{c[5]}") for c in _LARGE_CASES])
+def test_steps_equal_the_restatement_at_the_training_batch_sizes(pkg, storage_graph, B, d, K, mode, reg, tau):
+    """Section 1 at B = 513 and B = 2048 (three and eight parts of the sweep): per-sample terms, loss_out, the gradient recovered
+    from Adam's first moment and Adam itself within the same derived bounds, over two consecutive batches that repeat a user and
+    a positive across parts (rows 0..255 / the last part)."""
+    _run(pkg, storage_graph, mode, d, K, B, tau, reg, batches=large_batches(B, d, K))
+
+
 # ---- 2. masks and voids ------------------------------------------------------------------------------------------------------
 def test_duplicates_inside_one_tile_and_across_tiles(pkg, storage_graph):
     """The batch of 65 (three tiles): the same user and the same positive inside tile 0, across tiles 0 / 1 and 0 / 2."""
@@ -356,6 +402,31 @@ def test_voided_samples(pkg, storage_graph, what):
                 p[v_] = SC.M_ITEMS + i if i != 1 else -3
         _, m = _model(pkg, storage_graph, "fp32", d, K, batch=B, loss='inbatch', softmax_temp=0.2)
         share = _judge(pkg, m, (u, p), K, d, "fp32", "propagated", _tau32(0.2), 1, f"void {what}", void=void)[0]
+        assert all(v <= 1.0 for v in share.values()), share
+        with pytest.raises(pkg._lib.LgcnError, match="out-of-range"):
+            m.check_device_errors()
+        assert not bool(m._dev['G64'].any())
+    finally:
+        pkg.world.configure([])
+
+
+@pytest.mark.parametrize("what", ["user", "pos", "both"])
+def test_voided_samples_in_the_last_part(pkg, storage_graph, what):
+    """test_voided_samples at B = 513: the bad ids at row 0, in part 1 (row 300) and in the last part, whose only live row (512) is
+    then void -- a part with no sound sample at all.  The samples are void as rows and as columns of every part."""
+    try:
+        d, K, B = 64, 1, IB.MANY_PARTS_B
+        u, p = IB.make_batch(B, seed=5)
+        u, p = u.copy(), p.copy()
+        void = (0, 300, B - 1)
+        assert IB.last_part_rows(B).tolist() == [B - 1]
+        for i, v_ in enumerate(void):
+            if what in ("user", "both"):
+                u[v_] = SC.N_USERS + i if i != 1 else -1
+            if what in ("pos", "both"):
+                p[v_] = SC.M_ITEMS + i if i != 1 else -3
+        _, m = _model(pkg, storage_graph, "fp32", d, K, batch=B, loss='inbatch', softmax_temp=0.2)
+        share = _judge(pkg, m, (u, p), K, d, "fp32", "propagated", _tau32(0.2), 1, f"void {what} B={B}", void=void)[0]
         assert all(v <= 1.0 for v in share.values()), share
         with pytest.raises(pkg._lib.LgcnError, match="out-of-range"):
             m.check_device_errors()

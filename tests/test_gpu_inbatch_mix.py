@@ -116,7 +116,40 @@ def test_steps_equal_the_restatement(pkg, storage_graph, case):
     _run(pkg, storage_graph, mode, d, K, B, R, tau, reg, score, lq_on, MB.case_batches(case))
 
 
+# ---- 1b. the batch sizes the loss is trained and timed at ----------------------------------------------------------------------
+@pytest.mark.parametrize("case", [pytest.param(c, id=MB.case_id(c)) for c in MB.LARGE_CASES])
+def test_steps_equal_the_restatement_at_the_training_batch_sizes(pkg, storage_graph, case):
+    """Section 1 at (B, R) = (2048, 1) and (545, 16) (inbatch_mix_bounds.LARGE_CASES): eight and three parts on the USER side of the
+    step, which section 1 never takes beyond two; the same links within the same derived bounds (functions of B and R through
+    NP, NPu, the chain lengths and c(B)), over two consecutive batches that repeat a user, a positive and a pool id across parts."""
+    B, R, d, K, mode, reg, tau, (score, lq_on) = case
+    _run(pkg, storage_graph, mode, d, K, B, R, tau, reg, score, lq_on, MB.case_batches(case))
+
+
 # ---- 2. voids ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("score,lq_on", MB.OS)
+def test_an_out_of_range_negative_in_the_last_part_voids_the_sample(pkg, storage_graph, score, lq_on):
+    """test_an_out_of_range_negative_voids_the_sample at B = 513 (three user parts, the third one tile with one live row): the bad
+    negatives in part 1 (row 300) and in row 512, after which the last user part holds no sound sample at all."""
+    try:
+        d, K, B, R = 64, 1, IB.MANY_PARTS_B, 2
+        u, p, negs = IM.make_batch(B, R, seed=5)
+        negs = negs.copy()
+        void = (300, B - 1)
+        assert IB.last_part_rows(B).tolist() == [B - 1]
+        negs[B - 1, 1] = SC.M_ITEMS + 2
+        negs[300, 0] = -1
+        ds, m = _model(pkg, storage_graph, "fp32", d, K, batch=B, **_cfg(0.2, R, score, lq_on))
+        share = _judge(pkg, ds, m, (u, p, negs), K, d, "fp32", "propagated", MB.tau32(0.2), 1, f"void negative {score} B={B}", score, lq_on, void=void)[0]
+        assert all(v <= 1.0 for v in share.values()), share
+        with pytest.raises(pkg._lib.LgcnError, match="out-of-range"):
+            m.check_device_errors()
+        assert not bool(m._dev['G64'].any())
+    finally:
+        pkg.world.configure([])
+
+
+
 @pytest.mark.parametrize("score,lq_on", MB.OS)
 def test_an_out_of_range_negative_voids_the_sample(pkg, storage_graph, score, lq_on):
     """One negative id beyond the items (and one below zero) in a batch of 65, R = 2: err is set, the id check precedes the lq

@@ -43,6 +43,7 @@ from conftest import spmm_sum_bound
 from storage_cases import storage_graph  # noqa: F401  (fixture: the graph, written once per session)
 from test_gpu_gate_shapes import W1, _adam_checks
 from test_gpu_inbatch import _G, _c, _dev, _model, _parts, _same, _snapshot, _state, _tau32, _uncovered
+from test_gpu_inbatch import _LARGE_CASES as _PLAIN_LARGE_CASES, check_large_cases, large_batches
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -299,6 +300,29 @@ def test_steps_equal_the_restatement(pkg, storage_graph, B, d, K, mode, reg, tau
     _run(pkg, storage_graph, mode, d, K, B, tau, reg, opt[0], opt[1])
 
 
+# ---- 1b. the batch sizes the loss is trained and timed at ----------------------------------------------------------------------
+# tests/test_gpu_inbatch.py section 1b for the three new score options: B = 513 (three parts, the third one tile with one live
+# row) and B = 2048 (eight parts).  The projection runs per part and the parts meet in G64, so cosine reaches the per-part
+# addressing of t and of the partial rows beyond two parts here first.  The bounds are section 1's, unchanged (functions of B
+# through NP, n = min(Bp, 256) and c(B)).  With the four dot cases of tests/test_gpu_inbatch.py every width stands twice.
+_LARGE_CASES = [
+    (513, 64, 1, 'bf16', 'propagated', 0.2, ('cosine', False)),
+    (513, 256, 3, 'fp32', 'ego', 0.1, ('dot', True)),
+    (2048, 32, 3, 'fp32', 'propagated', 0.1, ('cosine', True)),
+    (2048, 128, 1, 'bf16', 'ego', 0.2, ('cosine', True)),
+]
+check_large_cases(_LARGE_CASES, lambda c: large_batches(c[0], c[1], c[2]))
+assert {c[6] for c in _LARGE_CASES} == set(_OS)
+assert sorted(c[1] for c in _LARGE_CASES + _PLAIN_LARGE_CASES) == [32, 32, 64, 64, 128, 128, 256, 256]
+
+
+@pytest.mark.parametrize("B,d,K,mode,reg,tau,opt", [pytest.param(*c, id=f"B{c[0]}-d{c[1]}-K{c[2]}-{c[3]}-{c[4]}-tau{c[5]}-{c[6][0]}{'-logq' if c[6][1] else ''}") for c in _LARGE_CASES])
+def test_steps_equal_the_restatement_at_the_training_batch_sizes(pkg, storage_graph, B, d, K, mode, reg, tau, opt):
+    """Section 1 at B = 513 and B = 2048: the same links within the same derived bounds, over two consecutive batches that repeat
+    a user and a positive across parts."""
+    _run(pkg, storage_graph, mode, d, K, B, tau, reg, opt[0], opt[1], batches=large_batches(B, d, K))
+
+
 # ---- 2. masks and voids ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("score,lq_on", _OS)
 def test_duplicates_inside_one_tile_and_across_tiles(pkg, storage_graph, score, lq_on):
@@ -327,6 +351,28 @@ def test_voided_samples(pkg, storage_graph, what):
                 p[v_] = SC.M_ITEMS + i if i != 1 else -3
         ds, m = _model(pkg, storage_graph, "fp32", d, K, batch=B, **_cfg(0.2, "cosine", True))
         share = _judge(pkg, ds, m, (u, p), K, d, "fp32", "propagated", _tau32(0.2), 1, f"void {what}", "cosine", True, void=void)[0]
+        assert all(v <= 1.0 for v in share.values()), share
+        with pytest.raises(pkg._lib.LgcnError, match="out-of-range"):
+            m.check_device_errors()
+        assert not bool(m._dev['G64'].any())
+    finally:
+        pkg.world.configure([])
+
+
+def test_voided_samples_in_the_last_part(pkg, storage_graph):
+    """test_voided_samples ("both") at B = 513, cosine + logq: the bad ids at row 0, in part 1 (row 300) and in the last part,
+    whose only live row (512) is then void."""
+    try:
+        d, K, B = 64, 1, IB.MANY_PARTS_B
+        u, p = IB.make_batch(B, seed=5)
+        u, p = u.copy(), p.copy()
+        void = (0, 300, B - 1)
+        assert IB.last_part_rows(B).tolist() == [B - 1]
+        for i, v_ in enumerate(void):
+            u[v_] = SC.N_USERS + i if i != 1 else -1
+            p[v_] = SC.M_ITEMS + i if i != 1 else -3
+        ds, m = _model(pkg, storage_graph, "fp32", d, K, batch=B, **_cfg(0.2, "cosine", True))
+        share = _judge(pkg, ds, m, (u, p), K, d, "fp32", "propagated", _tau32(0.2), 1, f"void both B={B}", "cosine", True, void=void)[0]
         assert all(v <= 1.0 for v in share.values()), share
         with pytest.raises(pkg._lib.LgcnError, match="out-of-range"):
             m.check_device_errors()

@@ -266,20 +266,21 @@ def _judge_pair(pkg, mN, mO, batch, R, K, d, mode, reg, step_no, tag, w=None, ke
     return share
 
 
-def _run_pair(pkg, path, mode, d, K, R, reg="propagated", w=None, dropout=None):
+def _run_pair(pkg, path, mode, d, K, R, reg="propagated", w=None, dropout=None, sizes=MN.BATCH_SIZES):
     try:
         cfg = {}
         if w is not None:
             cfg['layer_weights'] = str(list(w))
         if dropout is not None:
             cfg.update({'dropout': 1, 'keep_prob': dropout, 'seed': 2020})
-        _, mN = _model(pkg, path, mode, d, K, reg, dl=1, neg_ratio=R, **cfg)
-        mN._state(max_batch=64, need_ctx=True)
-        _, mO = _model(pkg, path, mode, d, K, reg, dl=1, batch=64 * R, **cfg)
-        mO._state(max_batch=64 * R, need_ctx=True)
+        cap = max(sizes)
+        _, mN = _model(pkg, path, mode, d, K, reg, dl=1, batch=cap, neg_ratio=R, **cfg)
+        mN._state(max_batch=cap, need_ctx=True)
+        _, mO = _model(pkg, path, mode, d, K, reg, dl=1, batch=cap * R, **cfg)
+        mO._state(max_batch=cap * R, need_ctx=True)
         assert mN._dev['dense_last'] and mO._dev['dense_last']
         top, bad = {}, []
-        for i, batch in enumerate(MN.make_batches(d, K, R)):
+        for i, batch in enumerate(MN.make_batches(d, K, R, sizes=sizes)):
             tag = f"{mode} d{d} K{K} R{R} {reg}" + (" wts" if w is not None else "") + (f" keep{dropout}" if dropout else "") + f" step {i + 1} B={len(batch[0])}"
             share = _judge_pair(pkg, mN, mO, batch, R, K, d, mode, reg, i + 1, tag, w=w, keep=dropout or 1.0)
             for k_, v in share.items():
@@ -302,6 +303,22 @@ def test_steps_equal_the_existing_step_on_the_flattened_batch(pkg, storage_graph
     """Per-sample terms, loss_out, the gradient recovered from Adam's first moment and Adam itself, new kernel against
     k_triplet_dense on the flattened batch from one state, each within the bound derived in the module docstring."""
     _run_pair(pkg, storage_graph, mode, d, K, R)
+
+
+# N reduces B per-sample terms, scaled by inv_R, with reduce_loss_wave (terms[lane], terms[lane + 64], ..): no batch above has
+# more than 64 samples, so its second addition is first taken here (MN.LARGE_BATCH_SIZES = 65, 300; c(B) in the loss_out line
+# counts it).  O reduces B R terms as before.  Every width, both storages, K in {1, 3}, both reg rows, R = 2 and 16.
+_LARGE_CASES = [(32, 3, 16, "fp32", "propagated"), (64, 1, 2, "bf16", "ego"), (128, 1, 16, "bf16", "propagated"), (256, 3, 2, "fp32", "ego")]
+assert {c[0] for c in _LARGE_CASES} == set(MN.DS) and {c[1] for c in _LARGE_CASES} == {1, 3} and {c[2] for c in _LARGE_CASES} == set(MN.LARGE_RS)
+assert {c[3] for c in _LARGE_CASES} == {"fp32", "bf16"} and {c[4] for c in _LARGE_CASES} == {"propagated", "ego"}
+assert all(_c(B) - 8 >= 2 for B in MN.LARGE_BATCH_SIZES)
+
+
+@pytest.mark.parametrize("d,K,R,mode,reg", [pytest.param(*c, id=f"d{c[0]}-K{c[1]}-R{c[2]}-{c[3]}-{c[4]}") for c in _LARGE_CASES])
+def test_pair_beyond_one_wave_of_terms(pkg, storage_graph, d, K, R, mode, reg):
+    """Batches of 65 and 300 samples (contexts of 300 and 300 R): the links of
+    test_steps_equal_the_existing_step_on_the_flattened_batch within the same bounds."""
+    _run_pair(pkg, storage_graph, mode, d, K, R, reg, sizes=MN.LARGE_BATCH_SIZES)
 
 
 def test_pair_with_reg_rows_ego(pkg, storage_graph):

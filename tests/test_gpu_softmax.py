@@ -246,16 +246,16 @@ def _judge(pkg, m, batch, R, K, d, mode, reg, tau, step_no, tag, w=None, keep=No
     return share, r, (term, regt, g_rec, slack, bd)
 
 
-def _run(pkg, path, mode, d, K, R, tau, reg="propagated", w=None, keep=None):
+def _run(pkg, path, mode, d, K, R, tau, reg="propagated", w=None, keep=None, sizes=MN.BATCH_SIZES):
     try:
         cfg = {'loss': 'softmax', 'softmax_temp': tau, 'neg_ratio': R}
         if w is not None:
             cfg['layer_weights'] = str(list(w))
         if keep is not None:
             cfg.update({'dropout': 1, 'keep_prob': keep, 'seed': 2020})
-        _, m = _model(pkg, path, mode, d, K, reg, dl=0, **cfg)           # --dense_last 0: _make_ctx must force the dense last layer
+        _, m = _model(pkg, path, mode, d, K, reg, dl=0, batch=max(sizes), **cfg)      # --dense_last 0: _make_ctx must force the dense last layer
         top, bad = {}, []
-        for i, batch in enumerate(SM.make_batches(d, K, R)):
+        for i, batch in enumerate(SM.make_batches(d, K, R, sizes=sizes)):
             tag = f"{mode} d{d} K{K} R{R} tau{tau} {reg}" + (" wts" if w is not None else "") + (f" keep{keep}" if keep else "") + f" step {i + 1} B={len(batch[0])}"
             share = _judge(pkg, m, batch, R, K, d, mode, reg, _tau32(tau), i + 1, tag, w=w, keep=keep)[0]
             for k_, v in share.items():
@@ -280,6 +280,21 @@ def test_steps_equal_the_restatement(pkg, storage_graph, d, R):
     """fp32 storage, K = 3, tau = 1: per-sample terms, loss_out, the gradient recovered from Adam's first moment, Adam itself,
     each within the bound derived in the module docstring, over batches of 64 / 64 / 37 / 1 samples."""
     _run(pkg, storage_graph, "fp32", d, 3, R, 1.0)
+
+
+# The per-sample terms of this step are scaled by inv_R and reduced by reduce_loss_wave, which adds terms[lane], terms[lane + 64],
+# ..: no batch above has more than 64 samples, so the second addition is first taken here (MN.LARGE_BATCH_SIZES = 65, 300; the
+# bound's c(B) = ceil(B / 64) + 8 counts it).  Every width, both storages, K in {1, 3}, both reg rows, R = 2 and 16.
+_LARGE_CASES = [(32, 1, 2, "bf16", "propagated", 1.0), (64, 3, 16, "fp32", "ego", 0.2), (128, 3, 2, "fp32", "propagated", 0.2), (256, 1, 16, "bf16", "ego", 1.0)]
+assert {c[0] for c in _LARGE_CASES} == set(MN.DS) and {c[1] for c in _LARGE_CASES} == {1, 3} and {c[2] for c in _LARGE_CASES} == set(MN.LARGE_RS)
+assert {c[3] for c in _LARGE_CASES} == {"fp32", "bf16"} and {c[4] for c in _LARGE_CASES} == {"propagated", "ego"}
+assert all(_c(B) - 8 >= 2 for B in MN.LARGE_BATCH_SIZES)
+
+
+@pytest.mark.parametrize("d,K,R,mode,reg,tau", [pytest.param(*c, id=f"d{c[0]}-K{c[1]}-R{c[2]}-{c[3]}-{c[4]}-tau{c[5]}") for c in _LARGE_CASES])
+def test_steps_equal_the_restatement_beyond_one_wave_of_terms(pkg, storage_graph, d, K, R, mode, reg, tau):
+    """Batches of 65 and 300 samples in a context of 300: the links of test_steps_equal_the_restatement within the same bounds."""
+    _run(pkg, storage_graph, mode, d, K, R, tau, reg, sizes=MN.LARGE_BATCH_SIZES)
 
 
 @pytest.mark.parametrize("K", [1, 2])

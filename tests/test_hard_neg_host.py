@@ -233,7 +233,7 @@ def test_hard_neg_zero_builds_what_was_built_before(pkg, storage_graph):
 
 
 # ---- 4. the GPU fixtures can discriminate -----------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", HN.CASES, ids=HN.case_id)
+@pytest.mark.parametrize("case", HN.CASES + HN.LARGE_CASES, ids=HN.case_id)
 def test_the_reference_alone_discriminates(pkg, storage_graph, case):
     """For every fixture of tests/test_gpu_hard_neg.py, from the float64 table alone (the case's initial table, float64 layers, no
     storage rounding): over the case's samples at most 5 % have a gap below 2 bound_b between the picked order statistic and a

@@ -64,6 +64,41 @@ def test_restatement_is_the_autograd_of_the_written_loss(pkg, storage_graph, d, 
                 assert float(r["W"].sum(1).abs().max()) <= 1e-15                     # every row of W sums to zero
 
 
+def _pin(r, loss_fn, A, table, K, w, B):
+    """A restatement r against torch float64 autograd of loss_fn(E, E0) -> (loss, sm, reg) at 1e-12 relative."""
+    E0 = torch.from_numpy(table.astype(np.float64)).requires_grad_(True)
+    E = IB.propagate(A, E0, K, w)
+    E.retain_grad()
+    loss, sm, reg_l = loss_fn(E, E0)
+    loss.backward()
+    for got, ref in zip(r["loss_out"], (loss.detach(), sm.detach(), reg_l.detach())):
+        assert abs(float(got) - float(ref)) <= 1e-12 * max(1.0, abs(float(ref)))
+    scale = float(E0.grad.abs().max())
+    assert float((r["G"] - E.grad).abs().max()) <= 1e-12 * scale
+    assert float((r["g_final"] - E0.grad).abs().max()) <= 1e-12 * scale
+    assert abs(-float(r["term"].sum()) / B - float(sm.detach())) <= 1e-12
+    assert abs(0.5 * float(r["regterm"].sum()) / B - float(reg_l.detach())) <= 1e-12
+
+
+@pytest.mark.parametrize("reg", ["propagated", "ego"])
+def test_restatement_is_the_autograd_of_the_written_loss_across_three_parts(pkg, storage_graph, reg):
+    """The same pin at B = 705 (23 tiles, three parts of the sweep; a user and a positive repeated across parts), d = 64, K = 3,
+    tau = 0.2: the restatement judges the device at B = 513 and B = 2048 (tests/test_gpu_inbatch.py, section 1b), so it is not
+    only pinned at B <= 260.  1e-12 relative, as above.  Every sample of the large batches keeps more than half of its B - 1
+    possible competitors (300 users and 560 items mask some pairs by themselves)."""
+    A, table = _inputs(pkg, storage_graph, 64)
+    B, K, tau = 705, 3, 0.2
+    batch = IB.make_batch(B)
+    u, p = batch
+    assert IB.parts(B) == 3 and u[B - 1] in u[:256] and p[B - 1] in p[:256] and u[300] in u[:256] and p[400] in p[:256]
+    for w in (None, [0.4, 0.1, 0.3, 0.2]):
+        r = IB.step(A, SC.N_USERS, K, SC.DECAY, tau, table, batch, reg == "ego", w)
+        _pin(r, lambda E, E0: IB.loss(E, E0, SC.N_USERS, batch, SC.DECAY, tau, reg == "ego"), A, table, K, w, B)
+        assert float(r["W"].sum(1).abs().max()) <= 1e-15
+    for Bl in IB.LARGE_BATCH_SIZES + (705,):
+        assert IB.kept_share(*IB.make_batch(Bl)) > 0.5
+
+
 # ---- 2. B = 2 is the sampled softmax with each other's positive as the negative ------------------------------------------------
 @pytest.mark.parametrize("d,K,tau", [(32, 1, 1.0), (64, 3, 0.2)])
 def test_two_samples_are_the_sampled_softmax_of_each_others_positive(pkg, storage_graph, d, K, tau):

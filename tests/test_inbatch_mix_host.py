@@ -21,7 +21,7 @@ import storage_cases as SC                       # noqa: E402
 from storage_cases import storage_graph          # noqa: E402,F401  (fixture: the graph, written once per session)
 from conftest import REPO                        # noqa: E402
 from test_gpu_inbatch import _uncovered          # noqa: E402
-from test_inbatch_host import _inputs, _model_with   # noqa: E402
+from test_inbatch_host import _inputs, _model_with, _pin   # noqa: E402
 
 _C = {}
 OPTIONS = (("dot", False), ("cosine", True), ("cosine", False))
@@ -125,6 +125,25 @@ def test_restatement_is_the_autograd_of_the_written_loss(pkg, storage_graph, d, 
     nb = len(bu)
     assert not keep[0, nb + 2 * nb + 1] and keep[5, nb + 2 * nb + 1] and keep[5, 0]      # n_{1,2} = p_0: masked for sample 0 only
     assert float(r["q"][5, nb + 0]) > 0.0 and float(r["q"][5, nb + nb + 0]) > 0.0      # the duplicate n_{0,0} = n_{0,1}: both count
+
+
+@pytest.mark.parametrize("score,lq_on", [("dot", False), ("cosine", True)])
+def test_restatement_is_the_autograd_of_the_written_loss_across_three_parts(pkg, storage_graph, score, lq_on):
+    """The same pin at (B, R) = (545, 16) -- three parts on the user side, 39 on the item side; a case of
+    inbatch_mix_bounds.LARGE_CASES -- d = 64, K = 3, tau = 0.2, both reg rows: the restatement judges the device at that size and at
+    (2048, 1) (tests/test_gpu_inbatch_mix.py, section 1b).  1e-12 relative, as above."""
+    A, table = _inputs(pkg, storage_graph, 64)
+    B, R, K, tau = 545, 16, 3, 0.2
+    assert (B, R) in MB.LARGE_BRS and MB.parts_users(B) == 3
+    lq = _logq(pkg, storage_graph, B, R) if lq_on else None
+    batch = IM.make_batch(B, R)
+    u, p, negs = batch
+    assert u[B - 1] in u[:256] and p[B - 1] in p[:256] and negs[B - 1, 0] in p[:256]      # across the parts of the user sweep
+    for reg in ("propagated", "ego"):
+        r = IM.step(A, SC.N_USERS, K, SC.DECAY, tau, table, batch, reg == "ego", None, score=score, logq=lq)
+        assert float(r["inv_u"].min()) > 0.0 and float(r["inv_p"].min()) > 0.0 and float(r["inv_n"].min()) > 0.0
+        _pin(r, lambda E, E0: IM.loss(E, E0, SC.N_USERS, batch, SC.DECAY, tau, reg == "ego", score=score, logq=lq), A, table, K, None, B)
+        assert float(r["W"].sum(1).abs().max()) <= 1e-15
 
 
 def test_the_pool_changes_the_step(pkg, storage_graph):

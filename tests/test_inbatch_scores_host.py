@@ -18,7 +18,7 @@ import inbatch_scores_restatement as IS          # noqa: E402
 import storage_cases as SC                       # noqa: E402
 from storage_cases import storage_graph          # noqa: E402,F401  (fixture: the graph, written once per session)
 from conftest import REPO                        # noqa: E402
-from test_inbatch_host import _inputs, _model_with   # noqa: E402
+from test_inbatch_host import _inputs, _model_with, _pin   # noqa: E402
 
 _LQ = {}
 
@@ -85,6 +85,22 @@ def test_restatement_is_the_autograd_of_the_written_loss(pkg, storage_graph, d, 
                 assert float((r["G"] - E.grad).abs().max()) <= 1e-12 * scale
                 assert float((r["g_final"] - E0.grad).abs().max()) <= 1e-12 * scale
                 assert float(r["W"].sum(1).abs().max()) <= 1e-15                     # every row of W sums to zero
+
+
+@pytest.mark.parametrize("score,lq_on", IS.NEW_OPTIONS)
+def test_restatement_is_the_autograd_of_the_written_loss_across_three_parts(pkg, storage_graph, score, lq_on):
+    """The same pin at B = 705 (three parts of the sweep), d = 64, K = 3, tau = 0.1, both reg rows: the restatement judges the device
+    at B = 513 and B = 2048 (tests/test_gpu_inbatch_scores.py, section 1b).  1e-12 relative, as above."""
+    A, table = _inputs(pkg, storage_graph, 64)
+    lq = _logq(pkg, storage_graph) if lq_on else None
+    B, K, tau = 705, 3, 0.1
+    batch = IB.make_batch(B)
+    assert IB.parts(B) == 3
+    for reg in ("propagated", "ego"):
+        r = IS.step(A, SC.N_USERS, K, SC.DECAY, tau, table, batch, reg == "ego", None, score=score, logq=lq)
+        assert float(r["inv_u"].min()) > 0.0 and float(r["inv_p"].min()) > 0.0
+        _pin(r, lambda E, E0: IS.loss(E, E0, SC.N_USERS, batch, SC.DECAY, tau, reg == "ego", score=score, logq=lq), A, table, K, None, B)
+        assert float(r["W"].sum(1).abs().max()) <= 1e-15
 
 
 def test_the_options_change_the_step(pkg, storage_graph):
