@@ -16,6 +16,8 @@ MAX_NEG_RATIO = 16     # LGCN_MAX_NEG_RATIO: negatives per positive of lgcn_trai
 LOSS_BPR, LOSS_SOFTMAX, LOSS_INBATCH = 0, 1, 2     # LGCN_LOSS_*: lgcn_ctx_set_loss
 LOSS_DIRECTAU = 4                                  # LGCN_LOSS_DIRECTAU: lgcn_ctx_set_directau
 SCORE_DOT, SCORE_COSINE = 0, 1                     # LGCN_SCORE_*: lgcn_ctx_set_inbatch_scores
+DP_ROWS, DP_DENSE, DP_ROW_SHARDED, DP_COLS = 0, 1, 2, 3                 # LGCN_DP_*: the `reduce` of lgcn_train_epoch_dp
+RS_FWD, RS_BPR, RS_SCATTER, RS_BWD, RS_FINISH = 0, 1, 2, 3, 4           # LGCN_RS_*: the phases of lgcn_rs_phase / lgcn_rs_buffer
 
 _c_i32p =C.POINTER(C.c_int32)
 _c_i64p = C.POINTER(C.c_int64)

@@ -16,7 +16,7 @@ import subprocess
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO_DIR = os.path.dirname(PKG_DIR)
 SOURCES = [os.path.join(PKG_DIR, "csrc", f) for f in
-           ("lgcn_device.hip", "lgcn_graph.cpp", "lgcn_train.cpp", "lgcn_eval.hip", "lgcn_eval_ranks.hip", "lgcn_eval_pop.hip", "lgcn_sampler.hip", "lgcn_shuffle.hip", "lgcn_ids.hip", "lgcn_i2i.hip", "lgcn_mf.hip", "lgcn_multineg.hip", "lgcn_hardneg.hip", "lgcn_inbatch.hip", "lgcn_directau.hip", "lgcn_dp_loopback.hip", "lgcn_dp.cpp", "lgcn_host.cpp")]
+           ("lgcn_device.hip", "lgcn_graph.cpp", "lgcn_ctx.cpp", "lgcn_train.cpp", "lgcn_train_dp.cpp", "lgcn_eval.hip", "lgcn_eval_ranks.hip", "lgcn_eval_pop.hip", "lgcn_sampler.hip", "lgcn_shuffle.hip", "lgcn_ids.hip", "lgcn_i2i.hip", "lgcn_mf.hip", "lgcn_multineg.hip", "lgcn_hardneg.hip", "lgcn_inbatch.hip", "lgcn_directau.hip", "lgcn_dp_loopback.hip", "lgcn_dp.cpp", "lgcn_host.cpp")]
 HEADER = os.path.join(REPO_DIR, "include", "lgcn_hip.h")
 LIB_PATH = os.environ.get("LGCN_LIB_PATH") or os.path.join(PKG_DIR, "liblgcn_hip.so")   # env: pick a tuning variant
 BASE_FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-shared", "-std=c++17"]
@@ -50,7 +50,7 @@ def source_hash(extra_flags=()):
 
 def kernel_hash():
     """Hash of the source of the training kernels and their launchers (csrc/lgcn_device.hip, which holds nothing else: the host
-    side is lgcn_graph.cpp and lgcn_train.cpp): what a PMC measurement of k_spmm stays valid for."""
+    side is lgcn_graph.cpp, lgcn_ctx.cpp, lgcn_train.cpp and lgcn_train_dp.cpp): what a PMC measurement of k_spmm stays valid for."""
     with open(os.path.join(PKG_DIR, "csrc", "lgcn_device.hip"), "rb") as fh:
         return hashlib.sha256(fh.read()).hexdigest()
 

@@ -9,7 +9,7 @@
 #include "lgcn_kernels.h"      // (every unit gets its macros -- XCDS, LONG_T, GATE_TPB, ... -- with it: keep such names out of the other files)
 
 extern "C" void lgcn_set_error(const char *msg);   // lgcn_host.cpp
-// 0 under LGCN_LOSS_BPR; else rc 3 and the message "<who>: the ... loss ... is implemented for ... only" (lgcn_train.cpp): ONE wording
+// 0 under LGCN_LOSS_BPR; else rc 3 and the message "<who>: the ... loss ... is implemented for ... only" (lgcn_ctx.cpp): ONE wording
 // for every entry point that does not train the loss set on the context.  The same callers cannot train hard negatives
 // (lgcn_ctx_set_hard_neg) either: while those are set it returns 3 and names them, whatever the loss
 int lgcn_refuse_loss(const lgcn_ctx *x, const char *who);
@@ -26,7 +26,7 @@ int lgcn_refuse_loss(const lgcn_ctx *x, const char *who);
     } while (0)
 
 // ---------------------------------------------------------------------------------
-// What lgcn_graph.cpp (graph object, propagation) and lgcn_train.cpp (training context, step driver) share
+// What lgcn_graph.cpp (graph object, propagation) and the training units (lgcn_ctx.cpp, lgcn_train.cpp, lgcn_train_dp.cpp) share
 // ---------------------------------------------------------------------------------
 // graph object: device CSR (borrowed) + the long-row plan and its scratch (owned)
 struct lgcn_graph {
@@ -46,7 +46,7 @@ int lgcn_graph_create_impl(const int32_t *indptr, const int32_t *indices, const 
                            int64_t n_rows, int64_t nnz, int32_t d_max, const int32_t *row_order,
                            int64_t n_order, const int64_t *xcd_start, int32_t long_ch, lgcn_graph **out);
 int lgcn_check_layer_weights(const char *who, const float *w, int n, int K);
-int64_t lgcn_fold_segment_steps();      // lgcn_train.cpp
+int64_t lgcn_fold_segment_steps();      // lgcn_ctx.cpp
 
 // a launch on `st` is about to use the graph's scratch: order it behind the previous user
 static inline int graph_acquire(const lgcn_graph *g, hipStream_t st) {

@@ -244,13 +244,20 @@ class DataParallelBPR:
                           "using torch.distributed collectives per step", file=sys.stderr)
         return self._comm_ok
 
+    def _c_loop_ok(self):
+        """May lgcn_train_epoch_dp run, the collectives on the library's own communicator?  CUDA tensors, no LGCN_DP_PYTHON_LOOP=1,
+        and every rank joined -- asked in this order: _own_communicator_ok() is itself a collective, never entered on a CPU or
+        a forced-loop run."""
+        return (self.model._table.device.type == 'cuda' and os.environ.get("LGCN_DP_PYTHON_LOOP") != "1"
+                and self._own_communicator_ok())
+
     def ranks_observed(self):
         """How many ranks the collectives of the data path actually span: a SUM all-reduce of 1.0 per rank through the
         library's own RCCL communicator (the one lgcn_train_epoch_dp issues its collectives on), or -- when the ranks agreed
         to fall back -- through torch.distributed.  -> (count, 'library RCCL communicator' | 'torch.distributed')."""
         dev = self.model._table.device
         one = torch.ones(1, dtype=torch.float32, device=dev)
-        if dev.type == 'cuda' and os.environ.get("LGCN_DP_PYTHON_LOOP") != "1" and self._own_communicator_ok():
+        if self._c_loop_ok():
             _lib.check(_lib.load().lgcn_dp_allreduce_sum_f32(self._communicator(), _lib.tp(one), 1, _lib.current_stream()),
                        "lgcn_dp_allreduce_sum_f32")
             return int(round(float(one.item()))), "library RCCL communicator"
@@ -282,13 +289,7 @@ class DataParallelBPR:
         m = self.model
         dev = m._table.device
         T = int(users.numel())
-        if self.shard == 'cols' and dev.type == 'cuda' and os.environ.get("LGCN_DP_PYTHON_LOOP") != "1" and self._own_communicator_ok():
-            users, pos, neg, st, losses = self._begin(users, pos, neg, 1, global_batch=int(global_batch))
-            _lib.check(_lib.load().lgcn_train_epoch_dp(st['ctx'], self._communicator(), _lib.tp(users), _lib.tp(pos), _lib.tp(neg), T,
-                                               int(global_batch), 3, None, None, _lib.tp(losses), _lib.current_stream()), "lgcn_train_epoch_dp")
-            m.invalidate_cache()
-            return losses
-        if dev.type != 'cuda' or os.environ.get("LGCN_DP_PYTHON_LOOP") == "1" or not self._own_communicator_ok():
+        if not self._c_loop_ok():
             if self.shard == 'rows':        # (no per-step form exists: _step would come straight back here)
                 raise RuntimeError("row-sharded propagation (shard='rows') runs only through the library's RCCL communicator "
                                    "on CUDA tensors; it has no torch.distributed per-step loop (LGCN_DP_PYTHON_LOOP / CPU)")
@@ -296,17 +297,22 @@ class DataParallelBPR:
                    for t in range(0, T, global_batch)]
             return torch.stack(out)
         # one host call per epoch: the C loop issues kernels and RCCL collectives on one stream
-        users, pos, neg, st, losses = self._begin(users, pos, neg, self.world, global_batch=int(global_batch),
-                                                  row_subset=owned_rows(self.ranges, self.rank) if self.shard == 'rows' else None)
+        cols, sharded = self.shard == 'cols', self.shard == 'rows'
+        mode = (_lib.DP_COLS if cols else _lib.DP_ROW_SHARDED if sharded else
+                _lib.DP_ROWS if self.reduce == 'rows' else _lib.DP_DENSE)
+        # (a column-sharded rank is an ordinary context of width d / world: its state is that of a world of one)
+        users, pos, neg, st, losses = self._begin(users, pos, neg, 1 if cols else self.world, global_batch=int(global_batch),
+                                                  row_subset=owned_rows(self.ranges, self.rank) if sharded else None)
         lib = _lib.load()
-        n = self.world * int(lib.lgcn_dp_block_floats(st['ctx'], int(global_batch), self.world))
-        if self.reduce == 'rows' and (self._gathered is None or self._gathered.numel() < n):
-            self._gathered = torch.empty(n, dtype=torch.float32, device=dev)
-        mode = 2 if self.shard == 'rows' else (0 if self.reduce == 'rows' else 1)
-        rr = np.ascontiguousarray(self.ranges, np.int64) if self.shard == 'rows' else None
+        gathered = None
+        if mode in (_lib.DP_ROWS, _lib.DP_ROW_SHARDED):      # the forms that all-gather the ranks' exchange blocks
+            n = self.world * int(lib.lgcn_dp_block_floats(st['ctx'], int(global_batch), self.world))
+            if self._gathered is None or self._gathered.numel() < n:
+                self._gathered = torch.empty(n, dtype=torch.float32, device=dev)
+            gathered = _lib.tp(self._gathered)
+        rr = np.ascontiguousarray(self.ranges, np.int64) if sharded else None
         _lib.check(lib.lgcn_train_epoch_dp(st['ctx'], self._communicator(), _lib.tp(users), _lib.tp(pos), _lib.tp(neg), T,
-                                           int(global_batch), mode, _lib.npp(rr) if rr is not None else None,
-                                           _lib.tp(self._gathered) if self.reduce == 'rows' else None,
+                                           int(global_batch), mode, _lib.npp(rr) if rr is not None else None, gathered,
                                            _lib.tp(losses), _lib.current_stream()), "lgcn_train_epoch_dp")
         m.invalidate_cache()
         return losses

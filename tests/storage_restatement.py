@@ -1,5 +1,5 @@
-"""float64 restatement of the fused step (run_forward, run_bpr, triplet_body / k_triplet_dense, triplet_finish,
-backward_layer of csrc/lgcn_train.cpp and the Adam epilogue of csrc/lgcn_device.hip) with every storage point written out, and its float32 twin
+"""float64 restatement of the fused step (train_forward, train_bpr, triplet_body / k_triplet_dense, triplet_finish,
+train_backward_layer of csrc/lgcn_train.cpp and the Adam epilogue of csrc/lgcn_device.hip) with every storage point written out, and its float32 twin
 (the same function with dtype = torch.float32 and the real casts).  Test infrastructure: tests/test_storage_restatement.py
 pins it to the oracle, tests/test_gpu_storage_step.py judges the bf16 / fp8 kernels by it.
 
@@ -90,7 +90,7 @@ def slots(batch, n_users):
 
 
 def constants(decay, B):
-    """inv_B and lam as run_bpr makes them (fp32 quotients of fp32 operands): inputs of both precisions."""
+    """inv_B and lam as train_bpr makes them (fp32 quotients of fp32 operands): inputs of both precisions."""
     return float(np.float32(1.0) / np.float32(B)), float(np.float32(decay) / np.float32(B))
 
 

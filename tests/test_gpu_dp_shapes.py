@@ -380,7 +380,7 @@ def test_column_shards_step_by_step(pkg, storage_graph, case):
 
 @pytest.mark.parametrize("case", D.COLS_FP8_CASES, ids=D.case_id)
 def test_column_shards_fp8_accepted(pkg, storage_graph, case):
-    """fp8 storage under column shards: no entry point of csrc/lgcn_train.cpp and nothing in model.py refuses it -- a rank is an
+    """fp8 storage under column shards: no entry point of csrc/lgcn_train_dp.cpp and nothing in model.py refuses it -- a rank is an
     ordinary fp8 context of width 64 / 128 -- so it is judged, under the fp8 bounds (module docstring)."""
     _run_cols_case(pkg, storage_graph, case)
 

@@ -3,7 +3,7 @@ in-batch softmax (plain; cosine + logQ), the mixed pool (R_max = 16, steps at R 
 sampled softmax, on the graph and table of tests/storage_cases.py.
 
 Why.  Every other test that judges these steps against float64 creates its context with max_batch = B, so the workspace capacity
-equals the padded batch.  The workspaces are carved by the CAPACITY (InBatchWs / DirectAuWs in csrc/lgcn_train.cpp: `part` holds 2
+equals the padded batch.  The workspaces are carved by the CAPACITY (InBatchWs / DirectAuWs in csrc/lgcn_ctx.h: `part` holds 2
 cap parts(cap) floats, ib_invu() recomputes its offset from cap, the mixed carving holds (1 + R_max) cap item rows) while the
 kernels index by the padded BATCH.  Training runs at capacity 2048 with a shorter last batch every epoch.  The "epoch equals the
 loop of steps" tests do run B < cap, but with the same capacity and the same sequence on both sides: a wrong offset, or a read of

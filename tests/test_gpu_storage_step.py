@@ -110,7 +110,7 @@ def _step_graphs(pkg, case, m):
 
 
 def _bwd_buffer(K, k):
-    return 1 if K == 2 else 1 + ((K - k) & 1)          # bwd_buffer() of csrc/lgcn_train.cpp: the table launch k > 1 writes
+    return 1 if K == 2 else 1 + ((K - k) & 1)          # train_bwd_buffer() of csrc/lgcn_train.cpp: the table launch k > 1 writes
 
 
 def _share(err, bound):

@@ -75,12 +75,16 @@ def test_source_hash_reads_every_file_the_library_includes(pkg):
 
 def test_training_kernels_live_in_one_file(pkg):
     """build.kernel_hash() is the hash of csrc/lgcn_device.hip and stands for "the training kernels": the host side of the graph
-    object and of the training step (lgcn_graph.*, lgcn_train.*) is built from files of its own that hold no kernel and no
-    launch, and every launcher the boundary header lgcn_kernels.h declares is defined in lgcn_device.hip, beside its kernel."""
+    object, of the training context and of the training step (lgcn_graph.*, lgcn_ctx.*, lgcn_train.*, lgcn_train_dp.*) is built
+    from files of its own that hold no kernel and no launch, every launcher the boundary header lgcn_kernels.h declares is defined
+    in lgcn_device.hip, beside its kernel, and no device unit sees the context (lgcn_ctx.h is the host units' header)."""
     b = pkg.build
     csrc = os.path.dirname(b.SOURCES[0])
     by_stem = {os.path.splitext(os.path.basename(f))[0]: f for f in b.SOURCES}
-    for stem in ("lgcn_graph", "lgcn_train"):
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith(".hip"):
+            assert '#include "lgcn_ctx.h"' not in open(os.path.join(csrc, f)).read(), f"{f} includes lgcn_ctx.h"
+    for stem in ("lgcn_graph", "lgcn_ctx", "lgcn_train", "lgcn_train_dp"):
         assert stem in by_stem and os.path.exists(by_stem[stem]), stem
         text = open(by_stem[stem]).read()
         for word in ("__global__", "__device__", "hipLaunchKernelGGL", "<<<"):

@@ -104,7 +104,7 @@ def test_backward_is_the_straight_through_gradient(pkg, storage_graph, mode, K, 
     rows = S.slots(batch, SC.N_USERS)
     f = S.forward(A, E0, K, mode, bool(dl), rows, q=S.ste)
     b = S.bpr(f["e"], E0[rows.reshape(-1)].reshape(f["e"].shape), E0.shape[0], rows, K, SC.DECAY, reg == "ego")
-    # the loss whose gradient the rows are: run_bpr's own fp32 constants inv_B = fl(1 / B) and lam = fl(decay / B), which differ
+    # the loss whose gradient the rows are: train_bpr's own fp32 constants inv_B = fl(1 / B) and lam = fl(decay / B), which differ
     # from the 1 / B and decay / B of loss_out in the last bit of an fp32 number (3e-8 for B = 37)
     inv_B, lam = S.constants(SC.DECAY, len(batch[0]))
     (-(inv_B * b["term"].sum()) + lam * 0.5 * b["regterm"].sum()).backward()
@@ -215,7 +215,7 @@ def _rel(a, b):
 
 def _autograd64(a, table, w, batch, reg, exact_w=None):
     """One step of test_gpu_layer_weights._WeightedRef in float64 on the CSR `a` (explicit zeros allowed) -> (loss, gradient,
-    table after torch.optim.Adam's first step).  The batch has 64 triplets and decay is fl32(DECAY), so that run_bpr's fp32
+    table after torch.optim.Adam's first step).  The batch has 64 triplets and decay is fl32(DECAY), so that train_bpr's fp32
     constants inv_B = fl32(1 / B) and lam = fl32(fl32(decay) / B) ARE the reference's 1 / B and decay / B (a power of two divides
     exactly) and the two sides differ by float64 rounding alone.  exact_w: weights that are no fp32 numbers (the mean's 1 / (K + 1))."""
     import test_gpu_layer_weights as LW

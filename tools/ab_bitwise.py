@@ -36,8 +36,14 @@ Cases (cases()):
             32/64/128; B 1/7/67 in rotation.  (The big-table instantiations need 2^32 bytes per table: tests/test_gpu_large.py.)
   directau  lgcn_train_step_directau: d 32/64/128/256, fp32 / bf16 tables, mean / layer weights, K 1/3, B 1/7/67, reg_rows propagated
             / ego, gamma 0 / 1; every value of every axis at every d (check_coverage); one batch with an out-of-range positive (a void
-            sample) and one lgcn_train_epoch_directau over T = 2 B + 3.  LAST in the list: the cases before it keep their numbers and
-            seeds, so a library or a tree from before this kind is compared on the cases both sides have.
+            sample) and one lgcn_train_epoch_directau over T = 2 B + 3.  Behind every kind that was there before it: the cases before
+            it keep their numbers and seeds, so a library or a tree from before this kind is compared on the cases both sides have.
+  dp        the data-parallel forms, W rank contexts in one process (run_dp_case), with the batches of tests/dp_cases.py (300, 65, 37,
+            5, 1 triplets) at capacity 300: rows0 / rows1 / dense / row_sharded at W 2 / 3 and d 32 / 64, fp32 / bf16 in rotation
+            and fp8 once, K 1 / 2 / 3 and dense_last 0 / 1 in rotation (every (form, K) pair: check_coverage); rows1 and dense with
+            the popularity gate and with item-item smoothing; column shards at rank widths 32 (fp32, bf16) and 64 (fp8).  All but
+            rows0 through lgcn_train_epoch_dp over the loopback communicator, whose all-reduce adds in rank order: deterministic,
+            column shards included.  Per rank: table, both moments, loss_out, error flag.  LAST, by the same rule as directau.
 
 A side whose tree does not know a case of the other side (an older checkout under --tree-a) is compared on the common cases; the
 cases only one side ran are counted in the report and never differ."""
@@ -60,6 +66,8 @@ SCORES, LOGQS, MIX_RS, MIX_RMAX, IB_TAU = ("dot", "cosine"), (False, True), (1, 
 IB_KINDS = ("inbatch", "inbatch_mix")
 STEP_KS, STEP_DLS, GATE_DS = (1, 2, 3), (0, 1), (32, 64, 128)
 AU_GAMMAS = (0.0, 1.0)
+DP_FORMS, DP_WS, DP_DS, DP_FP8_AT = ("rows0", "rows1", "dense", "row_sharded"), (2, 3), (32, 64), ("row_sharded", 2, 64)
+DP_TIMEOUT = 120                                           # seconds the rank threads of one lgcn_train_epoch_dp call may take
 
 
 def cases():
@@ -114,11 +122,29 @@ def cases():
     base = dict(kind="directau", d=64, mode="fp32", wts=False, K=3, B=7, reg="propagated", gamma=1.0)
     out.append(dict(base, void=3))                          # an out-of-range positive
     out.append(dict(base, mode="bf16", epoch=True))         # the epoch entry point over T = 2 B + 3
+    for f, form in enumerate(DP_FORMS):                     # dp (last: see the module docstring)
+        for j, (W, d) in enumerate(itertools.product(DP_WS, DP_DS)):
+            mode = "fp8" if (form, W, d) == DP_FP8_AT else MODES[(4 * f + j) % 2]
+            out.append(dict(kind="dp", form=form, W=W, d=d, mode=mode, K=1 + (f + j) % 3, dl=(f // 2 + j) % 2, cfg={}))
+    for j, form in enumerate(("rows1", "dense")):           # the optional branches: the forms that carry them
+        out.append(dict(kind="dp", form=form, W=2, d=32, mode=MODES[j], K=2, dl=0, cfg=dict(use_pop_gate=True)))
+        out.append(dict(kind="dp", form=form, W=2, d=32, mode=MODES[1 - j], K=2, dl=0, cfg=dict(use_item_item=True, i2i_build='cooc', i2i_alpha=0.5)))
+    out += [dict(kind="dp", form="cols", W=2, d=d, mode=mode, K=K, dl=0, cfg={}) for d, mode, K in ((64, "fp32", 1), (64, "bf16", 3), (128, "fp8", 2))]
     return out
 
 
 def check_coverage(cs):
-    multi = [c for c in cs if c["kind"] == "multi" and not c.get("void") and not c.get("saturate")]
+    dp = [c for c in cs if c["kind"] == "dp"]
+    assert dp and cs[-len(dp):] == dp, "the dp cases are the last ones"
+    cs = cs[:-len(dp)]
+    plain = [c for c in dp if not c["cfg"] and c["form"] != "cols"]
+    assert {(c["form"], c["K"]) for c in plain} == set(itertools.product(DP_FORMS, (1, 2, 3))), "dp: (form, K)"
+    assert {(c["form"], c["W"], c["d"]) for c in plain} == set(itertools.product(DP_FORMS, DP_WS, DP_DS)) and {c["dl"] for c in plain} == {0, 1}
+    assert [c["mode"] for c in plain].count("fp8") == 1 and {c["mode"] for c in plain} == {"fp32", "bf16", "fp8"}
+    assert all(c["d"] >= 64 and not c["cfg"] for c in dp if c["mode"] == "fp8")
+    assert {(c["form"], k) for c in dp for k in c["cfg"] if k.startswith("use_")} == set(itertools.product(("rows1", "dense"), ("use_pop_gate", "use_item_item")))
+    assert {(c["d"] // c["W"], c["mode"], c["K"]) for c in dp if c["form"] == "cols"} == {(32, "fp32", 1), (32, "bf16", 3), (64, "fp8", 2)}
+    multi =[c for c in cs if c["kind"] == "multi" and not c.get("void") and not c.get("saturate")]
     for d in DS:
         at = [c for c in multi if c["d"] == d]
         for key, values in (("mode", MODES), ("wts", WTS), ("K", KS), ("R", RS), ("B", BS), ("reg", REGS)):
@@ -169,10 +195,120 @@ def name(c):
                 + (f"-R{c['R']}of{MIX_RMAX}" if c["kind"] == "inbatch_mix" else "") + tag)
     if c["kind"] == "mf":
         return f"mf-d{c['d']}-B{c['B']}"
+    if c["kind"] == "dp":
+        return f"dp-{c['form']}-w{c['W']}-d{c['d']}-{c['mode']}-K{c['K']}-dl{c['dl']}" + "".join(f"-{k}" for k in c["cfg"] if k.startswith("use_"))
     if c["kind"] == "directau":
         tag = "-void" if c.get("void") else "-epoch" if c.get("epoch") else ""
         return f"directau-d{c['d']}-{c['mode']}-{'wts' if c['wts'] else 'mean'}-K{c['K']}-B{c['B']}-{c['reg']}-gamma{c['gamma']}" + tag
     return f"step-d{c['d']}-{c['mode']}-K{c['K']}-dl{c['dl']}-B{c['B']}" + "".join(f"-{k}" for k in c["cfg"] if k in ("dropout", "layer_weights", "use_pop_gate", "use_item_item"))
+
+
+def run_dp_case(pkg, c, path, dev):
+    """One dp case -> {field: array}: per rank the table, both Adam moments, the per-step losses and the error flag.  The forms of
+    the C loop (rows1 -- the loop turns dp_local on --, dense, row_sharded, cols) run lgcn_train_epoch_dp over the loopback
+    communicator, one thread per rank (tests/test_gpu_dp_shapes.py::_run_ranks; a join time limit, no second try), three epochs
+    at B = 300: T = 408 (a short last batch), T = 5 and T = 1 (ragged shards, an empty trailing rank).  rows0 exists as steps
+    only: part 1 on every rank, the blocks concatenated in rank order, part 2 on every rank, over the five batches."""
+    import ctypes as C
+    import threading
+    import torch
+    import dp_cases as D
+    import storage_cases as SC
+    L, lib, par = pkg._lib, pkg._lib.load(), pkg.parallel
+    W, d, form, B = c["W"], c["d"], c["form"], D.MAX_BATCH
+    case = (c["mode"], d, c["K"], c["dl"], -1, "propagated", W, form, B)
+    w = SC.configure(pkg, D.storage_case(case), path, B)
+    w.config.update(c["cfg"])
+    ds = pkg.dataloader.Loader(w.config, path=path)
+
+    def fresh():
+        pkg.utils.set_seed(SC.MODEL_SEED)
+        return SC.set_rows(pkg.model.LightGCN(w.config, ds)._table).detach().clone()
+    ranks = []
+    for r in range(W):
+        pkg.utils.set_seed(SC.MODEL_SEED)
+        if form == "cols":
+            m = par.column_shard(pkg.model.LightGCN, w.config, ds, W, r, dev)
+            lo, hi = par.column_range(d, W, r)
+            with torch.no_grad():
+                m._table.copy_(fresh()[:, lo:hi].to(dev))
+        else:
+            m = pkg.model.LightGCN(w.config, ds)
+            SC.set_rows(m._table)
+            m = m.to(dev)
+        m.train()
+        ranks.append(m)
+    ranges = par.row_ranges(ranks[0]._adj.indptr, ranks[0].n_users, W) if form == "row_sharded" else None
+    states = [m._state(max_batch=B, need_ctx=True, dp_world=1 if form == "cols" else W,
+                       row_subset=par.owned_rows(ranges, r) if ranges is not None else None) for r, m in enumerate(ranks)]
+
+    def ids(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(torch.int32).to(dev)
+    batches = D.make_batches(case)
+    losses = [[] for _ in range(W)]
+    if form == "rows0":
+        stream = L.current_stream()
+        for st in states:
+            L.check(lib.lgcn_ctx_set_dp_local(st['ctx'], 0), "lgcn_ctx_set_dp_local")
+        for u, p, n in batches:
+            u, p, n = ids(u), ids(p), ids(n)
+            b = int(u.numel())
+            blocks = []
+            for r, st in enumerate(states):
+                L.check(lib.lgcn_train_step_dp_part1(st['ctx'], L.tp(u), L.tp(p), L.tp(n), b, W, r, stream), "lgcn_train_step_dp_part1")
+                blocks.append(st['contrib'][:int(lib.lgcn_dp_block_floats(st['ctx'], b, W))].clone())
+            gathered = torch.cat(blocks)
+            for r, st in enumerate(states):
+                losses[r].append(torch.empty(1, 3, device=dev))
+                L.check(lib.lgcn_train_step_dp_part2(st['ctx'], L.tp(u), L.tp(p), L.tp(n), b, W, L.tp(gathered), L.tp(losses[r][-1]), stream),
+                        "lgcn_train_step_dp_part2")
+            torch.cuda.synchronize()
+    else:
+        code = {"rows1": L.DP_ROWS, "dense": L.DP_DENSE, "row_sharded": L.DP_ROW_SHARDED, "cols": L.DP_COLS}[form]
+        comms = (C.c_void_p * W)()
+        L.check(lib.lgcn_dp_init_loopback(W, comms), "lgcn_dp_init_loopback")
+        streams = [torch.cuda.Stream() for _ in range(W)]
+        gathered = [torch.empty(W * int(lib.lgcn_dp_block_floats(st['ctx'], B, W)), device=dev) if code in (L.DP_ROWS, L.DP_ROW_SHARDED) else None
+                    for st in states]
+        rr = np.ascontiguousarray(ranges, np.int64) if ranges is not None else None
+        for u, p, n in (tuple(np.concatenate([b[i] for b in batches]) for i in range(3)), batches[3], batches[4]):
+            u, p, n = ids(u), ids(p), ids(n)
+            T = int(u.numel())
+            for r in range(W):
+                losses[r].append(torch.empty((T + B - 1) // B, 3, device=dev))
+            torch.cuda.synchronize()
+            rcs = [None] * W
+
+            def rank_main(r):
+                rcs[r] = lib.lgcn_train_epoch_dp(states[r]['ctx'], comms[r], L.tp(u), L.tp(p), L.tp(n), T, B, code, L.npp(rr) if rr is not None else None,
+                                                 L.tp(gathered[r]) if gathered[r] is not None else None, L.tp(losses[r][-1]),
+                                                 C.c_void_p(streams[r].cuda_stream))
+            threads = [threading.Thread(target=rank_main, args=(r,), daemon=True) for r in range(W)]
+            for t in threads:
+                t.start()
+            for t in threads:
+                t.join(timeout=DP_TIMEOUT)
+            if any(t.is_alive() for t in threads):
+                raise SystemExit(f"{name(c)}: a rank did not come back from lgcn_train_epoch_dp")
+            torch.cuda.synchronize()
+            assert rcs == [0] * W, (name(c), rcs, lib.lgcn_last_error())
+        for r in range(W):
+            lib.lgcn_dp_destroy(comms[r])
+    out = {}
+    for r, m in enumerate(ranks):
+        try:
+            m.check_device_errors()
+            err = 0
+        except pkg._lib.LgcnError:
+            err = 1
+        assert err == 0 and not bool(m._dev['G64'].any()), (name(c), r, err)
+        out[f"loss_out.r{r}"] = torch.cat(losses[r]).cpu().numpy()
+        out[f"table.r{r}"] = m._table.detach().cpu().numpy()
+        out[f"adam_m.r{r}"] = m._dev['adam_m'].cpu().numpy()
+        out[f"adam_v.r{r}"] = m._dev['adam_v'].cpu().numpy()
+        out[f"err.r{r}"] = np.array([err], np.int32)
+        assert np.isfinite(out[f"loss_out.r{r}"]).all(), (name(c), r)
+    return out
 
 
 def child(out_path):
@@ -191,6 +327,10 @@ def child(out_path):
 
     for i, c in enumerate(cases()):
         rng = np.random.Generator(np.random.PCG64(7000 + i))
+        if c["kind"] == "dp":                                # (its batches are tests/dp_cases.make_batches': no draw from rng)
+            for field, v in run_dp_case(pkg, c, path, dev).items():
+                result[f"{i:03d} {name(c)} {field}"] = v
+            continue
         B = c["B"]
         if c["kind"] == "mf":
             w = SC.configure(pkg, ("fp32", c["d"], 1, 1, -1, "propagated"), path, 64)
