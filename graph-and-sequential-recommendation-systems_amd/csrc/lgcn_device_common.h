@@ -17,6 +17,7 @@
 #define FIXED_INV   8.8817841970012523e-16 /* 2^-50 */
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(16))) float f32x16;        // the accumulator of a 32 x 32 MFMA
 typedef __attribute__((ext_vector_type(2))) long long i64x2;      // (bf16_t: lgcn_kernels.h, whose args structs name it)
 
 // runs the statement with D a compile-time constant; any other d is the caller's error 3
@@ -75,6 +76,9 @@ __device__ __forceinline__ void slot_row(const MultiNegArgs &a, int64_t row, int
         }
     }
 }
+
+// tile row of accumulator register `reg` on lane half h (C/D layout of the 32x32 MFMAs; the column is lane & 31)
+__device__ __forceinline__ int mfma32_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
 // *g64 += g in the fixed point of G64
 __device__ __forceinline__ void fixed_add(long long *g64, float g) {

@@ -140,7 +140,7 @@ __global__ void __launch_bounds__(64) k_directau_norm(DirectAuArgs da) {
         int32_t ids[16];
         float qc[16];
 #pragma unroll
-        for (int reg = 0; reg < 16; reg++) { const int c = t * 32 + ib_row(reg, h); ids[reg] = da.uid[c]; qc[reg] = q[c]; }
+        for (int reg = 0; reg < 16; reg++) { const int c = t * 32 + mfma32_row(reg, h); ids[reg] = da.uid[c]; qc[reg] = q[c]; }
         f32x16 acc;
         if constexpr (D <= IB_REG_D) {
             const int tn = t + 1 < t1 ? t + 1 : t;
@@ -152,7 +152,7 @@ __global__ void __launch_bounds__(64) k_directau_norm(DirectAuArgs da) {
         }
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {    // register order: part of the result
-            const int c = t * 32 + ib_row(reg, h);
+            const int c = t * 32 + mfma32_row(reg, h);
             const bool ok = sb >= 0 && ids[reg] >= 0 && (LGCN_DIRECTAU_NORM_FULL ? c != b : c > b);
             const float k = au_k(qb, qc[reg], acc[reg]);
             z += ok ? k : 0.f;
@@ -238,7 +238,7 @@ __global__ void __launch_bounds__(64) k_directau_grad(DirectAuArgs da) {
         float qc[16], ob[16][CB];
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {
-            const int x = t * 32 + ib_row(reg, h);          // the other index (a row of the tile)
+            const int x = t * 32 + mfma32_row(reg, h);          // the other index (a row of the tile)
             ids[reg] = da.uid[x]; qc[reg] = q[x];
             if constexpr (D <= IB_REG_D) {
 #pragma unroll
@@ -256,7 +256,7 @@ __global__ void __launch_bounds__(64) k_directau_grad(DirectAuArgs da) {
         }
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {
-            const int x = t * 32 + ib_row(reg, h);
+            const int x = t * 32 + mfma32_row(reg, h);
             const bool ok = so >= 0 && ids[reg] >= 0 && x != o;
             const float s = w[reg];
             w[reg] = ok ? coef * au_k(qo, qc[reg], s) : 0.f;
@@ -265,7 +265,7 @@ __global__ void __launch_bounds__(64) k_directau_grad(DirectAuArgs da) {
         // g[owned][col] += sum_x W[x][owned] T[x][col]: register i of w is the A operand as it stands
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {
-            const float *orow = T + (int64_t)(t * 32 + ib_row(reg, h)) * D + col0 + j;
+            const float *orow = T + (int64_t)(t * 32 + mfma32_row(reg, h)) * D + col0 + j;
 #pragma unroll
             for (int cb = 0; cb < CB; cb++) {
                 float bv;
@@ -275,13 +275,13 @@ __global__ void __launch_bounds__(64) k_directau_grad(DirectAuArgs da) {
         }
     }
     tproj += __shfl_xor(tproj, 32);             // both lane halves: lane r and lane r + 32 hold owned row r's scalar
-    // rows of g: owned index bx * 32 + ib_row(reg, h); columns col0 + cb * 32 + j
+    // rows of g: owned index bx * 32 + mfma32_row(reg, h); columns col0 + cb * 32 + j
     const int32_t *rid = side == 0 ? da.uid : da.pid;
     const float *inv = side == 0 ? da.invx : da.invy;
 #pragma unroll
     for (int reg = 0; reg < 16; reg++) {
-        const int ob = bx * 32 + ib_row(reg, h);
-        const float t_row = __shfl(tproj, ib_row(reg, h));            // (every lane takes part: before the skip)
+        const int ob = bx * 32 + mfma32_row(reg, h);
+        const float t_row = __shfl(tproj, mfma32_row(reg, h));            // (every lane takes part: before the skip)
         const int32_t us = rid[ob];
         if (us < 0) continue;                   // void or padding: no row to add to (its W is zero)
         const int64_t row = side == 0 ? (int64_t)us : (int64_t)us + da.m.n_users;

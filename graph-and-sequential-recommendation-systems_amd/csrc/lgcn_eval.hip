@@ -26,13 +26,14 @@
 //     the FIRST slot holding the minimum, whatever its id, so of several items tying EXACTLY at the K-th score any may be
 //     the ones kept (every item strictly above that score is kept).  Making (score, id) the key was measured and costs
 //     3-13 % of the sweep (profiles/eval_topk_exact).
+// What this file shares with lgcn_eval_ranks.hip is defined in lgcn_eval_sweep.h: the bf16 split, the tile geometry, the CSR search, the
+// sums' launcher.  The operand, the tile stage and the score tile of k_eval_topk are still spelled below, and again in that header
+// for k_eval_ranks (why: profiles/eval_sweep/README.md).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
 
-#include "lgcn_device_common.h"
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
+#include "lgcn_eval_sweep.h"
 
 #define EVAL_KMAX 64
 #define EVAL_NEG_INF (-3.0e38f)
@@ -64,8 +65,7 @@ template <> struct ListId<uint16_t> { static constexpr uint16_t EMPTY = 0xffffu;
 // The large-K lists (KS > 64) pad each score row by 16 bytes, so the 16-byte reads of 16 lanes at one column start 4 banks
 // apart; the K <= 64 lists keep their shape.
 template <int D, int KS, typename IDT, int NW, bool SPLIT3> struct EvalShape {
-    static constexpr int RS = D + 4, RSB = D + 8, PLANE_B = 32 * RSB * 2;
-    static constexpr int TILE_F = SPLIT3 ? 3 * PLANE_B / 4 : 32 * RS;       // floats per item tile
+    static constexpr int TILE_F = SweepGeo<D, SPLIT3>::TILE_F;              // floats per item tile
     static constexpr int KSP = (KS + 7) / 8 * 8;
     static constexpr int KSPP = KS > EVAL_KMAX ? KSP + 4 : KSP;             // score row stride (floats)
     static constexpr int USERS = 32 * NW;
@@ -101,45 +101,14 @@ static __device__ __forceinline__ float pick(bool c, float hi, float lo) {
     return c ? hi : lo;
 }
 
-// SPLIT3: the fp32 product on the bf16 matrix cores.  Every fp32 value is EXACTLY the sum of three bf16 values
-// (x = h + m + l: 8 + 8 + 8 significant bits, by truncation: h = x & 0xffff0000, m = (x - h) & 0xffff0000, l = x - h - m,
-// every subtraction exact), and every bf16 x bf16 product is exact in fp32, so
-//     a . b = sum_k (ah + am + al)(bh + bm + bl)
-// is accumulated from the six product planes hh, hm, mh, hl, lh, mm (smallest first) by v_mfma_f32_32x32x16_bf16 -- 24 MFMAs of
-// 8 passes per 32 x 32 x 64 block instead of 32 of 16 passes.  The three planes left out (ml, lm, ll) are below 2^-23 of
-// |a_k b_k| per term: the rounding an fp32 dot product of this length carries anyway (the ranking is fp32-accurate, not
-// bit-identical to any one fp32 summation order -- neither is the reference's sgemm).
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
-struct Planes2 { uint32_t h, m, l; };                        // two consecutive values, bf16 pairs (low half = first value)
-static __device__ __forceinline__ Planes2 split3(float x0, float x1) {
-    const uint32_t M = 0xffff0000u;
-    const float h0 = __uint_as_float(__float_as_uint(x0) & M), h1 = __uint_as_float(__float_as_uint(x1) & M);
-    const float r0 = x0 - h0, r1 = x1 - h1;
-    const float m0 = __uint_as_float(__float_as_uint(r0) & M), m1 = __uint_as_float(__float_as_uint(r1) & M);
-    const float l0 = r0 - m0, l1 = r1 - m1;
-    Planes2 o;
-    o.h = (__float_as_uint(h0) >> 16) | __float_as_uint(h1);
-    o.m = (__float_as_uint(m0) >> 16) | __float_as_uint(m1);
-    o.l = (__float_as_uint(l0) >> 16) | (__float_as_uint(l1) & M);
-    return o;
-}
-static __device__ __forceinline__ f32x16 mfma_bf16(const u32x4 &a, const u32x4 &b, const f32x16 &c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
 template <int D, int KS, typename IDT, int WGS, int NBUF = 2, bool SPLIT3 = false, bool MASKS = false, int NW = 4>
                                                                 // KS: list slots per lane (a multiple of 4, >= K); WGS: workgroups per CU;
                                                                 // NBUF: item tile buffers in LDS (1: one more barrier per tile); NW: waves
 __global__ void __launch_bounds__(64 * NW, WGS) k_eval_topk(EvalArgs a) {
     constexpr int NT = 64 * NW, NU = 32 * NW;          // threads, users of the workgroup
     static_assert(EvalShape<D, KS, IDT, NW, SPLIT3>::lds(NBUF) <= EVAL_LDS_BYTES, "lists + item tiles exceed the LDS of a CU");
-    constexpr int HALF = D / 2, RS = D + 4;            // row stride of the LDS item tile (floats)
-    // SPLIT3: three bf16 planes per tile, rows of D + 8 bf16 (144 bytes at d = 64: the 16-byte reads of 16 lanes at one
-    // column start 36 banks apart and cover the 64 banks once)
-    constexpr int RSB = D + 8, NCH = D / 16, PLANE_B = 32 * RSB * 2;
-    constexpr int TILE_F = SPLIT3 ? 3 * PLANE_B / 4 : 32 * RS;
+    using G = SweepGeo<D, SPLIT3>;
+    constexpr int HALF = G::HALF, RS = G::RS, RSB = G::RSB, NCH = G::NCH, PLANE_B = G::PLANE_B, TILE_F = G::TILE_F;
     constexpr int LPT = 32 * D * 4 / 16 / NT;           // 16-byte pieces per thread per item tile
     static_assert(LPT >= 1, "tile smaller than the workgroup");
     __shared__ __attribute__((aligned(16))) float tile_lds[NBUF][TILE_F];
@@ -186,11 +155,7 @@ __global__ void __launch_bounds__(64 * NW, WGS) k_eval_topk(EvalArgs a) {
     if (MASKS) { if (t_begin < t_end) mask_next = (a.masks + (int64_t)t_begin * a.mask_stride)[slot32]; }
     else if (have && h == 0) {
         tp = a.train_ptr[uid]; tend = a.train_ptr[uid + 1];
-        if (t_begin > 0) {                                      // first train positive inside this workgroup's item range
-            int64_t lo = tp, hi = tend;
-            while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a.train_idx[mid] < t_begin * 32) lo = mid + 1; else hi = mid; }
-            tp = lo;
-        }
+        if (t_begin > 0 && tp < tend) tp = csr_lower_bound(a.train_idx, tp, tend, t_begin * 32);       // first train positive inside this workgroup's item range
         if (tp < tend) nid = a.train_idx[tp];
         if (tp + 1 < tend) nnid = a.train_idx[tp + 1];
     }
@@ -287,7 +252,7 @@ __global__ void __launch_bounds__(64 * NW, WGS) k_eval_topk(EvalArgs a) {
             __syncthreads();
             if (t + 1 < t_end) store_tile(0);
         }
-        // ---- my 16 scores: item row = (reg & 3) + 8 * (reg >> 2) + 4 * h.  First only MARK the ones that can
+        // ---- my 16 scores: item row = mfma32_row(reg, h).  First only MARK the ones that can
         //      enter the user's top K: above this lane's K-th best AND not below the partner lane's (the other
         //      half of the user's items: K items at or above that score already exist).  Then the marked scores
         //      are inserted one per round, all lanes together: the rounds of a tile are the LARGEST number of
@@ -302,7 +267,7 @@ __global__ void __launch_bounds__(64 * NW, WGS) k_eval_topk(EvalArgs a) {
         if (exact_mask) {
 #pragma unroll
             for (int reg = 0; reg < 16; reg++) {
-                const int row = (reg & 3) + 8 * (reg >> 2) + 4 * h;
+                const int row = mfma32_row(reg, h);
                 float sc = acc[reg];
                 if ((mask >> row) & 1u) sc = -1024.0f;                      // Procedure.py:181
                 if (base + row >= a.m_items) sc = EVAL_NEG_INF;             // past the table
@@ -335,7 +300,7 @@ __global__ void __launch_bounds__(64 * NW, WGS) k_eval_topk(EvalArgs a) {
                 const float f0 = pick(b1, e1, e0), f1 = pick(b1, e3, e2), f2 = pick(b1, e5, e4), f3 = pick(b1, e7, e6);
                 const float sc = pick(b3, pick(b2, f3, f2), pick(b2, f1, f0));
                 if (sc > thr) {                                         // thr may have risen since the marking
-                    const int row = (reg & 3) + 8 * (reg >> 2) + 4 * h;
+                    const int row = mfma32_row(reg, h);
                     list_s[ul][pmin] = sc; list_i[ul][pmin] = (IDT)(base + row - id0);
                     did = 1u;
                 }
@@ -462,36 +427,7 @@ struct MetricArgs {
     double *per_user;                                        // [n_eval, 3 * n_ks]: precision | recall | ndcg
 };
 
-__global__ void __launch_bounds__(256) k_eval_metrics(MetricArgs a) {
-    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (s >= a.n_eval) return;
-    const int64_t b = a.test_ptr[s], e = a.test_ptr[s + 1];
-    const int len = (int)(e - b);
-    uint64_t hits = 0;
-    for (int r = 0; r < a.K; r++) {
-        const int32_t id = a.topk[s * a.K + r];
-        int64_t lo = b, hi = e;
-        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a.test_idx[mid] < id) lo = mid + 1; else hi = mid; }
-        if (lo < e && a.test_idx[lo] == id) hits |= 1ull << r;
-    }
-    for (int q = 0; q < a.n_ks; q++) {
-        const int k = a.ks[q];
-        double right = 0.0, dcg = 0.0, idcg = 0.0;
-        for (int r = 0; r < k; r++) {
-            const double disc = 1.0 / log2((double)(r + 2));
-            if ((hits >> r) & 1ull) { right += 1.0; dcg += disc; }
-            if (r < len) idcg += disc;
-        }
-        if (idcg == 0.0) idcg = 1.0;
-        double *o = a.per_user + s * 3 * a.n_ks;
-        o[q] = right / (double)k;                         // utils.py:173-187
-        o[a.n_ks + q] = len > 0 ? right / (double)len : 0.0;
-        o[2 * a.n_ks + q] = dcg / idcg;                   // utils.py:190-203
-    }
-}
-
-// The same without the 64-bit hit mask (any K): running sums of hits, DCG and ideal DCG over the ranks, read out when the rank
-// reaches a cut-off.  The additions are those of k_eval_metrics in the same order, so for K <= 64 the results are bitwise its own.
+// Running sums of hits, DCG and ideal DCG over the ranks, read out when the rank reaches a cut-off (any K: no hit mask).
 __global__ void __launch_bounds__(256) k_eval_metrics_ex(MetricArgs a, int32_t kmax) {
     const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (s >= a.n_eval) return;
@@ -501,8 +437,7 @@ __global__ void __launch_bounds__(256) k_eval_metrics_ex(MetricArgs a, int32_t k
     double *o = a.per_user + s * 3 * a.n_ks;
     for (int r = 0; r < kmax; r++) {
         const int32_t id = a.topk[s * a.K + r];
-        int64_t lo = b, hi = e;
-        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a.test_idx[mid] < id) lo = mid + 1; else hi = mid; }
+        const int64_t lo = csr_lower_bound(a.test_idx, b, e, id);
         const double disc = 1.0 / log2((double)(r + 2));
         if (lo < e && a.test_idx[lo] == id) { right += 1.0; dcg += disc; }
         if (r < len) idcg += disc;
@@ -546,6 +481,10 @@ __global__ void __launch_bounds__(256) k_eval_masks(const int32_t *users, int32_
     }
 }
 
+void lgcn_eval_sum_launch(const double *per_user, int32_t n_eval, int32_t width, double *sums, hipStream_t stream) {
+    hipLaunchKernelGGL(k_eval_sum, dim3(1), dim3(256), 0, stream, per_user, n_eval, width, sums);
+}
+
 static inline int64_t eval_mask_stride(int32_t n_eval) { return ((int64_t)n_eval + 127) / 128 * 128; }
 
 extern "C" int64_t lgcn_eval_mask_words(int32_t m_items, int32_t n_eval) {
@@ -565,6 +504,76 @@ extern "C" int lgcn_eval_build_masks(const int32_t *users, int32_t n_eval, const
     return 0;
 }
 
+// A sweep in `parts` parts per user block, and the merge of their lists.  parts > 1: the partial lists and the block the parts
+// publish their K-th best in (NaN = nothing published) are one stream-ordered allocation, or a plain one freed after a
+// synchronise where the runtime has no pool; it is freed on every path.  `who` is the entry point the messages name.
+template <typename Sweep>
+static int sweep_in_parts(const char *who, EvalArgs &a, int parts, hipStream_t st, Sweep sweep) {
+    char msg[96];
+    void *tmp = nullptr;
+    bool tmp_sync = false, ok = true;
+    if (parts > 1) {
+        const size_t n = (size_t)a.n_eval * parts * a.K;
+        const size_t lists = (n * (sizeof(int32_t) + sizeof(float)) + 255) & ~(size_t)255;
+        const size_t pub = EVAL_PUB_TILES > 0 ? (size_t)parts * a.n_eval * sizeof(float) : 0;
+        if (hipMallocAsync(&tmp, lists + pub, st) != hipSuccess) {
+            (void)hipGetLastError();
+            tmp = nullptr;
+            if (hipMalloc(&tmp, lists + pub) != hipSuccess) {
+                snprintf(msg, sizeof msg, "%s: cannot allocate the partial lists", who); lgcn_set_error(msg); return 4;
+            }
+            tmp_sync = true;       // no stream-ordered pool on this runtime: plain allocation, freed after a synchronise
+        }
+        a.part_items = (int32_t *)tmp; a.part_scores = (float *)((int32_t *)tmp + n);
+        if (pub) {
+            a.thr_pub = (float *)((char *)tmp + lists);
+            ok = hipMemsetAsync(a.thr_pub, 0xff, pub, st) == hipSuccess;
+        }
+    }
+    if (ok) {
+        sweep(a);
+        if (parts > 1) hipLaunchKernelGGL(k_eval_merge, dim3((unsigned)((a.n_eval + 255) / 256)), dim3(256), 0, st, a, parts);
+    }
+    if (tmp) {
+        if (tmp_sync) { (void)hipStreamSynchronize(st); (void)hipFree(tmp); }
+        else (void)hipFreeAsync(tmp, st);
+    }
+    if (!ok) { snprintf(msg, sizeof msg, "%s: memset failed", who); lgcn_set_error(msg); return 10; }
+    if (hipGetLastError() != hipSuccess) { snprintf(msg, sizeof msg, "%s: launch failed", who); lgcn_set_error(msg); return 10; }
+    return 0;
+}
+
+// ---- K <= 64: 128 users per workgroup.  The compact forms (16-bit ids; the split bf16 product or the fp32 matrix instructions)
+//      where the parts are short enough for them, else the generic form: int32 ids, one workgroup per CU, fp32 matrix instructions.
+template <int D, int KS, typename IDT, int WGS, int NBUF, bool SPLIT3>
+static void launch_small(const EvalArgs &a, int parts, bool mk, hipStream_t st) {
+    const dim3 grid((unsigned)((a.n_eval + 127) / 128), (unsigned)parts);
+    if (mk) hipLaunchKernelGGL((k_eval_topk<D, KS, IDT, WGS, NBUF, SPLIT3, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_eval_topk<D, KS, IDT, WGS, NBUF, SPLIT3, false>), grid, dim3(256), 0, st, a);
+}
+
+template <int D>
+static void launch_small_generic(const EvalArgs &a, int parts, bool mk, hipStream_t st) {
+    if (a.K <= 20) launch_small<D, 20, int32_t, 1, 2, false>(a, parts, mk, st);
+    else if (a.K <= 32) launch_small<D, 32, int32_t, 1, 2, false>(a, parts, mk, st);
+    else launch_small<D, 64, int32_t, 1, (D >= 256 ? 1 : 2), false>(a, parts, mk, st);     // (d = 256: 64 slots leave room for one tile)
+}
+
+template <int D>
+static void launch_small_d(const EvalArgs &a, int parts, bool id16, bool split3, bool mk, hipStream_t st) {
+    const bool small = a.K <= 20;
+    if constexpr (D <= 64) {
+        if (id16 && small && split3) { launch_small<D, 20, uint16_t, EVAL_PARTS, EVAL_NBUF, true>(a, parts, mk, st); return; }
+        if (id16 && small) { launch_small<D, 20, uint16_t, EVAL_PARTS, EVAL_NBUF, false>(a, parts, mk, st); return; }
+        if (id16 && split3) { launch_small<D, 64, uint16_t, 2, 2, true>(a, parts, mk, st); return; }
+        if (id16) { launch_small<D, 64, uint16_t, 2, 2, false>(a, parts, mk, st); return; }
+    } else if constexpr (D == 128) {        // 256 registers: two workgroups per CU, K <= 20 alone; the six planes leave LDS for one tile
+        if (id16 && small && split3) { launch_small<D, 20, uint16_t, 2, 1, true>(a, parts, mk, st); return; }
+        if (id16 && small) { launch_small<D, 20, uint16_t, 2, 2, false>(a, parts, mk, st); return; }
+    }
+    launch_small_generic<D>(a, parts, mk, st);
+}
+
 static int eval_topk(const float *E, int32_t n_users, int32_t m_items, int32_t d,
                      const int32_t *users, int32_t n_eval,
                      const int64_t *train_indptr, const int32_t *train_indices,
@@ -574,9 +583,9 @@ static int eval_topk(const float *E, int32_t n_users, int32_t m_items, int32_t d
     }
     if (K < 1 || K > EVAL_KMAX || K > m_items) { lgcn_set_error("lgcn_eval_topk: K must be in 1..64 and <= m_items"); return 3; }
     if (n_eval == 0) return 0;
+    if (d != 32 && d != 64 && d != 128 && d != 256) { lgcn_set_error("embedding dim must be 32, 64, 128 or 256"); return 3; }
     EvalArgs a{E, n_users, m_items, users, n_eval, train_indptr, train_indices, K, topk_items, topk_scores, nullptr, nullptr, nullptr,
                masks, eval_mask_stride(n_eval)};
-    const unsigned blocks = (unsigned)((n_eval + 127) / 128);
     hipStream_t st = (hipStream_t)stream;
     // The item sweep is split over `parts` workgroups per user block, as many as fit a CU together, so that one's list
     // maintenance runs under the others' MFMAs.  Compact lists (16-bit ids relative to the part's first item: d <= 64,
@@ -589,57 +598,15 @@ static int eval_topk(const float *E, int32_t n_users, int32_t m_items, int32_t d
     const int want = (d <= 64 && small) ? EVAL_PARTS : 2;      // d = 128: 256 registers; K > 20: 64-slot lists -- two workgroups per CU
     const bool id16 = split && (ntiles + want - 1) / want + 1 <= EVAL_ID16_MAX_TILES;
     const int parts = id16 ? want : (split && small) ? 2 : 1;
-    void *tmp = nullptr;
-    bool tmp_sync = false;
-    if (parts > 1) {
-        const size_t n = (size_t)n_eval * parts * K;
-        const size_t lists = (n * (sizeof(int32_t) + sizeof(float)) + 255) & ~(size_t)255;
-        const size_t pub = EVAL_PUB_TILES > 0 ? (size_t)parts * n_eval * sizeof(float) : 0;
-        if (hipMallocAsync(&tmp, lists + pub, st) != hipSuccess) {
-            (void)hipGetLastError();
-            tmp = nullptr;
-            if (hipMalloc(&tmp, lists + pub) != hipSuccess) { lgcn_set_error("lgcn_eval_topk: cannot allocate the partial lists"); return 4; }
-            tmp_sync = true;       // no stream-ordered pool on this runtime: plain allocation, freed after a synchronise
-        }
-        a.part_items = (int32_t *)tmp; a.part_scores = (float *)((int32_t *)tmp + n);
-        if (pub) {
-            a.thr_pub = (float *)((char *)tmp + lists);
-            if (hipMemsetAsync(a.thr_pub, 0xff, pub, st) != hipSuccess) { lgcn_set_error("lgcn_eval_topk: memset failed"); return 10; }     // NaN = nothing published
-        }
-    }
-    const dim3 grid(blocks, parts);
     const bool mk = masks != nullptr;
-#define EV(...) do { if (mk) hipLaunchKernelGGL((k_eval_topk<__VA_ARGS__, true>), grid, dim3(256), 0, st, a); \
-                     else hipLaunchKernelGGL((k_eval_topk<__VA_ARGS__, false>), grid, dim3(256), 0, st, a); } while (0)
-    // the generic form: int32 ids, one workgroup per CU, fp32 matrix instructions
-#define EVAL_GENERIC(DD) do { if (K <= 20) EV(DD, 20, int32_t, 1, 2, false); else if (K <= 32) EV(DD, 32, int32_t, 1, 2, false); \
-                              else EV(DD, 64, int32_t, 1, (DD >= 256 ? 1 : 2), false); } while (0)
-#define EVAL_SMALL(DD) do { if (id16 && small && split3) EV(DD, 20, uint16_t, EVAL_PARTS, EVAL_NBUF, true); \
-                            else if (id16 && small) EV(DD, 20, uint16_t, EVAL_PARTS, EVAL_NBUF, false); \
-                            else if (id16 && split3) EV(DD, 64, uint16_t, 2, 2, true); \
-                            else if (id16) EV(DD, 64, uint16_t, 2, 2, false); \
-                            else EVAL_GENERIC(DD); } while (0)
-    switch (d) {
-    case 32: EVAL_SMALL(32); break;
-    case 64: EVAL_SMALL(64); break;
-    case 128:
-        if (id16 && small && split3) EV(128, 20, uint16_t, 2, 1, true);
-        else if (id16 && small) EV(128, 20, uint16_t, 2, 2, false);
-        else EVAL_GENERIC(128);
-        break;
-    case 256: EVAL_GENERIC(256); break;
-    default: if (tmp) { if (tmp_sync) (void)hipFree(tmp); else (void)hipFreeAsync(tmp, st); } lgcn_set_error("embedding dim must be 32, 64, 128 or 256"); return 3;
-    }
-#undef EVAL_SMALL
-#undef EVAL_GENERIC
-#undef EV
-    if (parts > 1) {
-        hipLaunchKernelGGL(k_eval_merge, dim3((unsigned)((n_eval + 255) / 256)), dim3(256), 0, st, a, parts);
-        if (tmp_sync) { (void)hipStreamSynchronize(st); (void)hipFree(tmp); }
-        else (void)hipFreeAsync(tmp, st);
-    }
-    if (hipGetLastError() != hipSuccess) { lgcn_set_error("lgcn_eval_topk: launch failed"); return 10; }
-    return 0;
+    return sweep_in_parts("lgcn_eval_topk", a, parts, st, [&](const EvalArgs &ea) {
+        switch (d) {
+        case 32: launch_small_d<32>(ea, parts, id16, split3, mk, st); break;
+        case 64: launch_small_d<64>(ea, parts, id16, split3, mk, st); break;
+        case 128: launch_small_d<128>(ea, parts, id16, split3, mk, st); break;
+        default: launch_small_d<256>(ea, parts, id16, split3, mk, st); break;
+        }
+    });
 }
 
 extern "C" int lgcn_eval_topk(const float *E, int32_t n_users, int32_t m_items, int32_t d, const int32_t *users, int32_t n_eval,
@@ -670,13 +637,15 @@ extern "C" int lgcn_eval_metrics(const int32_t *topk_items, int32_t n_eval, int3
     MetricArgs a{};
     a.topk = topk_items; a.n_eval = n_eval; a.K = K; a.test_ptr = test_indptr; a.test_idx = test_items_sorted;
     a.n_ks = n_ks; a.per_user = per_user;
+    int32_t kmax = 0;
     for (int q = 0; q < n_ks; q++) {
         if (ks[q] < 1 || ks[q] > K) { lgcn_set_error("lgcn_eval_metrics: a cut-off exceeds K"); return 3; }
         a.ks[q] = ks[q];
+        kmax = ks[q] > kmax ? ks[q] : kmax;
     }
     hipStream_t st = (hipStream_t)stream;
-    if (n_eval > 0) hipLaunchKernelGGL(k_eval_metrics, dim3((unsigned)((n_eval + 255) / 256)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_eval_sum, dim3(1), dim3(256), 0, st, per_user, n_eval, 3 * n_ks, sums);
+    if (n_eval > 0) hipLaunchKernelGGL(k_eval_metrics_ex, dim3((unsigned)((n_eval + 255) / 256)), dim3(256), 0, st, a, kmax);
+    lgcn_eval_sum_launch(per_user, n_eval, 3 * n_ks, sums, st);
     if (hipGetLastError() != hipSuccess) { lgcn_set_error("lgcn_eval_metrics: launch failed"); return 10; }
     return 0;
 }
@@ -751,33 +720,11 @@ static int eval_topk_big(const float *E, int32_t n_users, int32_t m_items, int32
         }
     }
     const bool id16 = (ntiles + parts - 1) / parts + 1 <= EVAL_ID16_MAX_TILES;
-    void *tmp = nullptr;
-    bool tmp_sync = false;
-    if (parts > 1) {
-        const size_t n = (size_t)n_eval * parts * K;
-        const size_t lists = (n * (sizeof(int32_t) + sizeof(float)) + 255) & ~(size_t)255;
-        const size_t pub = EVAL_PUB_TILES > 0 ? (size_t)parts * n_eval * sizeof(float) : 0;
-        if (hipMallocAsync(&tmp, lists + pub, st) != hipSuccess) {
-            (void)hipGetLastError();
-            tmp = nullptr;
-            if (hipMalloc(&tmp, lists + pub) != hipSuccess) { lgcn_set_error("lgcn_eval_topk_ex: cannot allocate the partial lists"); return 4; }
-            tmp_sync = true;
-        }
-        a.part_items = (int32_t *)tmp; a.part_scores = (float *)((int32_t *)tmp + n);
-        if (pub) {
-            a.thr_pub = (float *)((char *)tmp + lists);
-            if (hipMemsetAsync(a.thr_pub, 0xff, pub, st) != hipSuccess) { lgcn_set_error("lgcn_eval_topk_ex: memset failed"); return 10; }
-        }
-    }
-    if (K <= 128) launch_big_k<128>(d, a, parts, id16, split3, masks != nullptr, st);
-    else launch_big_k<256>(d, a, parts, id16, split3, masks != nullptr, st);
-    if (parts > 1) {
-        hipLaunchKernelGGL(k_eval_merge, dim3((unsigned)((n_eval + 255) / 256)), dim3(256), 0, st, a, parts);
-        if (tmp_sync) { (void)hipStreamSynchronize(st); (void)hipFree(tmp); }
-        else (void)hipFreeAsync(tmp, st);
-    }
-    if (hipGetLastError() != hipSuccess) { lgcn_set_error("lgcn_eval_topk_ex: launch failed"); return 10; }
-    return 0;
+    const bool mk = masks != nullptr;
+    return sweep_in_parts("lgcn_eval_topk_ex", a, parts, st, [&](const EvalArgs &ea) {
+        if (K <= 128) launch_big_k<128>(d, ea, parts, id16, split3, mk, st);
+        else launch_big_k<256>(d, ea, parts, id16, split3, mk, st);
+    });
 }
 
 extern "C" int32_t lgcn_eval_kmax(void) { return EVAL_KMAX_EX; }
@@ -815,7 +762,7 @@ extern "C" int lgcn_eval_metrics_ex(const int32_t *topk_items, int32_t n_eval, i
     }
     hipStream_t st = (hipStream_t)stream;
     if (n_eval > 0) hipLaunchKernelGGL(k_eval_metrics_ex, dim3((unsigned)((n_eval + 255) / 256)), dim3(256), 0, st, a, kmax);
-    hipLaunchKernelGGL(k_eval_sum, dim3(1), dim3(256), 0, st, per_user, n_eval, 3 * n_ks, sums);
+    lgcn_eval_sum_launch(per_user, n_eval, 3 * n_ks, sums, st);
     if (hipGetLastError() != hipSuccess) { lgcn_set_error("lgcn_eval_metrics_ex: launch failed"); return 10; }
     return 0;
 }

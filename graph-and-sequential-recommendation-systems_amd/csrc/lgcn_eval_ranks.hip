@@ -2,9 +2,9 @@
 // candidate items that score above it / equal to it, and from those counts precision / recall / NDCG at ANY cut-off, AUC
 // (utils.AUC, utils.py:203-209) and MRR.
 //
-// The item sweep is the one of lgcn_eval.hip (k_eval_topk: a workgroup of NW waves x 32 users, the users' rows in registers
-// as the B operand, item tiles of 32 rows double-buffered through LDS, a user on a lane pair with 16 of the tile's scores in
-// each lane's registers) with another consumer: no list, no insertion, no merge.  A user's test scores and two int32
+// The item sweep is lgcn_eval_sweep.h's: a workgroup of NW waves x 32 users, the users' rows in registers as the B operand, item
+// tiles of 32 rows double-buffered through LDS, a user on a lane pair with 16 of the tile's scores in each lane's registers.
+// It is the sweep of k_eval_topk with another consumer: no list, no insertion, no merge.  A user's test scores and two int32
 // counters per test item live in LDS; per tile a lane compares its 16 unmasked scores with each test score of its user.
 // The counts are integers, added in any order: the result does not depend on the split of the sweep and is bitwise
 // reproducible.  The cost does not depend on a cut-off.
@@ -20,14 +20,9 @@
 #include <stdint.h>
 #include <math.h>
 
-#include "lgcn_device_common.h"
+#include "lgcn_eval_sweep.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 
 #define RANKS_NEG_INF (-3.0e38f)
 #ifndef EVAL_RANKS_TB
@@ -40,24 +35,6 @@ typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 #define RANKS_MAX_PARTS 32
 #define RANKS_LDS_BYTES (160 * 1024)
 
-// the exact three-way bf16 split of lgcn_eval.hip (x = h + m + l by truncation; six of the nine product planes are summed)
-struct Planes2 { uint32_t h, m, l; };
-__device__ __forceinline__ Planes2 split3(float x0, float x1) {
-    const uint32_t M = 0xffff0000u;
-    const float h0 = __uint_as_float(__float_as_uint(x0) & M), h1 = __uint_as_float(__float_as_uint(x1) & M);
-    const float r0 = x0 - h0, r1 = x1 - h1;
-    const float m0 = __uint_as_float(__float_as_uint(r0) & M), m1 = __uint_as_float(__float_as_uint(r1) & M);
-    const float l0 = r0 - m0, l1 = r1 - m1;
-    Planes2 o;
-    o.h = (__float_as_uint(h0) >> 16) | __float_as_uint(h1);
-    o.m = (__float_as_uint(m0) >> 16) | __float_as_uint(m1);
-    o.l = (__float_as_uint(l0) >> 16) | (__float_as_uint(l1) & M);
-    return o;
-}
-__device__ __forceinline__ f32x16 mfma_bf16(const u32x4 &a, const u32x4 &b, const f32x16 &c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
 struct RankArgs {
     const float *E; int32_t n_users, m_items, d;
     const int32_t *users; int32_t n_eval;
@@ -66,11 +43,6 @@ struct RankArgs {
     float *score; int32_t *gt, *eq;
 };
 
-// first position in idx[lo, hi) whose value is >= v (idx ascending)
-__device__ __forceinline__ int64_t lower_bound(const int32_t *idx, int64_t lo, int64_t hi, int32_t v) {
-    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (idx[mid] < v) lo = mid + 1; else hi = mid; }
-    return lo;
-}
 __device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 // ---- score[t] for every (slot, test item): 16 lanes per pair, each a contiguous run of d / 16 elements summed in order, then a
@@ -88,7 +60,7 @@ __global__ void __launch_bounds__(256) k_eval_test_scores(RankArgs a) {
         if (lo < a.n_eval && item >= 0 && item < a.m_items) {
             const int32_t u = a.users[lo];
             const int64_t pb = a.train_ptr[u], pe = a.train_ptr[u + 1];
-            const int64_t q = lower_bound(a.train_idx, pb, pe, item);
+            const int64_t q = csr_lower_bound(a.train_idx, pb, pe, item);
             masked = q < pe && a.train_idx[q] == item;
             const int run = a.d / 16;
             const float *up = a.E + (int64_t)u * a.d + l * run, *ip = a.E + ((int64_t)a.n_users + item) * a.d + l * run;
@@ -100,8 +72,7 @@ __global__ void __launch_bounds__(256) k_eval_test_scores(RankArgs a) {
 }
 
 template <int D, bool SPLIT3, int NW> struct RankShape {
-    static constexpr int RS = D + 4, RSB = D + 8, PLANE_B = 32 * RSB * 2;
-    static constexpr int TILE_F = SPLIT3 ? 3 * PLANE_B / 4 : 32 * RS;
+    static constexpr int TILE_F = SweepGeo<D, SPLIT3>::TILE_F;
     static constexpr int lds = 2 * TILE_F * 4 + 32 * NW * ((RANKS_TB + 1) + (2 * RANKS_TB + 1)) * 4 + 64;
 };
 
@@ -110,11 +81,7 @@ template <int D, bool SPLIT3, int NW>
 __global__ void __launch_bounds__(64 * NW, 1) k_eval_ranks(RankArgs a) {
     constexpr int NT = 64 * NW, NU = 32 * NW, TB = RANKS_TB;
     static_assert(RankShape<D, SPLIT3, NW>::lds <= RANKS_LDS_BYTES, "test scores + counters + item tiles exceed the LDS of a CU");
-    constexpr int HALF = D / 2, RS = D + 4;
-    constexpr int RSB = D + 8, NCH = D / 16, PLANE_B = 32 * RSB * 2;
-    constexpr int TILE_F = RankShape<D, SPLIT3, NW>::TILE_F;
-    constexpr int LPT = 32 * D * 4 / 16 / NT;
-    static_assert(LPT >= 1, "tile smaller than the workgroup");
+    constexpr int TILE_F = SweepGeo<D, SPLIT3>::TILE_F;
     __shared__ __attribute__((aligned(16))) float tile_lds[2][TILE_F];
     __shared__ float ts_lds[NU][TB + 1];                    // the user's test scores of this pass (odd stride: no bank conflict)
     __shared__ uint32_t cnt_lds[NU][2 * TB + 1];            // [2 k] = gt, [2 k + 1] = eq of test item k of this pass
@@ -126,25 +93,8 @@ __global__ void __launch_bounds__(64 * NW, 1) k_eval_ranks(RankArgs a) {
     const int64_t slot = (int64_t)blockIdx.x * NU + wid * 32 + j;
     const bool have = slot < a.n_eval;
     const int32_t uid = have ? a.users[slot] : 0;
-    // ---- this lane's user: half a row in registers (B operand), as k_eval_topk
-    float b[SPLIT3 ? 1 : HALF];
-    u32x4 bh[SPLIT3 ? NCH : 1], bm[SPLIT3 ? NCH : 1], bl[SPLIT3 ? NCH : 1];
-    if constexpr (SPLIT3) {
-#pragma unroll
-        for (int c = 0; c < NCH; c++) {
-            const float *up = a.E + (int64_t)uid * D + 16 * c + 8 * h;
-            const f32x4 v0 = *reinterpret_cast<const f32x4 *>(up), v1 = *reinterpret_cast<const f32x4 *>(up + 4);
-            const Planes2 p0 = split3(v0.x, v0.y), p1 = split3(v0.z, v0.w), p2 = split3(v1.x, v1.y), p3 = split3(v1.z, v1.w);
-            bh[c] = u32x4{p0.h, p1.h, p2.h, p3.h}; bm[c] = u32x4{p0.m, p1.m, p2.m, p3.m}; bl[c] = u32x4{p0.l, p1.l, p2.l, p3.l};
-        }
-    } else {
-        const float *up = a.E + (int64_t)uid * D + h * HALF;
-#pragma unroll
-        for (int s = 0; s < HALF; s += 4) {
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(up + s);
-            b[s] = v.x; b[s + 1] = v.y; b[s + 2] = v.z; b[s + 3] = v.w;
-        }
-    }
+    SweepUser<D, SPLIT3> ub;                                // this lane's user: half a row in registers (B operand)
+    ub.load(a.E + (int64_t)uid * D, h);
     // ---- the user's test list, and the passes the workgroup needs: ceil(longest list / TB)
     int64_t tb0 = 0, te0 = 0;
     if (have) { tb0 = clamp64(a.test_ptr[slot], 0, a.n_test); te0 = clamp64(a.test_ptr[slot + 1], tb0, a.n_test); }
@@ -171,31 +121,7 @@ __global__ void __launch_bounds__(64 * NW, 1) k_eval_ranks(RankArgs a) {
     if (t_begin >= t_end) return;
     const int ul = wid * 32 + j;
 
-    f32x4 pre[LPT];
-    auto load_tile = [&](int t) {
-#pragma unroll
-        for (int q = 0; q < LPT; q++) {
-            const int p = tid + q * NT, r = p / (D / 4), c = p % (D / 4);
-            const int64_t item = (int64_t)t * 32 + r;
-            pre[q] = item < a.m_items ? *reinterpret_cast<const f32x4 *>(items + item * D + c * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-    };
-    auto store_tile = [&](int buf) {
-#pragma unroll
-        for (int q = 0; q < LPT; q++) {
-            const int p = tid + q * NT, r = p / (D / 4), c = p % (D / 4);
-            if constexpr (SPLIT3) {
-                const Planes2 p0 = split3(pre[q].x, pre[q].y), p1 = split3(pre[q].z, pre[q].w);
-                char *dst = reinterpret_cast<char *>(tile_lds[buf]) + (r * RSB + 4 * c) * 2;
-                *reinterpret_cast<uint2 *>(dst) = make_uint2(p0.h, p1.h);
-                *reinterpret_cast<uint2 *>(dst + PLANE_B) = make_uint2(p0.m, p1.m);
-                *reinterpret_cast<uint2 *>(dst + 2 * PLANE_B) = make_uint2(p0.l, p1.l);
-            } else {
-                *reinterpret_cast<f32x4 *>(&tile_lds[buf][r * RS + c * 4]) = pre[q];
-            }
-        }
-    };
-
+    SweepStage<D, NT> stage;
     for (int pass = 0; pass < npass; pass++) {
         const int32_t p0 = pass * TB;
         const int32_t mine = len - p0 < 0 ? 0 : len - p0 > TB ? TB : len - p0;          // my user's test items of this pass
@@ -205,14 +131,14 @@ __global__ void __launch_bounds__(64 * NW, 1) k_eval_ranks(RankArgs a) {
             cnt_lds[ul][2 * k] = 0u; cnt_lds[ul][2 * k + 1] = 0u;
         }
         int64_t cp = c_begin;
-        if (t_begin > 0) cp = lower_bound(cl, c_begin, c_end, t_begin * 32);
+        if (t_begin > 0) cp = csr_lower_bound(cl, c_begin, c_end, t_begin * 32);
         int32_t nid = cp < c_end ? cl[cp] : 0x7fffffff;
-        load_tile(t_begin);
-        store_tile(t_begin & 1);
+        sweep_load_tile(stage, items, a.m_items, t_begin, tid);
+        sweep_store_tile<D, SPLIT3>(stage, tile_lds, t_begin & 1, tid);
         __syncthreads();
         for (int t = t_begin; t < t_end; t++) {
             const int buf = t & 1;
-            if (t + 1 < t_end) load_tile(t + 1);                // in flight under this tile's work
+            if (t + 1 < t_end) sweep_load_tile(stage, items, a.m_items, t + 1, tid);                // in flight under this tile's work
             const int base = t * 32;
             if (trip > 0) {                                     // (wave-uniform: a wave whose lists are done only moves tiles)
                 // ---- the tile's exclusion word of my user: P_u | T_u
@@ -225,42 +151,14 @@ __global__ void __launch_bounds__(64 * NW, 1) k_eval_ranks(RankArgs a) {
                 const u32x2 mm = __builtin_amdgcn_permlane32_swap(m1, m1, false, false);
                 const uint32_t mask = mm.x | mm.y;
                 // ---- 32 items x 32 users
-                f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                if constexpr (SPLIT3) {
-                    const char *arow = reinterpret_cast<const char *>(tile_lds[buf]) + (j * RSB + 8 * h) * 2;
-                    u32x4 ah[NCH], am[NCH], al[NCH];
-#pragma unroll
-                    for (int c = 0; c < NCH; c++) {
-                        am[c] = *reinterpret_cast<const u32x4 *>(arow + PLANE_B + 32 * c);
-                        ah[c] = *reinterpret_cast<const u32x4 *>(arow + 32 * c);
-                        al[c] = *reinterpret_cast<const u32x4 *>(arow + 2 * PLANE_B + 32 * c);
-                    }
-#pragma unroll
-                    for (int c = 0; c < NCH; c++) acc = mfma_bf16(am[c], bm[c], acc);
-#pragma unroll
-                    for (int c = 0; c < NCH; c++) { acc = mfma_bf16(ah[c], bl[c], acc); acc = mfma_bf16(al[c], bh[c], acc); }
-#pragma unroll
-                    for (int c = 0; c < NCH; c++) { acc = mfma_bf16(ah[c], bm[c], acc); acc = mfma_bf16(am[c], bh[c], acc); }
-#pragma unroll
-                    for (int c = 0; c < NCH; c++) acc = mfma_bf16(ah[c], bh[c], acc);
-                } else {
-                    const float *arow = &tile_lds[buf][j * RS + h * HALF];
-#pragma unroll
-                    for (int s = 0; s < HALF; s += 4) {
-                        const f32x4 av = *reinterpret_cast<const f32x4 *>(arow + s);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b[s], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, b[s + 1], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, b[s + 2], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, b[s + 3], acc, 0, 0, 0);
-                    }
-                }
-                // ---- my 16 scores (item row = (reg & 3) + 8 (reg >> 2) + 4 h): excluded items and rows past the table drop
+                f32x16 acc = ub.scores(tile_lds[buf], j, h);
+                // ---- my 16 scores (item row = mfma32_row(reg, h)): excluded items and rows past the table drop
                 //      below every test score, once per tile; the compare loop itself is then two compares per score
                 const bool edge = base + 32 > a.m_items;
                 if (edge || __any(mask != 0u)) {
 #pragma unroll
                     for (int reg = 0; reg < 16; reg++) {
-                        const int row = (reg & 3) + 8 * (reg >> 2) + 4 * h;
+                        const int row = mfma32_row(reg, h);
                         if (((mask >> row) & 1u) || base + row >= a.m_items) acc[reg] = RANKS_NEG_INF;
                     }
                 }
@@ -277,7 +175,7 @@ __global__ void __launch_bounds__(64 * NW, 1) k_eval_ranks(RankArgs a) {
                     if (add) cnt_lds[ul][2 * k + h] += add;
                 }
             }
-            if (t + 1 < t_end) store_tile(buf ^ 1);
+            if (t + 1 < t_end) sweep_store_tile<D, SPLIT3>(stage, tile_lds, buf ^ 1, tid);
             __syncthreads();
         }
         // ---- this pass's counts into the global counters (each lane its own entries: written by this lane alone)
@@ -319,7 +217,7 @@ __global__ void __launch_bounds__(256) k_eval_rank_metrics(RankMetricArgs a) {
     int32_t mine = 0;
     for (int64_t i = tid; i < n; i += 256) {
         const int32_t it = a.test_idx[b + i];
-        const int64_t q = lower_bound(a.train_idx, pb, pe, it);
+        const int64_t q = csr_lower_bound(a.train_idx, pb, pe, it);
         mine += q < pe && a.train_idx[q] == it;
     }
     if (mine) atomicAdd(&inter, mine);
@@ -360,23 +258,6 @@ __global__ void __launch_bounds__(256) k_eval_rank_metrics(RankMetricArgs a) {
     // roc_auc_score(r_all, L_u): Mann-Whitney with ties counted half, over the n (m - n) (test, non-test) pairs
     o[3 * a.n_ks] = (n > 0 && n < m) ? (double)auc2 / (2.0 * (double)n * (double)(m - n)) : 0.0;
     o[3 * a.n_ks + 1] = n > 0 ? 1.0 / (1.0 + (double)a.sorted[b]) : 0.0;
-}
-
-// sums over the slots in a fixed order (one workgroup: deterministic)
-__global__ void __launch_bounds__(256) k_eval_rank_sum(const double *per_user, int32_t n_eval, int32_t width, double *sums) {
-    __shared__ double part[256];
-    for (int c = 0; c < width; c++) {
-        double acc = 0.0;
-        for (int64_t s = threadIdx.x; s < n_eval; s += 256) acc += per_user[s * width + c];
-        part[threadIdx.x] = acc;
-        __syncthreads();
-        for (int w = 128; w > 0; w >>= 1) {
-            if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) sums[c] = part[0];
-        __syncthreads();
-    }
 }
 
 template <int D, bool SPLIT3, int NW>
@@ -458,7 +339,7 @@ extern "C" int lgcn_eval_rank_metrics(int32_t n_eval, int32_t m_items, const int
         hipLaunchKernelGGL(k_eval_rank_metrics, dim3((unsigned)n_eval), dim3(256), 0, st, a);
         (void)hipFreeAsync(tmp, st);
     }
-    hipLaunchKernelGGL(k_eval_rank_sum, dim3(1), dim3(256), 0, st, per_user, n_eval, 3 * n_ks + 2, sums);
+    lgcn_eval_sum_launch(per_user, n_eval, 3 * n_ks + 2, sums, st);
     if (hipGetLastError() != hipSuccess) { lgcn_set_error("lgcn_eval_rank_metrics: launch failed"); return 10; }
     return 0;
 }

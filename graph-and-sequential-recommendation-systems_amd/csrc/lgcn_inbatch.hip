@@ -66,7 +66,7 @@
 //   k_inbatch_diag  merges the larger number of parts.
 //   k_inbatch_grad  role "users" owns Bp / 32 tiles and sweeps all item tiles, role "items" owns (1 + R) Bp / 32 tiles and sweeps the
 //                   user tiles: both extents differ, so the grid is flat (the users' workgroups first).
-#include "lgcn_inbatch_tile.h"      // f32x16, ib_row, ib_scores, IbRow / ib_load / ib_scores_reg, IB_REG_D
+#include "lgcn_inbatch_tile.h"      // ib_scores, IbRow / ib_load / ib_scores_reg, IB_REG_D
 
 // the three [cap] vectors of the score options, carved behind `part` in the context's workspace
 __device__ __forceinline__ float *ib_invu(const InBatchArgs &ia) { return ia.part + 2 * (int64_t)ia.cap * lgcn_inbatch_parts(ia.cap); }
@@ -252,14 +252,14 @@ __global__ void __launch_bounds__(64) k_inbatch_norm(InBatchArgs ia) {
         if constexpr (MIX) pool = t >= Bp / 32;
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {
-            const int c = t * 32 + ib_row(reg, h);
+            const int c = t * 32 + mfma32_row(reg, h);
             if constexpr (MIX) ucs[reg] = pool ? 0 : ia.uid[c]; else ucs[reg] = ia.uid[c];
             pcs[reg] = ia.pid[c];
         }
         float lqs[LQ ? 16 : 1];
         if constexpr (LQ) {
 #pragma unroll
-            for (int reg = 0; reg < 16; reg++) lqs[reg] = ibx_lq<MIX>(ia)[t * 32 + ib_row(reg, h)];
+            for (int reg = 0; reg < 16; reg++) lqs[reg] = ibx_lq<MIX>(ia)[t * 32 + mfma32_row(reg, h)];
         }
         f32x16 acc;
         if constexpr (D <= IB_REG_D) {
@@ -273,7 +273,7 @@ __global__ void __launch_bounds__(64) k_inbatch_norm(InBatchArgs ia) {
         float z[16], tmax = -INFINITY;
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {
-            const int c = t * 32 + ib_row(reg, h);
+            const int c = t * 32 + mfma32_row(reg, h);
             const int32_t uc = ucs[reg], pc = pcs[reg];
             bool ok = ub >= 0 && uc >= 0 && c != b && pc != pb && uc != ub;
             if constexpr (MIX) { if (pool) ok = ub >= 0 && pc >= 0 && pc != pb; }
@@ -384,7 +384,7 @@ __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
         if constexpr (MIX) pool = pool_o || (role == 0 && t >= Bp / 32);
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {
-            const int x = t * 32 + ib_row(reg, h);          // the other side's index (a row of the tile)
+            const int x = t * 32 + mfma32_row(reg, h);          // the other side's index (a row of the tile)
             if constexpr (MIX) uxs[reg] = (role == 0 && pool) ? 0 : ia.uid[x]; else uxs[reg] = ia.uid[x];
             pxs[reg] = ia.pid[x];
             // the USER of the pair owns s_bb and the merged (M, 1 + Zm1): the lane's under role 0, the row's under role 1
@@ -408,7 +408,7 @@ __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
         }
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {
-            const int x = t * 32 + ib_row(reg, h);
+            const int x = t * 32 + mfma32_row(reg, h);
             bool ok = uo >= 0 && uxs[reg] >= 0 && x != o && pxs[reg] != po && uxs[reg] != uo;
             // a pool pair: a sound user, a pool column that exists, another item than the user's positive
             if constexpr (MIX) { if (pool) ok = (role == 0 ? uo >= 0 && pxs[reg] >= 0 : uxs[reg] >= 0 && po >= 0) && pxs[reg] != po; }
@@ -425,7 +425,7 @@ __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
         // g[owned][col] += sum_x W[x][owned] Other[x][col]: register i of w is the A operand as it stands
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {
-            const float *orow = oth + (int64_t)(t * 32 + ib_row(reg, h)) * D + col0 + j;
+            const float *orow = oth + (int64_t)(t * 32 + mfma32_row(reg, h)) * D + col0 + j;
 #pragma unroll
             for (int cb = 0; cb < CB; cb++) {
                 float bv;
@@ -435,12 +435,12 @@ __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
         }
     }
     if constexpr (COS) tproj += __shfl_xor(tproj, 32);      // both lane halves: lane r and lane r + 32 hold owned row r's scalar
-    // rows of g: owned index blockIdx.x * 32 + ib_row(reg, h); columns col0 + cb * 32 + j
+    // rows of g: owned index blockIdx.x * 32 + mfma32_row(reg, h); columns col0 + cb * 32 + j
 #pragma unroll
     for (int reg = 0; reg < 16; reg++) {
-        const int ob = bx * 32 + ib_row(reg, h);
+        const int ob = bx * 32 + mfma32_row(reg, h);
         float t_row = 0.f;
-        if constexpr (COS) t_row = __shfl(tproj, ib_row(reg, h));             // (every lane takes part: before the skip)
+        if constexpr (COS) t_row = __shfl(tproj, mfma32_row(reg, h));             // (every lane takes part: before the skip)
         int32_t us;
         if constexpr (MIX) us = role == 0 ? ia.uid[ob] : ia.pid[ob]; else us = ia.uid[ob];        // (a pool row has only its item id)
         if (us < 0) continue;                   // void or padding: no row to add to (its W is zero)

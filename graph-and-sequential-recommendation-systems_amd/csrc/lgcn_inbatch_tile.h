@@ -6,10 +6,7 @@
 #define LGCN_INBATCH_TILE_H
 #include "lgcn_device_common.h"
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-// tile row of accumulator register `reg` on lane half h (C/D layout of the 32x32 MFMAs)
-__device__ __forceinline__ int ib_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
+// (the accumulator type f32x16 and its row formula mfma32_row: lgcn_device_common.h)
 
 // 32 x 32 scores acc[i][j] = sum_k A[i][k] B[j][k]: arow / brow point at this lane's row (lane & 31) of each operand, at column
 // h D/2.  MFMA number t multiplies columns (t, D/2 + t): the k order every score of this file is summed in.

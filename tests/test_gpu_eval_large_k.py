@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from conftest import EPS32
+from eval_cases import csr as _csr, problem as _problem
 
 DEV = "cuda:0"
 gpu = pytest.mark.gpu
@@ -17,36 +18,6 @@ gpu = pytest.mark.gpu
 
 def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _problem(m_items, d, n_users=300, n_eval=257, seed=0):
-    """Random table, train positives clustered across tile and part edges and at the table's end, an unsorted repeating user
-    list."""
-    rng = np.random.Generator(np.random.PCG64(seed + m_items + d))
-    E = rng.standard_normal((n_users + m_items, d)).astype(np.float32)
-    users = rng.integers(0, n_users, n_eval).astype(np.int32)
-    ntiles = (m_items + 31) // 32
-    rows = []
-    for u in range(n_users):
-        c = set(rng.integers(0, m_items, rng.integers(0, 60)).tolist())
-        t0 = int(rng.integers(0, max(1, ntiles - 1))) * 32
-        c |= set(range(t0 + int(rng.integers(0, 8)), min(m_items, t0 + 32 + int(rng.integers(0, 20)))))     # across a tile edge
-        for parts in (2, 3, 4):
-            b = (ntiles * (u % parts) // parts) * 32                                                    # around a part boundary
-            c |= {min(m_items - 1, max(0, b - 1)), min(m_items - 1, b), min(m_items - 1, b + 1)}
-        if u % 7 == 0:
-            c |= {m_items - 1, m_items - 2}
-        if u % 11 == 0:
-            c = set()
-        rows.append(np.array(sorted(c), np.int32))
-    return E, users, rows
-
-
-def _csr(rows):
-    ptr = np.zeros(len(rows) + 1, np.int64)
-    ptr[1:] = np.cumsum([len(r) for r in rows])
-    idx = np.concatenate(rows).astype(np.int32) if ptr[-1] else np.zeros(1, np.int32)
-    return ptr, idx
 
 
 def _run_ex(pkg, E, n_users, users, ptr, idx, K, masks=None, flags=0, cap=None):

@@ -98,6 +98,38 @@ def test_training_kernels_live_in_one_file(pkg):
         assert re.search(r"^(?:int|void) " + fn + r"\([^;{]*\)\s*\{", device, flags=re.M), f"{fn} is not defined in lgcn_device.hip"
 
 
+def test_evaluation_device_pieces_are_defined_once(pkg):
+    """What the evaluation units share has ONE definition under csrc/ (lgcn_eval_sweep.h, lgcn_device_common.h; k_eval_sum in
+    lgcn_eval.hip behind lgcn_eval_sum_launch), and no .hip file spells the accumulator-row formula or the lower-bound search of a
+    CSR row inline.  Two searches stay where they are: k_eval_test_scores looks for the last slot with test_ptr[s] <= p (another
+    predicate), and k_pop_slots keeps its own loop because its assembly changes with the call.  The sweep pieces (user operand,
+    score tile, tile stage) are defined in lgcn_eval_sweep.h and k_eval_ranks runs them from there: lgcn_eval_ranks.hip holds no
+    matrix instruction and no tile stage of its own.  (k_eval_topk still spells its own: DESIGN 4.28.)"""
+    csrc = os.path.dirname(pkg.build.SOURCES[0])
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".cpp"))}
+    defs = {"split3": r"\bPlanes2 split3\(", "mfma_bf16": r"\bf32x16 mfma_bf16\(", "Planes2": r"\bstruct Planes2\b",
+            "mfma32_row": r"\bint mfma32_row\(", "csr_lower_bound": r"\bint64_t csr_lower_bound\(", "k_eval_sum": r"\bvoid\s+(?:__launch_bounds__\(\d+\)\s+)?k_eval_sum\(",
+            "SweepUser": r"\bstruct SweepUser\b", "sweep_load_tile": r"\bvoid sweep_load_tile\(", "sweep_store_tile": r"\bvoid sweep_store_tile\("}
+    home = {"split3": "lgcn_eval_sweep.h", "mfma_bf16": "lgcn_eval_sweep.h", "Planes2": "lgcn_eval_sweep.h", "mfma32_row": "lgcn_device_common.h",
+            "csr_lower_bound": "lgcn_eval_sweep.h", "k_eval_sum": "lgcn_eval.hip", "SweepUser": "lgcn_eval_sweep.h",
+            "sweep_load_tile": "lgcn_eval_sweep.h", "sweep_store_tile": "lgcn_eval_sweep.h"}
+    for name, pat in defs.items():
+        assert [f for f, t in text.items() if re.search(pat, t)] == [home[name]], name
+    assert not any(re.search(r"\bk_eval_rank_sum\b|\bk_eval_metrics\b|\bib_row\b", t) for t in text.values())
+    ranks = text["lgcn_eval_ranks.hip"]
+    assert "__builtin_amdgcn_mfma" not in ranks and "mfma_bf16(" not in ranks and "split3(" not in ranks and "load_tile = [" not in ranks
+    assert all(w in ranks for w in ("ub.load(", "ub.scores(", "sweep_load_tile(", "sweep_store_tile<"))
+    for f, t in text.items():
+        if not f.endswith(".hip"):
+            continue
+        assert not re.search(r"\(\s*reg\s*&\s*3\s*\)\s*\+\s*8\s*\*?\s*\(\s*reg\s*>>\s*2\s*\)", t), f"{f} spells the accumulator-row formula"
+        if not f.startswith("lgcn_eval"):                  # (the sampler and the shuffle search other things than a CSR row of item ids)
+            continue
+        loops = re.findall(r"while \(lo < hi\)[^\n]*", t)
+        allowed = {"lgcn_eval_ranks.hip": ["test_ptr[mid + 1] <= p"], "lgcn_eval_pop.hip": ["a.test_idx[mid] < id"]}.get(f, [])
+        assert len(loops) == len(allowed) and all(w in l for w, l in zip(allowed, loops)), f"{f}: {loops}"
+
+
 def test_glibc_stream_and_randint(pkg):
     s = pkg.sampling
     s.seed(2020)

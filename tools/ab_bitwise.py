@@ -4,6 +4,7 @@ a refactor of the kernels must reproduce it exactly.
 
     python tools/ab_bitwise.py --lib-a PATH --lib-b PATH
     LGCN_LIB_PATH=PATH python tools/ab_bitwise.py --tree-a DIR --tree-b DIR
+    python tools/ab_bitwise.py --lib-a PATH --lib-b PATH --kinds eval        (only these kinds; the cases keep their numbers)
 
 The second form holds the library and compares two checkouts of the Python layer that drives it: each side's child is
 DIR/tools/ab_bitwise.py --child, run in DIR.
@@ -43,7 +44,15 @@ Cases (cases()):
             and fp8 once, K 1 / 2 / 3 and dense_last 0 / 1 in rotation (every (form, K) pair: check_coverage); rows1 and dense with
             the popularity gate and with item-item smoothing; column shards at rank widths 32 (fp32, bf16) and 64 (fp8).  All but
             rows0 through lgcn_train_epoch_dp over the loopback communicator, whose all-reduce adds in rank order: deterministic,
-            column shards included.  Per rank: table, both moments, loss_out, error flag.  LAST, by the same rule as directau.
+            column shards included.  Per rank: table, both moments, loss_out, error flag.  Behind directau, by the same rule.
+  eval      the fused evaluation on the problem of tests/eval_cases.py (Gaussian table, 300 users, 257 slots, train positives across
+            tile and part edges and at the table's end): m_items 3001 (one part) and 10007 (parts, 16-bit ids) at d 32/64/128/256,
+            270001 (parts with int32 ids) at d 32 and 128.  Per case, ids and scores of lgcn_eval_topk_ex at K 20/64/100/256, masks
+            on / off, flags 0 / LGCN_EVAL_FP32; lgcn_eval_topk, _masked and _fp32 at K = 20; lgcn_eval_metrics (K <= 64) and
+            lgcn_eval_metrics_ex on those lists with the cut-offs unsorted and one repeated; lgcn_eval_ranks with both flags and
+            lgcn_eval_rank_metrics; lgcn_eval_pop_metrics.  The K-th place of a list is not defined under an exact fp32 tie and the
+            parts' exchange is timing dependent, so the kind is run library against ITSELF first; a case that differs there gets
+            another seed (EVAL_SEEDS), never a looser comparison.  LAST, by the same rule as directau.
 
 A side whose tree does not know a case of the other side (an older checkout under --tree-a) is compared on the common cases; the
 cases only one side ran are counted in the report and never differ."""
@@ -67,6 +76,9 @@ IB_KINDS = ("inbatch", "inbatch_mix")
 STEP_KS, STEP_DLS, GATE_DS = (1, 2, 3), (0, 1), (32, 64, 128)
 AU_GAMMAS = (0.0, 1.0)
 DP_FORMS, DP_WS, DP_DS, DP_FP8_AT = ("rows0", "rows1", "dense", "row_sharded"), (2, 3), (32, 64), ("row_sharded", 2, 64)
+EVAL_MS, EVAL_DS, EVAL_BIG_M, EVAL_BIG_DS = (3001, 10007), DS, 270001, (32, 128)
+EVAL_KS, EVAL_SMALL_K, EVAL_USERS, EVAL_SLOTS, EVAL_GROUPS = (20, 64, 100, 256), 20, 300, 257, 3
+EVAL_SEEDS = {}                                            # (m_items, d) -> seed of the problem, where 0 ties at a K-th place
 DP_TIMEOUT = 120                                           # seconds the rank threads of one lgcn_train_epoch_dp call may take
 
 
@@ -130,10 +142,16 @@ def cases():
         out.append(dict(kind="dp", form=form, W=2, d=32, mode=MODES[j], K=2, dl=0, cfg=dict(use_pop_gate=True)))
         out.append(dict(kind="dp", form=form, W=2, d=32, mode=MODES[1 - j], K=2, dl=0, cfg=dict(use_item_item=True, i2i_build='cooc', i2i_alpha=0.5)))
     out += [dict(kind="dp", form="cols", W=2, d=d, mode=mode, K=K, dl=0, cfg={}) for d, mode, K in ((64, "fp32", 1), (64, "bf16", 3), (128, "fp8", 2))]
+    out += [dict(kind="eval", m_items=m, d=d) for m in EVAL_MS for d in EVAL_DS]      # eval (last: see the module docstring)
+    out += [dict(kind="eval", m_items=EVAL_BIG_M, d=d) for d in EVAL_BIG_DS]
     return out
 
 
 def check_coverage(cs):
+    ev = [c for c in cs if c["kind"] == "eval"]
+    assert ev and cs[-len(ev):] == ev, "the eval cases are the last ones"
+    assert {(c["m_items"], c["d"]) for c in ev} == set(itertools.product(EVAL_MS, EVAL_DS)) | {(EVAL_BIG_M, d) for d in EVAL_BIG_DS}
+    cs = cs[:-len(ev)]
     dp = [c for c in cs if c["kind"] == "dp"]
     assert dp and cs[-len(dp):] == dp, "the dp cases are the last ones"
     cs = cs[:-len(dp)]
@@ -195,6 +213,8 @@ def name(c):
                 + (f"-R{c['R']}of{MIX_RMAX}" if c["kind"] == "inbatch_mix" else "") + tag)
     if c["kind"] == "mf":
         return f"mf-d{c['d']}-B{c['B']}"
+    if c["kind"] == "eval":
+        return f"eval-m{c['m_items']}-d{c['d']}"
     if c["kind"] == "dp":
         return f"dp-{c['form']}-w{c['W']}-d{c['d']}-{c['mode']}-K{c['K']}-dl{c['dl']}" + "".join(f"-{k}" for k in c["cfg"] if k.startswith("use_"))
     if c["kind"] == "directau":
@@ -311,7 +331,64 @@ def run_dp_case(pkg, c, path, dev):
     return out
 
 
-def child(out_path):
+def run_eval_case(pkg, c, dev):
+    """One eval case -> {field: array}: every output of every evaluation entry point on one problem (see the module docstring)."""
+    import torch
+    import eval_cases as EC
+    L, lib = pkg._lib, pkg._lib.load()
+    m, d, n, nu = c["m_items"], c["d"], EVAL_SLOTS, EVAL_USERS
+    E, users, rows = EC.problem(m, d, n_users=nu, n_eval=n, seed=EVAL_SEEDS.get((m, d), 0))
+    rng = np.random.Generator(np.random.PCG64(11 + m + d))
+    tptr, tidx = EC.csr([np.sort(rng.choice(m, int(rng.integers(0, 30)), replace=False)).astype(np.int32) for _ in range(n)])
+    info = (rng.integers(0, 1000, m) * 8 + rng.integers(0, EVAL_GROUPS, m)).astype(np.int32)
+
+    def to_dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    ptr, idx = EC.csr(rows)
+    E, users, ptr, idx, tptr, tidx, info = (to_dev(a) for a in (E, users, ptr, idx, tptr, tidx, info))
+    masks = torch.empty(int(lib.lgcn_eval_mask_words(m, n)), dtype=torch.int32, device=dev)
+    L.check(lib.lgcn_eval_build_masks(L.tp(users), n, L.tp(ptr), L.tp(idx), m, L.tp(masks), L.current_stream()), "lgcn_eval_build_masks")
+    out = {}
+
+    def keep(tag, *tensors):
+        torch.cuda.synchronize()
+        for j, t in enumerate(tensors):
+            out[f"{tag}.{j}"] = t.cpu().numpy()
+
+    def lists(K):
+        return torch.full((n, K), -7, dtype=torch.int32, device=dev), torch.full((n, K), 7.0, dtype=torch.float32, device=dev)
+    for K in EVAL_KS:
+        ks = [K, 1, 5, 5, min(20, K)]                       # unsorted, one repeated
+        for mk in (False, True):
+            for fp32 in (False, True):
+                ids, sc = lists(K)
+                L.eval_topk(E, nu, users, ptr, idx, K, ids, sc, masks=masks if mk else None, fp32=fp32)
+                tag = f"topk_ex.K{K}.{'masks' if mk else 'cursor'}.{'fp32' if fp32 else 'split3'}"
+                keep(tag, ids, sc)
+                keep(tag + ".metrics_ex", *L.eval_metrics(ids, tptr, tidx, ks))
+                if K <= 64:
+                    pu, sums = torch.empty(n, 3 * len(ks), dtype=torch.float64, device=dev), torch.empty(3 * len(ks), dtype=torch.float64, device=dev)
+                    ks_h = torch.tensor(ks, dtype=torch.int32)      # (host memory: alive until the call has returned)
+                    L.check(lib.lgcn_eval_metrics(L.tp(ids), n, K, L.tp(tptr), L.tp(tidx), L.tp(ks_h), len(ks), L.tp(pu), L.tp(sums),
+                                                  L.current_stream()), "lgcn_eval_metrics")
+                    keep(tag + ".metrics", pu, sums)
+        pop = L.eval_pop_metrics(ids, tptr, tidx, info, EVAL_GROUPS, ks, per_slot=torch.empty(n, len(ks), 2, EVAL_GROUPS, dtype=torch.float64, device=dev),
+                                 want_exposure=True)
+        keep(f"pop.K{K}", pop['packed'], pop['exposure'], pop['per_slot'])
+    K = EVAL_SMALL_K
+    head = (L.tp(E), nu, m, d, L.tp(users), n, L.tp(ptr), L.tp(idx), K)
+    for entry, tail in (("lgcn_eval_topk", ()), ("lgcn_eval_topk_masked", (L.tp(masks),)), ("lgcn_eval_topk_fp32", ())):
+        ids, sc = lists(K)
+        L.check(getattr(lib, entry)(*head, L.tp(ids), L.tp(sc), *tail, L.current_stream()), entry)
+        keep(entry, ids, sc)
+    for fp32 in (False, True):
+        score, gt, eq = L.eval_ranks(E, nu, users, ptr, idx, tptr, tidx, fp32=fp32)
+        keep(f"ranks.{'fp32' if fp32 else 'split3'}", score, gt, eq)
+        keep(f"rank_metrics.{'fp32' if fp32 else 'split3'}", *L.eval_rank_metrics(m, users, ptr, idx, tptr, tidx, score, gt, eq, [100, 1, 20, 20, m]))
+    return out
+
+
+def child(out_path, kinds=()):
     sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
     sys.argv = [sys.argv[0]]                                 # world parses sys.argv on import: this tool's flags are not the package's
     import torch
@@ -326,7 +403,13 @@ def child(out_path):
         return torch.from_numpy(np.ascontiguousarray(a)).to(torch.int32).to(dev)
 
     for i, c in enumerate(cases()):
+        if kinds and c["kind"] not in kinds:
+            continue
         rng = np.random.Generator(np.random.PCG64(7000 + i))
+        if c["kind"] == "eval":
+            for field, v in run_eval_case(pkg, c, dev).items():
+                result[f"{i:03d} {name(c)} {field}"] = v
+            continue
         if c["kind"] == "dp":                                # (its batches are tests/dp_cases.make_batches': no draw from rng)
             for field, v in run_dp_case(pkg, c, path, dev).items():
                 result[f"{i:03d} {name(c)} {field}"] = v
@@ -406,13 +489,13 @@ def child(out_path):
         del m
     pkg.world.configure([])
     np.savez(out_path, **result)
-    print(f"CHILD OK {len(cases())} cases, library {pkg.build.LIB_PATH}")
+    print(f"CHILD OK {len({k.split(' ', 1)[0] for k in result})} cases, library {pkg.build.LIB_PATH}")
 
 
-def run_child(lib, out_path, timeout, tree=REPO):
+def run_child(lib, out_path, timeout, tree=REPO, kinds=()):
     env = dict(os.environ, LGCN_LIB_PATH=os.path.abspath(lib))
     tree = os.path.abspath(tree)
-    cmd = [sys.executable, os.path.join(tree, "tools", "ab_bitwise.py"), "--child", out_path]
+    cmd = [sys.executable, os.path.join(tree, "tools", "ab_bitwise.py"), "--child", out_path] + (["--kinds", ",".join(kinds)] if kinds else [])
     p = subprocess.Popen(cmd, cwd=tree, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, start_new_session=True)
     try:
         out, _ = p.communicate(timeout=timeout)
@@ -438,7 +521,7 @@ def driver(a):
     with tempfile.TemporaryDirectory(prefix="lgcn_ab_") as tmp:
         files = [os.path.join(tmp, f"{tag}.npz") for tag in "ab"]
         for lib, tree, f in zip((a.lib_a, a.lib_b), trees, files):
-            run_child(lib, f, a.child_timeout, tree)
+            run_child(lib, f, a.child_timeout, tree, a.kinds)
         za, zb = np.load(files[0]), np.load(files[1])
         common = [k for k in za.files if k in zb.files]
         only = sorted({k.rsplit(" ", 1)[0] for k in set(za.files) ^ set(zb.files)})
@@ -452,8 +535,8 @@ def driver(a):
                     differing.append(case)
                     n = int((x.view(np.uint32) != y.view(np.uint32)).sum()) if x.shape == y.shape else -1
                     print(f"DIFFERS {k}: {n} of {x.size} elements")
-    n = len(cases())
-    kinds = [c["kind"] for c in cases()]
+    kinds = [c["kind"] for c in cases() if not a.kinds or c["kind"] in a.kinds]
+    n = len(kinds)
     print("cases per kind: " + ", ".join(f"{k} {kinds.count(k)}" for k in dict.fromkeys(kinds)))
     if differing:
         print(f"first differing case: {differing[0]}")
@@ -471,9 +554,13 @@ if __name__ == "__main__":
     ap.add_argument("--tree-b", metavar="DIR")
     ap.add_argument("--child", default="", metavar="NPZ", help="child: run the cases on the library LGCN_LIB_PATH names and write this file")
     ap.add_argument("--child-timeout", type=int, default=480, help="seconds each child may take")
+    ap.add_argument("--kinds", default="", metavar="KIND[,KIND]", help="run only the cases of these kinds (default: all)")
     a = ap.parse_args()
+    a.kinds = tuple(k for k in a.kinds.split(",") if k)
+    if a.kinds and not set(a.kinds) <= {c["kind"] for c in cases()}:
+        ap.error(f"--kinds: unknown kind in {a.kinds}")
     if a.child:
-        child(a.child)
+        child(a.child, a.kinds)
     else:
         if a.tree_a and a.tree_b and not (a.lib_a or a.lib_b):      # two trees on ONE library: the one LGCN_LIB_PATH names
             a.lib_a = a.lib_b = os.environ.get("LGCN_LIB_PATH")
