@@ -13,7 +13,7 @@
 //
 // Four launches between the forward and the backward of the step, over a workspace of Bp = B rounded up to 32 rows (the in-batch
 // step's conventions: zero rows and id -1 for void samples and for the padding, no branch in the MFMA loop for raggedness):
-//   k_directau_rows   one lane group of min(D, 64) lanes per sample (the geometry and the id check of k_inbatch_rows): gathers
+//   k_directau_rows   one lane group of min(D, 64) lanes per sample (the sample prologue of lgcn_batch_rows.h): gathers
 //                     e_u, e_p through slot_row, writes x, y, inv, q, the ids and the alignment term |x - y|^2, the reg term, zeroes
 //                     the stale bitmap, flags the two rows, counts them and adds the lam terms to G64.
 //   k_directau_norm   one wave per (side, owner tile I, part of the sweep).  The score tile is T.T^T of ONE table on the fp32-input
@@ -32,8 +32,9 @@
 //                     MFMA (k_inbatch_grad's scheme); the projection inv_b (sum_c W x_c - t_b x_b) is applied to the partial rows in
 //                     the epilogue (it is linear) and they go to G64 with fixed_add: the split of the sweep has no ordering effect.
 // k in [e^-8, 1]: no maximum is subtracted and nothing underflows.  Operands up to D = 64 (IB_REG_D) live in registers with the
-// next tile prefetched, above that they are streamed, as in lgcn_inbatch.hip.
-#include "lgcn_inbatch_tile.h"
+// next tile prefetched, above that they are streamed: the sweep of lgcn_inbatch_tile.h, shared with lgcn_inbatch.hip.
+#include "lgcn_batch_rows.h"        // RowsGeo and the sample prologue, DISPATCH_ROWS
+#include "lgcn_inbatch_tile.h"      // the score tile and the pieces of the sweep round it
 
 #ifndef LGCN_DIRECTAU_NORM_FULL
 #define LGCN_DIRECTAU_NORM_FULL 0     /* 1 (A/B only, profiles/directau/README.md): the normaliser sweeps every tile and counts every pair
@@ -47,23 +48,11 @@ __device__ __forceinline__ float au_k(float qb, float qc, float s) { return expf
 template <int D, typename TI, bool WTS>
 __global__ void __launch_bounds__(256) k_directau_rows(DirectAuArgs da) {
     const MultiNegArgs &a = da.m;
-    constexpr int LPT = D < 64 ? D : 64, CPT = D / LPT, SPB = 256 / LPT;     // lanes per sample, samples per workgroup
-    // last step's row bitmap is dead: zero it here with plain stores (the two bitmaps alternate per step)
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.bitmap_words; i += (int64_t)gridDim.x * 256)
-        a.stale_bitmap[i] = 0u;
-    const int b = blockIdx.x * SPB + threadIdx.x / LPT, l = threadIdx.x % LPT;
+    ROWS_ZERO_STALE_BITMAP(a);
+    ROWS_GEOMETRY(D);
     const int Bp = lgcn_inbatch_rows(a.B);
     if (b >= Bp) return;                        // whole lane groups leave together
-    // every id is checked before anything is addressed with it: lane 0 holds the user, lane 1 the positive
-    int32_t id = 0;
-    bool idbad = false;
-    if (b < a.B) {
-        if (l == 0) { id = a.users[b]; idbad = id < 0 || id >= a.n_users; }
-        else if (l == 1) { id = a.pos[b]; idbad = id < 0 || (int64_t)id + a.n_users >= a.N; }
-    }
-    constexpr unsigned long long GROUP = LPT == 64 ? ~0ull : ((1ull << (LPT & 63)) - 1ull);
-    const int gshift = (threadIdx.x & 63) / LPT * LPT;                          // this group's first lane in the wave
-    const bool bad = b >= a.B || (__ballot(idbad) & (GROUP << gshift)) != 0ull;
+    ROWS_LOAD_IDS(a, ROWS_PAIR_FIRST, false, b < a.B);      // lane 0 holds the user, lane 1 the positive; the padding b >= B is bad too
     if (bad) {          // padding, or an out-of-range id: zero rows, masked in every pair by uid = -1
 #pragma unroll
         for (int j = 0; j < CPT; j++) { da.X[(int64_t)b * D + j * LPT + l] = 0.f; da.Y[(int64_t)b * D + j * LPT + l] = 0.f; }
@@ -78,14 +67,9 @@ __global__ void __launch_bounds__(256) k_directau_rows(DirectAuArgs da) {
     const int64_t ru = (int64_t)iu, rp = (int64_t)ip + a.n_users;
     const bool ego = a.reg_ego != 0;
     const float lam = ego ? 0.f : a.lam;
-    float u[CPT], p[CPT], t0[CPT];
+    float u[CPT], p[CPT];
     float ru2 = 0.f, rp2 = 0.f;
-    slot_row<D, TI, WTS>(a, ru, l, u, t0);
-#pragma unroll
-    for (int j = 0; j < CPT; j++) { const float v = ego ? t0[j] : u[j]; ru2 += v * v; }
-    slot_row<D, TI, WTS>(a, rp, l, p, t0);
-#pragma unroll
-    for (int j = 0; j < CPT; j++) { const float v = ego ? t0[j] : p[j]; rp2 += v * v; }
+    ROWS_PAIR((void)0)
     const float rr = group_sum<LPT>(ru2 + rp2);
     // |e| = sqrtf of the fp32 sum of squares, inv = 1 / |e| by an IEEE division (0 for a row of norm 0): k_inbatch_rows' COS form.
     // The reg term and lam e stay on the rows themselves
@@ -93,7 +77,7 @@ __global__ void __launch_bounds__(256) k_directau_rows(DirectAuArgs da) {
 #pragma unroll
     for (int j = 0; j < CPT; j++) { nu += u[j] * u[j]; np += p[j] * p[j]; }
     nu = group_sum<LPT>(nu); np = group_sum<LPT>(np);
-    const float inv_u = nu > 0.f ? 1.f / sqrtf(nu) : 0.f, inv_p = np > 0.f ? 1.f / sqrtf(np) : 0.f;
+    const float inv_u = rows_inv_norm(nu), inv_p = rows_inv_norm(np);
     float qx = 0.f, qy = 0.f, al = 0.f;
 #pragma unroll
     for (int j = 0; j < CPT; j++) {
@@ -114,8 +98,7 @@ __global__ void __launch_bounds__(256) k_directau_rows(DirectAuArgs da) {
     }
     if (l < 2) {                                // the 2 rows of the sample: one lane each
         const int64_t myrow = l == 0 ? ru : rp;
-        atomicOr(a.bitmap + (myrow >> 5), 1u << (myrow & 31));
-        if (a.cnt) atomicAdd(a.cnt + myrow, 1);
+        ROWS_FLAG(a, myrow, 1);
     }
 }
 
@@ -126,15 +109,13 @@ __global__ void __launch_bounds__(64) k_directau_norm(DirectAuArgs da) {
     const int bx = blockIdx.x, by = blockIdx.y, side = blockIdx.z;
     const float *T = side == 0 ? da.X : da.Y, *q = side == 0 ? da.qx : da.qy;
     const int b = bx * 32 + j;                  // this lane's owned index (a column of the tile)
-    const int t0 = by * LGCN_INBATCH_PART_TILES, t1 = t0 + LGCN_INBATCH_PART_TILES < nT ? t0 + LGCN_INBATCH_PART_TILES : nT;
+    IB_PART_BOUNDS(by, nT);
     const int ts = LGCN_DIRECTAU_NORM_FULL ? t0 : (t0 > bx ? t0 : bx);      // pairs are counted once, as (b, c > b): tiles below the owner's hold none
     const int32_t sb = da.uid[b];               // >= 0: the sample is sound
     const float qb = q[b];
     const float *brow = T + (int64_t)b * D + h * (D / 2);
     float z = 0.f;
-    constexpr int RD = D <= IB_REG_D ? D : 8;   // (the register form's types at a size that costs nothing where it is not used)
-    IbRow<RD> own, cur, nxt;
-    if constexpr (D <= IB_REG_D) { ib_load(own, brow); if (ts < t1) ib_load(cur, T + (int64_t)(ts * 32 + j) * D + h * (D / 2)); }
+    IB_SWEEP_BEGIN(D, own, T, ts, ts < t1)
 #pragma unroll 1
     for (int t = ts; t < t1; t++) {
         int32_t ids[16];
@@ -142,14 +123,7 @@ __global__ void __launch_bounds__(64) k_directau_norm(DirectAuArgs da) {
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) { const int c = t * 32 + mfma32_row(reg, h); ids[reg] = da.uid[c]; qc[reg] = q[c]; }
         f32x16 acc;
-        if constexpr (D <= IB_REG_D) {
-            const int tn = t + 1 < t1 ? t + 1 : t;
-            ib_load(nxt, T + (int64_t)(tn * 32 + j) * D + h * (D / 2));
-            acc = ib_scores_reg<RD>(cur, own);
-            cur = nxt;
-        } else {
-            acc = ib_scores<D>(T + (int64_t)(t * 32 + j) * D + h * (D / 2), brow);
-        }
+        IB_SWEEP_SCORES(D, acc, own, T, t);
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {    // register order: part of the result
             const int c = t * 32 + mfma32_row(reg, h);
@@ -166,8 +140,7 @@ __global__ void __launch_bounds__(64) k_directau_norm(DirectAuArgs da) {
 template <int D>
 __global__ void __launch_bounds__(256) k_directau_merge(DirectAuArgs da) {
     const MultiNegArgs &a = da.m;
-    constexpr int LPT = D < 64 ? D : 64, CPT = D / LPT, SPB = 256 / LPT;
-    const int b = blockIdx.x * SPB + threadIdx.x / LPT, l = threadIdx.x % LPT;
+    ROWS_GEOMETRY(D);
     // Z_X, Z_Y: every wave of the launch adds the same partials in the same order (lane-strided, then the tree)
     const int n = (lgcn_inbatch_rows(a.B) / 32) * lgcn_inbatch_parts(a.B);
     float zx = 0.f, zy = 0.f;
@@ -208,7 +181,7 @@ __global__ void __launch_bounds__(256) k_directau_merge(DirectAuArgs da) {
 
 template <int D>
 __global__ void __launch_bounds__(64) k_directau_grad(DirectAuArgs da) {
-    constexpr int CB = D < 128 ? D / 32 : 4;    // 32-column blocks of the output this workgroup accumulates
+    constexpr int CB = ib_grad_blocks(D);        // 32-column blocks of the output this workgroup accumulates
     const int l = threadIdx.x, j = l & 31, h = l >> 5;
     const int Bp = lgcn_inbatch_rows(da.m.B), nT = Bp / 32;
     const int side = blockIdx.z & 1, col0 = (blockIdx.z >> 1) * 128;
@@ -217,19 +190,13 @@ __global__ void __launch_bounds__(64) k_directau_grad(DirectAuArgs da) {
     if (coef == 0.f) return;
     const float *T = side == 0 ? da.X : da.Y, *q = side == 0 ? da.qx : da.qy;
     const int o = bx * 32 + j;                  // this lane's owned index (a column of the score tile)
-    const int t0 = by * LGCN_INBATCH_PART_TILES, t1 = t0 + LGCN_INBATCH_PART_TILES < nT ? t0 + LGCN_INBATCH_PART_TILES : nT;
+    IB_PART_BOUNDS(by, nT);
     const int32_t so = da.uid[o];
     const float qo = q[o];
     float tproj = 0.f;                          // sum_x W[x][o] s[x][o] over this lane's 16 rows of every tile
     const float *brow = T + (int64_t)o * D + h * (D / 2);
-    f32x16 g[CB];
-#pragma unroll
-    for (int cb = 0; cb < CB; cb++)
-#pragma unroll
-        for (int reg = 0; reg < 16; reg++) g[cb][reg] = 0.f;
-    constexpr int RD = D <= IB_REG_D ? D : 8;
-    IbRow<RD> ownr, cur, nxt;
-    if constexpr (D <= IB_REG_D) { ib_load(ownr, brow); ib_load(cur, T + (int64_t)(t0 * 32 + j) * D + h * (D / 2)); }
+    IB_GRAD_ZERO();
+    IB_SWEEP_BEGIN(D, ownr, T, t0, true)
 #pragma unroll 1
     for (int t = t0; t < t1; t++) {
         // the rows' ids and squared norms, the B operands of the second product and, in the register form, the next tile's rows are
@@ -240,20 +207,10 @@ __global__ void __launch_bounds__(64) k_directau_grad(DirectAuArgs da) {
         for (int reg = 0; reg < 16; reg++) {
             const int x = t * 32 + mfma32_row(reg, h);          // the other index (a row of the tile)
             ids[reg] = da.uid[x]; qc[reg] = q[x];
-            if constexpr (D <= IB_REG_D) {
-#pragma unroll
-                for (int cb = 0; cb < CB; cb++) ob[reg][cb] = T[(int64_t)x * D + col0 + j + cb * 32];
-            }
+            IB_GRAD_PREFETCH(D, T, x);
         }
         f32x16 w;
-        if constexpr (D <= IB_REG_D) {
-            const int tn = t + 1 < t1 ? t + 1 : t;
-            ib_load(nxt, T + (int64_t)(tn * 32 + j) * D + h * (D / 2));
-            w = ib_scores_reg<RD>(cur, ownr);
-            cur = nxt;
-        } else {
-            w = ib_scores<D>(T + (int64_t)(t * 32 + j) * D + h * (D / 2), brow);
-        }
+        IB_SWEEP_SCORES(D, w, ownr, T, t);
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {
             const int x = t * 32 + mfma32_row(reg, h);
@@ -262,50 +219,30 @@ __global__ void __launch_bounds__(64) k_directau_grad(DirectAuArgs da) {
             w[reg] = ok ? coef * au_k(qo, qc[reg], s) : 0.f;
             tproj += w[reg] * s;
         }
-        // g[owned][col] += sum_x W[x][owned] T[x][col]: register i of w is the A operand as it stands
-#pragma unroll
-        for (int reg = 0; reg < 16; reg++) {
-            const float *orow = T + (int64_t)(t * 32 + mfma32_row(reg, h)) * D + col0 + j;
-#pragma unroll
-            for (int cb = 0; cb < CB; cb++) {
-                float bv;
-                if constexpr (D <= IB_REG_D) bv = ob[reg][cb]; else bv = orow[cb * 32];
-                g[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[reg], bv, g[cb], 0, 0, 0);
-            }
-        }
+        IB_GRAD_PRODUCT(D, T, t);                // g[owned][col] += sum_x W[x][owned] T[x][col]
     }
-    tproj += __shfl_xor(tproj, 32);             // both lane halves: lane r and lane r + 32 hold owned row r's scalar
+    IB_GRAD_TPROJ_COMBINE();
     // rows of g: owned index bx * 32 + mfma32_row(reg, h); columns col0 + cb * 32 + j
     const int32_t *rid = side == 0 ? da.uid : da.pid;
     const float *inv = side == 0 ? da.invx : da.invy;
 #pragma unroll
     for (int reg = 0; reg < 16; reg++) {
         const int ob = bx * 32 + mfma32_row(reg, h);
-        const float t_row = __shfl(tproj, mfma32_row(reg, h));            // (every lane takes part: before the skip)
+        const float t_row = IB_GRAD_TPROJ_ROW(reg);       // (every lane takes part: before the skip)
         const int32_t us = rid[ob];
         if (us < 0) continue;                   // void or padding: no row to add to (its W is zero)
         const int64_t row = side == 0 ? (int64_t)us : (int64_t)us + da.m.n_users;
         const float inv_o = inv[ob];
-#pragma unroll
-        for (int cb = 0; cb < CB; cb++) {
-            const float oh = T[(int64_t)ob * D + col0 + cb * 32 + j];
-            fixed_add(da.m.G64 + row * D + col0 + cb * 32 + j, inv_o * (g[cb][reg] - t_row * oh));
-        }
+        IB_GRAD_ADD_PROJECTED(D, da.m.G64, T, inv_o);
     }
 }
 
 template <int D>
 static void launch_d(const DirectAuArgs &a, int act_dtype, bool wts, hipStream_t st) {
-    constexpr int SPB = 256 / (D < 64 ? D : 64);
+    constexpr int SPB = RowsGeo<D>::SPB;
     const int Bp = lgcn_inbatch_rows(a.m.B), NP = lgcn_inbatch_parts(a.m.B);
     const dim3 rows_grid((unsigned)((Bp + SPB - 1) / SPB)), merge_grid((unsigned)((a.m.B + SPB - 1) / SPB));
-    if (act_dtype == LGCN_F32) {
-        if (wts) hipLaunchKernelGGL((k_directau_rows<D, float, true>), rows_grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_directau_rows<D, float, false>), rows_grid, dim3(256), 0, st, a);
-    } else {
-        if (wts) hipLaunchKernelGGL((k_directau_rows<D, bf16_t, true>), rows_grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_directau_rows<D, bf16_t, false>), rows_grid, dim3(256), 0, st, a);
-    }
+    DISPATCH_ROWS(act_dtype, wts, hipLaunchKernelGGL((k_directau_rows<D, TI, WTS>), rows_grid, dim3(256), 0, st, a));
     hipLaunchKernelGGL((k_directau_norm<D>), dim3((unsigned)(Bp / 32), (unsigned)NP, 2u), dim3(64), 0, st, a);
     hipLaunchKernelGGL((k_directau_merge<D>), merge_grid, dim3(256), 0, st, a);
     hipLaunchKernelGGL((k_directau_grad<D>), dim3((unsigned)(Bp / 32), (unsigned)NP, 2u * (D > 128 ? D / 128 : 1)), dim3(64), 0, st, a);

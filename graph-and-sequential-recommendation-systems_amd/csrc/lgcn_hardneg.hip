@@ -26,28 +26,19 @@
 // The selected item id goes to sel_id[b] (library-owned): the backward chain's slot kernels (k_g32, k_finish) then run their
 // three-slot forms on (users, pos, sel_id).  sel_out[b] (the caller's, may be NULL) gets the selected INDEX r.  A sample with an
 // out-of-range id is void as in k_multineg (err flag, zero terms, nothing else) and stores -1 to both.
-// This file is its own translation unit so that the instantiations of k_multineg keep their code shape (lgcn_multineg.hip).
-#include "lgcn_device_common.h"
+// The sample prologue (geometry, stale-bitmap loop, id check, user / positive pair, flag and count) is lgcn_batch_rows.h's, the one
+// k_multineg opens with; the score pass and the emit are this kernel's own.  This file stays a translation unit of its own: the
+// kernel shares no pass with k_multineg, and a unit per loss keeps one loss's edit out of the other's compilation.
+#include "lgcn_batch_rows.h"      // RowsGeo and the sample prologue (bitmap loop, id check, user / positive pair, flag and count), DISPATCH_ROWS
 
 template <int D, typename TI, bool WTS>
 __global__ void __launch_bounds__(256) k_hardneg(HardNegArgs h) {
     const MultiNegArgs &a = h.m;
-    constexpr int LPT = D < 64 ? D : 64, CPT = D / LPT, SPB = 256 / LPT;     // lanes per sample, samples per workgroup
-    // last step's row bitmap is dead: zero it here with plain stores (the two bitmaps alternate per step)
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.bitmap_words; i += (int64_t)gridDim.x * 256)
-        a.stale_bitmap[i] = 0u;
-    const int b = blockIdx.x * SPB + threadIdx.x / LPT, l = threadIdx.x % LPT;
+    ROWS_ZERO_STALE_BITMAP(a);
+    ROWS_GEOMETRY(D);
     if (b >= a.B) return;                       // whole lane groups leave together
     const int R = a.R;
-    // every id is checked before anything is addressed with it: lane r < R holds candidate r, lanes R / R + 1 the user / positive
-    int32_t id = 0;
-    bool idbad = false;
-    if (l < R) { id = a.negs[(int64_t)l * a.neg_stride + b]; idbad = id < 0 || (int64_t)id + a.n_users >= a.N; }
-    else if (l == R) { id = a.users[b]; idbad = id < 0 || id >= a.n_users; }
-    else if (l == R + 1) { id = a.pos[b]; idbad = id < 0 || (int64_t)id + a.n_users >= a.N; }
-    constexpr unsigned long long GROUP = LPT == 64 ? ~0ull : ((1ull << (LPT & 63)) - 1ull);
-    const int gshift = (threadIdx.x & 63) / LPT * LPT;                          // this group's first lane in the wave
-    const bool bad = (__ballot(idbad) & (GROUP << gshift)) != 0ull;
+    ROWS_LOAD_IDS(a, ROWS_NEGS_FIRST, true, true);      // lane r < R holds candidate r, lanes R / R + 1 the user / positive
     if (bad) {                                  // an out-of-range id voids the whole sample: err flag, zero terms, no gradient
         if (l == 0) {
             atomicExch(a.err, 1); a.terms[b] = 0.f; a.terms[a.terms_stride + b] = 0.f;
@@ -59,14 +50,9 @@ __global__ void __launch_bounds__(256) k_hardneg(HardNegArgs h) {
     const int64_t ru = (int64_t)__shfl(id, R, LPT), rp = (int64_t)__shfl(id, R + 1, LPT) + a.n_users;
     const bool ego = a.reg_ego != 0;
     const float lam = ego ? 0.f : a.lam;
-    float u[CPT], p[CPT], t0[CPT];
+    float u[CPT], p[CPT];
     float ps = 0.f, ru2 = 0.f, rp2 = 0.f;
-    slot_row<D, TI, WTS>(a, ru, l, u, t0);
-#pragma unroll
-    for (int j = 0; j < CPT; j++) { const float v = ego ? t0[j] : u[j]; ru2 += v * v; }
-    slot_row<D, TI, WTS>(a, rp, l, p, t0);
-#pragma unroll
-    for (int j = 0; j < CPT; j++) { const float v = ego ? t0[j] : p[j]; ps += u[j] * p[j]; rp2 += v * v; }
+    ROWS_PAIR(ps += u[j] * p[j])
     ps = group_sum<LPT>(ps);
     // ---- score.  s_r into lane r; the next candidate's rows fly while this one is scored.  The pass reads ONE row per candidate,
     // the output-table row.  slot_row also hands back the table's own row (n0 / nn0): that is the first term of e, loaded either
@@ -99,7 +85,7 @@ __global__ void __launch_bounds__(256) k_hardneg(HardNegArgs h) {
         beaten += (sr > s || (sr == s && r < l)) ? 1 : 0;
     }
     const int jb = (int)lgcn_hn_rank(h.seed, h.step, b, h.top_m);
-    const unsigned long long votes = (__ballot(l < R && beaten == jb) >> gshift) & GROUP;
+    const unsigned long long votes = ROWS_VOTES(l < R && beaten == jb);
     const int sel = votes ? __ffsll(votes) - 1 : 0;
     const int32_t nid = __shfl(id, sel, LPT);
     const int64_t rn = (int64_t)nid + a.n_users;
@@ -128,22 +114,15 @@ __global__ void __launch_bounds__(256) k_hardneg(HardNegArgs h) {
     }
     if (l < 3) {                                // the three rows of the triplet: one lane each, every slot weighs 1
         const int64_t myrow = l == 0 ? ru : (l == 1 ? rp : rn);
-        atomicOr(a.bitmap + (myrow >> 5), 1u << (myrow & 31));
-        if (a.cnt) atomicAdd(a.cnt + myrow, 1);
+        ROWS_FLAG(a, myrow, 1);
     }
 }
 
 template <int D>
 static void launch_d(const HardNegArgs &h, int act_dtype, bool wts, hipStream_t st) {
-    constexpr int SPB = 256 / (D < 64 ? D : 64);
+    constexpr int SPB = RowsGeo<D>::SPB;
     const dim3 grid((unsigned)((h.m.B + SPB - 1) / SPB)), block(256);
-    if (act_dtype == LGCN_F32) {
-        if (wts) hipLaunchKernelGGL((k_hardneg<D, float, true>), grid, block, 0, st, h);
-        else hipLaunchKernelGGL((k_hardneg<D, float, false>), grid, block, 0, st, h);
-    } else {
-        if (wts) hipLaunchKernelGGL((k_hardneg<D, bf16_t, true>), grid, block, 0, st, h);
-        else hipLaunchKernelGGL((k_hardneg<D, bf16_t, false>), grid, block, 0, st, h);
-    }
+    DISPATCH_ROWS(act_dtype, wts, hipLaunchKernelGGL((k_hardneg<D, TI, WTS>), grid, block, 0, st, h));
 }
 
 int lgcn_hardneg_launch(const HardNegArgs &h, int d, int act_dtype, bool wts, hipStream_t st) {

@@ -10,7 +10,7 @@
 //   g_{u_b} = sum_c W[b,c] e_{p_c} + lam e_{u_b},   g_{p_c} = sum_b W[b,c] e_{u_b} + lam e_{p_c},   lam = decay / B
 //
 // Four launches between the forward and the backward of the step, over a workspace of Bp = B rounded up to 32 rows:
-//   k_inbatch_rows   one lane group of min(D, 64) lanes per sample (the geometry and the id check of k_multineg).  Gathers e_u
+//   k_inbatch_rows   one lane group of min(D, 64) lanes per sample (the sample prologue of lgcn_batch_rows.h).  Gathers e_u
 //                    and e_p through slot_row -- the expression every loss uses -- into dense fp32 U[Bp][D], P[Bp][D] (zero
 //                    rows for void samples and for the padding b >= B), writes s_{b,b}, the reg term, the ids (-1: void),
 //                    zeroes the stale bitmap, flags the two rows, counts them and adds the lam terms to G64.
@@ -30,6 +30,8 @@
 //                    split of the sweep has no ordering effect.
 // s_{b,c} has the same bits in all three places: the same k order (lane half h walks columns h D/2 .. h D/2 + D/2 - 1 of both
 // operands) and fp32 products commute, so exp(z - M) <= 1 everywhere and q, Q_b are consistent.
+// The sweep itself -- part bounds, operand forms, the second product, the projected epilogue -- is lgcn_inbatch_tile.h's, shared with
+// lgcn_directau.hip; k_inbatch_norm and k_inbatch_grad hold the roles, the masks and the weights.
 // Operands: up to D = 64 (IB_REG_D) a lane keeps its row of the owned side in registers for the whole sweep and loads the swept
 // side's NEXT tile (and this tile's ids, normalisers and second-product operands) while the score MFMAs of this tile run; above
 // that the rows are streamed from L2 in chunks of 8 columns per lane half (128 floats per operand would not fit beside the
@@ -66,7 +68,8 @@
 //   k_inbatch_diag  merges the larger number of parts.
 //   k_inbatch_grad  role "users" owns Bp / 32 tiles and sweeps all item tiles, role "items" owns (1 + R) Bp / 32 tiles and sweeps the
 //                   user tiles: both extents differ, so the grid is flat (the users' workgroups first).
-#include "lgcn_inbatch_tile.h"      // ib_scores, IbRow / ib_load / ib_scores_reg, IB_REG_D
+#include "lgcn_batch_rows.h"        // RowsGeo and the sample prologue, DISPATCH_ROWS
+#include "lgcn_inbatch_tile.h"      // the score tile (ib_scores, IbRow / ib_load / ib_scores_reg, IB_REG_D) and the pieces of the sweep round it
 
 // the three [cap] vectors of the score options, carved behind `part` in the context's workspace
 __device__ __forceinline__ float *ib_invu(const InBatchArgs &ia) { return ia.part + 2 * (int64_t)ia.cap * lgcn_inbatch_parts(ia.cap); }
@@ -89,26 +92,12 @@ __device__ __forceinline__ void ib_merge(float &m, float &r, float m2, float r2)
 template <int D, typename TI, bool WTS, bool COS, bool LQ, bool MIX>
 __global__ void __launch_bounds__(256) k_inbatch_rows(InBatchArgs ia) {
     const MultiNegArgs &a = ia.m;
-    constexpr int LPT = D < 64 ? D : 64, CPT = D / LPT, SPB = 256 / LPT;     // lanes per sample, samples per workgroup
-    // last step's row bitmap is dead: zero it here with plain stores (the two bitmaps alternate per step)
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.bitmap_words; i += (int64_t)gridDim.x * 256)
-        a.stale_bitmap[i] = 0u;
-    const int b = blockIdx.x * SPB + threadIdx.x / LPT, l = threadIdx.x % LPT;
+    ROWS_ZERO_STALE_BITMAP(a);
+    ROWS_GEOMETRY(D);
     const int Bp = lgcn_inbatch_rows(a.B);
     if (b >= Bp) return;                        // whole lane groups leave together
-    // every id is checked before anything is addressed with it: lane 0 holds the user, lane 1 the positive
-    int32_t id = 0;
-    bool idbad = false;
-    if (b < a.B) {
-        if (l == 0) { id = a.users[b]; idbad = id < 0 || id >= a.n_users; }
-        else if (l == 1) { id = a.pos[b]; idbad = id < 0 || (int64_t)id + a.n_users >= a.N; }
-        if constexpr (MIX) {                    // lanes 2 .. R + 1 hold the sample's negatives (R <= 16: inside the smallest group)
-            if (l >= 2 && l < 2 + a.R) { id = a.negs[(int64_t)(l - 2) * a.neg_stride + b]; idbad = id < 0 || (int64_t)id + a.n_users >= a.N; }
-        }
-    }
-    constexpr unsigned long long GROUP = LPT == 64 ? ~0ull : ((1ull << (LPT & 63)) - 1ull);
-    const int gshift = (threadIdx.x & 63) / LPT * LPT;                          // this group's first lane in the wave
-    const bool bad = b >= a.B || (__ballot(idbad) & (GROUP << gshift)) != 0ull;
+    // lane 0 holds the user, lane 1 the positive, with MIX lanes 2 .. R + 1 the sample's negatives; the padding b >= B is bad too
+    ROWS_LOAD_IDS(a, ROWS_PAIR_FIRST, MIX, b < a.B);
     if (bad) {          // padding, or an out-of-range id: a zero row and a zero column of the score matrix, masked by uid = -1
 #pragma unroll
         for (int j = 0; j < CPT; j++) { ia.U[(int64_t)b * D + j * LPT + l] = 0.f; ia.P[(int64_t)b * D + j * LPT + l] = 0.f; }
@@ -136,14 +125,9 @@ __global__ void __launch_bounds__(256) k_inbatch_rows(InBatchArgs ia) {
     const int64_t ru = (int64_t)iu, rp = (int64_t)ip + a.n_users;
     const bool ego = a.reg_ego != 0;
     const float lam = ego ? 0.f : a.lam;
-    float u[CPT], p[CPT], t0[CPT];
+    float u[CPT], p[CPT];
     float ps = 0.f, ru2 = 0.f, rp2 = 0.f;
-    slot_row<D, TI, WTS>(a, ru, l, u, t0);
-#pragma unroll
-    for (int j = 0; j < CPT; j++) { const float v = ego ? t0[j] : u[j]; ru2 += v * v; }
-    slot_row<D, TI, WTS>(a, rp, l, p, t0);
-#pragma unroll
-    for (int j = 0; j < CPT; j++) { const float v = ego ? t0[j] : p[j]; ps += u[j] * p[j]; rp2 += v * v; }
+    ROWS_PAIR(ps += u[j] * p[j])
     ps = group_sum<LPT>(ps);
     float rr = group_sum<LPT>(ru2 + rp2);
     if constexpr (MIX) {
@@ -162,7 +146,7 @@ __global__ void __launch_bounds__(256) k_inbatch_rows(InBatchArgs ia) {
 #pragma unroll
                 for (int j = 0; j < CPT; j++) nn += n[j] * n[j];
                 nn = group_sum<LPT>(nn);
-                inv_n = nn > 0.f ? 1.f / sqrtf(nn) : 0.f;
+                inv_n = rows_inv_norm(nn);
             }
 #pragma unroll
             for (int j = 0; j < CPT; j++) {
@@ -186,7 +170,7 @@ __global__ void __launch_bounds__(256) k_inbatch_rows(InBatchArgs ia) {
 #pragma unroll
         for (int j = 0; j < CPT; j++) { nu += u[j] * u[j]; np += p[j] * p[j]; }
         nu = group_sum<LPT>(nu); np = group_sum<LPT>(np);
-        const float inv_u = nu > 0.f ? 1.f / sqrtf(nu) : 0.f, inv_p = np > 0.f ? 1.f / sqrtf(np) : 0.f;
+        const float inv_u = rows_inv_norm(nu), inv_p = rows_inv_norm(np);
         ps = 0.f;
 #pragma unroll
         for (int j = 0; j < CPT; j++) {
@@ -217,13 +201,11 @@ __global__ void __launch_bounds__(256) k_inbatch_rows(InBatchArgs ia) {
     if constexpr (MIX) {
         if (l < 2 + a.R) {                      // the 2 + R rows of the sample: one lane each, counted as k_multineg counts them
             const int64_t myrow = l == 0 ? ru : (int64_t)id + a.n_users;
-            atomicOr(a.bitmap + (myrow >> 5), 1u << (myrow & 31));
-            if (a.cnt) atomicAdd(a.cnt + myrow, l < 2 ? a.R : 1);
+            ROWS_FLAG(a, myrow, l < 2 ? a.R : 1);
         }
     } else if (l < 2) {                         // the 2 rows of the sample: one lane each
         const int64_t myrow = l == 0 ? ru : rp;
-        atomicOr(a.bitmap + (myrow >> 5), 1u << (myrow & 31));
-        if (a.cnt) atomicAdd(a.cnt + myrow, 1);
+        ROWS_FLAG(a, myrow, 1);
     }
 }
 
@@ -234,16 +216,14 @@ __global__ void __launch_bounds__(64) k_inbatch_norm(InBatchArgs ia) {
     int nT = Bp / 32;                           // item tiles of the sweep
     if constexpr (MIX) nT = (1 + ia.m.R) * nT;  // ... the pool's behind the batch's own
     const int b = blockIdx.x * 32 + j;          // this lane's user (a column of the tile)
-    const int t0 = blockIdx.y * LGCN_INBATCH_PART_TILES, t1 = t0 + LGCN_INBATCH_PART_TILES < nT ? t0 + LGCN_INBATCH_PART_TILES : nT;
+    IB_PART_BOUNDS(blockIdx.y, nT);
     const int32_t ub = ia.uid[b], pb = ia.pid[b];
     const float sbb = ia.sbb[b], tau = ia.m.tau;
     float lqb = 0.f;                            // log Q of the lane's own positive
     if constexpr (LQ) lqb = ibx_lq<MIX>(ia)[b];
     const float *brow = ia.U + (int64_t)b * D + h * (D / 2);
     float m = -INFINITY, r = 0.f;
-    constexpr int RD = D <= IB_REG_D ? D : 8;   // (the register form's types at a size that costs nothing where it is not used)
-    IbRow<RD> own, cur, nxt;
-    if constexpr (D <= IB_REG_D) { ib_load(own, brow); ib_load(cur, ia.P + (int64_t)(t0 * 32 + j) * D + h * (D / 2)); }
+    IB_SWEEP_BEGIN(D, own, ia.P, t0, true)
 #pragma unroll 1
     for (int t = t0; t < t1; t++) {
         // this tile's ids and the next tile's rows are in flight while this tile is multiplied
@@ -262,14 +242,7 @@ __global__ void __launch_bounds__(64) k_inbatch_norm(InBatchArgs ia) {
             for (int reg = 0; reg < 16; reg++) lqs[reg] = ibx_lq<MIX>(ia)[t * 32 + mfma32_row(reg, h)];
         }
         f32x16 acc;
-        if constexpr (D <= IB_REG_D) {
-            const int tn = t + 1 < t1 ? t + 1 : t;
-            ib_load(nxt, ia.P + (int64_t)(tn * 32 + j) * D + h * (D / 2));
-            acc = ib_scores_reg<RD>(cur, own);
-            cur = nxt;
-        } else {
-            acc = ib_scores<D>(ia.P + (int64_t)(t * 32 + j) * D + h * (D / 2), brow);
-        }
+        IB_SWEEP_SCORES(D, acc, own, ia.P, t);
         float z[16], tmax = -INFINITY;
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {
@@ -301,8 +274,7 @@ __global__ void __launch_bounds__(64) k_inbatch_norm(InBatchArgs ia) {
 template <int D, bool COS, bool MIX>
 __global__ void __launch_bounds__(256) k_inbatch_diag(InBatchArgs ia) {
     const MultiNegArgs &a = ia.m;
-    constexpr int LPT = D < 64 ? D : 64, CPT = D / LPT, SPB = 256 / LPT;
-    const int b = blockIdx.x * SPB + threadIdx.x / LPT, l = threadIdx.x % LPT;
+    ROWS_GEOMETRY(D);
     if (b >= a.B) return;
     const int32_t iu = ia.uid[b], ip = ia.pid[b];
     if (iu < 0) return;                         // void: k_inbatch_rows wrote its zero terms
@@ -335,7 +307,7 @@ __global__ void __launch_bounds__(256) k_inbatch_diag(InBatchArgs ia) {
 
 template <int D, bool COS, bool LQ, bool MIX>
 __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
-    constexpr int CB = D < 128 ? D / 32 : 4;    // 32-column blocks of the output this workgroup accumulates
+    constexpr int CB = ib_grad_blocks(D);        // 32-column blocks of the output this workgroup accumulates
     const int l = threadIdx.x, j = l & 31, h = l >> 5;
     const int Bp = lgcn_inbatch_rows(ia.m.B);
     int nT = Bp / 32;                           // tiles of the swept side
@@ -353,7 +325,7 @@ __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
     }
     const float *own = role == 0 ? ia.U : ia.P, *oth = role == 0 ? ia.P : ia.U;
     const int o = bx * 32 + j;                  // this lane's owned index (a column of the score tile)
-    const int t0 = by * LGCN_INBATCH_PART_TILES, t1 = t0 + LGCN_INBATCH_PART_TILES < nT ? t0 + LGCN_INBATCH_PART_TILES : nT;
+    IB_PART_BOUNDS(by, nT);
     int32_t uo, po = ia.pid[o];
     float sbb_o, M_o, den_o;
     if constexpr (MIX) {                        // an owned item index may lie in the pool: no user, no s_bb, no merged pair there
@@ -365,14 +337,8 @@ __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
     if constexpr (LQ) lq_o = ibx_lq<MIX>(ia)[o];
     float tproj = 0.f;                          // cosine: sum_x W[x][o] s[x][o] over this lane's 16 rows of every tile
     const float *brow = own + (int64_t)o * D + h * (D / 2);
-    f32x16 g[CB];
-#pragma unroll
-    for (int cb = 0; cb < CB; cb++)
-#pragma unroll
-        for (int reg = 0; reg < 16; reg++) g[cb][reg] = 0.f;
-    constexpr int RD = D <= IB_REG_D ? D : 8;   // (the register form's types at a size that costs nothing where it is not used)
-    IbRow<RD> ownr, cur, nxt;
-    if constexpr (D <= IB_REG_D) { ib_load(ownr, brow); ib_load(cur, oth + (int64_t)(t0 * 32 + j) * D + h * (D / 2)); }
+    IB_GRAD_ZERO();
+    IB_SWEEP_BEGIN(D, ownr, oth, t0, true)
 #pragma unroll 1
     for (int t = t0; t < t1; t++) {
         // what the tile needs besides its scores is in flight while the scores are multiplied: the rows' ids, the users' s_bb and
@@ -392,20 +358,10 @@ __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
             Ms[reg] = role == 0 ? M_o : ia.mrg[2 * x]; dens[reg] = role == 0 ? den_o : ia.mrg[2 * x + 1];
             // lq of the pair's ITEM less lq of the pair's user's own positive: the row's less the lane's under role 0
             if constexpr (LQ) { const float lq_x = ibx_lq<MIX>(ia)[x]; lqd[reg] = role == 0 ? lq_x - lq_o : lq_o - lq_x; }
-            if constexpr (D <= IB_REG_D) {
-#pragma unroll
-                for (int cb = 0; cb < CB; cb++) ob[reg][cb] = oth[(int64_t)x * D + col0 + j + cb * 32];
-            }
+            IB_GRAD_PREFETCH(D, oth, x);
         }
         f32x16 w;
-        if constexpr (D <= IB_REG_D) {
-            const int tn = t + 1 < t1 ? t + 1 : t;
-            ib_load(nxt, oth + (int64_t)(tn * 32 + j) * D + h * (D / 2));
-            w = ib_scores_reg<RD>(cur, ownr);
-            cur = nxt;
-        } else {
-            w = ib_scores<D>(oth + (int64_t)(t * 32 + j) * D + h * (D / 2), brow);
-        }
+        IB_SWEEP_SCORES(D, w, ownr, oth, t);
 #pragma unroll
         for (int reg = 0; reg < 16; reg++) {
             const int x = t * 32 + mfma32_row(reg, h);
@@ -422,25 +378,15 @@ __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
                 w[reg] = ok ? expf(z - Ms[reg]) / dens[reg] * inv_tauB : 0.f;
             }
         }
-        // g[owned][col] += sum_x W[x][owned] Other[x][col]: register i of w is the A operand as it stands
-#pragma unroll
-        for (int reg = 0; reg < 16; reg++) {
-            const float *orow = oth + (int64_t)(t * 32 + mfma32_row(reg, h)) * D + col0 + j;
-#pragma unroll
-            for (int cb = 0; cb < CB; cb++) {
-                float bv;
-                if constexpr (D <= IB_REG_D) bv = ob[reg][cb]; else bv = orow[cb * 32];
-                g[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[reg], bv, g[cb], 0, 0, 0);
-            }
-        }
+        IB_GRAD_PRODUCT(D, oth, t);              // g[owned][col] += sum_x W[x][owned] Other[x][col]
     }
-    if constexpr (COS) tproj += __shfl_xor(tproj, 32);      // both lane halves: lane r and lane r + 32 hold owned row r's scalar
+    if constexpr (COS) IB_GRAD_TPROJ_COMBINE();
     // rows of g: owned index blockIdx.x * 32 + mfma32_row(reg, h); columns col0 + cb * 32 + j
 #pragma unroll
     for (int reg = 0; reg < 16; reg++) {
         const int ob = bx * 32 + mfma32_row(reg, h);
         float t_row = 0.f;
-        if constexpr (COS) t_row = __shfl(tproj, mfma32_row(reg, h));             // (every lane takes part: before the skip)
+        if constexpr (COS) t_row = IB_GRAD_TPROJ_ROW(reg);          // (every lane takes part: before the skip)
         int32_t us;
         if constexpr (MIX) us = role == 0 ? ia.uid[ob] : ia.pid[ob]; else us = ia.uid[ob];        // (a pool row has only its item id)
         if (us < 0) continue;                   // void or padding: no row to add to (its W is zero)
@@ -450,11 +396,7 @@ __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
         if constexpr (COS) {
             // the chain through the normalisation, per part (it is linear): inv_o (sum_x W own-side^ - t own^), DESIGN 4.20
             const float inv_o = (role == 0 ? ibx_invu<MIX>(ia) : ibx_invp<MIX>(ia))[ob];
-#pragma unroll
-            for (int cb = 0; cb < CB; cb++) {
-                const float oh = own[(int64_t)ob * D + col0 + cb * 32 + j];
-                fixed_add(ia.m.G64 + row * D + col0 + cb * 32 + j, inv_o * (g[cb][reg] - t_row * oh));
-            }
+            IB_GRAD_ADD_PROJECTED(D, ia.m.G64, own, inv_o);
         } else {
 #pragma unroll
             for (int cb = 0; cb < CB; cb++) fixed_add(ia.m.G64 + row * D + col0 + cb * 32 + j, g[cb][reg]);
@@ -464,16 +406,10 @@ __global__ void __launch_bounds__(64) k_inbatch_grad(InBatchArgs ia) {
 
 template <int D, bool COS, bool LQ, bool MIX>
 static void launch_d(const InBatchArgs &a, int act_dtype, bool wts, hipStream_t st) {
-    constexpr int SPB = 256 / (D < 64 ? D : 64);
+    constexpr int SPB = RowsGeo<D>::SPB;
     const int Bp = lgcn_inbatch_rows(a.m.B), NP = lgcn_inbatch_parts(a.m.B);
     const dim3 rows_grid((unsigned)((Bp + SPB - 1) / SPB)), diag_grid((unsigned)((a.m.B + SPB - 1) / SPB));
-    if (act_dtype == LGCN_F32) {
-        if (wts) hipLaunchKernelGGL((k_inbatch_rows<D, float, true, COS, LQ, MIX>), rows_grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_inbatch_rows<D, float, false, COS, LQ, MIX>), rows_grid, dim3(256), 0, st, a);
-    } else {
-        if (wts) hipLaunchKernelGGL((k_inbatch_rows<D, bf16_t, true, COS, LQ, MIX>), rows_grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_inbatch_rows<D, bf16_t, false, COS, LQ, MIX>), rows_grid, dim3(256), 0, st, a);
-    }
+    DISPATCH_ROWS(act_dtype, wts, hipLaunchKernelGGL((k_inbatch_rows<D, TI, WTS, COS, LQ, MIX>), rows_grid, dim3(256), 0, st, a));
     if constexpr (MIX) {
         // the item sweep is (1 + R) times as long; the gradient's grid is flat (users' workgroups, then the items')
         const int nT = Bp / 32, nTI = (1 + a.m.R) * nT, NPX = lgcn_inbatch_mix_parts(a.m.B, a.m.R);

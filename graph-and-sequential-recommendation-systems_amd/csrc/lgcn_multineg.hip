@@ -22,7 +22,8 @@
 // registers, so neither the register count nor anything else grows with R (#pragma unroll 1 over r; no LDS).
 // Lanes 0..R-1 of the group hold the negatives' ids (R <= 16 <= the smallest group), lanes R and R + 1 the user's and the
 // positive's row: one ballot voids a sample, the row flags and the reg_ego slot counts of all 2 + R rows are ONE atomic
-// instruction each.  LOSS is a compile-time axis, so an instantiation holds the code of its own loss only:
+// instruction each.  That prologue -- geometry, stale-bitmap loop, id check and ballot, user / positive pair, flag and count -- is
+// lgcn_batch_rows.h's, shared with k_hardneg, k_inbatch_rows and k_directau_rows.  LOSS is a compile-time axis, so an instantiation holds the code of its own loss only:
 //   BPR      one pass over the negatives: a negative's gradient row goes out as soon as its score is known.
 //   softmax  q_r needs ALL R scores of the sample before any gradient row can leave, so two passes with a step between:
 //     score      z_r stays in lane r of the group, the reg squares are summed.  No gradient leaves.
@@ -38,7 +39,7 @@
 // moved low bits of the gradient rows (profiles/batch_row_merge/README.md).  Keep the declaration order of sgb / sl / srn and
 // the row buffers for the same reason, and compare the compiler's resource report with the previous one after an edit.
 // Everything downstream consumes what the three-slot kernels write: G64 (2^50 fixed point), the row bitmap, cnt, terms, err.
-#include "lgcn_device_common.h"
+#include "lgcn_batch_rows.h"      // RowsGeo and the sample prologue (bitmap loop, id check, user / positive pair, flag and count), DISPATCH_ROWS
 
 // (slot_row, the output-table row of a slot, lives in lgcn_device_common.h: the in-batch launch gathers its rows through it too)
 
@@ -51,7 +52,7 @@
 template <int D, typename TI, bool WTS, bool EMIT>
 __device__ __forceinline__ void softmax_pass(const MultiNegArgs &a, int32_t id, int l, const float *u, float ps, bool ego, float lam_n,
                                              float *acc, float &sgb, float &srn, float &zq, float *n, float *n0, float *nn, float *nn0) {
-    constexpr int LPT = D < 64 ? D : 64, CPT = D / LPT;
+    constexpr int LPT = RowsGeo<D>::LPT, CPT = RowsGeo<D>::CPT;
     const int R = a.R;
     int64_t rn = (int64_t)__shfl(id, 0, LPT) + a.n_users;
     slot_row<D, TI, WTS>(a, rn, l, n, n0);
@@ -86,23 +87,12 @@ __device__ __forceinline__ void softmax_pass(const MultiNegArgs &a, int32_t id, 
 
 template <int D, typename TI, bool WTS, int LOSS>
 __global__ void __launch_bounds__(256) k_multineg(MultiNegArgs a) {
-    constexpr int LPT = D < 64 ? D : 64, CPT = D / LPT, SPB = 256 / LPT;     // lanes per sample, samples per workgroup
-    // last step's row bitmap is dead: zero it here with plain stores (the two bitmaps alternate per step)
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.bitmap_words; i += (int64_t)gridDim.x * 256)
-        a.stale_bitmap[i] = 0u;
-    const int b = blockIdx.x * SPB + threadIdx.x / LPT, l = threadIdx.x % LPT;
+    ROWS_ZERO_STALE_BITMAP(a);
+    ROWS_GEOMETRY(D);
     if (b >= a.B) return;                       // whole lane groups leave together
     const int R = a.R;
-    // every id is checked before anything is addressed with it: lane r < R holds negative r, lanes R / R + 1 the user / positive
-    int32_t id = 0;
-    bool idbad = false;
-    if (l < R) { id = a.negs[(int64_t)l * a.neg_stride + b]; idbad = id < 0 || (int64_t)id + a.n_users >= a.N; }
-    else if (l == R) { id = a.users[b]; idbad = id < 0 || id >= a.n_users; }
-    else if (l == R + 1) { id = a.pos[b]; idbad = id < 0 || (int64_t)id + a.n_users >= a.N; }
+    ROWS_LOAD_IDS(a, ROWS_NEGS_FIRST, true, true);      // lane r < R holds negative r, lanes R / R + 1 the user / positive
     const int64_t myrow = l == R ? (int64_t)id : (int64_t)id + a.n_users;      // (meaningful on lanes 0 .. R + 1)
-    constexpr unsigned long long GROUP = LPT == 64 ? ~0ull : ((1ull << (LPT & 63)) - 1ull);
-    const int gshift = (threadIdx.x & 63) / LPT * LPT;                          // this group's first lane in the wave
-    const bool bad = (__ballot(idbad) & (GROUP << gshift)) != 0ull;
     if (bad) {                                  // an out-of-range id voids the whole sample: err flag, zero terms, no gradient
         if (l == 0) { atomicExch(a.err, 1); a.terms[b] = 0.f; a.terms[a.terms_stride + b] = 0.f; }
         return;
@@ -110,14 +100,9 @@ __global__ void __launch_bounds__(256) k_multineg(MultiNegArgs a) {
     const int64_t ru = (int64_t)__shfl(id, R, LPT), rp = (int64_t)__shfl(id, R + 1, LPT) + a.n_users;
     const bool ego = a.reg_ego != 0;
     const float lam = ego ? 0.f : a.lam, lam_n = ego ? 0.f : a.lam_n;
-    float u[CPT], p[CPT], t0[CPT], acc[CPT];    // acc = sum_r gb_r e_{n_r}
+    float u[CPT], p[CPT], acc[CPT];             // acc = sum_r gb_r e_{n_r}
     float ps = 0.f, ru2 = 0.f, rp2 = 0.f;
-    slot_row<D, TI, WTS>(a, ru, l, u, t0);
-#pragma unroll
-    for (int j = 0; j < CPT; j++) { const float v = ego ? t0[j] : u[j]; ru2 += v * v; }
-    slot_row<D, TI, WTS>(a, rp, l, p, t0);
-#pragma unroll
-    for (int j = 0; j < CPT; j++) { const float v = ego ? t0[j] : p[j]; ps += u[j] * p[j]; rp2 += v * v; acc[j] = 0.f; }
+    ROWS_PAIR(ps += u[j] * p[j]; acc[j] = 0.f)
     ps = group_sum<LPT>(ps);
     float sgb = 0.f, sl = 0.f, srn = 0.f;       // sum_r gb_r, the loss term (BPR: sum_r logsigmoid(x_r)), sum_r |n_r|^2 (this lane's columns)
     float n[CPT], n0[CPT], nn[CPT], nn0[CPT];
@@ -156,7 +141,7 @@ __global__ void __launch_bounds__(256) k_multineg(MultiNegArgs a) {
         const float m = group_max<LPT>(z);
         const bool mine = l < R;
         // the term that is exp(0) = 1 exactly is left out of the sum: the positive's where m = 0, else the first maximal negative's
-        const unsigned long long atmax = (__ballot(mine && z == m) >> gshift) & GROUP;
+        const unsigned long long atmax = ROWS_VOTES(mine && z == m);
         const int first = m > 0.f ? __ffsll(atmax) - 1 : -1;
         const float ev = mine ? expf(z - m) : 0.f;
         const float zm1 = group_sum<LPT>(l == first ? 0.f : ev) + (m > 0.f ? expf(-m) : 0.f);      // Z - 1
@@ -175,22 +160,15 @@ __global__ void __launch_bounds__(256) k_multineg(MultiNegArgs a) {
         fixed_add(a.G64 + rp * D + j * LPT + l, gp);
     }
     if (l < R + 2) {                            // the 2 + R rows of the sample: one lane each
-        atomicOr(a.bitmap + (myrow >> 5), 1u << (myrow & 31));
-        if (a.cnt) atomicAdd(a.cnt + myrow, l < R ? 1 : R);     // a negative slot weighs 1/R of a user / positive slot (epilogue: decay / (B R))
+        ROWS_FLAG(a, myrow, l < R ? 1 : R);     // a negative slot weighs 1/R of a user / positive slot (epilogue: decay / (B R))
     }
 }
 
 template <int D, int LOSS>
 static void launch_d(const MultiNegArgs &a, int act_dtype, bool wts, hipStream_t st) {
-    constexpr int SPB = 256 / (D < 64 ? D : 64);
+    constexpr int SPB = RowsGeo<D>::SPB;
     const dim3 grid((unsigned)((a.B + SPB - 1) / SPB)), block(256);
-    if (act_dtype == LGCN_F32) {
-        if (wts) hipLaunchKernelGGL((k_multineg<D, float, true, LOSS>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_multineg<D, float, false, LOSS>), grid, block, 0, st, a);
-    } else {
-        if (wts) hipLaunchKernelGGL((k_multineg<D, bf16_t, true, LOSS>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_multineg<D, bf16_t, false, LOSS>), grid, block, 0, st, a);
-    }
+    DISPATCH_ROWS(act_dtype, wts, hipLaunchKernelGGL((k_multineg<D, TI, WTS, LOSS>), grid, block, 0, st, a));
 }
 
 int lgcn_multineg_launch(const MultiNegArgs &a, int d, int act_dtype, bool wts, hipStream_t st) {

@@ -130,6 +130,65 @@ def test_evaluation_device_pieces_are_defined_once(pkg):
         assert len(loops) == len(allowed) and all(w in l for w, l in zip(allowed, loops)), f"{f}: {loops}"
 
 
+def test_slot_form_device_pieces_are_defined_once(pkg):
+    """What the device side of the slot-form losses shares has ONE definition under csrc/ (DESIGN 4.29): the sample prologue of the four
+    batch-row kernels in lgcn_batch_rows.h, the sweep of the four tile kernels in lgcn_inbatch_tile.h.  No .hip among lgcn_multineg,
+    lgcn_hardneg, lgcn_inbatch, lgcn_directau spells the lane-group geometry, the group ballot, the stale-bitmap loop, the id range
+    rules, the flag-and-count pair, the part bounds, the register-form operands, the matrix instruction or the storage-type ladder
+    inline, and each kernel names the header's pieces.  Written out on purpose (profiles/loss_sweep/README.md):
+      the sum of squares in front of rows_inv_norm   as part of the function its multiply-adds fused differently at d 128 / 256, so
+                                                     k_inbatch_rows and k_directau_rows keep the sums and share the formula;
+      the BPR pass of k_multineg                     DESIGN 4.18: a pass shared with softmax moved bits of the gradient rows."""
+    csrc = os.path.dirname(pkg.build.SOURCES[0])
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".cpp"))}
+    rows_h, tile_h = "lgcn_batch_rows.h", "lgcn_inbatch_tile.h"
+    home = {rows_h: ["struct RowsGeo", "#define ROWS_GEOMETRY(", "#define ROWS_ZERO_STALE_BITMAP(", "#define ROWS_ITEM_BAD(", "#define ROWS_NEGS_FIRST(",
+                     "#define ROWS_PAIR_FIRST(", "#define ROWS_LOAD_IDS(", "#define ROWS_VOTES(", "#define ROWS_PAIR(", "#define ROWS_FLAG(",
+                     "float rows_inv_norm(", "#define DISPATCH_ROWS("],
+            tile_h: ["f32x16 ib_scores(", "f32x16 ib_scores_reg(", "struct IbRow", "#define IB_PART_BOUNDS(", "#define IB_TILE_ROW(", "#define IB_SWEEP_BEGIN(",
+                     "#define IB_SWEEP_SCORES(", "constexpr int ib_grad_blocks(", "#define IB_GRAD_ZERO(", "#define IB_GRAD_PREFETCH(", "#define IB_GRAD_PRODUCT(",
+                     "#define IB_GRAD_TPROJ_COMBINE(", "#define IB_GRAD_TPROJ_ROW(", "#define IB_GRAD_ADD_PROJECTED("]}
+    for h, names in home.items():
+        for name in names:
+            assert [f for f, t in text.items() if name in t] == [h], name
+    assert pkg.build.source_hash() and os.path.join(csrc, rows_h) in pkg.build.hashed_files()
+    units = ("lgcn_multineg.hip", "lgcn_hardneg.hip", "lgcn_inbatch.hip", "lgcn_directau.hip")
+    code = {f: re.sub(r"//[^\n]*", "", text[f]) for f in units}            # (the header comments describe the pieces in words)
+    inline = {"the group ballot": r"GROUP\s*<<\s*gshift|__ballot\(", "the lane-group geometry": r"D < 64 \? D : 64|256 / LPT",
+              "the stale-bitmap loop": r"stale_bitmap\s*\[", "the id range rules": r"n_users\s*>=\s*\w+\.N\b|>=\s*\w+\.n_users",
+              "the flag and count": r"atomicOr\(|atomicAdd\(\s*\w+\.cnt", "the part bounds": r"LGCN_INBATCH_PART_TILES", "the gradient's blocks": r"D < 128 \? D / 32",
+              "the operand forms": r"IbRow<|ib_load\(|ib_scores_reg<|ib_scores<", "the matrix instruction": r"__builtin_amdgcn_mfma",
+              "the cross-half shuffle": r"__shfl_xor\(tproj", "the norm formula": r"1\.f\s*/\s*sqrtf\(",
+              "the storage-type ladder": r"if \(wts\) hipLaunchKernelGGL|<D, (float|bf16_t), (true|false)"}
+    for f, t in code.items():
+        for what, pat in inline.items():
+            assert not re.search(pat, t), f"{f} spells {what} inline"
+
+    def body(f, kernel):
+        m = re.search(r"\bk_%s\(\w+ \w+\) \{\n(.*?)\n\}\n" % kernel[2:], code[f], re.S)
+        assert m, kernel
+        return m.group(1)
+    prologue = ("ROWS_ZERO_STALE_BITMAP(a)", "ROWS_GEOMETRY(D)", "ROWS_LOAD_IDS(a, ", "ROWS_PAIR(", "ROWS_FLAG(a, ")
+    for f, kernel, layout in (("lgcn_multineg.hip", "k_multineg", "ROWS_NEGS_FIRST"), ("lgcn_hardneg.hip", "k_hardneg", "ROWS_NEGS_FIRST"),
+                              ("lgcn_inbatch.hip", "k_inbatch_rows", "ROWS_PAIR_FIRST"), ("lgcn_directau.hip", "k_directau_rows", "ROWS_PAIR_FIRST")):
+        t = body(f, kernel)
+        assert all(t.count(w) >= 1 for w in prologue) and t.count("ROWS_LOAD_IDS(a, " + layout) == 1, kernel
+        assert t.index("ROWS_LOAD_IDS(") < t.index("slot_row" if "slot_row" in t else "ROWS_PAIR("), f"{kernel}: the ids are checked before a row is addressed"
+        assert "DISPATCH_ROWS(act_dtype, wts, hipLaunchKernelGGL((%s<D, TI, WTS" % kernel in code[f], kernel
+    for f, kernel in (("lgcn_inbatch.hip", "k_inbatch_rows"), ("lgcn_directau.hip", "k_directau_rows")):
+        assert body(f, kernel).count("rows_inv_norm(") >= 2 and "nu += u[j] * u[j]" in body(f, kernel), kernel
+    sweep, grad = ("IB_PART_BOUNDS(", "IB_SWEEP_BEGIN(D, ", "IB_SWEEP_SCORES(D, "), ("CB = ib_grad_blocks(D)", "IB_GRAD_ZERO()", "IB_GRAD_PREFETCH(D, ", "IB_GRAD_PRODUCT(D, ",
+                                                                                     "IB_GRAD_TPROJ_COMBINE()", "IB_GRAD_TPROJ_ROW(reg)", "IB_GRAD_ADD_PROJECTED(D, ")
+    for f, kernel, pieces in (("lgcn_inbatch.hip", "k_inbatch_norm", sweep), ("lgcn_directau.hip", "k_directau_norm", sweep),
+                              ("lgcn_inbatch.hip", "k_inbatch_grad", sweep + grad), ("lgcn_directau.hip", "k_directau_grad", sweep + grad)):
+        t = body(f, kernel)
+        assert all(t.count(w) == 1 for w in pieces), (kernel, [w for w in pieces if t.count(w) != 1])
+    # the one sweep that may be empty (DirectAU's normaliser starts at the owner tile) tells the operands so; the others hold a tile
+    begins = [re.search(r"IB_SWEEP_BEGIN\(D, \w+, [\w.]+, (\w+), ([^\n]*)\)\n", body(f, k) + "\n").groups()
+              for f, k in (("lgcn_directau.hip", "k_directau_norm"), ("lgcn_directau.hip", "k_directau_grad"), ("lgcn_inbatch.hip", "k_inbatch_norm"), ("lgcn_inbatch.hip", "k_inbatch_grad"))]
+    assert begins == [("ts", "ts < t1"), ("t0", "true"), ("t0", "true"), ("t0", "true")], begins
+
+
 def test_glibc_stream_and_randint(pkg):
     s = pkg.sampling
     s.seed(2020)

@@ -52,7 +52,18 @@ Cases (cases()):
             lgcn_eval_metrics_ex on those lists with the cut-offs unsorted and one repeated; lgcn_eval_ranks with both flags and
             lgcn_eval_rank_metrics; lgcn_eval_pop_metrics.  The K-th place of a list is not defined under an exact fp32 tie and the
             parts' exchange is timing dependent, so the kind is run library against ITSELF first; a case that differs there gets
-            another seed (EVAL_SEEDS), never a looser comparison.  LAST, by the same rule as directau.
+            another seed (EVAL_SEEDS), never a looser comparison.  Behind dp, by the same rule as directau.
+  hardneg   lgcn_train_step_multi on a context with lgcn_ctx_set_hard_neg (--hard_neg M): d 32/64/128/256, fp32 / bf16
+            tables, mean / layer weights, K 1/3, R 2/5/16, M 1 / 2 / R, B 1/7/67, reg_rows propagated / ego; every value of every
+            axis at every d (check_coverage); one batch per d with an out-of-range candidate and one lgcn_train_epoch_multi over
+            T = 2 B + 3.  Besides what the other kinds record, the selected index of every sample of every step (last_selection,
+            the context's sel_out).  Behind eval, by the same rule.
+  multipart (a tag, not a kind: the cases are of kind inbatch / inbatch_mix / directau and run with --kinds of those)  one case each
+            of inbatch, inbatch_mix (R = 2) and directau at d 64 (the register form of the tile operands) and d 128 (the streamed
+            form) at B = multipart_B(): the smallest batch that sweeps TWO parts with two tiles in the second one -- a prefetch
+            and the clamp at the part's end in a part shorter than LGCN_INBATCH_PART_TILES -- and one live row in the last tile;
+            DirectAU's normaliser starts the second part's sweep at the owner tile there.  Cosine scores with logQ for the two
+            in-batch kinds (the projected epilogue).  LAST, by the same rule.
 
 A side whose tree does not know a case of the other side (an older checkout under --tree-a) is compared on the common cases; the
 cases only one side ran are counted in the report and never differ."""
@@ -79,7 +90,23 @@ DP_FORMS, DP_WS, DP_DS, DP_FP8_AT = ("rows0", "rows1", "dense", "row_sharded"), 
 EVAL_MS, EVAL_DS, EVAL_BIG_M, EVAL_BIG_DS = (3001, 10007), DS, 270001, (32, 128)
 EVAL_KS, EVAL_SMALL_K, EVAL_USERS, EVAL_SLOTS, EVAL_GROUPS = (20, 64, 100, 256), 20, 300, 257, 3
 EVAL_SEEDS = {}                                            # (m_items, d) -> seed of the problem, where 0 ties at a K-th place
+HN_RS, HN_MS = (2, 5, 16), ("1", "2", "R")                 # --hard_neg M: 1, 2, or all R candidates
+MULTIPART_DS = (64, 128)
 DP_TIMEOUT = 120                                           # seconds the rank threads of one lgcn_train_epoch_dp call may take
+
+
+def multipart_B():
+    """The batch of the multipart cases: the smallest B with two parts of the sweep (tests/inbatch_restatement.parts) plus one
+    tile, so that the second part holds two tiles -- fewer than a full part -- and the last tile one live row."""
+    parts = restatement().parts
+    return next(B for B in itertools.count(1) if parts(B) == 2) + 32
+
+
+def restatement():
+    """tests/inbatch_restatement.py, whose parts() is the part count of the sweep (the driver has no tests/ on its path)."""
+    if os.path.join(REPO, "tests") not in sys.path:
+        sys.path[:0] = [os.path.join(REPO, "tests")]
+    return importlib.import_module("inbatch_restatement")
 
 
 def cases():
@@ -144,10 +171,40 @@ def cases():
     out += [dict(kind="dp", form="cols", W=2, d=d, mode=mode, K=K, dl=0, cfg={}) for d, mode, K in ((64, "fp32", 1), (64, "bf16", 3), (128, "fp8", 2))]
     out += [dict(kind="eval", m_items=m, d=d) for m in EVAL_MS for d in EVAL_DS]      # eval (last: see the module docstring)
     out += [dict(kind="eval", m_items=EVAL_BIG_M, d=d) for d in EVAL_BIG_DS]
+    for j, d in enumerate(DS):                              # hardneg (behind eval: see the module docstring): six cases per d
+        for i in range(6):
+            R, mk = HN_RS[i % 3], HN_MS[(i + i // 3) % 3]
+            out.append(dict(kind="hardneg", d=d, mode=MODES[(i + j) % 2], wts=WTS[(i // 2) % 2], K=KS[(i // 3) % 2], R=R, mk=mk,
+                            M=R if mk == "R" else int(mk), B=BS[(i + i // 3 + j) % 3], reg=REGS[((i + 1) // 2) % 2]))
+    for j, d in enumerate(DS):                              # one sample with an out-of-range candidate
+        out.append(dict(kind="hardneg", d=d, mode=MODES[j % 2], wts=False, K=1, R=5, mk="2", M=2, B=7, reg="propagated", void=3))
+    out.append(dict(kind="hardneg", d=64, mode="bf16", wts=False, K=3, R=5, mk="2", M=2, B=7, reg="propagated", epoch=True))
+    B = multipart_B()                                       # the multi-part batch (LAST: see the module docstring)
+    for j, d in enumerate(MULTIPART_DS):
+        for kind in IB_KINDS:
+            out.append(dict(kind=kind, d=d, mode=MODES[j % 2], wts=False, K=1, B=B, reg="propagated", score="cosine", logq=True, R=2, multipart=True))
+        out.append(dict(kind="directau", d=d, mode=MODES[j % 2], wts=False, K=1, B=B, reg="propagated", gamma=1.0, multipart=True))
     return out
 
 
 def check_coverage(cs):
+    mp = [c for c in cs if c.get("multipart")]
+    assert mp and cs[-len(mp):] == mp, "the multipart cases are the last ones"
+    assert sorted((c["kind"], c["d"]) for c in mp) == sorted(itertools.product(IB_KINDS + ("directau",), MULTIPART_DS))
+    IR = restatement()
+    B, tiles = mp[0]["B"], (mp[0]["B"] + 31) // 32
+    per = next(T for T in itertools.count(1) if IR.parts(32 * T + 1) == 2)       # tiles per part, from parts() itself
+    assert all(c["B"] == B for c in mp) and IR.parts(B) == 2 and IR.parts(B - 33) == 1 and 1 < tiles - per < per and B % 32 == 1, (B, per)
+    cs = cs[:-len(mp)]
+    hn = [c for c in cs if c["kind"] == "hardneg"]
+    assert hn and cs[-len(hn):] == hn, "the hardneg cases are behind every other kind"
+    cs = cs[:-len(hn)]
+    for d in DS:
+        at = [c for c in hn if c["d"] == d and not (c.get("void") or c.get("epoch"))]
+        for key, values in (("mode", MODES), ("wts", WTS), ("K", KS), ("R", HN_RS), ("mk", HN_MS), ("B", BS), ("reg", REGS)):
+            assert {c[key] for c in at} == set(values), ("hardneg", d, key)
+        assert sum(1 for c in hn if c["d"] == d and c.get("void")) == 1, ("hardneg", d, "void")
+    assert sum(1 for c in hn if c.get("epoch")) == 1 and all(1 <= c["M"] <= c["R"] for c in hn)
     ev = [c for c in cs if c["kind"] == "eval"]
     assert ev and cs[-len(ev):] == ev, "the eval cases are the last ones"
     assert {(c["m_items"], c["d"]) for c in ev} == set(itertools.product(EVAL_MS, EVAL_DS)) | {(EVAL_BIG_M, d) for d in EVAL_BIG_DS}
@@ -208,17 +265,20 @@ def name(c):
         return (f"multi-d{c['d']}-{c['mode']}-{'wts' if c['wts'] else 'mean'}-K{c['K']}-R{c['R']}-B{c['B']}-{c['reg']}-{c['loss']}"
                 + (f"{c['tau']}" if c["loss"] == "softmax" else "") + tag)
     if c["kind"] in IB_KINDS:
-        tag = "-void" if c.get("void") else "-epoch" if c.get("epoch") else "-then-plain" if c.get("then_plain") else ""
+        tag = "-void" if c.get("void") else "-epoch" if c.get("epoch") else "-then-plain" if c.get("then_plain") else "-multipart" if c.get("multipart") else ""
         return (f"{c['kind']}-d{c['d']}-{c['mode']}-{'wts' if c['wts'] else 'mean'}-K{c['K']}-B{c['B']}-{c['reg']}-{c['score']}-{'logq' if c['logq'] else 'nologq'}"
                 + (f"-R{c['R']}of{MIX_RMAX}" if c["kind"] == "inbatch_mix" else "") + tag)
     if c["kind"] == "mf":
         return f"mf-d{c['d']}-B{c['B']}"
+    if c["kind"] == "hardneg":
+        tag = "-void" if c.get("void") else "-epoch" if c.get("epoch") else ""
+        return f"hardneg-d{c['d']}-{c['mode']}-{'wts' if c['wts'] else 'mean'}-K{c['K']}-R{c['R']}-M{c['M']}-B{c['B']}-{c['reg']}" + tag
     if c["kind"] == "eval":
         return f"eval-m{c['m_items']}-d{c['d']}"
     if c["kind"] == "dp":
         return f"dp-{c['form']}-w{c['W']}-d{c['d']}-{c['mode']}-K{c['K']}-dl{c['dl']}" + "".join(f"-{k}" for k in c["cfg"] if k.startswith("use_"))
     if c["kind"] == "directau":
-        tag = "-void" if c.get("void") else "-epoch" if c.get("epoch") else ""
+        tag = "-void" if c.get("void") else "-epoch" if c.get("epoch") else "-multipart" if c.get("multipart") else ""
         return f"directau-d{c['d']}-{c['mode']}-{'wts' if c['wts'] else 'mean'}-K{c['K']}-B{c['B']}-{c['reg']}-gamma{c['gamma']}" + tag
     return f"step-d{c['d']}-{c['mode']}-K{c['K']}-dl{c['dl']}-B{c['B']}" + "".join(f"-{k}" for k in c["cfg"] if k in ("dropout", "layer_weights", "use_pop_gate", "use_item_item"))
 
@@ -428,6 +488,9 @@ def child(out_path, kinds=()):
         elif c["kind"] == "multi":
             w = SC.configure(pkg, (c["mode"], c["d"], c["K"], 1, -1, c["reg"]), path, 64)
             w.config.update({'neg_ratio': c["R"], 'loss': c["loss"], 'softmax_temp': c["tau"]}, **({'layer_weights': 'exp'} if c["wts"] else {}))
+        elif c["kind"] == "hardneg":
+            w = SC.configure(pkg, (c["mode"], c["d"], c["K"], 1, -1, c["reg"]), path, 64)
+            w.config.update({'neg_ratio': c["R"], 'loss': 'bpr', 'hard_neg': c["M"], 'hard_neg_record': 1}, **({'layer_weights': 'exp'} if c["wts"] else {}))
         else:
             w = SC.configure(pkg, (c["mode"], c["d"], c["K"], c["dl"], -1, "propagated"), path, 64)
             w.config.update(c["cfg"])
@@ -444,11 +507,11 @@ def child(out_path, kinds=()):
             assert (zs > 100.0).any() and (zs < -100.0).all(1).any(), "the saturating batch no longer reaches the m > 0 branch"
         m = m.to(dev)
         m.train()
-        losses, held = [], []
+        losses, held, sels = [], [], []
         T = 2 * B + 3 if c.get("epoch") else B              # an epoch case: ONE call of three batches, the last one short
         for step in range(1 if c.get("epoch") else STEPS):
             u, p = rng.integers(1, SC.N_USERS, T), rng.integers(1, SC.M_ITEMS, T)
-            n = rng.integers(1, SC.M_ITEMS, (T, c["R"]) if c["kind"] in ("multi", "inbatch_mix") else T)
+            n = rng.integers(1, SC.M_ITEMS, (T, c["R"]) if c["kind"] in ("multi", "inbatch_mix", "hardneg") else T)
             for a in (p, n):                                 # as tests/storage_cases.make_batches: no slot names these two rows
                 a[(a == SC.BIG_ITEM) | (a == SC.ISOLATED_ITEM)] = 20
             if c.get("saturate"):
@@ -468,11 +531,16 @@ def child(out_path, kinds=()):
                 losses.append(out)
             elif c["kind"] == "inbatch_mix":
                 losses.append(m.fused_step(ids(u), ids(p), ids(n.T)))
+            elif c["kind"] == "hardneg":                       # the multi-negative entry point on a context with lgcn_ctx_set_hard_neg
+                du, dp, dn = ids(u), ids(p), ids(n.T)
+                losses.append(m._fused_call("lgcn_train_step_multi", (pkg._lib.tp(du), pkg._lib.tp(dp), pkg._lib.tp(dn), B, c["R"], B), B))
             elif c["kind"] == "multi":                         # R = 1 under --loss bpr included: the batch-row launch, not the three-slot step
                 du, dp, dn = ids(u), ids(p), ids(n.T)
                 losses.append(m._fused_call("lgcn_train_step_multi", (pkg._lib.tp(du), pkg._lib.tp(dp), pkg._lib.tp(dn), B, c["R"], B), B))
             else:
                 losses.append(m.fused_step(ids(u), ids(p), ids(n)))
+            if c["kind"] == "hardneg":                        # (an epoch: the selection of its last, short batch)
+                sels.append(m.last_selection()[:3 if c.get("epoch") else B].clone())
         try:
             m.check_device_errors()
             err = 0
@@ -485,6 +553,9 @@ def child(out_path, kinds=()):
         result[key + " adam_m"] = m._dev['adam_m'].cpu().numpy()
         result[key + " adam_v"] = m._dev['adam_v'].cpu().numpy()
         result[key + " err"] = np.array([err], np.int32)
+        if sels:
+            result[key + " sel"] = torch.stack(sels).cpu().numpy()
+            assert ((result[key + " sel"] >= 0) & (result[key + " sel"] < c["R"])).sum() == result[key + " sel"].size - (STEPS if c.get("void") else 0), key
         assert np.isfinite(result[key + " loss_out"]).all(), key
         del m
     pkg.world.configure([])
